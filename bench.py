@@ -197,6 +197,27 @@ def device_time_us(eng, theta_dev, lp, st, stream, n, iters, warm=3, reps=1):
     return sorted(got)[len(got) // 2]
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays, seed=0):
+    """Write each 1-D float64 array as DIR/<name>.npy.  Past DUMP_LIMIT_BYTES in all, every array keeps the same share of
+    its elements: a fixed, seeded sample of indices, in increasing order.  Returns {name: what was written}."""
+    os.makedirs(dirname, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    out = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        rec = {'shape': list(a.shape), 'dtype': 'float64'}
+        if total > DUMP_LIMIT_BYTES:
+            k = int(a.size * DUMP_LIMIT_BYTES // total)
+            rec.update(sampled=k, sample='numpy.random.default_rng({}).choice({}, {}, replace=False), sorted'.format(seed, a.size, k))
+            a = a[np.sort(np.random.default_rng(seed).choice(a.size, k, replace=False))]
+        np.save(os.path.join(dirname, name + '.npy'), a)
+        out[name] = rec
+    return out
+
+
 def load_profile(name):
     p = os.path.join(ROOT, 'profiles', name)
     return json.load(open(p)) if os.path.exists(p) else None
@@ -251,7 +272,11 @@ def main():
                     help='N > 1: wait for each all-gather before the next launch (a single dependent chain)')
     ap.add_argument('--cpu-budget', type=float, default=12.0)
     ap.add_argument('--copy-gib', type=float, default=1.0)
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed (log-probabilities, walker statuses) as DIR/<name>.npy')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
     if args.config == 4:
         args.npix, args.phot, args.walkers = args.npix or 16384, True, args.walkers or 128
     if args.config == 5:
@@ -588,7 +613,8 @@ def main():
     gev_pool = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(8)]
 
     def timed_region():
-        """EXACTLY K steps between barrier + synchronize on both sides; returns (seconds, graph-replay event pairs)."""
+        """EXACTLY K steps between barrier + synchronize on both sides; returns (seconds, graph-replay event pairs, the
+        index that selected the last step's problem / theta batch / output buffer)."""
         nonlocal nev
         drain()
         torch.cuda.synchronize(dev)
@@ -626,9 +652,17 @@ def main():
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize(dev)
-        return time.perf_counter() - t0, gev_
+        # (the last step is the eager tail's, else step chunk - 1 of the last replay: the graph numbers its steps from 0)
+        return time.perf_counter() - t0, gev_, (args.steps - 1 if first_eager < args.steps else chunk - 1)
 
-    dt, gev = timed_region()
+    dt, gev, i_last = timed_region()
+    # what the last timed step handed its caller, copied out before anything else reuses the buffers
+    dump = None
+    if args.dump_outputs and rank == 0:
+        b_last = i_last & 1
+        dump = {'logp': logp[b_last].cpu().numpy(), 'status': status[b_last].cpu().numpy().astype(np.float64)}
+        if use_gather:
+            dump['logp_gathered'] = gathered[b_last].cpu().numpy()
     t = torch.tensor([dt], dtype=torch.float64, device=dev)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -670,7 +704,7 @@ def main():
         time.sleep(1.0)
         for i in range(args.warmup):
             launch(i)
-        dt_cold, _ = timed_region()
+        dt_cold, _, _ = timed_region()
         unramped = {'ms_per_step': dt_cold / args.steps * 1e3, 'value': n * world * args.steps / dt_cold,
                     'note': 'same {} steps after 1 s of idle + the {} warm-up steps, no untimed launches before the '
                             'timed region'.format(args.steps, args.warmup)}
@@ -936,6 +970,10 @@ def main():
                         'node at staging, mft6.py:366-378'}
         if extra:
             out['extra'] = extra
+        if dump is not None:
+            out['dumped_outputs'] = {'arrays': dump_outputs(args.dump_outputs, dump),
+                                     'note': 'the last timed step\'s log-probabilities and walker status codes (as float64){}'.format(
+                                         '; logp_gathered = the all-gathered vector of every rank' if use_gather else '')}
         sys.stdout.flush()
         os.write(result_fd, (json.dumps(out, default=lambda o: o.item() if hasattr(o, 'item') else str(o)) + '\n').encode())
     if world > 1 or force_gather:

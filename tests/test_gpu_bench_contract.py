@@ -90,3 +90,24 @@ def test_the_rooflines_kernel_name_comes_from_the_library():
         torch.cuda.synchronize()
         assert eng.ctx.last_form() == would['form_id'], (m, would)
     assert eng.ctx.launch_info(2048)['form'].startswith('pair') and eng.ctx.launch_info(1024)['form'] == 'fused'   # (8 walkers per CU)
+
+
+def test_dump_outputs_writes_the_last_timed_steps_arrays(tmp_path):
+    """--dump-outputs DIR: the last timed step's log-probabilities and walker statuses, float64.  Three plain launches +
+    one hipGraph of six steps: the last step is the graph's step 5, i.e. theta batch 1 (seed 4) -- not (K - 1) mod 4."""
+    import numpy as np
+    j = _run('--steps', '9', '--no-cpu-baseline', '--dump-outputs', str(tmp_path), env={'MSX_BENCH_HEAD': '3'})
+    assert j['steps'] == 9 and j['config']['step_loop'] == '3 eager + hipGraph of 6 steps x 1 replays + 0 eager'
+    assert sorted(os.listdir(tmp_path)) == ['logp.npy', 'status.npy'] and j['walker_error_statuses'] == 0
+    lp, st = np.load(tmp_path / 'logp.npy'), np.load(tmp_path / 'status.npy')
+    assert lp.dtype == st.dtype == np.float64 and lp.shape == st.shape == (256,)
+    sys.path.insert(0, ROOT)
+    import bench
+    from mcmc_spec_amd import _lib, synth
+    from mcmc_spec_amd.engine import Engine
+    eng = Engine(0)
+    W = bench.build_workload(eng, 4096, False)
+    want, want_st = eng.ctx.logprob_batch(synth.draw_walkers(256, seed=4, tmin=W['tmin'], tmax=W['tmax']), _lib.MODE_LOGPOST)
+    assert np.array_equal(st, want_st) and np.array_equal(np.isneginf(lp), np.isneginf(want))
+    fin = np.isfinite(want)
+    assert fin.any() and np.max(np.abs(lp[fin] - want[fin]) / np.abs(want[fin])) < 1e-12

@@ -304,9 +304,10 @@ int msx_sampler_enqueue_group(msx_ctx **ctxs, int32_t world, int32_t slot /* 0|1
 /* ---- measurement helpers ----------------------------------------------------------------------- */
 /* float4 device-to-device copy of `bytes` bytes, `iters` times; returns GB/s (read+write counted)  */
 int msx_stream_copy_gbps(msx_ctx *ctx, int64_t bytes, int32_t iters, double *gbps_out);
-/* bytes the hot kernel requests from the memory system per walker, for the variant an automatic launch of n walkers
- * of the staged problem takes (the one-workgroup-per-CU variants keep u and the data flux in LDS for the chi^2 pass:
- * 132 instead of 148 bytes per pixel of a binary)                                                                  */
+/* bytes the hot kernel requests from the memory system per walker, for the form and variant an automatic launch of n
+ * walkers of the staged problem takes (the one-workgroup-per-CU variants keep u and the data flux in LDS for the chi^2
+ * pass: 132 instead of 148 bytes per pixel of a binary); the launcher's own plan, so always msx_launch_info's figure for
+ * block_threads = 0, whatever the form (msx_set_path)                                                               */
 int msx_bytes_per_eval(msx_ctx *ctx, int64_t n, int64_t *requested_bytes);
 
 /* One launch of the fused / linked form over n walkers like msx_logprob_batch_dev -- with clock stamps: thread 0 of every
@@ -329,7 +330,7 @@ int msx_probe_launch(msx_ctx *ctx, int32_t mode, const double *d_theta, int64_t 
 int msx_set_grid_storage(msx_ctx *ctx, int32_t store_dtype);
 
 /* What an automatic launch of n walkers in `mode` (block_threads as for msx_logprob_batch_dev) WOULD take, asked of the
- * library's own launcher (nothing is queued): `name` receives the kernel's name and description, out8 = {form (MSX_FORM_*),
+ * plan the library's own launcher executes (nothing is queued): `name` receives the kernel's name and description, out8 = {form (MSX_FORM_*),
  * threads per workgroup, VGPRs, static LDS bytes, dynamic LDS bytes, bytes requested from the memory system per walker
  * (as msx_bytes_per_eval), workgroups of the first sub-batch, walkers of the first sub-batch}.                          */
 #define MSX_FORM_FUSED 0

@@ -1,5 +1,5 @@
 // logprob_kernel.h -- part of the single translation unit msx.hip (included there, in this order).
-// THE HOT KERNEL logprob_kernel<NS,U,MAXT,GM,CP,PF> and the walker's last lines (walker_done).
+// THE HOT KERNEL logprob_kernel<NS,MAXT,GM,SH,PF,LK,R32,FULL,GIVEN> and the walker's last lines (walker_done).
 #ifndef MSX_LOGPROB_KERNEL_H
 #define MSX_LOGPROB_KERNEL_H
 
@@ -250,8 +250,7 @@ struct ChiElem {
 extern __shared__ __attribute__((aligned(16))) unsigned char dyn_lds[];
 
 // MAXT = the workgroup size the variant is compiled for and launched with: 256 (three workgroups per CU, capped at
-//        168 VGPRs) or 512 (one per CU; with SH: two per CU, capped at 128 VGPRs).  U is the pixels per lane and trip:
-//        always 2, the two pixels of one table element (below).
+//        168 VGPRs) or 512 (one per CU; with SH: two per CU, capped at 128 VGPRs).
 // GM = the walker's model vector lives in global memory (spectra longer than ~17k pixels) instead of LDS.
 // SH = 512-thread variant that shares its CU with a second workgroup (MSX_BLOCK_512_SHARED).
 // PF = the walker-independent pixel vectors u and data flux are staged in LDS, in the tables' own layout, by the waves
@@ -289,14 +288,14 @@ extern __shared__ __attribute__((aligned(16))) unsigned char dyn_lds[];
 //        BASELINE's 4096 pixels): every lane of every trip holds live pixels, so the clamps of element and pixel indices,
 //        the per-pixel validity compares and their selects can be compiled out -- bit 0: of the blend, bit 1: of the chi^2
 //        pass and the candidates' gather.  Same arithmetic on the same pixels: same bits (the launcher picks it; msx.hip,
-//        choose_variant).  Which bits pay was measured per workgroup size (same box, alternating runs): the 256-thread
+//        plan_launch).  Which bits pay was measured per workgroup size (same box, alternating runs): the 256-thread
 //        variants gain from both (2,048 walkers 63.3 -> 60.4 us), the 512-thread headline variant gains from the chi^2
 //        pass's (14.63 -> 14.36 us per step) and LOSES with the blend's (14.67 -> 14.96: the loads' order changed); the
 //        two-per-CU and the linked 512-thread variants likewise (config 4's share 26.2 -> 25.8 us with bit 1, 26.4 with both).
 // GIVEN = the model values are not blended here: the in-path broadening kernels (inpath_kernels.h) have left them in
 //        P.given[walker][pixel]; everything else -- recipe (for the walker's status, its prior and band terms), fit sums,
 //        median, chi^2 pass -- is this kernel's.  One variant: 512 threads, quad trips.
-template <int NS, int U, int MAXT, bool GM = false, bool SH = false, bool PF = false, bool LK = false, bool R32 = false, int FULL = 0,
+template <int NS, int MAXT, bool GM = false, bool SH = false, bool PF = false, bool LK = false, bool R32 = false, int FULL = 0,
           bool GIVEN = false>
 // (second launch bound = waves per SIMD the register allocation must leave room for: k workgroups of T threads per
 // CU <=> k T / 256.  256 threads: three per CU = 168 VGPRs; 512 threads sharing a CU: two per CU = four waves per
@@ -374,7 +373,8 @@ logprob_kernel(const double *theta, const unsigned char *__restrict__ rblk, int 
     const int lane = tid & 63, wave = tid >> 6;
     constexpr int nw = B >> 6;
     const int npix = (int)P.npix;
-    static_assert(U == 2 && (MAXT == 256 || MAXT == 512), "one two-pixel element per lane and trip; 256 or 512 threads");
+    static_assert(MAXT == 256 || MAXT == 512, "256 or 512 threads");
+    constexpr int U = 2;  // pixels per lane and trip: the two pixels of one table element (below)
     const int ne = (int)P.npair;  // table elements (pixel pairs), a multiple of 256
     // PF: u and data flux in LDS behind the model vector, in the tables' own pair layout (16-byte aligned)
     double2 *const lds_u2 = PF ? reinterpret_cast<double2 *>(reinterpret_cast<double *>(dyn_lds) + ((npix + 1) & ~1)) : nullptr;

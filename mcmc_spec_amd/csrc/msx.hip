@@ -79,9 +79,6 @@ struct msx_ctx {
     bool problem_staged = false;
     DevProblem P;
     std::vector<void *> prob_allocs;
-    // scratch for host-pointer entry points
-    double *d_theta = nullptr, *d_logp = nullptr;
-    int32_t *d_status = nullptr;  // points into d_logp's allocation
     void *h_pin = nullptr;        // pinned host staging for the host-pointer entry points
     int64_t cap_walkers = 0;
     double *d_misc = nullptr;  // composite args / desc / small outputs
@@ -93,12 +90,6 @@ struct msx_ctx {
     int max_dyn_lds = 0;
     bool pf_ok = false;   // the LDS-staged-statics variants fit (msx_stage_problem)
     bool pf256_ok = false; // ... the 256-thread two-per-CU one (two workgroups of it in a CU's LDS)
-    bool use_pf = true;   // MSX_NO_PF=1 in the environment turns them off (A/B measurements)
-    bool use_full = true; // MSX_NO_FULL=1: never the FULL (no-clamp) variants of the fused kernel
-    int q256 = -1;           // 256-thread launches: the two-per-CU quad-trip variant always (1) / never (0) / up to two walkers per CU (-1); MSX_Q256
-    bool force_sh2 = false;  // MSX_NO_SH2=0: binaries take the <= 128-VGPR variant even with a CU to themselves (A/B measurements)
-    bool zero_copy = true;   // host-pointer entry point without copy commands; MSX_ZERO_COPY=0 restores them
-    int64_t pad_lds = 0;     // MSX_PAD_LDS=bytes: extra dynamic LDS per workgroup (occupancy experiments only)
     bool model_in_global = false;
     // RCCL all-gather of log-probabilities: communicator + its own stream + per-slot events
     void *rccl_comm = nullptr;
@@ -349,16 +340,6 @@ DevProblem problem_at(const DevProblem &P0, int64_t off, int mode, int ndim) {
     return P;
 }
 
-// a 512-thread workgroup of a launch of n walkers has its CU to itself (long spectra: one per CU anyway)
-bool owns_cu(const msx_ctx *c, int64_t n) {
-    return n <= c->prop.multiProcessorCount || sizeof(double) * (size_t)c->P.npix > 70 * 1024;
-}
-// ... and takes the variant that keeps u and the data flux in LDS for the chi^2 pass (PF)
-bool takes_pf(const msx_ctx *c, int64_t n) {
-    return !c->model_in_global && !(c->P.nspec == 2 && c->force_sh2 && sizeof(double) * (size_t)c->P.npix <= 70 * 1024) &&
-           owns_cu(c, n) && c->pf_ok && c->use_pf;
-}
-
 // ---- the variants of logprob_kernel, as a TABLE: the launcher, msx_launch_info (what bench.py prints as the roofline's
 // kernel) and the dynamic-LDS limits all read this one list -- nobody mirrors the choice -------------------------------
 struct Variant {
@@ -366,147 +347,102 @@ struct Variant {
     int ns, threads;
     bool gm, sh, pf, lk, r32;
     int full;  // FULL bits of the variant (logprob_kernel.h): 1 blend, 2 chi^2 pass
+    bool given;  // model values given (in-path broadening)
     const char *what;
-    bool given = false;  // model values given (in-path broadening): the one such entry at the table's end
 };
-#define MSX_V(NS_, T_, GM_, SH_, PF_, LK_, WHAT_) \
-    {(const void *)logprob_kernel<NS_, 2, T_, GM_, SH_, PF_, LK_>, NS_, T_, GM_, SH_, PF_, LK_, false, 0, WHAT_}
-#define MSX_V32(T_, SH_, PF_, WHAT_) \
-    {(const void *)logprob_kernel<2, 2, T_, false, SH_, PF_, false, true>, 2, T_, false, SH_, PF_, false, true, 0, WHAT_}
-#define MSX_VF(T_, SH_, PF_, F_, WHAT_) \
-    {(const void *)logprob_kernel<2, 2, T_, false, SH_, PF_, false, false, F_>, 2, T_, false, SH_, PF_, false, false, F_, WHAT_}
-constexpr int kFull256 = 3;  // (measured against 1 and 2 as well: profiles/r4_ab_full.txt)
+template <int NS, int T, bool GM, bool SH, bool PF, bool LK, bool R32 = false, int FULL = 0, bool GIVEN = false>
+Variant variant(const char *what) {
+    return {(const void *)logprob_kernel<NS, T, GM, SH, PF, LK, R32, FULL, GIVEN>, NS, T, GM, SH, PF, LK, R32, FULL, GIVEN, what};
+}
 const Variant kVariants[] = {
-    MSX_V(2, 256, false, false, false, false, "three workgroups per CU"),
-    MSX_V(2, 256, false, true, false, false, "two per CU, four pixels per lane and trip"),
-    MSX_V(2, 256, false, true, true, false, "two per CU, u / flux staged in LDS during the recipe, four pixels per lane and trip"),
-    MSX_V(2, 512, false, false, false, false, "one workgroup per CU, four pixels per lane and trip"),
-    MSX_V(2, 512, false, true, false, false, "<= 128 VGPRs: two workgroups fit a CU; rows one star at a time"),
-    MSX_V(2, 512, false, false, true, false, "one workgroup per CU, u / flux staged in LDS during the recipe, four pixels per lane and trip"),
-    MSX_V(3, 256, false, false, false, false, "three workgroups per CU"),
-    MSX_V(3, 512, false, false, false, false, "one workgroup per CU, four pixels per lane and trip"),
-    MSX_V(3, 512, false, false, true, false, "one workgroup per CU, u / flux staged in LDS during the recipe, four pixels per lane and trip"),
-    MSX_V(2, 512, false, false, false, true, "one workgroup per walker and 8192-pixel segment; partial sums and histogram counters exchanged inside the launch; the segment's data flux staged in LDS; four pixels per lane and trip"),
-    MSX_V(3, 512, false, false, false, true, "one workgroup per walker and 8192-pixel segment; partial sums and histogram counters exchanged inside the launch; the segment's data flux staged in LDS; four pixels per lane and trip"),
-    MSX_V(2, 512, true, false, false, false, "model vector in global memory (spectra beyond the LDS), sub-batched"),
-    MSX_V(3, 512, true, false, false, false, "model vector in global memory (spectra beyond the LDS), sub-batched"),
+    //     NS  threads GM     SH     PF     LK     R32    FULL
+    variant<2, 256, false, false, false, false>("three workgroups per CU"),
+    variant<2, 256, false, true, false, false>("two per CU, four pixels per lane and trip"),
+    variant<2, 256, false, true, true, false>("two per CU, u / flux staged in LDS during the recipe, four pixels per lane and trip"),
+    variant<2, 512, false, false, false, false>("one workgroup per CU, four pixels per lane and trip"),
+    variant<2, 512, false, true, false, false>("<= 128 VGPRs: two workgroups fit a CU; rows one star at a time"),
+    variant<2, 512, false, false, true, false>("one workgroup per CU, u / flux staged in LDS during the recipe, four pixels per lane and trip"),
+    variant<3, 256, false, false, false, false>("three workgroups per CU"),
+    variant<3, 512, false, false, false, false>("one workgroup per CU, four pixels per lane and trip"),
+    variant<3, 512, false, false, true, false>("one workgroup per CU, u / flux staged in LDS during the recipe, four pixels per lane and trip"),
+    variant<2, 512, false, false, false, true>("one workgroup per walker and 8192-pixel segment; partial sums and histogram counters exchanged inside the launch; the segment's data flux staged in LDS; four pixels per lane and trip"),
+    variant<3, 512, false, false, false, true>("one workgroup per walker and 8192-pixel segment; partial sums and histogram counters exchanged inside the launch; the segment's data flux staged in LDS; four pixels per lane and trip"),
+    variant<2, 512, true, false, false, false>("model vector in global memory (spectra beyond the LDS), sub-batched"),
+    variant<3, 512, true, false, false, false>("model vector in global memory (spectra beyond the LDS), sub-batched"),
     // the fused binary variants once more over the FLOAT32 copy of the R table (msx_set_grid_storage(MSX_STORE_F32))
-    MSX_V32(256, false, false, "three workgroups per CU; R table stored in float32"),
-    MSX_V32(256, true, false, "two per CU, four pixels per lane and trip; R table stored in float32"),
-    MSX_V32(256, true, true, "two per CU, u / flux staged in LDS during the recipe, four pixels per lane and trip; R table stored in float32"),
-    MSX_V32(512, false, false, "one workgroup per CU, four pixels per lane and trip; R table stored in float32"),
-    MSX_V32(512, true, false, "<= 128 VGPRs: two workgroups fit a CU; rows one star at a time; R table stored in float32"),
-    MSX_V32(512, false, true, "one workgroup per CU, u / flux staged in LDS during the recipe, four pixels per lane and trip; R table stored in float32"),
+    variant<2, 256, false, false, false, false, true>("three workgroups per CU; R table stored in float32"),
+    variant<2, 256, false, true, false, false, true>("two per CU, four pixels per lane and trip; R table stored in float32"),
+    variant<2, 256, false, true, true, false, true>("two per CU, u / flux staged in LDS during the recipe, four pixels per lane and trip; R table stored in float32"),
+    variant<2, 512, false, false, false, false, true>("one workgroup per CU, four pixels per lane and trip; R table stored in float32"),
+    variant<2, 512, false, true, false, false, true>("<= 128 VGPRs: two workgroups fit a CU; rows one star at a time; R table stored in float32"),
+    variant<2, 512, false, false, true, false, true>("one workgroup per CU, u / flux staged in LDS during the recipe, four pixels per lane and trip; R table stored in float32"),
     // the binary variants once more for spectra that fill their trips exactly (FULL: no clamps, no validity selects; bit 0
     // in the blend, bit 1 in the chi^2 pass).  Same box, general / FULL, us per batch of 4096 px -- 256 threads, both bits:
     // 512 walkers 24.2 / 23.1, 1,024: 39.5 / 37.8, 2,048: 63.3 / 60.4, 2,304: 68.9 / 66.7.  512 threads, one workgroup per
     // CU (the 256-walker headline), per step: both bits 14.35 -> 14.55 (slower), the blend's alone 14.67 -> 14.96 (slower:
     // without the clamps the scheduler orders the trip's loads differently), the chi^2 pass's alone 14.63 -> 14.36.
-    MSX_VF(256, false, false, kFull256, "three workgroups per CU; whole trips, no clamps"),
-    MSX_VF(256, true, false, kFull256, "two per CU, four pixels per lane and trip; whole trips, no clamps"),
-    MSX_VF(256, true, true, kFull256, "two per CU, u / flux staged in LDS during the recipe, four pixels per lane and trip; whole trips, no clamps"),
-    MSX_VF(512, false, true, 2, "one workgroup per CU, u / flux staged in LDS during the recipe, four pixels per lane and trip; whole trips, no clamps in the chi^2 pass"),
-    MSX_VF(512, true, false, 2, "<= 128 VGPRs: two workgroups fit a CU; rows one star at a time; whole trips, no clamps in the chi^2 pass"),
-    {(const void *)logprob_kernel<2, 2, 512, false, false, true, false, true, 2>, 2, 512, false, false, true, false, true, 2,
-     "float32-stored grid table R; one workgroup per CU, u / flux staged in LDS; whole trips, no clamps in the chi^2 pass"},
+    // (The 256-thread bits measured against 1 and 2 as well: profiles/r4_ab_full.txt.)
+    variant<2, 256, false, false, false, false, false, 3>("three workgroups per CU; whole trips, no clamps"),
+    variant<2, 256, false, true, false, false, false, 3>("two per CU, four pixels per lane and trip; whole trips, no clamps"),
+    variant<2, 256, false, true, true, false, false, 3>("two per CU, u / flux staged in LDS during the recipe, four pixels per lane and trip; whole trips, no clamps"),
+    variant<2, 512, false, false, true, false, false, 2>("one workgroup per CU, u / flux staged in LDS during the recipe, four pixels per lane and trip; whole trips, no clamps in the chi^2 pass"),
+    variant<2, 512, false, true, false, false, false, 2>("<= 128 VGPRs: two workgroups fit a CU; rows one star at a time; whole trips, no clamps in the chi^2 pass"),
+    variant<2, 512, false, false, true, false, true, 2>("float32-stored grid table R; one workgroup per CU, u / flux staged in LDS; whole trips, no clamps in the chi^2 pass"),
     // the linked form for whole-trip segments: no clamps in the segment's chi^2 pass and candidates' gather
-    {(const void *)logprob_kernel<2, 2, 512, false, false, false, true, false, 2>, 2, 512, false, false, false, true, false, 2,
-     "linked: one workgroup per walker and 8192-pixel segment; whole trips, no clamps in the chi^2 pass"},
+    variant<2, 512, false, false, false, true, false, 2>("linked: one workgroup per walker and 8192-pixel segment; whole trips, no clamps in the chi^2 pass"),
     // in-path broadening (inpath_kernels.h): the model values are given, the blend is compiled out
-    {(const void *)logprob_kernel<2, 2, 512, false, false, false, false, false, 0, true>, 2, 512, false, false, false, false, false, 0,
-     "model values given by the in-path broadening kernels; four pixels per lane and trip", true},
+    variant<2, 512, false, false, false, false, false, 0, true>("model values given by the in-path broadening kernels; four pixels per lane and trip"),
 };
-#undef MSX_V
-#undef MSX_V32
-#undef MSX_VF
-const Variant *find_variant(int ns, int threads, bool gm, bool sh, bool pf, bool lk, bool r32 = false, int full = 0) {
-    for (const Variant &v : kVariants)
-        if (!v.given && v.ns == ns && v.threads == threads && v.gm == gm && v.sh == sh && v.pf == pf && v.lk == lk && v.r32 == r32 && v.full == full) return &v;
-    return nullptr;
-}
-const Variant *given_variant() {
-    for (const Variant &v : kVariants)
-        if (v.given) return &v;
-    return nullptr;
-}
-struct VariantChoice {
-    const Variant *v;
-    size_t dyn_lds;
-};
-// Which variant a launch of n walkers with workgroups of B threads takes (LK: the linked form, one workgroup per walker
-// and segment; else the fused kernel in the variant the table in pick_block() names), and its dynamic LDS.
-VariantChoice choose_variant(const msx_ctx *c, const DevProblem &P, int64_t n, int B, bool shared512, bool LK) {
-    if (P.given) return {given_variant(), sizeof(double) * (size_t)P.npix + (size_t)c->pad_lds};  // (in-path form: launch_inpath)
-    // dynamic LDS: the model vector (linked: one segment of it, and the segment's data flux behind it)
-    const size_t lds = LK ? sizeof(double) * (size_t)(2 * kSegElems) + sizeof(double2) * (size_t)kSegElems
-                          : sizeof(double) * (size_t)P.npix + (size_t)c->pad_lds;
-    // PF adds u and the data flux in the tables' pair layout
-    const size_t lds_pf = sizeof(double) * (size_t)((P.npix + 1) & ~1ll) + 2 * sizeof(double2) * (size_t)P.npair;
-    const int ns = P.nspec == 2 ? 2 : 3;
-    if (LK) {
-        const bool full_lk = ns == 2 && c->use_full && P.npix == 2 * P.npair && P.npair % 1024 == 0;
-        return {find_variant(ns, 512, false, false, false, true, false, full_lk ? 2 : 0), lds};
-    }
-    // spectra longer than the LDS: the model vector lives in the global scratch (the kernel writes it there itself)
-    if (c->model_in_global) return {find_variant(ns, 512, true, false, false, false), 0};
-    // pixel statics staged in LDS (PF): 512-thread workgroups that own their CU and whose 3 npix doubles fit
-    const bool own_cu = owns_cu(c, n);
-    // binaries between one and two walkers per CU: the <= 128-VGPR variant, two workgroups per CU.  With a CU to
-    // itself a workgroup takes the quad-walking variants (pixel statics staged in LDS when they fit): 256 walkers x
-    // 4096 px 16.7-16.9 us against 17.0-17.1 for the <= 128-VGPR variant; MSX_NO_SH2=0 in the environment forces the latter
-    const bool sh2 = B == 512 && P.nspec == 2 && lds <= 70 * 1024 && c->force_sh2;
-    const bool pf = B == 512 && !shared512 && !sh2 && takes_pf(c, n);
-    const bool sh = B == 512 && !pf && (sh2 || shared512 || !own_cu);
-    const bool r32 = c->store_f32;  // (msx_stage_problem has checked that the problem has such variants: fused binaries)
-    if (ns == 2 && r32) {
-        const bool q256 = c->q256 > 0 || (c->q256 < 0 && n <= 2 * (int64_t)c->prop.multiProcessorCount);
-        if (B == 256 && q256 && c->pf256_ok && c->use_pf) return {find_variant(2, 256, false, true, true, false, true), lds_pf};
-        if (B == 256 && q256) return {find_variant(2, 256, false, true, false, false, true), lds};
-        if (B == 256) return {find_variant(2, 256, false, false, false, false, true), lds};
-        if (pf && c->use_full && P.npix == 2 * P.npair && P.npair % 1024 == 0)
-            return {find_variant(2, 512, false, false, true, false, true, 2), lds_pf};
-        if (pf) return {find_variant(2, 512, false, false, true, false, true), lds_pf};
-        if (sh) return {find_variant(2, 512, false, true, false, false, true), lds};
-        return {find_variant(2, 512, false, false, false, false, true), lds};
-    }
-    // FULL: no pad pixels and whole trips (a trip of the 256-thread variants is 512 elements = 1024 pixels): the variants
-    // without clamps (MSX_NO_FULL=1 in the environment keeps the general ones: A/B measurements)
-    const bool full = ns == 2 && B == 256 && c->use_full && P.npix == 2 * P.npair && P.npair % 512 == 0;
-    if (full) {
-        const bool q256 = c->q256 > 0 || (c->q256 < 0 && n <= 2 * (int64_t)c->prop.multiProcessorCount);
-        if (q256 && c->pf256_ok && c->use_pf) return {find_variant(2, 256, false, true, true, false, false, kFull256), lds_pf};
-        if (q256) return {find_variant(2, 256, false, true, false, false, false, kFull256), lds};
-        return {find_variant(2, 256, false, false, false, false, false, kFull256), lds};
-    }
-    if (ns == 2 && B == 512 && pf && c->use_full && P.npix == 2 * P.npair && P.npair % 1024 == 0)
-        return {find_variant(2, 512, false, false, true, false, false, 2), lds_pf};
-    if (ns == 2 && B == 512 && sh && c->use_full && P.npix == 2 * P.npair && P.npair % 1024 == 0)
-        return {find_variant(2, 512, false, true, false, false, false, 2), lds};
-    if (ns == 2) {
-        // 256 threads, at most two walkers per CU (config 5's 512 x 1194 px): the variant compiled for two workgroups per
-        // CU has the registers for quad trips (16.0 against 16.3 us); beyond, three per CU matter more (MSX_Q256=1 / 0 forces)
-        const bool q256 = c->q256 > 0 || (c->q256 < 0 && n <= 2 * (int64_t)c->prop.multiProcessorCount);
-        // (... with u and the data flux staged in LDS when two such workgroups still fit a CU)
-        if (B == 256 && q256 && c->pf256_ok && c->use_pf) return {find_variant(2, 256, false, true, true, false), lds_pf};
-        if (B == 256 && q256) return {find_variant(2, 256, false, true, false, false), lds};
-        if (B == 256) return {find_variant(2, 256, false, false, false, false), lds};
-        if (pf) return {find_variant(2, 512, false, false, true, false), lds_pf};
-        if (sh) return {find_variant(2, 512, false, true, false, false), lds};   // two workgroups per CU
-        return {find_variant(2, 512, false, false, false, false), lds};
-    }
-    // triples: twelve corners do not fit the shared variant's 128 VGPRs -- it is the plain one
-    if (B == 256) return {find_variant(3, 256, false, false, false, false), lds};
-    if (pf) return {find_variant(3, 512, false, false, true, false), lds_pf};
-    return {find_variant(3, 512, false, false, false, false), lds};
-}
 
-// One launch of the chosen variant over A.n walkers.
-template <bool LK>
-int launch_logprob(msx_ctx *c, const DevProblem &P, const LaunchArgs &A, int B, bool shared512) {
-    const VariantChoice ch = choose_variant(c, P, A.n, B, shared512, LK);
-    if (!ch.v) return fail(c, MSX_ERR_STATE, "no kernel variant for this launch");
-    // (linked: block = (walker / 8) * 8 segments + segment * 8 + walker % 8, see the kernel)
-    const dim3 g((unsigned)(LK ? ((A.n + 7) & ~7ll) * c->nseg : A.n));
+// The pair kernel (pair_kernel.h): 512 threads, two workgroups per CU at <= 128 VGPRs: 16 waves per CU (the 256-thread
+// variants -- two per CU at 256 VGPRs, 8 waves -- measured 411.8 us against 344.8 at 16,384 walkers and are not built);
+// NT element trips per lane, the smallest that covers the spectrum (2 / 4 = up to 2048 / 4096 pixels).  Always the
+// variant that loads the extinction terms: a problem staged without extinction -- every walker at redc = 0 -- takes the
+// unreddened values from it all the same and pays for the H rows; the variant without them spilled registers at 4096
+// pixels and is not built.  FULL: the spectrum fills the variant exactly -- no clamps, no validity selects.
+struct PairVariant {
+    void (*fn)(const double *, const unsigned char *, int, int, int64_t, double, double, const int32_t *, DevProblem, double *, int32_t *);
+    int nt;
+    bool full;
+};
+const PairVariant kPairVariants[] = {
+    {logprob_pair_kernel<512, 2, true>, 2, false},
+    {logprob_pair_kernel<512, 2, true, true>, 2, true},
+    {logprob_pair_kernel<512, 4, true>, 4, false},
+    {logprob_pair_kernel<512, 4, true, true>, 4, true},
+};
+
+// The entry of kVariants with `want`'s shape (ns, threads, gm, sh, pf, lk, r32, given); its FULL one if it has one and
+// the spectrum is whole trips of it (`whole`).  nullptr: the table has no entry of that shape.
+const Variant *find_variant(const Variant &want, bool whole) {
+    const Variant *hit = nullptr;
+    for (const Variant &v : kVariants)
+        if (v.ns == want.ns && v.threads == want.threads && v.gm == want.gm && v.sh == want.sh && v.pf == want.pf &&
+            v.lk == want.lk && v.r32 == want.r32 && v.given == want.given && (v.full == 0 || whole) && (!hit || v.full != 0))
+            hit = &v;
+    return hit;
+}
+// no pad pixels, and npair a whole number of trips of `trip` elements
+bool whole_trips(const DevProblem &P, int64_t trip) { return P.npix == 2 * P.npair && P.npair % trip == 0; }
+
+// THE launch decision, for the launcher (per sub-batch), msx_launch_info and msx_bytes_per_eval alike: how a launch of n
+// walkers in form f with workgroups of block_threads (0: automatic; shared512: MSX_BLOCK_512_SHARED) runs.
+struct LaunchPlan {
+    int64_t rows = 0;  // walkers per sub-batch of the form
+    int64_t m = 0;     // walkers of the first sub-batch: min(n, rows)
+    int block = 0;     // the workgroup size asked for (the variant's own may differ: linked, GM, in-path take 512)
+    const Variant *v = nullptr;       // the logprob_kernel variant (fused, linked, in-path) ...
+    const PairVariant *pv = nullptr;  // ... or the pair kernel's
+    const void *fn = nullptr;
+    int threads = 0;
+    size_t dyn_lds = 0;
+    int64_t grid = 0;
+    int64_t bytes = 0;  // requested from the memory system per walker (requested_bytes_of)
+};
+
+
+// One launch of the planned logprob_kernel variant over A.n = pl.m walkers.
+int launch_logprob(msx_ctx *c, const DevProblem &P, const LaunchArgs &A, const LaunchPlan &pl) {
     // the kernel's arguments, in its own order (the leading 14 dwords arrive preloaded in SGPRs: logprob_kernel)
     const double *a_theta = P.smp_on ? (const double *)P.smp_coords : A.theta;
     const unsigned char *a_rblk = (const unsigned char *)c->d_recipe_block;
@@ -518,13 +454,13 @@ int launch_logprob(msx_ctx *c, const DevProblem &P, const LaunchArgs &A, int B, 
     double *a_logp = A.logp;
     int32_t *a_status = A.status;
     void *args[] = {&a_theta, &a_rblk, &a_niso_nt, &a_word, &a_n, &a_tmin, &a_tmax, &a_rec, &a_P, &a_logp, &a_status};
-    HIP_TRY(c, hipLaunchKernel(ch.v->fn, g, dim3((unsigned)ch.v->threads), args, ch.dyn_lds, A.s));
+    HIP_TRY(c, hipLaunchKernel(pl.fn, dim3((unsigned)pl.grid), dim3((unsigned)pl.threads), args, pl.dyn_lds, A.s));
     return MSX_OK;
 }
 
 // The in-path broadening form over A.n <= inp_rows walkers (inpath_kernels.h): recipe -> composite of the raw window rows,
 // convolved -> edge patches, reddening, resample -> logprob_kernel<GIVEN>.
-int launch_inpath(msx_ctx *c, const DevProblem &P, const LaunchArgs &A) {
+int launch_inpath(msx_ctx *c, const DevProblem &P, const LaunchArgs &A, const LaunchPlan &pl) {
     const int64_t m = A.n, nwin = c->raw_n;
     hipLaunchKernelGGL(inpath_recipe_kernel, dim3((unsigned)((m + kPlanThreads - 1) / kPlanThreads)), dim3(kPlanThreads), 0, A.s, A.theta,
                        (const unsigned char *)c->d_recipe_block, A.niso_nt, A.ng_mode_fast, m, P.tmin, P.tmax, c->d_inp_rec, P);
@@ -541,7 +477,7 @@ int launch_inpath(msx_ctx *c, const DevProblem &P, const LaunchArgs &A) {
     DevProblem Pg = P;
     Pg.given = c->d_inp_given;
     Pg.given_stride = c->inp_gstride;
-    return launch_logprob<false>(c, Pg, A, 512, false);
+    return launch_logprob(c, Pg, A, pl);
 }
 
 // Does MSX_PATH_AUTO take the linked form for n walkers (of a problem and mode that have one)?  While every workgroup
@@ -621,9 +557,98 @@ FormChoice decide_form(msx_ctx *c, int64_t n, int mode, bool peek) {
     return f;
 }
 
-// The pair form over A.n walkers (pair_kernel.h): the variant compiled for the smallest trip count that covers the
-// spectrum (2 / 4 element trips per lane = up to 2048 / 4096 pixels).
-int launch_pair(msx_ctx *c, const DevProblem &P, const LaunchArgs &A) {
+// bytes the form / variant a launch takes requests from the memory system, per walker
+int64_t requested_bytes_of(const msx_ctx *c, const FormChoice &f, const Variant *v) {
+    const int64_t npix = c->P.npix;
+    // the pair form: two walkers per set of loads -- rows, extinction terms, the fit sweep's data flux / u, the pass's three
+    // vectors -- + the planner's record
+    if (f.pair) return npix * (12 * 8 + 12 + 16 + 24) / 2 + (int64_t)sizeof(PairRec) + 8 * 6 + 12;
+    //   blend: 12-B {R f64, H f32} per corner + {k_lo f64, dk f32} + data flux, u (f64)        per pixel
+    //   chi^2 pass: 1/err^2, and -- unless the variant kept them in LDS (PF) -- u and data flux again
+    const bool pf = v && v->pf;
+    const int64_t per_corner = (v && v->r32) ? 8 : 12;  // {R f64 | f32, H f32}
+    int64_t b = npix * (per_corner * (int64_t)c->P.nspec * 4 + 12 + 16 + (pf ? 8 : 24)) + 8 * (2 * c->P.nspec + 2) + 12;
+    // the linked form: every segment's workgroup reads theta and writes its partials (counters, sums, range; chi^2 sum
+    // and candidates: <= 64 of them as a rule), reads the other segments' partials, and one of them their candidates
+    if (f.linked) {
+        const int64_t S = c->nseg, part = 4 * kSegBins + 64, fin = 16 + 8 * 64;
+        b += (S - 1) * (8 * (2 * c->P.nspec + 2)) + S * (part + fin) + S * (S - 1) * part + (S - 1) * fin;
+    }
+    return b;
+}
+
+LaunchPlan plan_launch(const msx_ctx *c, const FormChoice &f, int64_t n, int block_threads, bool shared512) {
+    const DevProblem &P = c->P;
+    const int64_t cus = c->prop.multiProcessorCount > 0 ? c->prop.multiProcessorCount : 256;
+    LaunchPlan pl;
+    // sub-batches: the in-path form's rows, the pair form's item lists, and the scratch of the linked form and of the
+    // fused kernel's global model vectors (spectra beyond the LDS)
+    pl.rows = f.inpath ? c->inp_rows : f.pair ? c->pair_rows : (f.linked || c->model_in_global) ? c->scratch_rows : n;
+    pl.m = std::min(n, pl.rows);
+    const int64_t m = pl.m;
+    pl.block = (f.linked || f.inpath) ? 512 : block_threads > 0 ? block_threads : pick_block(c, m, P.npix);
+    if (f.pair) {
+        // a trip of the pair kernel is NT x 512 elements
+        const int nt = P.npair <= 2 * 512 ? 2 : 4;
+        for (const PairVariant &pv : kPairVariants)
+            if (pv.nt == nt && pv.full == whole_trips(P, nt * 512)) pl.pv = &pv;
+        pl.fn = pl.pv ? (const void *)pl.pv->fn : nullptr;
+        pl.threads = 512;
+        pl.grid = m;
+        pl.bytes = requested_bytes_of(c, f, nullptr);
+        return pl;
+    }
+    // 1. the shape the launch wants
+    const int B = pl.block;
+    Variant want = {};
+    want.ns = P.nspec == 2 ? 2 : 3;
+    want.threads = 512;
+    want.lk = f.linked;       // one workgroup per walker and segment
+    want.given = f.inpath;    // model values given by the in-path kernels
+    want.gm = !f.linked && !f.inpath && c->model_in_global;  // spectra longer than the LDS: the model vector in global scratch
+    want.r32 = c->store_f32;  // (msx_stage_problem has checked that the problem has such variants: fused binaries)
+    if (!want.lk && !want.given && !want.gm) {
+        want.threads = B;
+        if (B == 256) {
+            // at most two walkers per CU (config 5's 512 x 1194 px): the variant compiled for two workgroups per CU has the
+            // registers for quad trips (16.0 against 16.3 us); beyond, three per CU matter more.  With u and the data flux
+            // staged in LDS (PF) when two such workgroups still fit a CU.
+            want.sh = m <= 2 * cus;
+            want.pf = want.sh && c->pf256_ok;
+        } else {
+            // PF: 512-thread workgroups that own their CU (long spectra: one per CU anyway) and whose 3 npix doubles fit
+            // (256 walkers x 4096 px 16.7-16.9 us against 17.0-17.1 for the <= 128-VGPR variant).  Between one and two
+            // walkers per CU, or when asked for: the <= 128-VGPR variant, two workgroups per CU.
+            const bool own_cu = m <= cus || sizeof(double) * (size_t)P.npix > 70 * 1024;
+            want.pf = !shared512 && own_cu && c->pf_ok;
+            want.sh = !want.pf && (shared512 || !own_cu);
+        }
+    }
+    // 2. its entry of the table -- triples have no SH variant (twelve corners do not fit its 128 VGPRs) and take the plain
+    //    one; the FULL entry when the spectrum is whole trips of 2 x threads elements
+    const bool whole = whole_trips(P, 2 * (int64_t)want.threads);
+    pl.v = find_variant(want, whole);
+    if (!pl.v) {
+        want.sh = want.pf = false;
+        pl.v = find_variant(want, whole);
+    }
+    if (!pl.v) return pl;
+    pl.fn = pl.v->fn;
+    pl.threads = pl.v->threads;
+    // dynamic LDS: the model vector (linked: one segment of it, and the segment's data flux behind it); PF adds u and the
+    // data flux in the tables' pair layout
+    pl.dyn_lds = pl.v->lk ? sizeof(double) * (size_t)(2 * kSegElems) + sizeof(double2) * (size_t)kSegElems
+                 : pl.v->gm ? 0
+                 : pl.v->pf ? sizeof(double) * (size_t)((P.npix + 1) & ~1ll) + 2 * sizeof(double2) * (size_t)P.npair
+                            : sizeof(double) * (size_t)P.npix;
+    // (linked: block = (walker / 8) * 8 segments + segment * 8 + walker % 8, see the kernel)
+    pl.grid = pl.v->lk ? ((m + 7) & ~7ll) * c->nseg : m;
+    pl.bytes = requested_bytes_of(c, f, pl.v);
+    return pl;
+}
+
+// The pair form over A.n walkers (pair_kernel.h), in the planned variant.
+int launch_pair(msx_ctx *c, const DevProblem &P, const LaunchArgs &A, const LaunchPlan &pl) {
     // 1. the planner: every walker's recipe (one thread per walker), final values of the rejected / failed ones, and
     //    who shares a workgroup
     const int32_t *plan = c->d_pair_plan;
@@ -632,26 +657,8 @@ int launch_pair(msx_ctx *c, const DevProblem &P, const LaunchArgs &A) {
                        c->d_pair_plan, c->d_pair_items, c->d_pair_singles, A.logp, A.status, c->h_pair_stats, P);
     HIP_TRY(c, hipGetLastError());
     // 2. the planner's items: singles + pairs <= n workgroups; those beyond the planner's count leave after one load
-    const dim3 g((unsigned)A.n);
-    const int64_t ne = P.npair;
-#define MSX_PAIR_GO2(T_, NT_, RED_)                                                                                   \
-    hipLaunchKernelGGL((logprob_pair_kernel<T_, NT_, RED_>), g, dim3(T_), 0, A.s, A.theta, (const unsigned char *)c->d_recipe_block, \
-                       A.niso_nt, A.ng_mode_fast, (int64_t)A.n, P.tmin, P.tmax, plan, P, A.logp, A.status)
-    // (always the variant that loads the extinction terms: a problem staged without extinction -- every walker at
-    // redc = 0 -- takes the unreddened values from it all the same and pays for the H rows; the variant without them
-    // spilled registers at 4096 pixels and is not built)
-#define MSX_PAIR_GO(T_, NT_) do { if (full) MSX_PAIR_GOF(T_, NT_); else MSX_PAIR_GO2(T_, NT_, true); } while (0)
-#define MSX_PAIR_GOF(T_, NT_)                                                                                                \
-    hipLaunchKernelGGL((logprob_pair_kernel<T_, NT_, true, true>), g, dim3(T_), 0, A.s, A.theta, (const unsigned char *)c->d_recipe_block, \
-                       A.niso_nt, A.ng_mode_fast, (int64_t)A.n, P.tmin, P.tmax, plan, P, A.logp, A.status)
-    // (FULL: the spectrum fills the variant exactly -- no clamps, no validity selects; pair_kernel.h)
-    const bool full = c->use_full && P.npix == 2 * ne && (ne == 2 * 512 || ne == 4 * 512);
-    // (512 threads, two workgroups per CU at <= 128 VGPRs: 16 waves per CU.  The 256-thread variants -- two per CU at
-    // 256 VGPRs, 8 waves -- measured 411.8 us against 344.8 at 16,384 walkers and are not built.)
-    if (ne <= 2 * 512) MSX_PAIR_GO(512, 2); else MSX_PAIR_GO(512, 4);
-#undef MSX_PAIR_GO
-#undef MSX_PAIR_GOF
-#undef MSX_PAIR_GO2
+    hipLaunchKernelGGL(pl.pv->fn, dim3((unsigned)pl.grid), dim3((unsigned)pl.threads), 0, A.s, A.theta, (const unsigned char *)c->d_recipe_block,
+                       A.niso_nt, A.ng_mode_fast, (int64_t)A.n, P.tmin, P.tmax, plan, P, A.logp, A.status);
     HIP_TRY(c, hipGetLastError());
     return MSX_OK;
 }
@@ -697,13 +704,7 @@ int msx_create(int device, msx_ctx **out) {
     msx_ctx *c = new msx_ctx();
     c->device = device;
     memset(&c->P, 0, sizeof(c->P));
-    if (const char *e = getenv("MSX_NO_PF")) c->use_pf = !(e[0] == '1');
-    if (const char *e = getenv("MSX_NO_FULL")) c->use_full = !(e[0] == '1');
-    if (const char *e = getenv("MSX_NO_SH2")) c->force_sh2 = e[0] == '0';
-    if (const char *e = getenv("MSX_Q256")) c->q256 = e[0] == '1' ? 1 : 0;
     if (const char *e = getenv("MSX_LINKED")) c->linked = e[0] == '1' ? 1 : 0;
-    if (const char *e = getenv("MSX_ZERO_COPY")) c->zero_copy = !(e[0] == '0');
-    if (const char *e = getenv("MSX_PAD_LDS")) c->pad_lds = std::max<int64_t>(0, atoll(e));
     *out = c;  // returned even on failure so the caller can read msx_last_error
     HIP_TRY(c, hipSetDevice(device));
     HIP_TRY(c, hipGetDeviceProperties(&c->prop, device));
@@ -718,7 +719,7 @@ void msx_destroy(msx_ctx *c) {
     sampler_free(c);
     free_problem(c);
     free_grid(c);
-    void *ptrs[] = {c->d_theta, c->d_logp, c->d_misc, c->d_spec, c->d_opt_flux, c->d_opt_med, c->d_opt_chain};
+    void *ptrs[] = {c->d_misc, c->d_spec, c->d_opt_flux, c->d_opt_med, c->d_opt_chain};
     if (c->h_pin) (void)hipHostFree(c->h_pin);
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
@@ -1078,15 +1079,18 @@ int msx_stage_problem(msx_ctx *c, const msx_problem *p) {
     c->max_dyn_lds = (int)need_lds;
     c->model_in_global = model_in_global;
     {   // the PF variants' dynamic LDS -- model + u2 + f2 -- must fit beside their static LDS (asked of the functions
-        // themselves: the static part has grown over the rounds, a constant here once let 5,800..6,270 pixels through)
-        hipFuncAttributes a2, a3;
-        HIP_TRY(c, hipFuncGetAttributes(&a2, (const void *)logprob_kernel<2, 2, 512, false, false, true>));
-        HIP_TRY(c, hipFuncGetAttributes(&a3, (const void *)logprob_kernel<3, 2, 512, false, false, true>));
-        const int64_t room = (160 * 1024 - (int64_t)std::max(a2.sharedSizeBytes, a3.sharedSizeBytes)) & ~15ll;
-        c->pf_ok = !model_in_global && (int64_t)sizeof(double) * ((p->npix + 1) & ~1ll) + 32 * npair + (int64_t)c->pad_lds <= room;
-        hipFuncAttributes a256;
-        HIP_TRY(c, hipFuncGetAttributes(&a256, (const void *)logprob_kernel<2, 2, 256, false, true, true>));
-        c->pf256_ok = 2 * ((int64_t)sizeof(double) * ((p->npix + 1) & ~1ll) + 32 * npair + (int64_t)a256.sharedSizeBytes) <= 160 * 1024;
+        // themselves: the static part has grown over the rounds, a constant here once let 5,800..6,270 pixels through).
+        // 512 threads: one workgroup per CU; 256 threads: two of them in a CU's LDS.
+        const int64_t dyn_pf = (int64_t)sizeof(double) * ((p->npix + 1) & ~1ll) + 32 * npair;
+        c->pf_ok = !model_in_global;
+        c->pf256_ok = true;
+        for (const Variant &v : kVariants) {
+            if (!v.pf) continue;
+            hipFuncAttributes at;
+            HIP_TRY(c, hipFuncGetAttributes(&at, v.fn));
+            if (v.threads == 512) c->pf_ok = c->pf_ok && dyn_pf <= ((160 * 1024 - (int64_t)at.sharedSizeBytes) & ~15ll);
+            else c->pf256_ok = c->pf256_ok && 2 * (dyn_pf + (int64_t)at.sharedSizeBytes) <= 160 * 1024;
+        }
     }
     if ((rc = raise_dynamic_lds_limits(c))) return rc;
     c->recipe_fast = P.niso <= 4 * kWave && P.nt <= kWave && P.ng <= 32 && P.nav + 1 <= 2 * kWave;
@@ -1142,14 +1146,12 @@ int msx_stage_problem(msx_ctx *c, const msx_problem *p) {
     // beyond `scratch_rows` walkers is then cut into sub-batches.  Everything else (config 2, 3, 5) allocates nothing.
     c->nseg = (int)((npair + kSegElems - 1) / kSegElems);
     const bool can_link = c->nseg >= 2 && c->nseg <= 8;  // (a workgroup of the linked form holds one segment: up to 65,536 pixels)
-    P.linked_fault = 0;
-    if (const char *e = getenv("MSX_LINKED_FAULT")) P.linked_fault = e[0] == '1';  // (tests: the bounded wait)
+    P.linked_fault = 0;  // (msx_test_hook)
     if (model_in_global || can_link) {
         int64_t budget = 96ll << 20;
         if (const char *e = getenv("MSX_SCRATCH_MB")) budget = std::max<int64_t>(1, atoll(e)) << 20;
         int64_t sb = budget / (int64_t)(sizeof(double) * p->npix);
         sb = std::max<int64_t>(256, std::min<int64_t>(sb, 16384));
-        if (const char *e = getenv("MSX_SCRATCH_ROWS")) sb = std::max<int64_t>(1, atoll(e));
         HIP_TRY(c, hipMalloc((void **)&c->d_model_scratch, sizeof(double) * sb * p->npix));
         c->scratch_rows = sb;
         P.model_scratch = c->d_model_scratch;
@@ -1168,8 +1170,7 @@ int msx_stage_problem(msx_ctx *c, const msx_problem *p) {
     // (vectors the early histogram cannot handle) leases one of kPairSpillRows scratch rows (32 MB at 4096 pixels); the
     // planner's items take 256 bytes per walker of a sub-batch.
     if (p->nspec == 2 && p->npix <= kPairMaxPix && c->recipe_fast && !p->no_spectrum) {
-        int64_t rows = 16384;
-        if (const char *e = getenv("MSX_PAIR_ROWS")) rows = std::max<int64_t>(2, atoll(e));
+        const int64_t rows = 16384;
         HIP_TRY(c, hipMalloc((void **)&c->d_model_scratch, sizeof(double) * kPairSpillRows * p->npix));
         P.model_scratch = c->d_model_scratch;
         // the planner's header and, behind it, the leases of the spill rows
@@ -1280,34 +1281,20 @@ int msx_logprob_batch_dev(msx_ctx *c, int32_t mode, const double *d_theta, int64
     // ---- which form of the path (decide_form) ---------------------------------------------------------------
     const FormChoice form = decide_form(c, n, mode, false);
     if (form.err != MSX_OK) return fail(c, form.err, form.msg);
-    const bool linked = form.linked, pair = form.pair, inpath = form.inpath;
     if (c->smp_overlap_launch) A.ng_mode_fast |= 1 << 20;
     if (c->probe_launch) A.ng_mode_fast |= 1 << 21;
-    c->last_form = inpath ? MSX_FORM_INPATH : pair ? MSX_FORM_PAIR : linked ? MSX_FORM_LINKED : MSX_FORM_FUSED;
-    // sub-batches: the linked form's scratch, and the fused kernel's global model vectors for spectra beyond the LDS,
-    // hold scratch_rows walkers; the pair form's spill rows pair_rows
-    const int64_t step = inpath ? c->inp_rows : pair ? c->pair_rows : (linked || c->model_in_global) ? c->scratch_rows : n;
-    for (int64_t off = 0; off < n; off += step) {
-        const int64_t m = std::min<int64_t>(step, n - off);
+    if (form.linked) A.ng_mode_fast |= c->nseg << 24;
+    c->last_form = form.inpath ? MSX_FORM_INPATH : form.pair ? MSX_FORM_PAIR : form.linked ? MSX_FORM_LINKED : MSX_FORM_FUSED;
+    // ---- how (plan_launch), per sub-batch: the last one, if shorter, is planned for its own walker count ------------
+    LaunchPlan pl = plan_launch(c, form, n, block_threads, shared512);
+    for (int64_t off = 0; off < n; off += pl.rows) {
+        const int64_t m = std::min<int64_t>(pl.rows, n - off);
+        if (m != pl.m) pl = plan_launch(c, form, m, block_threads, shared512);
+        if (!pl.fn) return fail(c, MSX_ERR_STATE, "no kernel variant for this launch");
         A.theta = d_theta + off * ndim; A.logp = d_logp + off; A.status = d_status + off; A.n = m;
         const DevProblem P = problem_at(Pc, off, mode, ndim);
-        const int B = block_threads > 0 ? block_threads : pick_block(c, m, Pc.npix);
-        int rc;
-        if (inpath) {
-            if ((rc = launch_inpath(c, P, A))) return rc;
-            continue;
-        }
-        if (pair) {
-            if ((rc = launch_pair(c, P, A))) return rc;
-            continue;
-        }
-        if (linked) {
-            LaunchArgs A5 = A;
-            A5.ng_mode_fast |= c->nseg << 24;
-            if ((rc = launch_logprob<true>(c, P, A5, 512, false))) return rc;
-        } else {
-            if ((rc = launch_logprob<false>(c, P, A, B, shared512))) return rc;
-        }
+        const int rc = form.inpath ? launch_inpath(c, P, A, pl) : form.pair ? launch_pair(c, P, A, pl) : launch_logprob(c, P, A, pl);
+        if (rc) return rc;
     }
     return MSX_OK;
 }
@@ -1356,17 +1343,9 @@ int msx_logprob_batch(msx_ctx *c, int32_t mode, const double *theta, int64_t n, 
     if (n == 0) return MSX_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     if (n > c->cap_walkers) {
-        if (c->d_theta) (void)hipFree(c->d_theta);
-        if (c->d_logp) (void)hipFree(c->d_logp);
         if (c->h_pin) (void)hipHostFree(c->h_pin);
-        c->d_theta = c->d_logp = nullptr; c->d_status = nullptr; c->h_pin = nullptr; c->cap_walkers = 0;
+        c->h_pin = nullptr; c->cap_walkers = 0;
         const int64_t cap = std::max<int64_t>(n, 1024);
-        HIP_TRY(c, hipMalloc((void **)&c->d_theta, sizeof(double) * cap * MSX_MAX_DIM));
-        // log-probs and statuses share one device allocation
-        HIP_TRY(c, hipMalloc((void **)&c->d_logp, (sizeof(double) + sizeof(int32_t)) * cap));
-        c->d_status = reinterpret_cast<int32_t *>(c->d_logp + cap);
-        // pinned staging: async copies from / to pageable memory are staged synchronously by the runtime and
-        // cost ~15 us each; through pinned memory the whole call is launch + ~12 us
         HIP_TRY(c, hipHostMalloc((void **)&c->h_pin, (sizeof(double) * (MSX_MAX_DIM + 1) + sizeof(int32_t)) * cap, hipHostMallocDefault));
         c->cap_walkers = cap;
     }
@@ -1374,28 +1353,15 @@ int msx_logprob_batch(msx_ctx *c, int32_t mode, const double *theta, int64_t n, 
     double *h_theta = reinterpret_cast<double *>(c->h_pin);
     double *h_out = h_theta + cap * MSX_MAX_DIM;  // [cap] log-probs followed by [cap] int32 statuses
     memcpy(h_theta, theta, sizeof(double) * n * ndim);
-    if (c->zero_copy) {
-        // the kernel reads theta from, and writes its n results to, the pinned (device-mapped, coherent) staging
-        // buffer itself -- 48 + 12 bytes per walker over PCIe instead of two copy commands (41 -> 38 us per
-        // 256-walker call, 122 -> 111 us at 2,048)
-        int32_t *h_st = reinterpret_cast<int32_t *>(h_out + n);
-        int rc = msx_logprob_batch_dev(c, mode, h_theta, n, ndim, h_out, h_st, c->stream, 0);
-        if (rc) return rc;
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        memcpy(logp_out, h_out, sizeof(double) * n);
-        memcpy(status_out, h_st, sizeof(int32_t) * n);
-        note_handover(c, status_out, n);
-        return MSX_OK;
-    }
-    HIP_TRY(c, hipMemcpyAsync(c->d_theta, h_theta, sizeof(double) * n * ndim, hipMemcpyHostToDevice, c->stream));
-    // the statuses go right behind this call's n log-probs, so that one copy brings both back
-    int32_t *d_st = reinterpret_cast<int32_t *>(c->d_logp + n);
-    int rc = msx_logprob_batch_dev(c, mode, c->d_theta, n, ndim, c->d_logp, d_st, c->stream, 0);
+    // the kernel reads theta from, and writes its n results to, the pinned (device-mapped, coherent) staging buffer
+    // itself -- 48 + 12 bytes per walker over PCIe instead of two copy commands (41 -> 38 us per 256-walker call,
+    // 122 -> 111 us at 2,048)
+    int32_t *h_st = reinterpret_cast<int32_t *>(h_out + n);
+    int rc = msx_logprob_batch_dev(c, mode, h_theta, n, ndim, h_out, h_st, c->stream, 0);
     if (rc) return rc;
-    HIP_TRY(c, hipMemcpyAsync(h_out, c->d_logp, (sizeof(double) + sizeof(int32_t)) * n, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     memcpy(logp_out, h_out, sizeof(double) * n);
-    memcpy(status_out, reinterpret_cast<int32_t *>(h_out + n), sizeof(int32_t) * n);
+    memcpy(status_out, h_st, sizeof(int32_t) * n);
     note_handover(c, status_out, n);
     return MSX_OK;
 }
@@ -2167,34 +2133,12 @@ int msx_stream_copy_gbps(msx_ctx *c, int64_t bytes, int32_t iters, double *gbps_
     return MSX_OK;
 }
 
-// bytes the form / variant an automatic launch of n walkers takes requests from the memory system, per walker
-static int64_t requested_bytes_of(msx_ctx *c, int64_t n, const FormChoice &f, const Variant *v) {
-    const int64_t npix = c->P.npix;
-    // the pair form: two walkers per set of loads -- rows, extinction terms, the fit sweep's data flux / u, the pass's three
-    // vectors -- + the planner's record
-    if (f.pair) return npix * (12 * 8 + 12 + 16 + 24) / 2 + (int64_t)sizeof(PairRec) + 8 * 6 + 12;
-    //   blend: 12-B {R f64, H f32} per corner + {k_lo f64, dk f32} + data flux, u (f64)        per pixel
-    //   chi^2 pass: 1/err^2, and -- unless the variant kept them in LDS (PF) -- u and data flux again
-    const bool pf = v && v->pf;
-    const int64_t per_corner = (v && v->r32) ? 8 : 12;  // {R f64 | f32, H f32}
-    int64_t b = npix * (per_corner * (int64_t)c->P.nspec * 4 + 12 + 16 + (pf ? 8 : 24)) + 8 * (2 * c->P.nspec + 2) + 12;
-    // the linked form: every segment's workgroup reads theta and writes its partials (counters, sums, range; chi^2 sum
-    // and candidates: <= 64 of them as a rule), reads the other segments' partials, and one of them their candidates
-    if (f.linked) {
-        const int64_t S = c->nseg, part = 4 * kSegBins + 64, fin = 16 + 8 * 64;
-        b += (S - 1) * (8 * (2 * c->P.nspec + 2)) + S * (part + fin) + S * (S - 1) * part + (S - 1) * fin;
-    }
-    return b;
-}
-
 int msx_bytes_per_eval(msx_ctx *c, int64_t n, int64_t *requested_bytes) {
     if (!c || !requested_bytes || n < 1) return MSX_ERR_INVALID;
     if (!c->problem_staged) return fail(c, MSX_ERR_STATE, "msx_bytes_per_eval: no problem staged");
     const FormChoice f = decide_form(c, n, MSX_MODE_LOGPOST, true);
     if (f.err != MSX_OK) return fail(c, f.err, f.msg);
-    const int64_t m = f.pair ? std::min<int64_t>(n, c->pair_rows) : (f.linked || c->model_in_global) && c->scratch_rows ? std::min<int64_t>(n, c->scratch_rows) : n;
-    const VariantChoice ch = choose_variant(c, c->P, m, f.linked ? 512 : pick_block(c, m, c->P.npix), false, f.linked);
-    *requested_bytes = requested_bytes_of(c, n, f, ch.v);
+    *requested_bytes = plan_launch(c, f, n, 0, false).bytes;
     return MSX_OK;
 }
 
@@ -2209,43 +2153,28 @@ int msx_launch_info(msx_ctx *c, int32_t mode, int64_t n, int32_t block_threads, 
     const FormChoice f = decide_form(c, n, mode, true);
     if (f.err != MSX_OK) return fail(c, f.err, f.msg);
     // (the first sub-batch stands for the launch: sub-batches only differ in their walker count)
-    const int64_t m = f.inpath ? std::min<int64_t>(n, c->inp_rows) : f.pair ? std::min<int64_t>(n, c->pair_rows) : (f.linked || c->model_in_global) && c->scratch_rows ? std::min<int64_t>(n, c->scratch_rows) : n;
+    const LaunchPlan pl = plan_launch(c, f, n, block_threads, shared512);
+    if (!pl.fn) return fail(c, MSX_ERR_STATE, "no kernel variant for this launch");
     std::string nm;
-    const void *fn = nullptr;
-    int64_t threads = 0, dyn = 0, grid = 0;
-    const Variant *v = nullptr;
-    if (f.pair) {
-        const bool nt2 = c->P.npair <= 2 * 512;
-        const bool full = c->use_full && c->P.npix == 2 * c->P.npair && (c->P.npair == 2 * 512 || c->P.npair == 4 * 512);
-        fn = full ? (nt2 ? (const void *)logprob_pair_kernel<512, 2, true, true> : (const void *)logprob_pair_kernel<512, 4, true, true>)
-                  : (nt2 ? (const void *)logprob_pair_kernel<512, 2, true> : (const void *)logprob_pair_kernel<512, 4, true>);
-        nm = std::string("pair_plan_kernel + logprob_pair_kernel<512 threads, ") + (nt2 ? "2" : "4") +
-             " element trips per lane" + (full ? ", FULL" : "") + "> (planner: one thread per walker; two walkers of one grid cell per workgroup, one set of row loads, model values in registers; two workgroups per CU)";
-        threads = 512; grid = m;
+    if (pl.pv) {
+        nm = std::string("pair_plan_kernel + logprob_pair_kernel<512 threads, ") + std::to_string(pl.pv->nt) +
+             " element trips per lane" + (pl.pv->full ? ", FULL" : "") + "> (planner: one thread per walker; two walkers of one grid cell per workgroup, one set of row loads, model values in registers; two workgroups per CU)";
     } else {
-        const int B = (f.linked || f.inpath) ? 512 : block_threads > 0 ? block_threads : pick_block(c, m, c->P.npix);
-        DevProblem Pq = c->P;
-        if (f.inpath) { Pq.given = c->d_inp_given; Pq.given_stride = c->inp_gstride; }
-        const VariantChoice ch = choose_variant(c, Pq, m, B, shared512, f.linked);
-        if (!ch.v) return fail(c, MSX_ERR_STATE, "no kernel variant for this launch");
-        v = ch.v;
-        fn = v->fn;
-        threads = v->threads; dyn = (int64_t)ch.dyn_lds;
-        grid = f.linked ? ((m + 7) & ~7ll) * c->nseg : m;
+        const Variant *v = pl.v;
         nm = std::string("logprob_kernel<NS=") + std::to_string(v->ns) + ", " + std::to_string(v->threads) + " threads" +
              (v->lk ? ", linked" : v->gm ? ", GM" : v->pf && v->sh ? ", SH, PF" : v->pf ? ", PF" : v->sh ? ", SH" : "") + (v->r32 ? ", R32" : "") + (v->full == 3 ? ", FULL" : v->full == 2 ? ", FULL(chi2 pass)" : "") + (v->given ? ", GIVEN" : "") + "> (" + v->what + ")";
         if (f.inpath) nm = "inpath_recipe_kernel + inpath_conv_kernel + inpath_resample_kernel + " + nm;
     }
     hipFuncAttributes at;
-    HIP_TRY(c, hipFuncGetAttributes(&at, fn));
+    HIP_TRY(c, hipFuncGetAttributes(&at, pl.fn));
     out8[0] = f.inpath ? MSX_FORM_INPATH : f.pair ? MSX_FORM_PAIR : f.linked ? MSX_FORM_LINKED : MSX_FORM_FUSED;
-    out8[1] = threads;
+    out8[1] = pl.threads;
     out8[2] = at.numRegs;
     out8[3] = (int64_t)at.sharedSizeBytes;
-    out8[4] = dyn;
-    out8[5] = requested_bytes_of(c, n, f, v);
-    out8[6] = grid;
-    out8[7] = m;
+    out8[4] = (int64_t)pl.dyn_lds;
+    out8[5] = pl.bytes;
+    out8[6] = pl.grid;
+    out8[7] = pl.m;
     if (name && name_len > 0) {
         strncpy(name, nm.c_str(), (size_t)name_len - 1);
         name[name_len - 1] = 0;

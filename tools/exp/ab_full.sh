@@ -1,6 +1,7 @@
 #!/bin/bash
-# Same-box A/B of the FULL (no-clamp) variants of the fused kernel against the general ones: one library, MSX_NO_FULL=1 for A.
-# tools/ab_full.sh <out dir> [reps]
+# Same-box A/B of the FULL (no-clamp) variants of the fused kernel against the general ones: one library built with
+# tools/exp/measurement_switches.patch applied (the product library has no MSX_NO_FULL), MSX_NO_FULL=1 for A.
+# tools/exp/ab_full.sh <out dir> [reps]
 out=$1; reps=${2:-3}
 mkdir -p $out
 for r in $(seq 1 $reps); do

@@ -122,6 +122,16 @@ int msx_broaden(msx_ctx *ctx, const double *wl, const double *flux, int64_t n, d
                 double maxsig, double *out);
 /* every staged node, in place, over grid samples [i0, i0+n): the staging step mft6.py:366-378     */
 int msx_broaden_grid(msx_ctx *ctx, int64_t i0, int64_t n, double resolution, double maxsig);
+/* Rotational broadening (pyasl.rotBroad(wl, flux, limb, vsini), edgeHandling "firstlast"; mft6.py:133-134; DESIGN.md
+ * "Rotational broadening"): v sin i [km/s] > 0, linear limb darkening 0 <= limb <= 1, both finite, else MSX_ERR_RANGE; an
+ * ascending, evenly spaced axis (positive wavelengths).  msx_broaden then msx_rot_broaden is the reference's broaden(). */
+/* one host spectrum: rotation only                                                                  */
+int msx_rot_broaden(msx_ctx *ctx, const double *wl, const double *flux, int64_t n, double vsini, double limb,
+                    double *out);
+/* every staged node, in place, over grid samples [i0, i0+n) (the same window as msx_broaden_grid, after it).  Like
+ * msx_broaden_grid it drops the staged problem; it also releases the raw window kept for MSX_PATH_INPATH (that form
+ * applies the Gaussian only): problems staged afterwards refuse the in-path form until the next msx_broaden_grid. */
+int msx_rot_broaden_grid(msx_ctx *ctx, int64_t i0, int64_t n, double vsini, double limb);
 /* Where the broadening is PLACED: MSX_BROADEN_STAGING (default) -- once per grid node, by msx_broaden_grid: the
  * reference's live path; MSX_BROADEN_IN_PATH -- msx_broaden_grid additionally keeps the window's rows as they were, and
  * the problems staged afterwards get the per-walker form MSX_PATH_INPATH (below) beside all the others.  Takes effect at the

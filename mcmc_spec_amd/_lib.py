@@ -93,6 +93,8 @@ def load():
         'msx_resample_linear': (C.c_int, [vp, _dp, _dp, C.c_int64, _dp, C.c_int64, _dp]),
         'msx_broaden': (C.c_int, [vp, _dp, _dp, C.c_int64, C.c_double, C.c_double, _dp]),
         'msx_broaden_grid': (C.c_int, [vp, C.c_int64, C.c_int64, C.c_double, C.c_double]),
+        'msx_rot_broaden': (C.c_int, [vp, _dp, _dp, C.c_int64, C.c_double, C.c_double, _dp]),
+        'msx_rot_broaden_grid': (C.c_int, [vp, C.c_int64, C.c_int64, C.c_double, C.c_double]),
         'msx_read_node': (C.c_int, [vp, C.c_int32, C.c_int32, _dp]),
         'msx_stage_problem': (C.c_int, [vp, C.POINTER(MsxProblem)]),
         'msx_logprob_batch': (C.c_int, [vp, C.c_int32, _dp, C.c_int64, C.c_int32, _dp, C.POINTER(C.c_int32)]),
@@ -143,7 +145,7 @@ def load():
 
 EXPORTED = ['msx_create', 'msx_destroy', 'msx_last_error', 'msx_device_info', 'msx_stage_grid', 'msx_ccm89_k',
             'msx_resample_linear',
-            'msx_broaden', 'msx_broaden_grid', 'msx_read_node', 'msx_stage_problem', 'msx_logprob_batch',
+            'msx_broaden', 'msx_broaden_grid', 'msx_rot_broaden', 'msx_rot_broaden_grid', 'msx_read_node', 'msx_stage_problem', 'msx_logprob_batch',
             'msx_logprob_batch_dev', 'msx_probe_launch', 'msx_set_path', 'msx_set_grid_storage', 'msx_set_broadening', 'msx_opt_init', 'msx_opt_step', 'msx_sampler_run', 'msx_sampler_begin',
             'msx_sampler_shard', 'msx_sampler_enqueue', 'msx_sampler_enqueue_drawn', 'msx_sampler_draw', 'msx_sampler_collect', 'msx_sampler_end', 'msx_make_composite', 'msx_comm_unique_id', 'msx_comm_init', 'msx_comm_allgather_dev', 'msx_comm_wait_slot',
             'msx_comm_init_loopback', 'msx_sampler_enqueue_group',
@@ -244,6 +246,16 @@ class Context:
 
     def broaden_grid(self, i0, n, resolution, maxsig=5.0):
         self.check(self.lib.msx_broaden_grid(self.h, int(i0), int(n), float(resolution), float(maxsig)))
+
+    def rot_broaden(self, wl, flux, vsini, limb):
+        """pyasl.rotBroad(wl, flux, limb, vsini) (edgeHandling 'firstlast'): rotation only; ValueError on a bad vsini / limb."""
+        wl, flux = as_f64(wl), as_f64(flux)
+        out = np.empty_like(flux)
+        self.check(self.lib.msx_rot_broaden(self.h, dptr(wl), dptr(flux), len(wl), float(vsini), float(limb), dptr(out)))
+        return out
+
+    def rot_broaden_grid(self, i0, n, vsini, limb):
+        self.check(self.lib.msx_rot_broaden_grid(self.h, int(i0), int(n), float(vsini), float(limb)))
 
     def read_node(self, it, ig):
         out = np.empty(self.nwl)

@@ -119,6 +119,7 @@ struct msx_ctx {
     int64_t raw_i0 = 0, raw_n = 0;
     int raw_lx = 0;
     double raw_dx = 0.0, raw_sigma = 0.0;
+    bool grid_rotated = false;      // msx_rot_broaden_grid ran since the last msx_broaden_grid / grid: no raw window (named in INPATH's refusal)
     InpathRec *d_inp_rec = nullptr;
     double *d_inp_tmp = nullptr, *d_inp_given = nullptr;
     const int64_t *d_pix_lo = nullptr;
@@ -242,6 +243,7 @@ void free_grid(msx_ctx *c) {
     c->d_present = nullptr;
     if (c->d_raw_win) (void)hipFree(c->d_raw_win);
     c->d_raw_win = nullptr; c->raw_n = 0;
+    c->grid_rotated = false;
     c->grid_staged = false;
 }
 
@@ -547,6 +549,11 @@ FormChoice decide_form(msx_ctx *c, int64_t n, int mode, bool peek) {
     if (f.pair) f.linked = false;
     // in-path broadening (inpath_kernels.h): never taken by MSX_PATH_AUTO -- the per-node placement is the reference's
     if (c->path == MSX_PATH_INPATH) {
+        if (c->inp_rows <= 0 && c->grid_rotated) {
+            f.err = MSX_ERR_STATE;
+            f.msg = "msx_set_path(INPATH): the grid was rotationally broadened (msx_rot_broaden_grid); the per-walker form applies the Gaussian only and would not match it";
+            return f;
+        }
         if (c->inp_rows <= 0 || !fast || Pc.smp_on || !lp_mode || c->store_f32 || c->probe_launch) {
             f.err = MSX_ERR_STATE;
             f.msg = "msx_set_path(INPATH): needs msx_set_broadening(MSX_BROADEN_IN_PATH) before msx_broaden_grid, a binary whose data pixels lie inside that window, float64 tables, the register-resident recipe and a likelihood / posterior / chi^2 mode";
@@ -678,6 +685,7 @@ hipError_t raise_all() {
     for (const Variant &v : kVariants)
         if (e == hipSuccess && !v.gm) e = raise_one(v.fn);
     if (e == hipSuccess) e = raise_one((const void *)broaden_conv_kernel);
+    if (e == hipSuccess) e = raise_one((const void *)rot_broaden_kernel<true>);
     return e;
 }
 constexpr int kMaxDevices = 64;
@@ -691,6 +699,44 @@ int raise_dynamic_lds_limits(msx_ctx *c) {
     if (done[c->device]) return MSX_OK;
     HIP_TRY(c, raise_all());
     done[c->device] = true;
+    return MSX_OK;
+}
+
+// pyasl.rotBroad's checks and constants for the slice wl[0..n): MSX_ERR_RANGE on a bad v sin i / limb (or an axis the
+// kernel cannot take); vc = vsini / c, binnu = int(floor(vc * max(wl) / dwl)) + 1
+int rot_params(msx_ctx *c, const double *wl, int64_t n, double vsini, double limb, double *vc, int *binnu) {
+    if (!isfinite(vsini) || !isfinite(limb))
+        return fail(c, MSX_ERR_RANGE, "rotational broadening: vsini and limb must be finite");
+    if (vsini <= 0.0) return fail(c, MSX_ERR_RANGE, "rotational broadening: vsini must be positive.");
+    if (limb < 0.0 || limb > 1.0)
+        return fail(c, MSX_ERR_RANGE, "rotational broadening: Linear limb-darkening coefficient, epsilon, should be '0 < epsilon < 1'.");
+    int rc = check_even_spacing(c, wl, n);
+    if (rc) return rc;
+    const double dwl = wl[1] - wl[0];
+    if (!(dwl > 0.0) || !(wl[0] > 0.0))
+        return fail(c, MSX_ERR_RANGE, "rotational broadening: needs an ascending axis of positive wavelengths");
+    *vc = vsini / 299792.458;
+    const double b = floor((*vc * wl[n - 1]) / dwl);
+    if (!(b < (double)kRotMaxBinnu))
+        return fail(c, MSX_ERR_RANGE, "rotational broadening: vsini too large for this axis (more than 2^19 samples of halo)");
+    *binnu = (int)b + 1;
+    return MSX_OK;
+}
+
+// rot_broaden_kernel over `rows` rows of n samples (out of place): the LDS-staged form while the tile's span fits
+int launch_rot(msx_ctx *c, const double *d_in, int64_t in_stride, const double *d_wl, int64_t n, int64_t rows, double dwl,
+               double vc, double eps, int binnu, double *d_out, int64_t out_stride) {
+    int rc = raise_dynamic_lds_limits(c);
+    if (rc) return rc;
+    const dim3 g((unsigned)((n + kRotTile - 1) / kRotTile), (unsigned)((rows + kRotRows - 1) / kRotRows));
+    const size_t lds = rot_lds_bytes(binnu);
+    if (lds <= (size_t)(160 * 1024))
+        hipLaunchKernelGGL(rot_broaden_kernel<true>, g, dim3(kRotTile), lds, c->stream, d_in, in_stride, d_wl, n, rows, dwl, vc,
+                           eps, binnu, d_out, out_stride);
+    else
+        hipLaunchKernelGGL(rot_broaden_kernel<false>, g, dim3(kRotTile), 0, c->stream, d_in, in_stride, d_wl, n, rows, dwl, vc,
+                           eps, binnu, d_out, out_stride);
+    HIP_TRY(c, hipGetLastError());
     return MSX_OK;
 }
 
@@ -880,6 +926,7 @@ int msx_broaden_grid(msx_ctx *c, int64_t i0, int64_t n, double resolution, doubl
     // in-path placement (msx_set_broadening): the window's rows as they are NOW are kept for the per-walker form; the grid
     // is broadened in place all the same, so that every other form -- and the band tables -- see the reference's live path
     if (c->d_raw_win) { (void)hipFree(c->d_raw_win); c->d_raw_win = nullptr; c->raw_n = 0; }
+    c->grid_rotated = false;
     if (c->broaden_placement == MSX_BROADEN_IN_PATH) {
         HIP_TRY(c, hipMalloc((void **)&c->d_raw_win, sizeof(double) * rows * n));
         HIP_TRY(c, hipMemcpy2D(c->d_raw_win, sizeof(double) * n, c->d_grid + i0, sizeof(double) * c->nwl, sizeof(double) * n, (size_t)rows,
@@ -898,6 +945,61 @@ int msx_broaden_grid(msx_ctx *c, int64_t i0, int64_t n, double resolution, doubl
     }
     (void)hipFree(d_tmp);
     // any staged problem was derived from the pre-broadening grid
+    free_problem(c);
+    return rc;
+}
+
+int msx_rot_broaden(msx_ctx *c, const double *wl, const double *flux, int64_t n, double vsini, double limb, double *out) {
+    if (!c || !wl || !flux || !out || n < 2) return fail(c, MSX_ERR_INVALID, "msx_rot_broaden: bad arguments (need n >= 2)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    double vc;
+    int binnu;
+    int rc = rot_params(c, wl, n, vsini, limb, &vc, &binnu);
+    if (rc) return rc;
+    double *d_wl = nullptr, *d_in = nullptr, *d_out = nullptr;
+    hipError_t e = hipMalloc((void **)&d_wl, sizeof(double) * n);
+    if (e == hipSuccess) e = hipMalloc((void **)&d_in, sizeof(double) * n);
+    if (e == hipSuccess) e = hipMalloc((void **)&d_out, sizeof(double) * n);
+    if (e == hipSuccess) e = hipMemcpy(d_wl, wl, sizeof(double) * n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_in, flux, sizeof(double) * n, hipMemcpyHostToDevice);
+    if (e != hipSuccess) rc = fail(c, MSX_ERR_HIP, hipGetErrorString(e));
+    if (rc == MSX_OK) rc = launch_rot(c, d_in, n, d_wl, n, 1, wl[1] - wl[0], vc, limb, binnu, d_out, n);
+    if (rc == MSX_OK) {
+        e = hipStreamSynchronize(c->stream);
+        if (e == hipSuccess) e = hipMemcpy(out, d_out, sizeof(double) * n, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = fail(c, MSX_ERR_HIP, hipGetErrorString(e));
+    }
+    (void)hipFree(d_wl);
+    (void)hipFree(d_in);
+    (void)hipFree(d_out);
+    return rc;
+}
+
+int msx_rot_broaden_grid(msx_ctx *c, int64_t i0, int64_t n, double vsini, double limb) {
+    if (!c) return MSX_ERR_INVALID;
+    if (!c->grid_staged) return fail(c, MSX_ERR_STATE, "msx_rot_broaden_grid: no grid staged");
+    if (i0 < 0 || n < 2 || i0 + n > c->nwl) return fail(c, MSX_ERR_INVALID, "msx_rot_broaden_grid: bad window");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const double *wl = c->h_wl.data() + i0;
+    double vc;
+    int binnu;
+    int rc = rot_params(c, wl, n, vsini, limb, &vc, &binnu);
+    if (rc) return rc;
+    const int64_t rows = (int64_t)c->nt * c->ng;
+    double *d_tmp = nullptr;
+    HIP_TRY(c, hipMalloc((void **)&d_tmp, sizeof(double) * rows * n));
+    rc = launch_rot(c, c->d_grid + i0, c->nwl, c->d_wl + i0, n, rows, wl[1] - wl[0], vc, limb, binnu, d_tmp, n);
+    if (rc == MSX_OK) {
+        hipError_t e = hipMemcpy2DAsync(c->d_grid + i0, sizeof(double) * c->nwl, d_tmp, sizeof(double) * n, sizeof(double) * n,
+                                        (size_t)rows, hipMemcpyDeviceToDevice, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) rc = fail(c, MSX_ERR_HIP, hipGetErrorString(e));
+    }
+    (void)hipFree(d_tmp);
+    // the raw window of the in-path form is the unrotated grid: the per-walker Gaussian would no longer match the grid
+    if (c->d_raw_win) { (void)hipFree(c->d_raw_win); c->d_raw_win = nullptr; c->raw_n = 0; }
+    c->grid_rotated = true;
+    // any staged problem (R/H and band tables) was derived from the unrotated grid
     free_problem(c);
     return rc;
 }

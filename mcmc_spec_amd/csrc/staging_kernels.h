@@ -162,6 +162,88 @@ broaden_conv_kernel(const double *__restrict__ in, int64_t in_stride, double *__
     }
 }
 
+// Rotational broadening (pyasl.rotBroad, edgeHandling="firstlast"; DESIGN.md "Rotational broadening"): each row of the
+// slice wl[0..n) is extended by `binnu` copies of its first / last value at wl[0] - m dwl / wl[n-1] + m dwl, and
+//   out[i] = sum_j f_ext[j] g_j / sum_j g_j,   x_j = (wl[i] - wl_ext[j]) / dlmax,  dlmax = vc wl[i],
+//   g_j = c1 sqrt(1 - x_j^2) + c2 (1 - x_j^2) where |x_j| < 1.
+// The weights depend on the pixel only: a workgroup of kRotTile threads (one per output pixel) computes every g_j once
+// and applies it to kRotRows rows at a time.  STAGED: the tile's span of kRotTile + 2 binnu extended samples -- the
+// wavelengths and the kRotRows rows -- is staged in LDS (rot_lds_bytes); otherwise (a halo too wide for the LDS) the
+// same values are read from global memory through L2.  Rows past `rows` (the last group) are read clamped and not
+// written.  The host checks binnu <= kRotMaxBinnu: |k| <= K + 2 then holds every tap with |x| < 1 (K = dlmax / dwl).
+constexpr int kRotTile = 256;
+constexpr int kRotRows = 8;
+constexpr int kRotMaxBinnu = 1 << 19;
+inline size_t rot_lds_bytes(int binnu) { return sizeof(double) * (size_t)(kRotRows + 1) * (size_t)(kRotTile + 2 * binnu); }
+
+// extended sample je (0 <= je < n + 2 binnu, or past it on the right) of the slice's wavelengths / of one row
+__device__ __forceinline__ double rot_ext_wl(const double *__restrict__ wl, int64_t n, double dwl, int binnu, int64_t je) {
+#pragma clang fp contract(off)
+    // the float64 product m * dwl, then one subtraction / addition (np.arange(binnu) + 1) * dwl: no fused multiply-add
+    if (je < binnu) return wl[0] - (double)(binnu - je) * dwl;
+    if (je >= binnu + n) return wl[n - 1] + (double)(je - binnu - n + 1) * dwl;
+    return wl[je - binnu];
+}
+__device__ __forceinline__ double rot_ext_flux(const double *__restrict__ row, int64_t n, int binnu, int64_t je) {
+    return je < binnu ? row[0] : je >= binnu + n ? row[n - 1] : row[je - binnu];
+}
+
+template <bool STAGED>
+__global__ void __launch_bounds__(kRotTile)
+rot_broaden_kernel(const double *__restrict__ in, int64_t in_stride, const double *__restrict__ wl, int64_t n, int64_t rows,
+                   double dwl, double vc, double eps, int binnu, double *__restrict__ out, int64_t out_stride) {
+#pragma clang fp contract(off)
+    const int tid = threadIdx.x;
+    const int64_t t0 = (int64_t)blockIdx.x * kRotTile;
+    const int64_t r0 = (int64_t)blockIdx.y * kRotRows;
+    const int span = kRotTile + 2 * binnu;  // extended samples t0 .. t0 + span - 1
+    const double *src[kRotRows];
+#pragma unroll
+    for (int b = 0; b < kRotRows; ++b) src[b] = in + (r0 + b < rows ? r0 + b : rows - 1) * in_stride;
+    double *lwl = reinterpret_cast<double *>(dyn_lds);  // [span] wavelengths, then [kRotRows][span] fluxes
+    if (STAGED) {
+        for (int j = tid; j < span; j += kRotTile) {
+            lwl[j] = rot_ext_wl(wl, n, dwl, binnu, t0 + j);
+#pragma unroll
+            for (int b = 0; b < kRotRows; ++b) lwl[(b + 1) * span + j] = rot_ext_flux(src[b], n, binnu, t0 + j);
+        }
+        __syncthreads();
+    }
+    const int64_t i = t0 + tid;
+    if (i >= n) return;
+    const double wli = wl[i];
+    const double dlmax = vc * wli;
+    const double inv = 1.0 / dlmax;
+    const double c1 = 2. * (1. - eps) / (M_PI * dlmax * (1. - eps / 3.));
+    const double c2 = eps / (2. * dlmax * (1. - eps / 3.));
+    const double kf = dlmax / dwl + 2.0;  // taps with |k| > K + 2 lie outside |x| < 1 (spacing checked to 1e-6)
+    const int kmax = kf < (double)binnu ? (int)kf : binnu;
+    double acc[kRotRows];
+#pragma unroll
+    for (int b = 0; b < kRotRows; ++b) acc[b] = 0.0;
+    double sg = 0.0;
+    // extended index of tap k: tid + binnu + k (local to the tile's span)
+    for (int j = tid + binnu - kmax; j <= tid + binnu + kmax; ++j) {
+        const double dl = wli - (STAGED ? lwl[j] : rot_ext_wl(wl, n, dwl, binnu, t0 + j));
+        double x = dl * inv;
+        // near the edge the exact quotient decides the tap and its weight (g is steep there); inside, the reciprocal
+        if (!(fabs(x) < 0.875)) {
+            x = dl / dlmax;
+            if (!(fabs(x) < 1.0)) continue;
+        }
+        const double t = 1. - x * x;
+        const double g = c1 * sqrt(t) + c2 * t;
+        sg += g;
+#pragma unroll
+        for (int b = 0; b < kRotRows; ++b)
+            acc[b] = fma(STAGED ? lwl[(b + 1) * span + j] : rot_ext_flux(src[b], n, binnu, t0 + j), g, acc[b]);
+    }
+    const double rs = 1.0 / sg;
+#pragma unroll
+    for (int b = 0; b < kRotRows; ++b)
+        if (r0 + b < rows) out[(r0 + b) * out_stride + i] = acc[b] * rs;
+}
+
 // f3: linear resample of one tabulated spectrum (x sorted ascending) onto query wavelengths with
 // np.interp / scipy interp1d(kind='linear') arithmetic (mft6.py:369-371): one thread per query.
 __global__ void resample_kernel(const double *__restrict__ xs, const double *__restrict__ ys, int64_t n,

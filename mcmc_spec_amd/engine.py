@@ -50,16 +50,21 @@ class Engine:
         teff, logg, wl, flux, present = staging.parse_specs(specs)
         self.stage_grid(wl, teff, logg, flux, present)
 
-    def broaden_grid_window(self, w_aa, resolution, placement='staging'):
+    def broaden_grid_window(self, w_aa, resolution, placement='staging', vsini=0, limb=0):
         """Broaden every node over the data window ``[min(w), max(w)]`` [A] in place: the staging step
         of ``spec_interpolator`` (mft6.py:366-378).  ``placement='in_path'`` additionally keeps the raw window on the
         device: problems staged afterwards can be evaluated with the broadening applied per walker
-        (``ctx.set_path(_lib.PATH_INPATH)``) beside the default forms."""
+        (``ctx.set_path(_lib.PATH_INPATH)``) beside the default forms.
+
+        ``vsini`` [km/s] / ``limb``: when both are nonzero (the reference's condition, mft6.py:133), the same window is
+        then rotationally broadened (``pyasl.rotBroad``; ValueError on a bad value).  A rotated grid has no in-path form."""
         self.ctx.set_broadening(placement)
         wl = self.grid['wl']
         idx = np.where((wl >= min(w_aa)) & (wl <= max(w_aa)))[0]
         self.ctx.broaden_grid(int(idx[0]), int(idx.size), resolution, 5.0)
         self.tables = None
+        if vsini != 0 and limb != 0:
+            self.ctx.rot_broaden_grid(int(idx[0]), int(idx.size), vsini, limb)
 
     # ---- problem ------------------------------------------------------------------------------------
     def stage_problem(self, data, err, fr, r, ctm, ptm, tmi, tma, matrix, nspec=2, bands=None, av_table=None,

@@ -4,7 +4,7 @@
 Text parsing is host work by nature; every flux operation runs on the GPU: the per-node linear
 resample onto the common 0.2 A grid (``msx_resample_linear``), the upload of the dense grid
 (``msx_stage_grid``) and the Gaussian broadening of the data window of every node in place
-(``msx_broaden_grid``).  The returned object is a ``dict`` with the reference's keys
+(``msx_broaden_grid``; with ``vsini`` / ``limb``, then the rotational broadening, ``msx_rot_broaden_grid``).  The returned object is a ``dict`` with the reference's keys
 (``'{T}, {g}'`` -> float64 array, ``'wl'``) -- so the reference's own code can keep indexing it --
 that also remembers the engine holding the staged copy: ``mcmc_spec_amd.mft6`` reuses it instead
 of uploading the grid again.
@@ -53,11 +53,13 @@ def _node_lists(files, trange, lgrange):
 
 
 def spec_interpolator(w, trange, lgrange, specrange, npix=3, resolution=10000, metal=0, write_file=True,
-                      models='btsettl', grid_dir=GRID_DIR, device=None, cache=None):
+                      models='btsettl', grid_dir=GRID_DIR, device=None, cache=None, vsini=0, limb=0):
     """Read, resample, stage and broaden the model grid.  ``w`` = data window [A] (``[spmin*1e4, spmax*1e4]``
     at mft6.py:3512), ``specrange`` = [specmin, specmax] [A].  Returns ``StagedSpecs``.
 
-    ``cache``: optional ``.npz`` path; reused when the file list, mtimes, ranges and resolution match."""
+    ``cache``: optional ``.npz`` path; reused when the file list, mtimes, ranges, resolution, vsini and limb match.
+    ``vsini`` [km/s], ``limb`` (extensions of the reference's signature): when both are nonzero, the data window of
+    every node is also rotationally broadened after the Gaussian (``broaden(..., vsini, limb)``, mft6.py:133-134)."""
     if models != 'btsettl':
         raise NotImplementedError("only models='btsettl' is on the hot path (SURVEY.md §2)")
     from . import mft6 as _api
@@ -67,7 +69,8 @@ def spec_interpolator(w, trange, lgrange, specrange, npix=3, resolution=10000, m
     t, l = _node_lists(files, trange, lgrange)
     wl = np.arange(min(specrange), max(specrange), 0.2)  # mft6.py:343
     stamp = np.array([os.path.getmtime(f) for f in files] + [min(w), max(w), min(specrange), max(specrange),
-                                                             float(resolution), len(t), len(l)])
+                                                             float(resolution), len(t), len(l), float(vsini),
+                                                             float(limb)])
     eng = Engine(_api._DEVICE if device is None else device)
     teff, logg = sorted(t), sorted(l)
     flux = np.zeros((len(teff), len(logg), len(wl)))
@@ -93,7 +96,7 @@ def spec_interpolator(w, trange, lgrange, specrange, npix=3, resolution=10000, m
                     xs, ys = xs[order], ys[order]
                 flux[it, ig] = eng.ctx.resample_linear(xs, ys, wl)  # mft6.py:369-371
         eng.stage_grid(wl, np.array(teff, float), np.array(logg, float), flux)
-        eng.broaden_grid_window([min(w), max(w)], resolution)  # mft6.py:373-378
+        eng.broaden_grid_window([min(w), max(w)], resolution, vsini=vsini, limb=limb)  # mft6.py:373-378
         for it in range(len(teff)):
             for ig in range(len(logg)):
                 flux[it, ig] = eng.ctx.read_node(it, ig)

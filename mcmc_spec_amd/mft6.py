@@ -250,15 +250,17 @@ def _flat_matrix():
 
 
 def broaden(even_wl, modelspec_interp, res, vsini=0, limb=0, plot=False):
-    """mft6.py:124-152 with ``vsini = limb = 0``: Gaussian instrumental broadening + the two edge patches."""
-    if vsini != 0 and limb != 0:
-        raise NotImplementedError('rotational broadening is dead code in the reference path (vsini = 0)')
+    """mft6.py:124-152 (``plot=False``): Gaussian instrumental broadening + the two edge patches, then, when
+    ``vsini != 0 and limb != 0``, ``pyasl.rotBroad(even_wl, broad, limb, vsini)`` (DESIGN.md "Rotational broadening").
+    Rotation raises ValueError for ``vsini <= 0``, ``limb`` outside [0, 1] (pyasl's checks) and non-finite values."""
     if _GRIDS:
         ctx = next(reversed(_GRIDS.values()))[1].ctx
     else:
         from ._lib import Context
         ctx = Context(_DEVICE)
     out = ctx.broaden(np.asarray(even_wl, float), np.asarray(modelspec_interp, float), res, 5.0)
+    if vsini != 0 and limb != 0:
+        out = ctx.rot_broaden(np.asarray(even_wl, float), out, vsini, limb)
     return np.array(even_wl), out
 
 

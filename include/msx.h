@@ -132,6 +132,20 @@ int msx_rot_broaden(msx_ctx *ctx, const double *wl, const double *flux, int64_t 
  * msx_broaden_grid it drops the staged problem; it also releases the raw window kept for MSX_PATH_INPATH (that form
  * applies the Gaussian only): problems staged afterwards refuse the in-path form until the next msx_broaden_grid. */
 int msx_rot_broaden_grid(msx_ctx *ctx, int64_t i0, int64_t n, double vsini, double limb);
+/* ---- Component grids (DESIGN.md "Component grids"): one v sin i / limb per star.  A component grid holds ncomp copies of
+ * every node row, copy s at rows [s nt ng, (s+1) nt ng); component s of every walker reads copy s.  1 <= ncomp <=
+ * MSX_MAX_SPEC, else MSX_ERR_RANGE; an ordinary grid is ncomp = 1.  msx_broaden_grid / msx_rot_broaden_grid act on every
+ * copy.  Problems staged on a component grid need nspec == ncomp (MSX_ERR_RANGE) and refuse MSX_PATH_INPATH.            */
+/* duplicate the staged rows into ncomp contiguous copies (device to device; drops the staged problem)                   */
+int msx_split_components(msx_ctx *ctx, int32_t ncomp);
+/* msx_stage_grid with flux [ncomp][nt][ng][nwl] (present [nt][ng] is shared by the copies)                               */
+int msx_stage_grid_components(msx_ctx *ctx, const double *wl, int64_t nwl, const double *teff_nodes, int32_t nt,
+                              const double *logg_nodes, int32_t ng, const double *flux, const uint8_t *present,
+                              int32_t ncomp);
+/* msx_rot_broaden_grid on copy comp only (the same checks and errors)                                                   */
+int msx_rot_broaden_grid_component(msx_ctx *ctx, int32_t comp, int64_t i0, int64_t n, double vsini, double limb);
+/* msx_read_node of copy comp                                                                                            */
+int msx_read_node_component(msx_ctx *ctx, int32_t comp, int32_t it, int32_t ig, double *out);
 /* Where the broadening is PLACED: MSX_BROADEN_STAGING (default) -- once per grid node, by msx_broaden_grid: the
  * reference's live path; MSX_BROADEN_IN_PATH -- msx_broaden_grid additionally keeps the window's rows as they were, and
  * the problems staged afterwards get the per-walker form MSX_PATH_INPATH (below) beside all the others.  Takes effect at the

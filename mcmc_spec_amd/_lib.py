@@ -95,6 +95,11 @@ def load():
         'msx_broaden_grid': (C.c_int, [vp, C.c_int64, C.c_int64, C.c_double, C.c_double]),
         'msx_rot_broaden': (C.c_int, [vp, _dp, _dp, C.c_int64, C.c_double, C.c_double, _dp]),
         'msx_rot_broaden_grid': (C.c_int, [vp, C.c_int64, C.c_int64, C.c_double, C.c_double]),
+        'msx_split_components': (C.c_int, [vp, C.c_int32]),
+        'msx_stage_grid_components': (C.c_int, [vp, _dp, C.c_int64, _dp, C.c_int32, _dp, C.c_int32, _dp,
+                                                C.POINTER(C.c_uint8), C.c_int32]),
+        'msx_rot_broaden_grid_component': (C.c_int, [vp, C.c_int32, C.c_int64, C.c_int64, C.c_double, C.c_double]),
+        'msx_read_node_component': (C.c_int, [vp, C.c_int32, C.c_int32, C.c_int32, _dp]),
         'msx_read_node': (C.c_int, [vp, C.c_int32, C.c_int32, _dp]),
         'msx_stage_problem': (C.c_int, [vp, C.POINTER(MsxProblem)]),
         'msx_logprob_batch': (C.c_int, [vp, C.c_int32, _dp, C.c_int64, C.c_int32, _dp, C.POINTER(C.c_int32)]),
@@ -145,7 +150,8 @@ def load():
 
 EXPORTED = ['msx_create', 'msx_destroy', 'msx_last_error', 'msx_device_info', 'msx_stage_grid', 'msx_ccm89_k',
             'msx_resample_linear',
-            'msx_broaden', 'msx_broaden_grid', 'msx_rot_broaden', 'msx_rot_broaden_grid', 'msx_read_node', 'msx_stage_problem', 'msx_logprob_batch',
+            'msx_broaden', 'msx_broaden_grid', 'msx_rot_broaden', 'msx_rot_broaden_grid', 'msx_split_components',
+            'msx_stage_grid_components', 'msx_rot_broaden_grid_component', 'msx_read_node_component', 'msx_read_node', 'msx_stage_problem', 'msx_logprob_batch',
             'msx_logprob_batch_dev', 'msx_probe_launch', 'msx_set_path', 'msx_set_grid_storage', 'msx_set_broadening', 'msx_opt_init', 'msx_opt_step', 'msx_sampler_run', 'msx_sampler_begin',
             'msx_sampler_shard', 'msx_sampler_enqueue', 'msx_sampler_enqueue_drawn', 'msx_sampler_draw', 'msx_sampler_collect', 'msx_sampler_end', 'msx_make_composite', 'msx_comm_unique_id', 'msx_comm_init', 'msx_comm_allgather_dev', 'msx_comm_wait_slot',
             'msx_comm_init_loopback', 'msx_sampler_enqueue_group',
@@ -224,6 +230,28 @@ class Context:
         self.check(self.lib.msx_stage_grid(self.h, dptr(wl), nwl, dptr(teff_nodes), nt, dptr(logg_nodes), ng,
                                            dptr(flux), pp))
         self.nwl = nwl
+        self.ncomp = 1
+
+    def stage_grid_components(self, wl, teff_nodes, logg_nodes, flux, present=None):
+        """A component grid from the host: ``flux`` [ncomp][nt][ng][nwl], copy s for star s (``present`` [nt][ng] shared)."""
+        wl, teff_nodes, logg_nodes = as_f64(wl), as_f64(teff_nodes), as_f64(logg_nodes)
+        flux = as_f64(flux)
+        nt, ng, nwl = len(teff_nodes), len(logg_nodes), len(wl)
+        if flux.ndim != 4 or flux.shape[1:] != (nt, ng, nwl):
+            raise ValueError('flux must be [ncomp][nt][ng][nwl]')
+        pp = None
+        if present is not None:
+            present = np.ascontiguousarray(present, dtype=np.uint8)
+            pp = present.ctypes.data_as(C.POINTER(C.c_uint8))
+        self.check(self.lib.msx_stage_grid_components(self.h, dptr(wl), nwl, dptr(teff_nodes), nt, dptr(logg_nodes), ng,
+                                                      dptr(flux), pp, int(flux.shape[0])))
+        self.nwl = nwl
+        self.ncomp = int(flux.shape[0])
+
+    def split_components(self, ncomp):
+        """Duplicate the staged rows into ``ncomp`` copies, one per star (drops the staged problem)."""
+        self.check(self.lib.msx_split_components(self.h, int(ncomp)))
+        self.ncomp = int(ncomp)
 
     def ccm89_k(self, wl, rv=3.1):
         wl = as_f64(np.atleast_1d(wl))
@@ -256,6 +284,14 @@ class Context:
 
     def rot_broaden_grid(self, i0, n, vsini, limb):
         self.check(self.lib.msx_rot_broaden_grid(self.h, int(i0), int(n), float(vsini), float(limb)))
+
+    def rot_broaden_grid_component(self, comp, i0, n, vsini, limb):
+        self.check(self.lib.msx_rot_broaden_grid_component(self.h, int(comp), int(i0), int(n), float(vsini), float(limb)))
+
+    def read_node_component(self, comp, it, ig):
+        out = np.empty(self.nwl)
+        self.check(self.lib.msx_read_node_component(self.h, int(comp), int(it), int(ig), dptr(out)))
+        return out
 
     def read_node(self, it, ig):
         out = np.empty(self.nwl)

@@ -69,6 +69,8 @@ struct DevProblem {
     int64_t win_j0, win_n;
     // isochrone (A1)
     int32_t niso;
+    int32_t node_stride;  // component grid (msx_split_components): star s reads node + s * node_stride; 0 = one copy
+                          // (here: in the padding before iso_t, so that no other member moves)
     const double *iso_t, *iso_g, *iso_l;
     // prior (f1)
     int32_t nav;

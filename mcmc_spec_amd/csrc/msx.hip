@@ -120,6 +120,7 @@ struct msx_ctx {
     int raw_lx = 0;
     double raw_dx = 0.0, raw_sigma = 0.0;
     bool grid_rotated = false;      // msx_rot_broaden_grid ran since the last msx_broaden_grid / grid: no raw window (named in INPATH's refusal)
+    int32_t ncomp = 1;              // copies of the node rows (msx_split_components / msx_stage_grid_components): d_grid is [ncomp][nt*ng][nwl]
     InpathRec *d_inp_rec = nullptr;
     double *d_inp_tmp = nullptr, *d_inp_given = nullptr;
     const int64_t *d_pix_lo = nullptr;
@@ -244,8 +245,12 @@ void free_grid(msx_ctx *c) {
     if (c->d_raw_win) (void)hipFree(c->d_raw_win);
     c->d_raw_win = nullptr; c->raw_n = 0;
     c->grid_rotated = false;
+    c->ncomp = 1;
     c->grid_staged = false;
 }
+
+// the staged rows: nt*ng per copy, ncomp copies
+int64_t grid_rows(const msx_ctx *c) { return (int64_t)c->ncomp * c->nt * c->ng; }
 
 int conv_taps(double mean_wl, double dx, double resolution, double maxsig, double *sigma_out, int *lx_out) {
     // pyasl.instrBroadGaussFast: fwhm = mean(wl)/R; sigma = fwhm/(2 sqrt(2 ln 2)); broadGaussFast:
@@ -549,6 +554,11 @@ FormChoice decide_form(msx_ctx *c, int64_t n, int mode, bool peek) {
     if (f.pair) f.linked = false;
     // in-path broadening (inpath_kernels.h): never taken by MSX_PATH_AUTO -- the per-node placement is the reference's
     if (c->path == MSX_PATH_INPATH) {
+        if (c->ncomp > 1) {
+            f.err = MSX_ERR_STATE;
+            f.msg = "msx_set_path(INPATH): the grid holds one copy per component (msx_split_components); the per-walker form reads one raw window and would not match it";
+            return f;
+        }
         if (c->inp_rows <= 0 && c->grid_rotated) {
             f.err = MSX_ERR_STATE;
             f.msg = "msx_set_path(INPATH): the grid was rotationally broadened (msx_rot_broaden_grid); the per-walker form applies the Gaussian only and would not match it";
@@ -740,6 +750,36 @@ int launch_rot(msx_ctx *c, const double *d_in, int64_t in_stride, const double *
     return MSX_OK;
 }
 
+// msx_rot_broaden_grid over copies [comp0, comp0 + ncopy) of the staged rows (`who` names the entry in the messages)
+int rot_grid_rows(msx_ctx *c, int comp0, int ncopy, int64_t i0, int64_t n, double vsini, double limb, const char *who) {
+    if (!c->grid_staged) return fail(c, MSX_ERR_STATE, std::string(who) + ": no grid staged");
+    if (i0 < 0 || n < 2 || i0 + n > c->nwl) return fail(c, MSX_ERR_INVALID, std::string(who) + ": bad window");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const double *wl = c->h_wl.data() + i0;
+    double vc;
+    int binnu;
+    int rc = rot_params(c, wl, n, vsini, limb, &vc, &binnu);
+    if (rc) return rc;
+    const int64_t rows = (int64_t)ncopy * c->nt * c->ng;
+    double *const g0 = c->d_grid + (int64_t)comp0 * c->nt * c->ng * c->nwl;
+    double *d_tmp = nullptr;
+    HIP_TRY(c, hipMalloc((void **)&d_tmp, sizeof(double) * rows * n));
+    rc = launch_rot(c, g0 + i0, c->nwl, c->d_wl + i0, n, rows, wl[1] - wl[0], vc, limb, binnu, d_tmp, n);
+    if (rc == MSX_OK) {
+        hipError_t e = hipMemcpy2DAsync(g0 + i0, sizeof(double) * c->nwl, d_tmp, sizeof(double) * n, sizeof(double) * n,
+                                        (size_t)rows, hipMemcpyDeviceToDevice, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) rc = fail(c, MSX_ERR_HIP, hipGetErrorString(e));
+    }
+    (void)hipFree(d_tmp);
+    // the raw window of the in-path form is the unrotated grid: the per-walker Gaussian would no longer match the grid
+    if (c->d_raw_win) { (void)hipFree(c->d_raw_win); c->d_raw_win = nullptr; c->raw_n = 0; }
+    c->grid_rotated = true;
+    // any staged problem (R/H and band tables) was derived from the unrotated grid
+    free_problem(c);
+    return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -798,8 +838,16 @@ int msx_device_info(msx_ctx *c, int64_t *out3, char *name, int name_len) {
 
 int msx_stage_grid(msx_ctx *c, const double *wl, int64_t nwl, const double *teff_nodes, int32_t nt,
                    const double *logg_nodes, int32_t ng, const double *flux, const uint8_t *present) {
+    return msx_stage_grid_components(c, wl, nwl, teff_nodes, nt, logg_nodes, ng, flux, present, 1);
+}
+
+int msx_stage_grid_components(msx_ctx *c, const double *wl, int64_t nwl, const double *teff_nodes, int32_t nt,
+                              const double *logg_nodes, int32_t ng, const double *flux, const uint8_t *present,
+                              int32_t ncomp) {
     if (!c || !wl || !teff_nodes || !logg_nodes || !flux || nwl < 2 || nt < 1 || ng < 1)
         return fail(c, MSX_ERR_INVALID, "msx_stage_grid: bad arguments");
+    if (ncomp < 1 || ncomp > MSX_MAX_SPEC)
+        return fail(c, MSX_ERR_RANGE, "msx_stage_grid_components: ncomp must be 1, 2 or 3 (one copy per component, at most MSX_MAX_SPEC)");
     HIP_TRY(c, hipSetDevice(c->device));
     free_problem(c);
     free_grid(c);
@@ -808,8 +856,9 @@ int msx_stage_grid(msx_ctx *c, const double *wl, int64_t nwl, const double *teff
     c->h_wl.assign(wl, wl + nwl);
     c->h_teff.assign(teff_nodes, teff_nodes + nt);
     c->h_logg.assign(logg_nodes, logg_nodes + ng);
-    HIP_TRY(c, hipMalloc((void **)&c->d_grid, sizeof(double) * nn * nwl));
-    HIP_TRY(c, hipMemcpy(c->d_grid, flux, sizeof(double) * nn * nwl, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMalloc((void **)&c->d_grid, sizeof(double) * ncomp * nn * nwl));
+    HIP_TRY(c, hipMemcpy(c->d_grid, flux, sizeof(double) * ncomp * nn * nwl, hipMemcpyHostToDevice));
+    c->ncomp = ncomp;
     int rc;
     if ((rc = dev_alloc_copy(c, nullptr, wl, nwl, &c->d_wl))) return rc;
     if ((rc = dev_alloc_copy(c, nullptr, teff_nodes, (int64_t)nt, &c->d_teff))) return rc;
@@ -922,7 +971,7 @@ int msx_broaden_grid(msx_ctx *c, int64_t i0, int64_t n, double resolution, doubl
     double sigma;
     int lx;
     conv_taps(mean, wl[1] - wl[0], resolution, maxsig, &sigma, &lx);
-    const int64_t rows = (int64_t)c->nt * c->ng;
+    const int64_t rows = grid_rows(c);
     // in-path placement (msx_set_broadening): the window's rows as they are NOW are kept for the per-walker form; the grid
     // is broadened in place all the same, so that every other form -- and the band tables -- see the reference's live path
     if (c->d_raw_win) { (void)hipFree(c->d_raw_win); c->d_raw_win = nullptr; c->raw_n = 0; }
@@ -977,39 +1026,52 @@ int msx_rot_broaden(msx_ctx *c, const double *wl, const double *flux, int64_t n,
 
 int msx_rot_broaden_grid(msx_ctx *c, int64_t i0, int64_t n, double vsini, double limb) {
     if (!c) return MSX_ERR_INVALID;
-    if (!c->grid_staged) return fail(c, MSX_ERR_STATE, "msx_rot_broaden_grid: no grid staged");
-    if (i0 < 0 || n < 2 || i0 + n > c->nwl) return fail(c, MSX_ERR_INVALID, "msx_rot_broaden_grid: bad window");
-    HIP_TRY(c, hipSetDevice(c->device));
-    const double *wl = c->h_wl.data() + i0;
-    double vc;
-    int binnu;
-    int rc = rot_params(c, wl, n, vsini, limb, &vc, &binnu);
-    if (rc) return rc;
-    const int64_t rows = (int64_t)c->nt * c->ng;
-    double *d_tmp = nullptr;
-    HIP_TRY(c, hipMalloc((void **)&d_tmp, sizeof(double) * rows * n));
-    rc = launch_rot(c, c->d_grid + i0, c->nwl, c->d_wl + i0, n, rows, wl[1] - wl[0], vc, limb, binnu, d_tmp, n);
-    if (rc == MSX_OK) {
-        hipError_t e = hipMemcpy2DAsync(c->d_grid + i0, sizeof(double) * c->nwl, d_tmp, sizeof(double) * n, sizeof(double) * n,
-                                        (size_t)rows, hipMemcpyDeviceToDevice, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) rc = fail(c, MSX_ERR_HIP, hipGetErrorString(e));
-    }
-    (void)hipFree(d_tmp);
-    // the raw window of the in-path form is the unrotated grid: the per-walker Gaussian would no longer match the grid
-    if (c->d_raw_win) { (void)hipFree(c->d_raw_win); c->d_raw_win = nullptr; c->raw_n = 0; }
-    c->grid_rotated = true;
-    // any staged problem (R/H and band tables) was derived from the unrotated grid
-    free_problem(c);
-    return rc;
+    return rot_grid_rows(c, 0, c->ncomp, i0, n, vsini, limb, "msx_rot_broaden_grid");
 }
 
-int msx_read_node(msx_ctx *c, int32_t it, int32_t ig, double *out) {
+int msx_rot_broaden_grid_component(msx_ctx *c, int32_t comp, int64_t i0, int64_t n, double vsini, double limb) {
+    if (!c) return MSX_ERR_INVALID;
+    if (c->grid_staged && (comp < 0 || comp >= c->ncomp))
+        return fail(c, MSX_ERR_RANGE, "msx_rot_broaden_grid_component: comp is not a copy of the staged grid (0 <= comp < ncomp)");
+    return rot_grid_rows(c, comp, 1, i0, n, vsini, limb, "msx_rot_broaden_grid_component");
+}
+
+int msx_split_components(msx_ctx *c, int32_t ncomp) {
+    if (!c) return MSX_ERR_INVALID;
+    if (!c->grid_staged) return fail(c, MSX_ERR_STATE, "msx_split_components: no grid staged");
+    if (ncomp < 1 || ncomp > MSX_MAX_SPEC)
+        return fail(c, MSX_ERR_RANGE, "msx_split_components: ncomp must be 1, 2 or 3 (one copy per component, at most MSX_MAX_SPEC)");
+    if (c->ncomp != 1) return fail(c, MSX_ERR_STATE, "msx_split_components: the grid is split already");
+    HIP_TRY(c, hipSetDevice(c->device));
+    free_problem(c);  // its tables index the one copy
+    if (ncomp == 1) return MSX_OK;
+    const size_t copy = sizeof(double) * (size_t)c->nt * c->ng * c->nwl;
+    double *d = nullptr;
+    HIP_TRY(c, hipMalloc((void **)&d, copy * ncomp));
+    hipError_t e = hipSuccess;
+    for (int s = 0; s < ncomp && e == hipSuccess; ++s)
+        e = hipMemcpyAsync(reinterpret_cast<char *>(d) + copy * s, c->d_grid, copy, hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        (void)hipFree(d);
+        return fail(c, MSX_ERR_HIP, hipGetErrorString(e));
+    }
+    (void)hipFree(c->d_grid);
+    c->d_grid = d;
+    c->ncomp = ncomp;
+    return MSX_OK;
+}
+
+int msx_read_node(msx_ctx *c, int32_t it, int32_t ig, double *out) { return msx_read_node_component(c, 0, it, ig, out); }
+
+int msx_read_node_component(msx_ctx *c, int32_t comp, int32_t it, int32_t ig, double *out) {
     if (!c || !out) return MSX_ERR_INVALID;
     if (!c->grid_staged) return fail(c, MSX_ERR_STATE, "msx_read_node: no grid staged");
     if (it < 0 || it >= c->nt || ig < 0 || ig >= c->ng) return fail(c, MSX_ERR_INVALID, "msx_read_node: bad node");
+    if (comp < 0 || comp >= c->ncomp)
+        return fail(c, MSX_ERR_RANGE, "msx_read_node_component: comp is not a copy of the staged grid (0 <= comp < ncomp)");
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemcpy(out, c->d_grid + ((int64_t)it * c->ng + ig) * c->nwl, sizeof(double) * c->nwl,
+    HIP_TRY(c, hipMemcpy(out, c->d_grid + (((int64_t)comp * c->nt + it) * c->ng + ig) * c->nwl, sizeof(double) * c->nwl,
                          hipMemcpyDeviceToHost));
     return MSX_OK;
 }
@@ -1020,6 +1082,9 @@ int msx_stage_problem(msx_ctx *c, const msx_problem *p) {
         return fail(c, MSX_ERR_INVALID, "msx_stage_problem: struct_size mismatch (header/library skew)");
     if (!c->grid_staged) return fail(c, MSX_ERR_STATE, "msx_stage_problem: stage the grid first");
     if (p->nspec < 2 || p->nspec > MSX_MAX_SPEC) return fail(c, MSX_ERR_INVALID, "nspec must be 2 or 3");
+    if (c->ncomp > 1 && p->nspec != c->ncomp)
+        return fail(c, MSX_ERR_RANGE, "msx_stage_problem: the grid holds one copy per component (ncomp = " + std::to_string(c->ncomp) +
+                                          "): nspec = " + std::to_string(p->nspec) + " must equal ncomp");
     if (p->npix < 4) return fail(c, MSX_ERR_INVALID, "npix too small");
     if (p->n_contrast < 0 || p->n_contrast > MSX_MAX_BANDS || p->n_phot < 0 || p->n_phot > MSX_MAX_BANDS)
         return fail(c, MSX_ERR_INVALID, "too many bands");
@@ -1041,6 +1106,7 @@ int msx_stage_problem(msx_ctx *c, const msx_problem *p) {
     DevProblem &P = c->P;
     memset(&P, 0, sizeof(P));
     P.grid = c->d_grid; P.kgrid = c->d_kgrid; P.nwl = c->nwl; P.nt = c->nt; P.ng = c->ng;
+    P.node_stride = c->ncomp > 1 ? c->nt * c->ng : 0;  // component s reads copy s: node + s * stride
     P.teff_nodes = c->d_teff; P.logg_nodes = c->d_logg; P.present = c->d_present;
     P.npix = p->npix; P.median_flux = p->median_flux; P.nspec = p->nspec;
     memcpy(P.minv, p->fit_minv, sizeof(P.minv));
@@ -1074,7 +1140,7 @@ int msx_stage_problem(msx_ctx *c, const msx_problem *p) {
     if ((rc = dev_alloc_copy(c, &tr, p->av_mu, (int64_t)p->nav, &d))) return rc; P.av_mu = d;
     if ((rc = dev_alloc_copy(c, &tr, p->av_sig, (int64_t)p->nav, &d))) return rc; P.av_sig = d;
 
-    const int64_t nn = (int64_t)c->nt * c->ng;
+    const int64_t nn = grid_rows(c);  // every copy's rows
     // the blend's tables in two-pixel elements (logprob_kernel.h "TABLE LAYOUT"): per node R (f64) + H (f32),
     // per pixel k[lo], dk, data flux, u
     int64_t *d_lo = nullptr;

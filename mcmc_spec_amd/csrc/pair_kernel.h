@@ -519,7 +519,7 @@ __device__ __forceinline__ void stage_scalar_tables(const unsigned char *__restr
     if (tid < 2 * kWave) { s_avm[tid] = v_avm; s_avs[tid] = v_avs; }
     if (tid <= kPlanNodePad) { s_teff[tid] = tid < nt ? v_teff : INFINITY; s_logg[tid] = tid < ng ? v_logg : INFINITY; }
     if (tid < kWave) s_pmask[tid] = tid < nt ? v_mask : 0u;
-    T = ScalarTabs{s_isot, s_teff, s_logg, s_isopack, s_pmask, s_ave, niso, nt, ng, nav};
+    T = ScalarTabs{s_isot, s_teff, s_logg, s_isopack, s_pmask, s_ave, niso, nt, ng, nav, P.node_stride};
     TP = ScalarPriorTabs{s_isot, s_isol, s_avm, s_avs};
 }
 

@@ -56,7 +56,8 @@ __device__ void build_desc(const DevProblem &P, const double *teff, const double
             sc = (s == 0) ? 1.0 : rad[s - 1] * rad[s - 1];  // mft6.py:703
         }
         starscale[s] = sc;
-        int nd4[4] = {n11, n12, n21, n22};
+        const int off = s * P.node_stride;  // component grid: star s reads copy s (0 for one copy)
+        int nd4[4] = {n11 + off, n12 + off, n21 + off, n22 + off};
         double w4[4] = {(1.0 - b) * (1.0 - a) * sc, (1.0 - b) * a * sc, b * (1.0 - a) * sc, b * a * sc};
         sort4_by_node(nd4, w4);  // canonical corner order (blend.h)
         for (int k = 0; k < 4; ++k) { D->node[4 * s + k] = nd4[k]; D->w[4 * s + k] = w4[k]; }
@@ -293,6 +294,10 @@ __device__ __forceinline__ void build_recipe_wave(const DevProblem &P, const Rec
     if (lane == 0) {
 #pragma unroll
         for (int c = 0; c < NS * 4; ++c) { D.node[c] = node[c]; D.w[c] = w[c]; }
+        if (P.node_stride != 0) {  // component grid: star s reads copy s (one offset per star keeps its sorted order)
+#pragma unroll
+            for (int c = 4; c < NS * 4; ++c) D.node[c] += (c >> 2) * P.node_stride;
+        }
     }
     // same-wave LDS hand-off (lane 0 -> all lanes): LDS ops of one wave complete in order; the fence
     // keeps the compiler from moving the reads above the writes
@@ -638,6 +643,9 @@ __device__ __forceinline__ void recipe_part1_regs(const DevProblem &P, const Gat
     int node[4] = {T.i1 * ng + g1, T.i1 * ng + g2, T.i2 * ng + g1, T.i2 * ng + g2};
     double w[4] = {(1.0 - bw) * (1.0 - a) * sc, (1.0 - bw) * a * sc, bw * (1.0 - a) * sc, bw * a * sc};
     sort4_by_node(node, w);  // canonical corner order (blend.h): a function of the grid cell alone
+    // component grid: star s reads copy s.  One offset for the star's four corners leaves their order as sorted; added
+    // at the store, in the one lane that writes (uniform, scalar): the VGPR budget of the variants stays as it was
+    const int off = star * P.node_stride;
     MSX_STAMP(P, wk, 10);
     if (lane == LT) {
         if (!alive) {
@@ -647,7 +655,7 @@ __device__ __forceinline__ void recipe_part1_regs(const DevProblem &P, const Gat
         } else {
             if (st == MSX_W_OK) {
 #pragma unroll
-                for (int c = 0; c < 4; ++c) { D.node[4 * star + c] = node[c]; D.w[4 * star + c] = w[c]; }
+                for (int c = 0; c < 4; ++c) { D.node[4 * star + c] = node[c] + off; D.w[4 * star + c] = w[c]; }
                 if (star == 0) D.redc = redden_rule(mode, G.use_av, tv[NS]) ? -0.4 * kLog2Of10 * tv[NS] : 0.0;
             }
             D.stat[star] = st;
@@ -669,6 +677,7 @@ struct ScalarTabs {
     const unsigned int *pmask;
     const double *av_edges;  // (the prior's A_V(distance) table rides along: its search runs beside the recipe's)
     int niso, nt, ng, nav;
+    int stride;  // DevProblem::node_stride
 };
 constexpr int kPlanIsoPad = 256, kPlanNodePad = 64;
 // One level of a 4-ary search for c = #{i : xs[i] <= v} in a sorted table padded with +inf: three probes, read together.
@@ -787,7 +796,8 @@ __device__ __forceinline__ int recipe_scalar2(const GateArgs &G, const ScalarTab
         const unsigned int mA = T.pmask[i1[star]], mB = T.pmask[i2[star]];
         const bool have = (((mA >> g1) & (mA >> g2) & (mB >> g1) & (mB >> g2)) & 1u) != 0u;
         if (st == MSX_W_OK && !have) st = MSX_W_KEYERROR;
-        int nd[4] = {i1[star] * T.ng + g1, i1[star] * T.ng + g2, i2[star] * T.ng + g1, i2[star] * T.ng + g2};
+        const int off = star * T.stride;  // component grid: star s reads copy s
+        int nd[4] = {i1[star] * T.ng + g1 + off, i1[star] * T.ng + g2 + off, i2[star] * T.ng + g1 + off, i2[star] * T.ng + g2 + off};
         double ww[4] = {(1.0 - bw) * (1.0 - a) * sc, (1.0 - bw) * a * sc, bw * (1.0 - a) * sc, bw * a * sc};
         sort4_by_node(nd, ww);
 #pragma unroll

@@ -32,6 +32,24 @@ def _raise_for_status(status, theta):
     raise RuntimeError('unknown walker status {} for {}'.format(code, where))
 
 
+def component_rotations(vsini, limb):
+    """``None`` for scalar ``vsini`` and ``limb`` (one rotation for the whole grid); else the list of per-star
+    ``(vsini, limb)`` pairs, 1..3 of them (a scalar beside a sequence is repeated).  ValueError on unequal lengths."""
+    seq_v, seq_l = np.ndim(vsini) > 0, np.ndim(limb) > 0
+    if not seq_v and not seq_l:
+        return None
+    v = [float(x) for x in np.ravel(vsini)] if seq_v else None
+    lb = [float(x) for x in np.ravel(limb)] if seq_l else None
+    n = len(v) if v is not None else len(lb)
+    v = v if v is not None else [float(vsini)] * n
+    lb = lb if lb is not None else [float(limb)] * n
+    if len(v) != len(lb):
+        raise ValueError('vsini and limb: one value per star each ({} and {} given)'.format(len(v), len(lb)))
+    if not 1 <= n <= _lib.MAX_SPEC:
+        raise ValueError('vsini / limb per star: 1 to {} stars, {} given'.format(_lib.MAX_SPEC, n))
+    return list(zip(v, lb))
+
+
 class Engine:
     def __init__(self, device=0):
         self.ctx = _lib.Context(device)
@@ -42,13 +60,23 @@ class Engine:
     # ---- A0 ---------------------------------------------------------------------------------------
     def stage_grid(self, wl, teff_nodes, logg_nodes, flux, present=None):
         self.ctx.stage_grid(wl, teff_nodes, logg_nodes, flux, present)
+        self._grid_meta(wl, teff_nodes, logg_nodes)
+
+    def stage_specs(self, specs):
+        """``specs``: the reference's dict, or a tuple of ``nspec`` such dicts -- one per star, sharing keys and ``wl``
+        (``parse_component_specs``) -- staged as a component grid (copy s for star s)."""
+        if isinstance(specs, (tuple, list)):
+            teff, logg, wl, flux, present = staging.parse_component_specs(specs)
+            self.ctx.stage_grid_components(wl, teff, logg, flux, present)
+            self._grid_meta(wl, teff, logg)
+            return
+        teff, logg, wl, flux, present = staging.parse_specs(specs)
+        self.stage_grid(wl, teff, logg, flux, present)
+
+    def _grid_meta(self, wl, teff_nodes, logg_nodes):
         self.grid = dict(wl=np.asarray(wl, dtype=float), teff=np.asarray(teff_nodes, dtype=float),
                          logg=np.asarray(logg_nodes, dtype=float))
         self.tables = None
-
-    def stage_specs(self, specs):
-        teff, logg, wl, flux, present = staging.parse_specs(specs)
-        self.stage_grid(wl, teff, logg, flux, present)
 
     def broaden_grid_window(self, w_aa, resolution, placement='staging', vsini=0, limb=0):
         """Broaden every node over the data window ``[min(w), max(w)]`` [A] in place: the staging step
@@ -57,14 +85,27 @@ class Engine:
         (``ctx.set_path(_lib.PATH_INPATH)``) beside the default forms.
 
         ``vsini`` [km/s] / ``limb``: when both are nonzero (the reference's condition, mft6.py:133), the same window is
-        then rotationally broadened (``pyasl.rotBroad``; ValueError on a bad value).  A rotated grid has no in-path form."""
+        then rotationally broadened (``pyasl.rotBroad``; ValueError on a bad value).  A rotated grid has no in-path form.
+
+        Per star (an extension of the reference's signature): ``vsini`` and ``limb`` may be sequences of one value per
+        star (a scalar beside a sequence is repeated).  The grid is then split after the Gaussian into a component
+        grid of ``ncomp`` copies (DESIGN.md "Component grids"), and copy s is rotated with ``(vsini[s], limb[s])`` under
+        the same condition; a copy whose pair fails it stays Gaussian-only.  Problems staged on it need
+        ``nspec == ncomp``."""
+        pairs = component_rotations(vsini, limb)
         self.ctx.set_broadening(placement)
         wl = self.grid['wl']
         idx = np.where((wl >= min(w_aa)) & (wl <= max(w_aa)))[0]
         self.ctx.broaden_grid(int(idx[0]), int(idx.size), resolution, 5.0)
         self.tables = None
-        if vsini != 0 and limb != 0:
-            self.ctx.rot_broaden_grid(int(idx[0]), int(idx.size), vsini, limb)
+        if pairs is None:
+            if vsini != 0 and limb != 0:
+                self.ctx.rot_broaden_grid(int(idx[0]), int(idx.size), vsini, limb)
+            return
+        self.ctx.split_components(len(pairs))
+        for s, (vs, ls) in enumerate(pairs):
+            if vs != 0 and ls != 0:
+                self.ctx.rot_broaden_grid_component(s, int(idx[0]), int(idx.size), vs, ls)
 
     # ---- problem ------------------------------------------------------------------------------------
     def stage_problem(self, data, err, fr, r, ctm, ptm, tmi, tma, matrix, nspec=2, bands=None, av_table=None,

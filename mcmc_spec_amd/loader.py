@@ -26,6 +26,11 @@ class StagedSpecs(dict):
     engine = None
 
 
+class StagedComponentSpecs(tuple):
+    """One ``specs`` dict per star + the Engine that holds them in HBM as one component grid."""
+    engine = None
+
+
 def _read_two_columns(path, lo, hi):
     """Samples of one BT-Settl text file with lo <= wavelength <= hi (mft6.py:353-357)."""
     xs, ys = [], []
@@ -59,29 +64,41 @@ def spec_interpolator(w, trange, lgrange, specrange, npix=3, resolution=10000, m
 
     ``cache``: optional ``.npz`` path; reused when the file list, mtimes, ranges, resolution, vsini and limb match.
     ``vsini`` [km/s], ``limb`` (extensions of the reference's signature): when both are nonzero, the data window of
-    every node is also rotationally broadened after the Gaussian (``broaden(..., vsini, limb)``, mft6.py:133-134)."""
+    every node is also rotationally broadened after the Gaussian (``broaden(..., vsini, limb)``, mft6.py:133-134).
+
+    Per star: ``vsini=(v1, v2), limb=(l1, l2)`` (one value per star; a scalar beside a sequence is repeated) returns a
+    tuple of ``ncomp`` such dicts, dict s rotated with ``(vs, ls)`` under the same condition -- bit for bit what the
+    scalar call with ``(vs, ls)`` returns.  Pass the tuple as ``specs`` to the drop-ins (``mcmc_spec_amd.mft6``): star s
+    is then interpolated from dict s."""
     if models != 'btsettl':
         raise NotImplementedError("only models='btsettl' is on the hot path (SURVEY.md §2)")
     from . import mft6 as _api
+    from .engine import component_rotations
+    pairs = component_rotations(vsini, limb)
+    rot_stamp = [float(vsini), float(limb)] if pairs is None else [float(len(pairs))] + [x for p in pairs for x in p]
     files = sorted(glob(os.path.join(grid_dir, 'lte*')))
     if not files:
         raise IndexError('list index out of range')  # what glob(...)[0] raises in find_model, mft6.py:251
     t, l = _node_lists(files, trange, lgrange)
     wl = np.arange(min(specrange), max(specrange), 0.2)  # mft6.py:343
     stamp = np.array([os.path.getmtime(f) for f in files] + [min(w), max(w), min(specrange), max(specrange),
-                                                             float(resolution), len(t), len(l), float(vsini),
-                                                             float(limb)])
+                                                             float(resolution), len(t), len(l)] + rot_stamp)
     eng = Engine(_api._DEVICE if device is None else device)
     teff, logg = sorted(t), sorted(l)
-    flux = np.zeros((len(teff), len(logg), len(wl)))
+    ncomp = 1 if pairs is None else len(pairs)
+    flux = np.zeros((ncomp, len(teff), len(logg), len(wl)))
     cached = None
     if cache and os.path.exists(cache):
         z = np.load(cache)
         if z['stamp'].shape == stamp.shape and np.array_equal(z['stamp'], stamp):
             cached = z
     if cached is not None:
-        flux = cached['flux']
-        eng.stage_grid(wl, np.array(teff, float), np.array(logg, float), flux)
+        flux = cached['flux'].reshape(ncomp, len(teff), len(logg), len(wl))
+        if pairs is None:
+            eng.stage_grid(wl, np.array(teff, float), np.array(logg, float), flux[0])
+        else:
+            eng.ctx.stage_grid_components(wl, np.array(teff, float), np.array(logg, float), flux)
+            eng._grid_meta(wl, teff, logg)
     else:
         for it, tt in enumerate(teff):
             for ig, ll in enumerate(logg):
@@ -94,19 +111,27 @@ def spec_interpolator(w, trange, lgrange, specrange, npix=3, resolution=10000, m
                 if np.any(np.diff(xs) < 0):  # interp1d sorts its abscissa (stable)
                     order = np.argsort(xs, kind='mergesort')
                     xs, ys = xs[order], ys[order]
-                flux[it, ig] = eng.ctx.resample_linear(xs, ys, wl)  # mft6.py:369-371
-        eng.stage_grid(wl, np.array(teff, float), np.array(logg, float), flux)
+                flux[0, it, ig] = eng.ctx.resample_linear(xs, ys, wl)  # mft6.py:369-371
+        eng.stage_grid(wl, np.array(teff, float), np.array(logg, float), flux[0])
         eng.broaden_grid_window([min(w), max(w)], resolution, vsini=vsini, limb=limb)  # mft6.py:373-378
-        for it in range(len(teff)):
-            for ig in range(len(logg)):
-                flux[it, ig] = eng.ctx.read_node(it, ig)
+        for s in range(ncomp):
+            for it in range(len(teff)):
+                for ig in range(len(logg)):
+                    flux[s, it, ig] = eng.ctx.read_node_component(s, it, ig)
         if cache:
-            np.savez(cache, stamp=stamp, flux=flux)
-    specs = StagedSpecs()
-    for it, tt in enumerate(teff):
-        for ig, ll in enumerate(logg):
-            specs['{}, {}'.format(tt, ll)] = flux[it, ig]
-    specs['wl'] = wl  # the splice of mft6.py:381 re-assembles the same vector
+            np.savez(cache, stamp=stamp, flux=flux if pairs is not None else flux[0])
+    comps = []
+    for s in range(ncomp):
+        d = StagedSpecs()
+        for it, tt in enumerate(teff):
+            for ig, ll in enumerate(logg):
+                d['{}, {}'.format(tt, ll)] = flux[s, it, ig]
+        d['wl'] = wl  # the splice of mft6.py:381 re-assembles the same vector
+        comps.append(d)
+    if pairs is None:
+        specs = comps[0]
+    else:
+        specs = StagedComponentSpecs(comps)
     specs.engine = eng
     eng._problem_key = None
     eng._problem_refs = None

@@ -14,6 +14,11 @@ Differences from the reference, all at the boundary:
     the GPU on first use and cached by object identity: treat them as immutable while you sample.
   * pyphot / dustmaps are not importable here, so the passbands and the A_V(distance) prior table are
     registered explicitly (functions above) instead of being created at import.
+  * ``specs`` may also be a tuple of ``nspec`` specs dicts, one per star (``logposterior``, ``loglikelihood``,
+    ``make_composite``, ``device_sampler``): star s is interpolated from ``specs[s]`` -- e.g. the per-star rotated
+    grids of ``spec_interpolator(..., vsini=(v1, v2), limb=(l1, l2))``.  The dicts must share their keys and ``wl``
+    (ValueError otherwise); they are staged as one component grid (DESIGN.md "Component grids").  A single dict is
+    the reference's behaviour.
 """
 from __future__ import annotations
 
@@ -83,6 +88,7 @@ def _invalidate_problems():
 
 
 def _engine_for(specs):
+    """The Engine holding ``specs`` (a dict, or a tuple of per-star dicts: a component grid), staged on first use."""
     key = id(specs)
     hit = _GRIDS.get(key)
     if hit is not None and hit[0] is specs:

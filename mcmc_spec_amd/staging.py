@@ -46,6 +46,29 @@ def parse_specs(specs):
     return np.array(teff, dtype=float), np.array(logg, dtype=float), wl, flux, present
 
 
+def parse_component_specs(specs_seq):
+    """A tuple of ``nspec`` ``specs`` dicts, one per star (an extension of the reference's ``specs`` argument) ->
+    (teff_nodes, logg_nodes, wl, flux[ncomp][nt][ng][nwl], present).  The dicts must share their keys and ``wl``
+    exactly: ValueError otherwise."""
+    specs_seq = list(specs_seq)
+    if not 1 <= len(specs_seq) <= 3:
+        raise ValueError('specs: one dict per star, 1 to 3 of them ({} given)'.format(len(specs_seq)))
+    for s, d in enumerate(specs_seq):
+        if not isinstance(d, dict):
+            raise ValueError('specs[{}]: a specs dict expected, got {}'.format(s, type(d).__name__))
+    keys0 = set(specs_seq[0])
+    wl0 = np.asarray(specs_seq[0]['wl'], dtype=np.float64)
+    for s, d in enumerate(specs_seq[1:], 1):
+        if set(d) != keys0:
+            raise ValueError('specs[{}] does not have the keys of specs[0]: the per-star dicts must share their nodes'.format(s))
+        w = np.asarray(d['wl'], dtype=np.float64)
+        if w.shape != wl0.shape or not np.array_equal(w, wl0):
+            raise ValueError("specs[{}]['wl'] differs from specs[0]['wl']: the per-star dicts must share one axis".format(s))
+    parts = [parse_specs(d) for d in specs_seq]
+    teff, logg, wl, _, present = parts[0]
+    return teff, logg, wl, np.stack([p[3] for p in parts]), present
+
+
 def composite_window_um(r, tmi, tma, ctm, ptm):
     """The window make_composite passes to get_spec, in micron (mft6.py:663-673,687)."""
     wlmin, wlmax = np.inf, 0

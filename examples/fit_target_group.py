@@ -1,0 +1,85 @@
+#!/usr/bin/env python3
+"""Several synthetic targets fitted together: one staged problem per target (each its own Engine), their walkers
+evaluated in ONE launch per half-step (TargetGroup), their ensembles stepped in lock-step (GroupSampler).
+
+Every target gets its own data spectrum (a binary at its own truth, its own pixel count and noise) on one synthetic grid.
+Target k's chain is the chain a separate EnsembleSampler with target k's seed would walk.
+
+    python examples/fit_target_group.py --targets 4 --nwalkers 32 --nsteps 200
+"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--targets', type=int, default=4)
+    ap.add_argument('--nwalkers', type=int, default=32)
+    ap.add_argument('--nsteps', type=int, default=200)
+    ap.add_argument('--seed', type=int, default=1)
+    args = ap.parse_args()
+
+    from scipy.interpolate import interp1d
+    from mcmc_spec_amd import bands, synth
+    from mcmc_spec_amd.engine import Engine
+    from mcmc_spec_amd.group import GroupSampler, TargetGroup
+    from oracle import mft6_oracle as orc
+
+    rng = np.random.default_rng(args.seed)
+    teffs, loggs = np.arange(3000, 4300, 100), np.array([4.0, 4.5, 5.0, 5.5])
+    wl = np.arange(5000, 24000, 0.2)
+    specs = synth.grid_to_specs(teffs, loggs, wl, synth.make_grid(teffs, loggs, wl, nlines=800, seed=5))
+    matrix = synth.make_isochrone_matrix()
+    ctm, ptm = synth.synthetic_contrast_filters(), synth.synthetic_phot_filters()
+    tabs, (vw, vf) = synth.synthetic_band_tables(), synth.synthetic_vega()
+    fr = [synth.EXAMPLE_CMAG, synth.EXAMPLE_CERR, ['lp600', 'Kp'], synth.EXAMPLE_PMAG, synth.EXAMPLE_PERR,
+          ['sdss,r', 'sdss,i', 'sdss,z', 'j', 'h', 'k']]
+    tmi = min(min(w) for w in ctm[0] + ptm[0])
+    tma = max(max(w) for w in ctm[0] + ptm[0])
+    obl = orc.make_band_library(tabs, vw, vf)
+    bl = bands.make_bands(tabs, vw, vf)
+    tmin, tmax = 3000.0, 4200.0
+
+    engines, truths = [], []
+    for k in range(args.targets):
+        truth = synth.TRUTH_THETA.copy()
+        truth[:2] = np.clip(truth[:2] + rng.uniform(-150.0, 150.0, size=2), tmin + 50.0, tmax - 50.0)
+        wl_um = synth.data_wavelengths_um(int(rng.integers(400, 1200)))
+        r = [min(wl_um), max(wl_um)]
+        lg = [float(orc.get_logg(t, matrix)) for t in truth[:2]]
+        w1, c1, _, _, _, _ = orc.make_composite(truth[:2], lg, truth[3:5], truth[5], fr[2], fr[5], r, specs, ctm, ptm,
+                                                tmi, tma, bandlib=obl)
+        f = interp1d(w1, orc.extinct(w1, c1, truth[2]))(wl_um * 1e4)
+        d = f + rng.normal(0, 0.01 * f)
+        eng = Engine(0)
+        eng.stage_specs(specs)
+        eng.stage_problem([wl_um, d / np.median(d)], 0.01 * f / np.median(d), fr, r, ctm, ptm, tmi, tma, matrix, nspec=2,
+                          bands=bl, tmin=tmin, tmax=tmax)
+        engines.append(eng)
+        truths.append(truth)
+
+    group = TargetGroup(engines)
+    print('one launch:', group.launch_info([args.nwalkers] * args.targets)['kernel'])
+    p0s = [truths[k] + 1e-3 * np.abs(truths[k]) * rng.normal(size=(args.nwalkers, 6)) for k in range(args.targets)]
+    sampler = GroupSampler([args.nwalkers] * args.targets, 6, group.logposterior, seeds=[args.seed + k for k in range(args.targets)])
+    t0 = time.time()
+    sampler.run_mcmc(p0s, args.nsteps)
+    dt = time.time() - t0
+    print('{} targets x {} walkers x {} steps in {:.2f} s ({:.0f} evaluations/s)'.format(
+        args.targets, args.nwalkers, args.nsteps, dt, args.targets * args.nwalkers * args.nsteps / dt))
+    for k in range(args.targets):
+        flat = sampler.get_chain(k, discard=args.nsteps // 2, flat=True)
+        print('target {}: Teff {:.0f} / {:.0f} (truth {:.0f} / {:.0f}), acceptance {:.2f}'.format(
+            k, *np.median(flat[:, :2], axis=0), *truths[k][:2], sampler.acceptance_fraction[k].mean()))
+    group.close()
+    return sampler
+
+
+if __name__ == '__main__':
+    main()

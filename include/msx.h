@@ -47,8 +47,10 @@ extern "C" {
 #define MSX_MAX_SPEC 3
 #define MSX_MAX_BANDS 8
 #define MSX_MAX_DIM 8
+#define MSX_MAX_GROUP 64        /* members of a target group (msx_group_create)                     */
 
 typedef struct msx_ctx msx_ctx;
+typedef struct msx_group msx_group;
 
 /* Everything that is static per dataset.  Built on the host by mcmc_spec_amd/staging.py from the
  * reference's own arguments (data, err, fr, ctm, ptm, matrix, prior ...); copied at stage time. */
@@ -368,6 +370,35 @@ int msx_last_form(msx_ctx *ctx, int32_t *form);
 /* the planner's counts for the pair form's last launch (a sub-batch): out2[0] = pairs, out2[1] = walkers evaluated alone;
  * synchronises */
 int msx_pair_stats(msx_ctx *ctx, int64_t *out2);
+
+/* ---- target groups: the walkers of several staged targets in one launch -------------------------
+ * A group is 1..MSX_MAX_GROUP contexts on one device, each with its own staged grid and problem (data, pixel count, bands,
+ * priors, Teff box, A_V table, dist_fit / use_av / rad_prior, no_spectrum, ordinary / rotated / component grid may all
+ * differ); they must share nspec (so ndim).  A launch evaluates a batch whose walkers come in contiguous blocks: the
+ * first counts[0] are member 0's, the next counts[1] member 1's, ... (a count may be 0).  One workgroup per walker, the
+ * fused form's; walker i of member m gets the bits and the status member m's own msx_logprob_batch gives it.  Modes
+ * MSX_MODE_LOGLIKE, _LOGPOST, _CHISQ and _LOGPRIOR; no sampler, pair, linked or in-path form.
+ * msx_group_create snapshots the members' staged problems (the tables stay theirs: keep the contexts alive).  Refused
+ * there, naming the member: float32 grid storage (MSX_ERR_STATE), spectra over 17,152 pixels (MSX_ERR_RANGE), unequal
+ * nspec (MSX_ERR_RANGE), members on different devices or without a problem (MSX_ERR_STATE).  A launch after a member's
+ * problem was dropped or staged again (msx_stage_problem, grid staging, broadening, rotation, splitting) or after a
+ * member was destroyed is refused with MSX_ERR_STATE; create the group again.  *out is set even on failure (read
+ * msx_group_last_error, then msx_group_destroy).  Calls on a group are serialised by the caller like a context's.      */
+int msx_group_create(msx_ctx **ctxs, int32_t k, msx_group **out);
+void msx_group_destroy(msx_group *group);
+const char *msx_group_last_error(msx_group *group);
+/* host buffers: theta [sum counts][ndim], logp_out / status_out [sum counts]; counts [k]; synchronous, on member 0's stream */
+int msx_group_logprob_batch(msx_group *group, int32_t mode, const double *theta, const int64_t *counts, int32_t ndim,
+                            double *logp_out, int32_t *status_out);
+/* device buffers on a caller stream (does not synchronise); counts is a HOST array [k]; block_threads as for
+ * msx_logprob_batch_dev, the variant chosen by its rules for (all walkers, the longest member with walkers) among the ones
+ * every member with walkers can take */
+int msx_group_logprob_batch_dev(msx_group *group, int32_t mode, const double *d_theta, const int64_t *counts, int32_t ndim,
+                                double *d_logp, int32_t *d_status, void *hip_stream, int32_t block_threads);
+/* what that launch WOULD take, in msx_launch_info's shape: out8[5] is the members' bytes per walker averaged over the
+ * launch's walkers, out8[6] = out8[7] = all walkers (one launch, no sub-batches) */
+int msx_group_launch_info(msx_group *group, int32_t mode, const int64_t *counts, int32_t block_threads, char *name,
+                          int32_t name_len, int64_t *out8);
 
 /* ---- test hooks (used by tests/ only) ------------------------------------------------------------ */
 /* MSX_HOOK_LINKED_FAULT: value != 0 makes the workgroups of the linked form skip their signal -- and the walkers of an

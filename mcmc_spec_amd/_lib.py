@@ -27,6 +27,7 @@ FORM_NAMES = {0: 'fused', 1: 'pair (planner + two walkers of one grid cell per w
               3: 'in-path broadening (recipe, composite + convolution, resample, then the fused kernel on the given model values)'}
 HOOK_LINKED_FAULT, HOOK_PAIR_LEASES = 1, 2  # include/msx.h MSX_HOOK_*
 MAX_SPEC, MAX_BANDS, MAX_DIM = 3, 8, 8
+MAX_GROUP = 64  # include/msx.h MSX_MAX_GROUP: members of a target group
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int64)
@@ -139,6 +140,12 @@ def load():
         'msx_pair_stats': (C.c_int, [vp, _ip]),
         'msx_sampler_overlapped': (C.c_int, [vp, C.POINTER(C.c_int32)]),
         'msx_sampler_policy': (C.c_int, [vp, C.c_int32]),
+        'msx_group_create': (C.c_int, [C.POINTER(vp), C.c_int32, C.POINTER(vp)]),
+        'msx_group_destroy': (None, [vp]),
+        'msx_group_last_error': (C.c_char_p, [vp]),
+        'msx_group_logprob_batch': (C.c_int, [vp, C.c_int32, _dp, _ip, C.c_int32, _dp, C.POINTER(C.c_int32)]),
+        'msx_group_logprob_batch_dev': (C.c_int, [vp, C.c_int32, vp, _ip, C.c_int32, vp, vp, vp, C.c_int32]),
+        'msx_group_launch_info': (C.c_int, [vp, C.c_int32, _ip, C.c_int32, C.c_char_p, C.c_int32, _ip]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = header/library skew, fail loudly
@@ -155,7 +162,9 @@ EXPORTED = ['msx_create', 'msx_destroy', 'msx_last_error', 'msx_device_info', 'm
             'msx_logprob_batch_dev', 'msx_probe_launch', 'msx_set_path', 'msx_set_grid_storage', 'msx_set_broadening', 'msx_opt_init', 'msx_opt_step', 'msx_sampler_run', 'msx_sampler_begin',
             'msx_sampler_shard', 'msx_sampler_enqueue', 'msx_sampler_enqueue_drawn', 'msx_sampler_draw', 'msx_sampler_collect', 'msx_sampler_end', 'msx_make_composite', 'msx_comm_unique_id', 'msx_comm_init', 'msx_comm_allgather_dev', 'msx_comm_wait_slot',
             'msx_comm_init_loopback', 'msx_sampler_enqueue_group',
-            'msx_stream_copy_gbps', 'msx_bytes_per_eval', 'msx_launch_info', 'msx_last_form', 'msx_test_hook', 'msx_pair_stats', 'msx_sampler_overlapped', 'msx_sampler_policy']
+            'msx_stream_copy_gbps', 'msx_bytes_per_eval', 'msx_launch_info', 'msx_last_form', 'msx_test_hook', 'msx_pair_stats', 'msx_sampler_overlapped', 'msx_sampler_policy',
+            'msx_group_create', 'msx_group_destroy', 'msx_group_last_error', 'msx_group_logprob_batch',
+            'msx_group_logprob_batch_dev', 'msx_group_launch_info']
 
 
 def as_f64(a):
@@ -516,3 +525,76 @@ class Context:
 
     def test_hook(self, what, value):
         self.check(self.lib.msx_test_hook(self.h, int(what), int(value)))
+
+
+class Group:
+    """One ``msx_group`` (include/msx.h, target groups): the walkers of several staged contexts on one device, each
+    against its own problem, in one launch.  The contexts must stay open while the group is used; closing one, or
+    staging its problem again, makes the group refuse every launch (MsxError, MSX_ERR_STATE)."""
+
+    def __init__(self, contexts):
+        self.lib = load()
+        contexts = list(contexts)
+        arr = (C.c_void_p * len(contexts))(*[c.h for c in contexts])
+        h = C.c_void_p()
+        rc = self.lib.msx_group_create(arr, len(contexts), C.byref(h))
+        self.h = h
+        self.k = len(contexts)
+        if rc != MSX_OK:
+            msg = self.lib.msx_group_last_error(h).decode() if h else 'allocation failed'
+            if h:
+                self.lib.msx_group_destroy(h)
+                self.h = None
+            raise ValueError(msg) if rc == MSX_ERR_RANGE else MsxError(rc, msg)
+
+    def close(self):
+        if getattr(self, 'h', None):
+            self.lib.msx_group_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def check(self, rc):
+        if rc != MSX_OK:
+            msg = self.lib.msx_group_last_error(self.h).decode()
+            if rc == MSX_ERR_RANGE:
+                raise ValueError(msg)
+            raise MsxError(rc, msg)
+
+    def _counts(self, counts):
+        counts = np.ascontiguousarray(counts, dtype=np.int64)
+        if counts.shape != (self.k,):
+            raise ValueError('one walker count per member ({} given, {} members)'.format(counts.size, self.k))
+        return counts
+
+    def logprob_batch(self, theta, counts, mode=MODE_LOGPOST):
+        """theta [sum(counts)][ndim]: member 0's walkers first, then member 1's, ... -> (logp, status)."""
+        theta = as_f64(theta)
+        counts = self._counts(counts)
+        n, ndim = theta.shape
+        logp = np.empty(n)
+        status = np.empty(n, dtype=np.int32)
+        self.check(self.lib.msx_group_logprob_batch(self.h, int(mode), dptr(theta), iptr(counts), ndim, dptr(logp),
+                                                    status.ctypes.data_as(C.POINTER(C.c_int32))))
+        return logp, status
+
+    def logprob_batch_dev(self, d_theta_ptr, counts, ndim, d_logp_ptr, d_status_ptr, stream_ptr, mode=MODE_LOGPOST,
+                          block_threads=0):
+        counts = self._counts(counts)
+        self.check(self.lib.msx_group_logprob_batch_dev(self.h, int(mode), C.c_void_p(d_theta_ptr), iptr(counts), int(ndim),
+                                                        C.c_void_p(d_logp_ptr), C.c_void_p(d_status_ptr),
+                                                        C.c_void_p(stream_ptr), int(block_threads)))
+
+    def launch_info(self, counts, mode=MODE_LOGPOST, block_threads=0):
+        """What a launch of ``counts`` walkers per member would take (msx_group_launch_info), in Context.launch_info's keys."""
+        counts = self._counts(counts)
+        out = np.zeros(8, dtype=np.int64)
+        name = C.create_string_buffer(512)
+        self.check(self.lib.msx_group_launch_info(self.h, int(mode), iptr(counts), int(block_threads), name, 512, iptr(out)))
+        return {'kernel': name.value.decode(), 'form': FORM_NAMES[int(out[0])], 'form_id': int(out[0]), 'threads': int(out[1]),
+                'vgprs': int(out[2]), 'static_lds_bytes': int(out[3]), 'dynamic_lds_bytes': int(out[4]),
+                'requested_bytes_per_eval': int(out[5]), 'workgroups': int(out[6]), 'walkers_per_sub_batch': int(out[7])}

@@ -20,6 +20,8 @@
 //   recipe.h           phase 0: gates, isochrone, brackets, weights, prior and band terms
 //   median.h           exact median selects (block_median, logbin_median, radix fallback)
 //   logprob_kernel.h   the hot kernel and its variants (fused; linked = several workgroups per walker in one launch)
+//   logprob_body.h     the fused kernel's body, included as text by logprob_kernel and logprob_group_kernel
+//   group_kernel.h     target groups: the fused body over the walkers of several staged problems in one launch
 //   pair_kernel.h      the pair form: two walkers of one grid cell per workgroup, one set of row loads
 //   staging_kernels.h  CCM89, pair gather, band integrals, broadening, resample, composite, stream copy
 //   msx.hip            host context + the C ABI of include/msx.h
@@ -56,6 +58,7 @@
 #include "recipe.h"
 #include "median.h"
 #include "logprob_kernel.h"
+#include "group_kernel.h"
 #include "pair_kernel.h"
 #include "staging_kernels.h"
 #include "inpath_kernels.h"
@@ -149,8 +152,31 @@ struct msx_ctx {
     int32_t smp_overlap_policy = -1;   // msx_sampler_policy: -1 = overlap half-steps when the rule allows, 0 = never
     int32_t store_dtype = MSX_STORE_F64;  // msx_set_grid_storage: what the NEXT msx_stage_problem builds the R table in
     bool store_f32 = false;               // ... and what the staged problem holds
+    // target groups (msx_group_*): the problem's GENERATION, counted up whenever the staged problem is dropped (free_problem:
+    // restaging, grid staging, broadening, rotation, splitting) -- a group refuses a member whose generation moved -- and
+    // the groups this context belongs to (back-pointers: msx_destroy clears its slots in them, msx_group_destroy leaves)
+    uint64_t prob_gen = 0;
+    std::vector<struct msx_group *> groups;
 };
 static void sampler_free(msx_ctx *c);
+
+// A TARGET GROUP (include/msx.h): 1..MSX_MAX_GROUP staged contexts on one device whose walkers one launch of
+// logprob_group_kernel evaluates, each against its own member's problem.  The group owns snapshots of the members'
+// DevProblems and launch records in device memory; the tables they point to stay the members' own.
+struct msx_group {
+    int device = 0;
+    std::string err;
+    std::vector<msx_ctx *> members;       // nullptr: the member was destroyed (msx_destroy clears the slot)
+    std::vector<uint64_t> gen;            // the members' problem generations at msx_group_create
+    std::vector<DevProblem> probs;        // host copies of the snapshots (the launch plan reads them)
+    std::vector<char> pf_ok, pf256_ok;    // the members' LDS-staged-statics variants fit
+    int32_t nspec = 0;
+    int64_t cus = 256;
+    DevProblem *d_probs = nullptr;        // [k] the snapshots: sampler, probe, optimiser and in-path fields cleared
+    GroupMember *d_members = nullptr;     // [k] their launch records
+    void *h_pin = nullptr;                // pinned host staging of msx_group_logprob_batch
+    int64_t cap_walkers = 0;
+};
 
 namespace {
 
@@ -217,6 +243,7 @@ int dev_alloc_copy(msx_ctx *c, std::vector<void *> *track, const T *host, int64_
 
 void free_problem(msx_ctx *c) {
     sampler_free(c);  // a sampler in flight holds pointers into the problem's tables
+    ++c->prob_gen;    // (target groups holding a snapshot of the problem refuse this member from now on)
     for (void *p : c->prob_allocs) (void)hipFree(p);
     c->prob_allocs.clear();
     c->problem_staged = false;
@@ -664,6 +691,98 @@ LaunchPlan plan_launch(const msx_ctx *c, const FormChoice &f, int64_t n, int blo
     return pl;
 }
 
+// ---- target groups (group_kernel.h): the instances of logprob_group_kernel, in a table of their own -- the fused
+// entries of kVariants that a group can take (no GM, linked, in-path or float32 storage) -- except the three-per-CU
+// FULL one, which as a group instance spilled 36 bytes per lane to scratch: whole-trip members take the plain entry there
+// (same bits) ----------------------------------------------------------------------------------------------------------
+struct GroupVariant {
+    const void *fn;
+    int ns, threads;
+    bool sh, pf;
+    int full;
+    const char *what;
+};
+template <int NS, int T, bool SH, bool PF, int FULL = 0>
+GroupVariant group_variant(const char *what) {
+    return {(const void *)logprob_group_kernel<NS, T, SH, PF, FULL>, NS, T, SH, PF, FULL, what};
+}
+const GroupVariant kGroupVariants[] = {
+    //           NS  threads SH     PF    FULL
+    group_variant<2, 256, false, false>("three workgroups per CU"),
+    group_variant<2, 256, true, false>("two per CU, four pixels per lane and trip"),
+    group_variant<2, 256, true, true>("two per CU, u / flux staged in LDS during the recipe, four pixels per lane and trip"),
+    group_variant<2, 512, false, false>("one workgroup per CU, four pixels per lane and trip"),
+    group_variant<2, 512, true, false>("<= 128 VGPRs: two workgroups fit a CU; rows one star at a time"),
+    group_variant<2, 512, false, true>("one workgroup per CU, u / flux staged in LDS during the recipe, four pixels per lane and trip"),
+    group_variant<3, 256, false, false>("three workgroups per CU"),
+    group_variant<3, 512, false, false>("one workgroup per CU, four pixels per lane and trip"),
+    group_variant<3, 512, false, true>("one workgroup per CU, u / flux staged in LDS during the recipe, four pixels per lane and trip"),
+    group_variant<2, 256, true, false, 3>("two per CU, four pixels per lane and trip; whole trips, no clamps"),
+    group_variant<2, 256, true, true, 3>("two per CU, u / flux staged in LDS during the recipe, four pixels per lane and trip; whole trips, no clamps"),
+    group_variant<2, 512, false, true, 2>("one workgroup per CU, u / flux staged in LDS during the recipe, four pixels per lane and trip; whole trips, no clamps in the chi^2 pass"),
+    group_variant<2, 512, true, false, 2>("<= 128 VGPRs: two workgroups fit a CU; rows one star at a time; whole trips, no clamps in the chi^2 pass"),
+};
+
+struct GroupPlan {
+    const GroupVariant *v = nullptr;
+    size_t dyn_lds = 0;
+    int64_t bytes = 0;  // requested from the memory system per walker, averaged over the launch's walkers
+};
+
+// plan_launch's rules for the fused form, applied to (the launch's walkers, its longest member), restricted to the entries
+// every member with walkers can take: FULL only if every one of them is whole trips of it, PF only if every one's statics
+// fit (pf_ok / pf256_ok).  counts[m] = member m's walkers; total = their sum (> 0).
+GroupPlan plan_group_launch(const msx_group *g, const int64_t *counts, int64_t total, int block_threads, bool shared512) {
+    GroupPlan pl;
+    const int64_t cus = g->cus;
+    const int k = (int)g->members.size();
+    int64_t npix = 0;
+    bool pf = true, pf256 = true;
+    for (int m = 0; m < k; ++m)
+        if (counts[m] > 0) {
+            npix = std::max<int64_t>(npix, g->probs[m].npix);
+            pf = pf && g->pf_ok[m];
+            pf256 = pf256 && g->pf256_ok[m];
+        }
+    // (pick_block's rule)
+    const int B = block_threads > 0 ? block_threads
+                  : npix >= 8192 ? 512 : total <= cus ? 512 : npix <= 2048 ? 256 : total <= 2 * cus ? 512 : 256;
+    bool want_sh, want_pf;
+    if (B == 256) {
+        want_sh = total <= 2 * cus;
+        want_pf = want_sh && pf256;
+    } else {
+        const bool own_cu = total <= cus || sizeof(double) * (size_t)npix > 70 * 1024;
+        want_pf = !shared512 && own_cu && pf;
+        want_sh = !want_pf && (shared512 || !own_cu);
+    }
+    const int ns = g->nspec == 2 ? 2 : 3;
+    for (int attempt = 0; attempt < 2 && !pl.v; ++attempt) {
+        if (attempt == 1) want_sh = want_pf = false;  // triples have no SH variant
+        bool whole = true;
+        for (int m = 0; m < k; ++m)
+            if (counts[m] > 0) whole = whole && whole_trips(g->probs[m], 2 * (int64_t)B);
+        for (const GroupVariant &v : kGroupVariants)
+            if (v.ns == ns && v.threads == B && v.sh == want_sh && v.pf == want_pf && (v.full == 0 || whole) && (!pl.v || v.full != 0))
+                pl.v = &v;
+    }
+    if (!pl.v) return pl;
+    // dynamic LDS: the longest member's model vector; PF: the largest member's model vector + u and data flux in pairs
+    double bytes = 0.0;
+    for (int m = 0; m < k; ++m) {
+        if (counts[m] <= 0) continue;
+        const DevProblem &P = g->probs[m];
+        const size_t lds = pl.v->pf ? sizeof(double) * (size_t)((P.npix + 1) & ~1ll) + 2 * sizeof(double2) * (size_t)P.npair
+                                    : sizeof(double) * (size_t)P.npix;
+        pl.dyn_lds = std::max(pl.dyn_lds, lds);
+        // requested_bytes_of's fused-form count for this member
+        const int64_t b = P.npix * (12 * (int64_t)P.nspec * 4 + 12 + 16 + (pl.v->pf ? 8 : 24)) + 8 * (2 * P.nspec + 2) + 12;
+        bytes += (double)b * (double)counts[m];
+    }
+    pl.bytes = (int64_t)(bytes / (double)total + 0.5);
+    return pl;
+}
+
 // The pair form over A.n walkers (pair_kernel.h), in the planned variant.
 int launch_pair(msx_ctx *c, const DevProblem &P, const LaunchArgs &A, const LaunchPlan &pl) {
     // 1. the planner: every walker's recipe (one thread per walker), final values of the rejected / failed ones, and
@@ -694,6 +813,8 @@ hipError_t raise_all() {
     hipError_t e = hipSuccess;
     for (const Variant &v : kVariants)
         if (e == hipSuccess && !v.gm) e = raise_one(v.fn);
+    for (const GroupVariant &v : kGroupVariants)
+        if (e == hipSuccess) e = raise_one(v.fn);
     if (e == hipSuccess) e = raise_one((const void *)broaden_conv_kernel);
     if (e == hipSuccess) e = raise_one((const void *)rot_broaden_kernel<true>);
     return e;
@@ -812,6 +933,9 @@ void msx_destroy(msx_ctx *c) {
     if (c->rccl_comm && rccl().ok) (void)rccl().CommDestroy(c->rccl_comm);
     for (msx_ctx *p : c->loop_peers)  // a loopback group ends with its first member
         if (p != c) { p->loop_peers.clear(); p->comm_world = 0; p->comm_rank = 0; }
+    for (msx_group *g : c->groups)  // target groups outlive their members: the slot is cleared, the group refuses it
+        for (msx_ctx *&m : g->members)
+            if (m == c) m = nullptr;
     if (c->loop_eval_done) (void)hipEventDestroy(c->loop_eval_done);
     if (c->loop_copied) (void)hipEventDestroy(c->loop_copied);
     if (c->comm_stream) (void)hipStreamDestroy(c->comm_stream);
@@ -2365,6 +2489,214 @@ int msx_pair_stats(msx_ctx *c, int64_t *out2) {
     HIP_TRY(c, hipMemcpy(h, c->d_pair_plan, sizeof(h), hipMemcpyDeviceToHost));
     out2[0] = h[0];
     out2[1] = h[1];
+    return MSX_OK;
+}
+
+// ---- target groups (include/msx.h, group_kernel.h) -------------------------------------------------------------------
+static int gfail(msx_group *g, int code, const std::string &msg) {
+    if (g) g->err = msg;
+    return code;
+}
+#define GROUP_HIP_TRY(g, expr)                                                                     \
+    do {                                                                                           \
+        hipError_t e__ = (expr);                                                                   \
+        if (e__ != hipSuccess)                                                                     \
+            return gfail(g, MSX_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__));      \
+    } while (0)
+
+int msx_group_create(msx_ctx **ctxs, int32_t k, msx_group **out) {
+    if (!out) return MSX_ERR_INVALID;
+    msx_group *g = new msx_group();
+    *out = g;  // returned even on failure so the caller can read msx_group_last_error
+    if (!ctxs) return gfail(g, MSX_ERR_INVALID, "msx_group_create: null context list");
+    if (k < 1 || k > MSX_MAX_GROUP)
+        return gfail(g, MSX_ERR_RANGE, "msx_group_create: 1 to " + std::to_string(MSX_MAX_GROUP) + " members, " + std::to_string(k) + " given");
+    for (int m = 0; m < k; ++m) {
+        const msx_ctx *c = ctxs[m];
+        const std::string who = "msx_group_create: member " + std::to_string(m);
+        if (!c) return gfail(g, MSX_ERR_INVALID, who + " is a null context");
+        if (!c->problem_staged) return gfail(g, MSX_ERR_STATE, who + ": no problem staged");
+        if (c->device != ctxs[0]->device)
+            return gfail(g, MSX_ERR_STATE, who + " is on device " + std::to_string(c->device) + ", member 0 on device " +
+                                               std::to_string(ctxs[0]->device) + ": a group lives on one device");
+        if (c->P.nspec != ctxs[0]->P.nspec)
+            return gfail(g, MSX_ERR_RANGE, who + " has nspec = " + std::to_string(c->P.nspec) + ", member 0 nspec = " +
+                                               std::to_string(ctxs[0]->P.nspec) + ": the members of a group share nspec (and ndim)");
+        if (c->store_f32)
+            return gfail(g, MSX_ERR_STATE, who + " is staged with float32 grid storage (msx_set_grid_storage): groups take float64 tables only");
+        if (c->model_in_global)
+            return gfail(g, MSX_ERR_RANGE, who + " has " + std::to_string(c->P.npix) +
+                                               " pixels: groups take spectra of at most 17,152 pixels (the model vector in LDS)");
+    }
+    g->device = ctxs[0]->device;
+    g->nspec = ctxs[0]->P.nspec;
+    g->cus = ctxs[0]->prop.multiProcessorCount > 0 ? ctxs[0]->prop.multiProcessorCount : 256;
+    std::vector<GroupMember> recs((size_t)k);
+    for (int m = 0; m < k; ++m) {
+        msx_ctx *c = ctxs[m];
+        DevProblem q = c->P;
+        // the fused form's fields only: no sampler, clock probe, optimiser or in-path inputs
+        q.opt_flux = nullptr; q.opt_med = nullptr; q.opt_chain = nullptr;
+        q.smp_on = 0; q.smp_defer = 0; q.smp_coords = nullptr; q.smp_logp = nullptr; q.smp_q = nullptr;
+        q.smp_sidx = q.smp_cidx = q.smp_partner = nullptr;
+        q.smp_zz = q.smp_zfac = q.smp_logu = nullptr;
+        q.smp_rec = nullptr; q.smp_naccept = nullptr; q.smp_chain_row = q.smp_lp_row = nullptr; q.smp_worst = nullptr;
+        q.smp_overlap = 0; q.smp_stride = 0; q.smp_ver = nullptr; q.smp_gran = nullptr; q.smp_gwalkers = 0;
+        q.clk_probe = nullptr;
+        q.given = nullptr; q.given_stride = 0;
+        q.linked_fault = 0;
+        g->probs.push_back(q);
+        g->pf_ok.push_back(c->pf_ok);
+        g->pf256_ok.push_back(c->pf256_ok);
+        g->members.push_back(c);
+        g->gen.push_back(c->prob_gen);
+        GroupMember &r = recs[(size_t)m];
+        r.rblk = (const unsigned char *)c->d_recipe_block;
+        // (msx_logprob_batch_dev's packing)
+        r.niso_nt = (int)(std::min<int64_t>(q.niso, 0xffff) | ((int64_t)std::min<int64_t>(q.nt, 0x7fff) << 16));
+        r.ng_fast = (int)std::min<int64_t>(q.ng, 0xff) | ((c->recipe_fast ? 1 : 0) << 16) | ((q.dist_fit ? 1 : 0) << 18) |
+                    ((q.use_av ? 1 : 0) << 19);
+        r.tmin = q.tmin;
+        r.tmax = q.tmax;
+    }
+    GROUP_HIP_TRY(g, hipSetDevice(g->device));
+    GROUP_HIP_TRY(g, hipMalloc((void **)&g->d_probs, sizeof(DevProblem) * (size_t)k));
+    GROUP_HIP_TRY(g, hipMalloc((void **)&g->d_members, sizeof(GroupMember) * (size_t)k));
+    GROUP_HIP_TRY(g, hipMemcpy(g->d_probs, g->probs.data(), sizeof(DevProblem) * (size_t)k, hipMemcpyHostToDevice));
+    GROUP_HIP_TRY(g, hipMemcpy(g->d_members, recs.data(), sizeof(GroupMember) * (size_t)k, hipMemcpyHostToDevice));
+    for (msx_ctx *c : g->members)  // (back-pointers, once per context: a context may stand for several members)
+        if (std::find(c->groups.begin(), c->groups.end(), g) == c->groups.end()) c->groups.push_back(g);
+    return MSX_OK;
+}
+
+void msx_group_destroy(msx_group *g) {
+    if (!g) return;
+    for (msx_ctx *c : g->members)
+        if (c) c->groups.erase(std::remove(c->groups.begin(), c->groups.end(), g), c->groups.end());
+    (void)hipSetDevice(g->device);
+    if (g->d_probs) (void)hipFree(g->d_probs);
+    if (g->d_members) (void)hipFree(g->d_members);
+    if (g->h_pin) (void)hipHostFree(g->h_pin);
+    delete g;
+}
+
+const char *msx_group_last_error(msx_group *g) { return g ? g->err.c_str() : "null group"; }
+
+// Every member alive and still holding the problem the group snapshotted; the counts valid.  *total = their sum.
+static int group_check(msx_group *g, const char *who, int32_t mode, const int64_t *counts, int32_t ndim, int64_t *total) {
+    if (g->members.empty()) return gfail(g, MSX_ERR_STATE, std::string(who) + ": the group was not created");
+    for (size_t m = 0; m < g->members.size(); ++m) {
+        const msx_ctx *c = g->members[m];
+        if (!c)
+            return gfail(g, MSX_ERR_STATE, std::string(who) + ": member " + std::to_string(m) + " was destroyed (msx_destroy) before its group");
+        if (c->prob_gen != g->gen[m])
+            return gfail(g, MSX_ERR_STATE, std::string(who) + ": member " + std::to_string(m) +
+                                               "'s problem was dropped or staged again since msx_group_create; create the group again");
+    }
+    if (mode < MSX_MODE_LOGLIKE || mode > MSX_MODE_LOGPRIOR)
+        return gfail(g, MSX_ERR_INVALID, std::string(who) + ": mode must be MSX_MODE_LOGLIKE, _LOGPOST, _CHISQ or _LOGPRIOR");
+    if (ndim != 2 * g->nspec + 2)
+        return gfail(g, MSX_ERR_INVALID, "P0 doesn't match what I was expecting (ndim must be 2*nspec+2)");
+    if (!counts) return gfail(g, MSX_ERR_INVALID, std::string(who) + ": null counts");
+    int64_t t = 0;
+    for (size_t m = 0; m < g->members.size(); ++m) {
+        if (counts[m] < 0) return gfail(g, MSX_ERR_INVALID, std::string(who) + ": member " + std::to_string(m) + " has a negative walker count");
+        t += counts[m];
+        if (t > 0x7fffffff) return gfail(g, MSX_ERR_RANGE, std::string(who) + ": more than 2^31 - 1 walkers in one launch");
+    }
+    *total = t;
+    return MSX_OK;
+}
+
+int msx_group_logprob_batch_dev(msx_group *g, int32_t mode, const double *d_theta, const int64_t *counts, int32_t ndim,
+                                double *d_logp, int32_t *d_status, void *hip_stream, int32_t block_threads) {
+    if (!g) return MSX_ERR_INVALID;
+    int64_t total = 0;
+    if (int rc = group_check(g, "msx_group_logprob_batch", mode, counts, ndim, &total)) return rc;
+    if (total == 0) return MSX_OK;
+    if (!d_theta || !d_logp || !d_status) return gfail(g, MSX_ERR_INVALID, "msx_group_logprob_batch: bad arguments");
+    const bool shared512 = block_threads == MSX_BLOCK_512_SHARED;
+    if (shared512) block_threads = 512;
+    if (block_threads != 0 && block_threads != 256 && block_threads != 512)
+        return gfail(g, MSX_ERR_INVALID, "block_threads must be 0, 256, 512 or MSX_BLOCK_512_SHARED");
+    const GroupPlan pl = plan_group_launch(g, counts, total, block_threads, shared512);
+    if (!pl.v) return gfail(g, MSX_ERR_STATE, "no kernel variant for this group launch");
+    GroupStarts st;
+    st.k = (int32_t)g->members.size();
+    int64_t acc = 0;
+    for (int m = 0; m < st.k; ++m) { st.start[m] = (int32_t)acc; acc += counts[m]; }
+    for (int m = st.k; m <= MSX_MAX_GROUP; ++m) st.start[m] = (int32_t)acc;
+    // the kernel's arguments, in its own order
+    const double *a_theta = d_theta;
+    const void *a_members = g->d_members, *a_probs = g->d_probs;  // (read by the kernel through the constant address space)
+    int a_mode = mode;
+    int64_t a_n = total;
+    double *a_logp = d_logp;
+    int32_t *a_status = d_status;
+    void *args[] = {&a_theta, &a_members, &a_probs, &a_mode, &a_n, &st, &a_logp, &a_status};
+    GROUP_HIP_TRY(g, hipSetDevice(g->device));
+    GROUP_HIP_TRY(g, hipLaunchKernel(pl.v->fn, dim3((unsigned)total), dim3((unsigned)pl.v->threads), args, pl.dyn_lds, (hipStream_t)hip_stream));
+    return MSX_OK;
+}
+
+int msx_group_logprob_batch(msx_group *g, int32_t mode, const double *theta, const int64_t *counts, int32_t ndim,
+                            double *logp_out, int32_t *status_out) {
+    if (!g) return MSX_ERR_INVALID;
+    int64_t n = 0;
+    if (int rc = group_check(g, "msx_group_logprob_batch", mode, counts, ndim, &n)) return rc;
+    if (n == 0) return MSX_OK;
+    if (!theta || !logp_out || !status_out) return gfail(g, MSX_ERR_INVALID, "msx_group_logprob_batch: bad arguments");
+    GROUP_HIP_TRY(g, hipSetDevice(g->device));
+    if (n > g->cap_walkers) {  // (msx_logprob_batch's pinned staging: the kernel reads theta and writes its results there)
+        if (g->h_pin) (void)hipHostFree(g->h_pin);
+        g->h_pin = nullptr; g->cap_walkers = 0;
+        const int64_t cap = std::max<int64_t>(n, 1024);
+        GROUP_HIP_TRY(g, hipHostMalloc((void **)&g->h_pin, (sizeof(double) * (MSX_MAX_DIM + 1) + sizeof(int32_t)) * cap, hipHostMallocDefault));
+        g->cap_walkers = cap;
+    }
+    double *h_theta = reinterpret_cast<double *>(g->h_pin);
+    double *h_out = h_theta + g->cap_walkers * MSX_MAX_DIM;
+    int32_t *h_st = reinterpret_cast<int32_t *>(h_out + n);
+    memcpy(h_theta, theta, sizeof(double) * n * ndim);
+    hipStream_t s = g->members[0]->stream;  // member 0's stream
+    if (int rc = msx_group_logprob_batch_dev(g, mode, h_theta, counts, ndim, h_out, h_st, s, 0)) return rc;
+    GROUP_HIP_TRY(g, hipStreamSynchronize(s));
+    memcpy(logp_out, h_out, sizeof(double) * n);
+    memcpy(status_out, h_st, sizeof(int32_t) * n);
+    return MSX_OK;
+}
+
+int msx_group_launch_info(msx_group *g, int32_t mode, const int64_t *counts, int32_t block_threads, char *name, int32_t name_len,
+                          int64_t *out8) {
+    if (!g || !out8) return MSX_ERR_INVALID;
+    int64_t total = 0;
+    if (int rc = group_check(g, "msx_group_launch_info", mode, counts, 2 * g->nspec + 2, &total)) return rc;
+    if (total < 1) return gfail(g, MSX_ERR_INVALID, "msx_group_launch_info: no walkers");
+    const bool shared512 = block_threads == MSX_BLOCK_512_SHARED;
+    if (shared512) block_threads = 512;
+    if (block_threads != 0 && block_threads != 256 && block_threads != 512)
+        return gfail(g, MSX_ERR_INVALID, "block_threads must be 0, 256, 512 or MSX_BLOCK_512_SHARED");
+    const GroupPlan pl = plan_group_launch(g, counts, total, block_threads, shared512);
+    if (!pl.v) return gfail(g, MSX_ERR_STATE, "no kernel variant for this group launch");
+    const GroupVariant *v = pl.v;
+    const std::string nm = std::string("logprob_group_kernel<NS=") + std::to_string(v->ns) + ", " + std::to_string(v->threads) + " threads" +
+                           (v->pf && v->sh ? ", SH, PF" : v->pf ? ", PF" : v->sh ? ", SH" : "") +
+                           (v->full == 3 ? ", FULL" : v->full == 2 ? ", FULL(chi2 pass)" : "") + "> (" + v->what + ")";
+    GROUP_HIP_TRY(g, hipSetDevice(g->device));
+    hipFuncAttributes at;
+    GROUP_HIP_TRY(g, hipFuncGetAttributes(&at, v->fn));
+    out8[0] = MSX_FORM_FUSED;
+    out8[1] = v->threads;
+    out8[2] = at.numRegs;
+    out8[3] = (int64_t)at.sharedSizeBytes;
+    out8[4] = (int64_t)pl.dyn_lds;
+    out8[5] = pl.bytes;
+    out8[6] = total;
+    out8[7] = total;
+    if (name && name_len > 0) {
+        strncpy(name, nm.c_str(), (size_t)name_len - 1);
+        name[name_len - 1] = 0;
+    }
     return MSX_OK;
 }
 

@@ -1,0 +1,199 @@
+"""Target groups: several staged targets evaluated in one launch, and a sampler that steps their ensembles together.
+
+``TargetGroup(engines)`` wraps ``msx_group`` (include/msx.h): each ``Engine`` keeps its own grid and problem -- data,
+bands, priors and grid may all differ, ``nspec`` must not -- and one launch evaluates every target's walkers, one
+workgroup per walker, each against its own target.  Walker i of target k gets the bits ``engines[k]`` gives it alone.
+
+``GroupSampler`` runs K stretch-move ensembles in lock-step from the host: per half-step, every target's proposals go
+through ONE batched call ``f(list_of_thetas) -> list_of_logp`` (``TargetGroup.logposterior``: one launch).  Each target
+draws its randomness from its own ``EnsembleSampler`` state, so target k's chain is bit for bit the chain of
+``EnsembleSampler(nwalkers[k], ndim, f_k, vectorize=True, seed=seeds[k])`` run alone.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import _lib
+from .engine import _raise_for_status
+from .sampler import EnsembleSampler, State
+
+
+class TargetGroup:
+    """The walkers of several staged ``Engine``s in one launch.  ``thetas`` is a sequence of K arrays ``(nw_k, ndim)``
+    (``nw_k`` may be 0); results are a list of K arrays.  The engines must stay open and staged: a target staged again,
+    or closed, makes the group refuse every launch (create a new one)."""
+
+    def __init__(self, engines):
+        self.engines = list(engines)
+        if not self.engines:
+            raise ValueError('TargetGroup: at least one engine')
+        for k, e in enumerate(self.engines):
+            if e.tables is None:
+                raise RuntimeError('TargetGroup: target {} has no staged problem'.format(k))
+        self.ndim = self.engines[0].ndim
+        self.group = _lib.Group([e.ctx for e in self.engines])
+
+    def __len__(self):
+        return len(self.engines)
+
+    def _stack(self, thetas):
+        if len(thetas) != len(self.engines):
+            raise ValueError('one array of walkers per target ({} given, {} targets)'.format(len(thetas), len(self.engines)))
+        arrs = []
+        for t in thetas:
+            a = np.asarray(t, dtype=float).reshape(-1, self.ndim) if np.size(t) == 0 else np.asarray(t, dtype=float)
+            if a.ndim != 2 or a.shape[1] != self.ndim:
+                raise ValueError("P0 doesn't match what I was expecting")  # (Engine's message, mft6.py:1457)
+            arrs.append(a)
+        counts = np.array([a.shape[0] for a in arrs], dtype=np.int64)
+        theta = np.concatenate(arrs) if counts.sum() else np.empty((0, self.ndim))
+        return arrs, counts, theta
+
+    def _eval(self, thetas, mode):
+        arrs, counts, theta = self._stack(thetas)
+        if theta.shape[0] == 0:
+            return [np.empty(0) for _ in arrs]
+        logp, status = self.group.logprob_batch(theta, counts, mode)
+        out, o = [], 0
+        for k, a in enumerate(arrs):
+            st = status[o:o + len(a)]
+            try:
+                _raise_for_status(st, a)
+            except (KeyError, IndexError, ValueError, RuntimeError) as e:
+                raise type(e)('target {}: {}'.format(k, e.args[0] if e.args else e)) from None
+            out.append(logp[o:o + len(a)].copy())
+            o += len(a)
+        return out
+
+    def logposterior(self, thetas):
+        return self._eval(thetas, _lib.MODE_LOGPOST)
+
+    def logprior(self, thetas):
+        return self._eval(thetas, _lib.MODE_LOGPRIOR)
+
+    def loglikelihood(self, thetas, optimize=False):
+        return self._eval(thetas, _lib.MODE_CHISQ if optimize else _lib.MODE_LOGLIKE)
+
+    def launch_info(self, counts, mode=_lib.MODE_LOGPOST, block_threads=0):
+        """What one launch of ``counts[k]`` walkers of target k would take (kernel, resources, workgroups)."""
+        return self.group.launch_info(counts, mode, block_threads)
+
+    def close(self):
+        self.group.close()
+
+
+class GroupSampler:
+    """K stretch-move ensembles stepped in lock-step, one batched call per half-step.
+
+    ``nwalkers`` and ``seeds``: one entry per target.  ``log_prob_fn(list_of_thetas) -> list_of_logp`` evaluates K arrays
+    ``(n_k, ndim)`` at once (``TargetGroup.logposterior``, or any host function for tests)."""
+
+    def __init__(self, nwalkers, ndim, log_prob_fn, a=2.0, seeds=None):
+        nwalkers = [int(n) for n in nwalkers]
+        seeds = [None] * len(nwalkers) if seeds is None else list(seeds)
+        if len(seeds) != len(nwalkers):
+            raise ValueError('one seed per target')
+        self.ndim = int(ndim)
+        self.log_prob_fn = log_prob_fn
+        # one EnsembleSampler per target holds its generators and its bookkeeping; its own log_prob_fn is never called
+        self.samplers = [EnsembleSampler(n, ndim, None, a=a, vectorize=True, seed=s) for n, s in zip(nwalkers, seeds)]
+
+    @property
+    def nwalkers(self):
+        return [s.nwalkers for s in self.samplers]
+
+    def reset(self):
+        for s in self.samplers:
+            s.reset()
+
+    def compute_log_prob(self, coords):
+        """``log_prob_fn`` over K arrays, with ``EnsembleSampler.compute_log_prob``'s checks per target."""
+        coords = [np.asarray(c, dtype=float) for c in coords]
+        for c in coords:
+            if np.any(~np.isfinite(c)):
+                raise ValueError('At least one parameter value was infinite or NaN')
+        lps = self.log_prob_fn(coords)
+        if len(lps) != len(coords):
+            raise ValueError('log_prob_fn returned the wrong number of targets')
+        out = []
+        for c, lp in zip(coords, lps):
+            lp = np.asarray(lp, dtype=float)
+            if lp.shape != (len(c),):
+                raise ValueError('log_prob_fn returned the wrong shape')
+            if np.any(np.isnan(lp)):
+                raise ValueError('Probability function returned NaN')
+            out.append(lp)
+        return out
+
+    def _stretch_step(self, coords, logp):
+        """One iteration of every target: EnsembleSampler._stretch_step's arithmetic, the K targets' half-steps batched."""
+        draws = [s._draw_split(1) + s._draw_moves(1) for s in self.samplers]
+        accepted = [np.zeros(s.nwalkers, dtype=bool) for s in self.samplers]
+        for h in (0, 1):
+            qs, moves = [], []
+            for k, (sidx, cidx, part, zz_, zfac_, logu_) in enumerate(draws):
+                s_idx, c_idx, zz, partner_idx = sidx[0, h], cidx[0, h], zz_[0, h], part[0, h]
+                s, c = coords[k][s_idx], coords[k][c_idx]
+                partner = c[partner_idx]
+                qs.append(partner - (partner - s) * zz[:, None])
+                moves.append((s_idx, zfac_[0, h], logu_[0, h]))
+            new_lps = self.compute_log_prob(qs)
+            for k, ((s_idx, zfac, logu), q, new_lp) in enumerate(zip(moves, qs, new_lps)):
+                with np.errstate(invalid='ignore'):  # -inf - -inf = nan -> compares False -> rejected
+                    lnpdiff = zfac + new_lp - logp[k][s_idx]
+                acc = logu < lnpdiff
+                coords[k][s_idx[acc]] = q[acc]
+                logp[k][s_idx[acc]] = new_lp[acc]
+                accepted[k][s_idx[acc]] = True
+        return accepted
+
+    def sample(self, initial_states, iterations=1, store=True):
+        """``initial_states``: one State or coordinate array ``(nwalkers[k], ndim)`` per target.  Yields a list of K States
+        per iteration."""
+        if len(initial_states) != len(self.samplers):
+            raise ValueError('one initial state per target')
+        coords, logp, missing = [], [], []
+        for k, (st, smp) in enumerate(zip(initial_states, self.samplers)):
+            if isinstance(st, State):
+                c, lp = st.coords.copy(), st.log_prob.copy()
+            else:
+                c, lp = np.array(st, dtype=float), None
+            if c.shape != (smp.nwalkers, self.ndim):
+                raise ValueError('incompatible input dimensions (target {})'.format(k))
+            if lp is None or lp.shape != (smp.nwalkers,):
+                missing.append(k)
+            coords.append(c)
+            logp.append(lp)
+        if missing:  # (one batched call for every target that came without its log-probabilities)
+            for k, lp in zip(missing, self.compute_log_prob([coords[k] for k in missing])):
+                logp[k] = lp
+        for _ in range(int(iterations)):
+            acc = self._stretch_step(coords, logp)
+            states = []
+            for k, smp in enumerate(self.samplers):
+                smp._accepted += acc[k]
+                smp.iteration += 1
+                if store:
+                    smp._chain.append(coords[k].copy())
+                    smp._logp.append(logp[k].copy())
+                smp._last = State(coords[k], logp[k])
+                states.append(smp._last)
+            yield states
+
+    def run_mcmc(self, initial_states, nsteps, **kw):
+        st = None
+        for st in self.sample(initial_states, iterations=nsteps, **kw):
+            pass
+        return st
+
+    def get_chain(self, k, **kw):
+        """Target k's chain, (nsteps, nwalkers[k], ndim) (``EnsembleSampler.get_chain``'s keywords)."""
+        return self.samplers[k].get_chain(**kw)
+
+    def get_log_prob(self, k, **kw):
+        return self.samplers[k].get_log_prob(**kw)
+
+    @property
+    def acceptance_fraction(self):
+        """One array per target."""
+        return [s.acceptance_fraction for s in self.samplers]

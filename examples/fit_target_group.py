@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
 """Several synthetic targets fitted together: one staged problem per target (each its own Engine), their walkers
-evaluated in ONE launch per half-step (TargetGroup), their ensembles stepped in lock-step (GroupSampler).
+evaluated in ONE launch per half-step (TargetGroup), their ensembles stepped in lock-step (GroupSampler; with --device
+the ensembles stay on the GPU, DeviceGroupSampler: no host round trip between half-steps, same chains).
 
 Every target gets its own data spectrum (a binary at its own truth, its own pixel count and noise) on one synthetic grid.
 Target k's chain is the chain a separate EnsembleSampler with target k's seed would walk.
 
-    python examples/fit_target_group.py --targets 4 --nwalkers 32 --nsteps 200
+    python examples/fit_target_group.py --targets 4 --nwalkers 32 --nsteps 200 [--device]
 """
 import argparse
 import os
@@ -23,12 +24,13 @@ def main():
     ap.add_argument('--nwalkers', type=int, default=32)
     ap.add_argument('--nsteps', type=int, default=200)
     ap.add_argument('--seed', type=int, default=1)
+    ap.add_argument('--device', action='store_true', help='keep the ensembles on the GPU (DeviceGroupSampler)')
     args = ap.parse_args()
 
     from scipy.interpolate import interp1d
     from mcmc_spec_amd import bands, synth
     from mcmc_spec_amd.engine import Engine
-    from mcmc_spec_amd.group import GroupSampler, TargetGroup
+    from mcmc_spec_amd.group import DeviceGroupSampler, GroupSampler, TargetGroup
     from oracle import mft6_oracle as orc
 
     rng = np.random.default_rng(args.seed)
@@ -67,7 +69,11 @@ def main():
     group = TargetGroup(engines)
     print('one launch:', group.launch_info([args.nwalkers] * args.targets)['kernel'])
     p0s = [truths[k] + 1e-3 * np.abs(truths[k]) * rng.normal(size=(args.nwalkers, 6)) for k in range(args.targets)]
-    sampler = GroupSampler([args.nwalkers] * args.targets, 6, group.logposterior, seeds=[args.seed + k for k in range(args.targets)])
+    seeds = [args.seed + k for k in range(args.targets)]
+    if args.device:
+        sampler = DeviceGroupSampler([args.nwalkers] * args.targets, 6, group, seeds=seeds)
+    else:
+        sampler = GroupSampler([args.nwalkers] * args.targets, 6, group.logposterior, seeds=seeds)
     t0 = time.time()
     sampler.run_mcmc(p0s, args.nsteps)
     dt = time.time() - t0

@@ -377,7 +377,7 @@ int msx_pair_stats(msx_ctx *ctx, int64_t *out2);
  * differ); they must share nspec (so ndim).  A launch evaluates a batch whose walkers come in contiguous blocks: the
  * first counts[0] are member 0's, the next counts[1] member 1's, ... (a count may be 0).  One workgroup per walker, the
  * fused form's; walker i of member m gets the bits and the status member m's own msx_logprob_batch gives it.  Modes
- * MSX_MODE_LOGLIKE, _LOGPOST, _CHISQ and _LOGPRIOR; no sampler, pair, linked or in-path form.
+ * MSX_MODE_LOGLIKE, _LOGPOST, _CHISQ and _LOGPRIOR; no pair, linked or in-path form (the group's own sampler: below).
  * msx_group_create snapshots the members' staged problems (the tables stay theirs: keep the contexts alive).  Refused
  * there, naming the member: float32 grid storage (MSX_ERR_STATE), spectra over 17,152 pixels (MSX_ERR_RANGE), unequal
  * nspec (MSX_ERR_RANGE), members on different devices or without a problem (MSX_ERR_STATE).  A launch after a member's
@@ -399,6 +399,30 @@ int msx_group_logprob_batch_dev(msx_group *group, int32_t mode, const double *d_
  * launch's walkers, out8[6] = out8[7] = all walkers (one launch, no sub-batches) */
 int msx_group_launch_info(msx_group *group, int32_t mode, const int64_t *counts, int32_t block_threads, char *name,
                           int32_t name_len, int64_t *out8);
+/* ---- a target group's DEVICE-RESIDENT SAMPLER: msx_sampler_begin / _enqueue / _collect / _end over
+ * a group.  One resident ensemble -- the members' walkers concatenated in member order, counts[m] of member m -- and per
+ * half-step exactly ONE launch of the group kernel over the active half of every member's ensemble; no host round trip
+ * between half-steps.  The chain of member m is the chain msx_sampler_* gives member m's context alone, fed the same
+ * randomness.  counts[m] is even and >= 2 (MSX_ERR_INVALID), mode MSX_MODE_LOGPOST or _LOGLIKE; a member restaged or
+ * destroyed since msx_group_create is refused (MSX_ERR_STATE).  Memory: besides the state and two slots as
+ * msx_sampler_begin's, 2 * max_chunk_steps * 2 * k snapshots of the members' problems (about 1.2 KB each).
+ * coords [sum counts][ndim], logp [sum counts], naccept [sum counts] or NULL (zeros).  A run still open ends.         */
+int msx_group_sampler_begin(msx_group *group, int32_t mode, const int64_t *counts, int32_t ndim, int64_t max_chunk_steps,
+                            const double *coords, const double *logp, const int64_t *naccept);
+/* one chunk of nsteps <= max_chunk_steps iterations into slot 0|1, without waiting for it.  Each array is
+ * [nsteps][2][sum counts / 2] in msx_sampler_enqueue's layout, its walker axis the members' active halves side by side
+ * (member 0's counts[0] / 2 entries, then member 1's, ...); the indices are MEMBER-LOCAL (sidx, cidx < counts[m],
+ * partner < counts[m] / 2) and range-checked (MSX_ERR_INVALID, nothing queued).  A member restaged or destroyed during the
+ * run makes this fail with MSX_ERR_STATE; after that, and after any failure that queued part of a chunk, only
+ * msx_group_sampler_end is accepted.                                                                                   */
+int msx_group_sampler_enqueue(msx_group *group, int32_t slot, int64_t nsteps, const int32_t *sidx, const int32_t *cidx,
+                              const int32_t *partner, const double *zz, const double *zfac, const double *logu);
+/* waits for the chunk in `slot`: chain_out [nsteps][sum counts][ndim], logp_out [nsteps][sum counts], naccept [sum counts]
+ * (cumulative over the run), worst_status [k] (the worst walker status of each member's walkers in the chunk)          */
+int msx_group_sampler_collect(msx_group *group, int32_t slot, double *chain_out, double *logp_out, int64_t *naccept,
+                              int32_t *worst_status);
+/* ends the run (waits for it); coords / logp (may be NULL) receive the final state.  msx_group_destroy also ends it.  */
+int msx_group_sampler_end(msx_group *group, double *coords, double *logp);
 
 /* ---- test hooks (used by tests/ only) ------------------------------------------------------------ */
 /* MSX_HOOK_LINKED_FAULT: value != 0 makes the workgroups of the linked form skip their signal -- and the walkers of an

@@ -146,6 +146,11 @@ def load():
         'msx_group_logprob_batch': (C.c_int, [vp, C.c_int32, _dp, _ip, C.c_int32, _dp, C.POINTER(C.c_int32)]),
         'msx_group_logprob_batch_dev': (C.c_int, [vp, C.c_int32, vp, _ip, C.c_int32, vp, vp, vp, C.c_int32]),
         'msx_group_launch_info': (C.c_int, [vp, C.c_int32, _ip, C.c_int32, C.c_char_p, C.c_int32, _ip]),
+        'msx_group_sampler_begin': (C.c_int, [vp, C.c_int32, _ip, C.c_int32, C.c_int64, _dp, _dp, _ip]),
+        'msx_group_sampler_enqueue': (C.c_int, [vp, C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                                C.POINTER(C.c_int32), _dp, _dp, _dp]),
+        'msx_group_sampler_collect': (C.c_int, [vp, C.c_int32, _dp, _dp, _ip, C.POINTER(C.c_int32)]),
+        'msx_group_sampler_end': (C.c_int, [vp, _dp, _dp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = header/library skew, fail loudly
@@ -164,7 +169,8 @@ EXPORTED = ['msx_create', 'msx_destroy', 'msx_last_error', 'msx_device_info', 'm
             'msx_comm_init_loopback', 'msx_sampler_enqueue_group',
             'msx_stream_copy_gbps', 'msx_bytes_per_eval', 'msx_launch_info', 'msx_last_form', 'msx_test_hook', 'msx_pair_stats', 'msx_sampler_overlapped', 'msx_sampler_policy',
             'msx_group_create', 'msx_group_destroy', 'msx_group_last_error', 'msx_group_logprob_batch',
-            'msx_group_logprob_batch_dev', 'msx_group_launch_info']
+            'msx_group_logprob_batch_dev', 'msx_group_launch_info', 'msx_group_sampler_begin', 'msx_group_sampler_enqueue',
+            'msx_group_sampler_collect', 'msx_group_sampler_end']
 
 
 def as_f64(a):
@@ -598,3 +604,50 @@ class Group:
         return {'kernel': name.value.decode(), 'form': FORM_NAMES[int(out[0])], 'form_id': int(out[0]), 'threads': int(out[1]),
                 'vgprs': int(out[2]), 'static_lds_bytes': int(out[3]), 'dynamic_lds_bytes': int(out[4]),
                 'requested_bytes_per_eval': int(out[5]), 'workgroups': int(out[6]), 'walkers_per_sub_batch': int(out[7])}
+
+    # ---- the group's device-resident sampler (msx_group_sampler_*) ----
+    def sampler_begin(self, mode, coords, logp, counts, max_chunk_steps, naccept=None):
+        """Start a run over the group (msx_group_sampler_begin): coords [sum(counts)][ndim] and logp [sum(counts)], member
+        0's walkers first."""
+        coords, logp = as_f64(coords), as_f64(logp)
+        counts = self._counts(counts)
+        n, ndim = coords.shape
+        if logp.shape != (n,) or int(counts.sum()) != n:
+            raise ValueError('sampler_begin: coords, logp and counts disagree')
+        nacc = None if naccept is None else np.ascontiguousarray(naccept, dtype=np.int64)
+        self.check(self.lib.msx_group_sampler_begin(self.h, int(mode), iptr(counts), ndim, int(max_chunk_steps), dptr(coords),
+                                                    dptr(logp), None if nacc is None else iptr(nacc)))
+        self._smp_shape = (n, ndim)
+
+    def sampler_enqueue(self, slot, sidx, cidx, partner, zz, zfac, logu):
+        """Queue one chunk: arrays (nsteps, 2, sum(counts)/2), the members' active halves side by side, indices member-local."""
+        i32p = C.POINTER(C.c_int32)
+        arrs = [np.ascontiguousarray(a, dtype=np.int32) for a in (sidx, cidx, partner)]
+        dbl = [as_f64(a) for a in (zz, zfac, logu)]
+        nsteps = dbl[0].shape[0]
+        for a in arrs + dbl:
+            if a.shape != (nsteps, 2, self._smp_shape[0] // 2):
+                raise ValueError('sampler_enqueue: arrays must have shape (nsteps, 2, sum(counts)/2)')
+        self.check(self.lib.msx_group_sampler_enqueue(self.h, int(slot), nsteps, arrs[0].ctypes.data_as(i32p),
+                                                      arrs[1].ctypes.data_as(i32p), arrs[2].ctypes.data_as(i32p),
+                                                      dptr(dbl[0]), dptr(dbl[1]), dptr(dbl[2])))
+        return nsteps
+
+    def sampler_collect(self, slot, nsteps):
+        """Wait for the chunk in `slot`: (chain [nsteps][n][ndim], logp [nsteps][n], naccept [n], worst [k])."""
+        n, ndim = self._smp_shape
+        chain, lpc = np.empty((nsteps, n, ndim)), np.empty((nsteps, n))
+        nacc = np.zeros(n, dtype=np.int64)
+        worst = np.zeros(self.k, dtype=np.int32)
+        self.check(self.lib.msx_group_sampler_collect(self.h, int(slot), dptr(chain), dptr(lpc), iptr(nacc),
+                                                      worst.ctypes.data_as(C.POINTER(C.c_int32))))
+        return chain, lpc, nacc, worst
+
+    def sampler_end(self, want_state=False):
+        if not want_state:
+            self.check(self.lib.msx_group_sampler_end(self.h, None, None))
+            return None
+        n, ndim = self._smp_shape
+        coords, logp = np.empty((n, ndim)), np.empty(n)
+        self.check(self.lib.msx_group_sampler_end(self.h, dptr(coords), dptr(logp)))
+        return coords, logp

@@ -41,21 +41,30 @@ __device__ __forceinline__ int group_member_of(const GroupStarts &st, int32_t wk
 }
 
 // One workgroup per walker of the whole group, the fused kernel's launch shape and launch bounds, and its body
-// (logprob_body.h) over the walker's member.  No sampler, probe, GM, linked or in-path bits: the group's snapshots have
-// those fields cleared (msx_group_create) and the packed word carries none of them.  (The names the body declares are
-// its own: what this kernel adds is prefixed g_.)
-template <int NS, int MAXT, bool SH = false, bool PF = false, int FULL = 0>
+// (logprob_body.h) over the walker's member.  No probe, GM, linked or in-path bits: the group's snapshots have those
+// fields cleared (msx_group_create) and the packed word carries none of them.  (The names the body declares are its own:
+// what this kernel adds is prefixed g_.)
+// SMP = a half-step of the group's device-resident sampler (msx_group_sampler_*): the packed word gets the sampler bit,
+// `theta` is the group's resident ensemble and g_smp_rec the half-step's records, whose si / ci are GROUP-level ensemble
+// indices (member offset + local index); g_probs is the set of member snapshots built for this (slot, step, half) at
+// msx_group_sampler_begin, whose sampler fields point at the group's arrays.  The plain instances (SMP = false) ignore
+// g_smp_rec: their body is compiled with the sampler path off, as before.
+template <int NS, int MAXT, bool SH = false, bool PF = false, int FULL = 0, bool SMP = false>
 __global__ void __launch_bounds__(MAXT, MAXT == 256 ? (SH ? 2 : 3) : (MAXT == 512 && SH) ? 4 : 1)
 logprob_group_kernel(const double *theta, ConstGroupMember *__restrict__ g_members, ConstDevProblem *__restrict__ g_probs,
-                     int g_mode, int64_t n, GroupStarts g_st, double *__restrict__ logp, int32_t *__restrict__ status) {
+                     int g_mode, int64_t n, GroupStarts g_st, double *__restrict__ logp, int32_t *__restrict__ status,
+                     const SmpRec *__restrict__ g_smp_rec) {
     constexpr bool GM = false, LK = false, R32 = false, GIVEN = false;
     const int g_m = group_member_of(g_st, (int32_t)blockIdx.x);
     ConstGroupMember *const g_rec = g_members + g_m;
     // what logprob_kernel receives as its leading arguments, from the member's launch record
     const unsigned char *const rblk = g_rec->rblk;
-    const int niso_nt = g_rec->niso_nt, ng_mode_fast = g_rec->ng_fast | (g_mode << 8);
+    // (the sampler's instances: ng, fast, dist_fit and use_av of the record only -- no overlap or probe bits, whose paths the
+    // compiler then drops -- and the sampler bit)
+    const int niso_nt = g_rec->niso_nt;
+    const int ng_mode_fast = SMP ? (g_rec->ng_fast & 0xd00ff) | (g_mode << 8) | (1 << 17) : g_rec->ng_fast | (g_mode << 8);
     const double gate_tmin = g_rec->tmin, gate_tmax = g_rec->tmax;
-    const SmpRec *const smp_rec = nullptr;
+    const SmpRec *const smp_rec = SMP ? g_smp_rec : nullptr;
     const DevProblem &P = *(const DevProblem *)(g_probs + g_m);
 #include "logprob_body.h"
 }

@@ -176,7 +176,10 @@ struct msx_group {
     GroupMember *d_members = nullptr;     // [k] their launch records
     void *h_pin = nullptr;                // pinned host staging of msx_group_logprob_batch
     int64_t cap_walkers = 0;
+    struct GroupRun *run = nullptr;       // the device-resident sampler in flight (msx_group_sampler_begin .. _end)
 };
+static void group_run_drain(msx_group *g);
+static void group_run_free(msx_group *g);
 
 namespace {
 
@@ -243,6 +246,7 @@ int dev_alloc_copy(msx_ctx *c, std::vector<void *> *track, const T *host, int64_
 
 void free_problem(msx_ctx *c) {
     sampler_free(c);  // a sampler in flight holds pointers into the problem's tables
+    for (msx_group *g : c->groups) group_run_drain(g);  // ... and so does a group's (its next enqueue is refused)
     ++c->prob_gen;    // (target groups holding a snapshot of the problem refuse this member from now on)
     for (void *p : c->prob_allocs) (void)hipFree(p);
     c->prob_allocs.clear();
@@ -697,22 +701,27 @@ LaunchPlan plan_launch(const msx_ctx *c, const FormChoice &f, int64_t n, int blo
 // (same bits) ----------------------------------------------------------------------------------------------------------
 struct GroupVariant {
     const void *fn;
+    const void *smp_fn;  // the same entry as a half-step of the group's device-resident sampler (SMP)
     int ns, threads;
     bool sh, pf;
     int full;
     const char *what;
 };
-template <int NS, int T, bool SH, bool PF, int FULL = 0>
+// SMP = false: no sampler instance of this entry -- as one it spilled 36 bytes per lane to scratch (the sampler's scalars
+// on top of the member lookup's); the group's sampler takes a neighbour there (group_smp_variant, same bits)
+template <int NS, int T, bool SH, bool PF, int FULL = 0, bool SMP = true>
 GroupVariant group_variant(const char *what) {
-    return {(const void *)logprob_group_kernel<NS, T, SH, PF, FULL>, NS, T, SH, PF, FULL, what};
+    const void *smp = nullptr;
+    if constexpr (SMP) smp = (const void *)logprob_group_kernel<NS, T, SH, PF, FULL, true>;
+    return {(const void *)logprob_group_kernel<NS, T, SH, PF, FULL>, smp, NS, T, SH, PF, FULL, what};
 }
 const GroupVariant kGroupVariants[] = {
     //           NS  threads SH     PF    FULL
     group_variant<2, 256, false, false>("three workgroups per CU"),
     group_variant<2, 256, true, false>("two per CU, four pixels per lane and trip"),
-    group_variant<2, 256, true, true>("two per CU, u / flux staged in LDS during the recipe, four pixels per lane and trip"),
+    group_variant<2, 256, true, true, 0, false>("two per CU, u / flux staged in LDS during the recipe, four pixels per lane and trip"),
     group_variant<2, 512, false, false>("one workgroup per CU, four pixels per lane and trip"),
-    group_variant<2, 512, true, false>("<= 128 VGPRs: two workgroups fit a CU; rows one star at a time"),
+    group_variant<2, 512, true, false, 0, false>("<= 128 VGPRs: two workgroups fit a CU; rows one star at a time"),
     group_variant<2, 512, false, true>("one workgroup per CU, u / flux staged in LDS during the recipe, four pixels per lane and trip"),
     group_variant<3, 256, false, false>("three workgroups per CU"),
     group_variant<3, 512, false, false>("one workgroup per CU, four pixels per lane and trip"),
@@ -720,7 +729,7 @@ const GroupVariant kGroupVariants[] = {
     group_variant<2, 256, true, false, 3>("two per CU, four pixels per lane and trip; whole trips, no clamps"),
     group_variant<2, 256, true, true, 3>("two per CU, u / flux staged in LDS during the recipe, four pixels per lane and trip; whole trips, no clamps"),
     group_variant<2, 512, false, true, 2>("one workgroup per CU, u / flux staged in LDS during the recipe, four pixels per lane and trip; whole trips, no clamps in the chi^2 pass"),
-    group_variant<2, 512, true, false, 2>("<= 128 VGPRs: two workgroups fit a CU; rows one star at a time; whole trips, no clamps in the chi^2 pass"),
+    group_variant<2, 512, true, false, 2, false>("<= 128 VGPRs: two workgroups fit a CU; rows one star at a time; whole trips, no clamps in the chi^2 pass"),
 };
 
 struct GroupPlan {
@@ -732,6 +741,7 @@ struct GroupPlan {
 // plan_launch's rules for the fused form, applied to (the launch's walkers, its longest member), restricted to the entries
 // every member with walkers can take: FULL only if every one of them is whole trips of it, PF only if every one's statics
 // fit (pf_ok / pf256_ok).  counts[m] = member m's walkers; total = their sum (> 0).
+GroupPlan group_plan_lds(const msx_group *g, const int64_t *counts, int64_t total, const GroupVariant *v);
 GroupPlan plan_group_launch(const msx_group *g, const int64_t *counts, int64_t total, int block_threads, bool shared512) {
     GroupPlan pl;
     const int64_t cus = g->cus;
@@ -767,6 +777,14 @@ GroupPlan plan_group_launch(const msx_group *g, const int64_t *counts, int64_t t
                 pl.v = &v;
     }
     if (!pl.v) return pl;
+    return group_plan_lds(g, counts, total, pl.v);
+}
+
+// the plan's dynamic LDS and bytes for entry v
+GroupPlan group_plan_lds(const msx_group *g, const int64_t *counts, int64_t total, const GroupVariant *v) {
+    GroupPlan pl;
+    pl.v = v;
+    const int k = (int)g->members.size();
     // dynamic LDS: the longest member's model vector; PF: the largest member's model vector + u and data flux in pairs
     double bytes = 0.0;
     for (int m = 0; m < k; ++m) {
@@ -813,8 +831,10 @@ hipError_t raise_all() {
     hipError_t e = hipSuccess;
     for (const Variant &v : kVariants)
         if (e == hipSuccess && !v.gm) e = raise_one(v.fn);
-    for (const GroupVariant &v : kGroupVariants)
+    for (const GroupVariant &v : kGroupVariants) {
         if (e == hipSuccess) e = raise_one(v.fn);
+        if (e == hipSuccess && v.smp_fn) e = raise_one(v.smp_fn);
+    }
     if (e == hipSuccess) e = raise_one((const void *)broaden_conv_kernel);
     if (e == hipSuccess) e = raise_one((const void *)rot_broaden_kernel<true>);
     return e;
@@ -1731,20 +1751,49 @@ struct SamplerRun {
         int64_t nsteps = 0;
         bool busy = false;
     } slot[2];
+    // The ensemble's members: the context's run has one; a target group's run (msx_group_sampler_*) one per target, their
+    // walkers concatenated.  Member m owns walkers [m_off[m], m_off[m] + m_nw[m]) and entries [m_astart[m], + m_nw[m] / 2)
+    // of every half-step's ns.
+    std::vector<int64_t> m_nw, m_off, m_astart;
+    // A chunk's arrays in its slot are laid out for `layout_steps` iterations whatever its length, or (0) for its own
+    // length: the group's launches read their per-half-step pointers from snapshots built once, at begin.
+    int64_t layout_steps = 0;
+    int32_t nworst = 1;  // worst statuses behind a chunk's acceptance counts (the group's run: one per member)
+    int64_t lay(int64_t st) const { return layout_steps > 0 ? layout_steps : st; }
     double *coords_now() const { return d_coords + (overlap == 1 ? (steps_done & 1) * nw * ndim : 0); }
     size_t in_bytes(int64_t st) const {  // [zz | zfac | logu | sidx | cidx | partner | records]
         return (size_t)(st * 2 * ns) * (3 * sizeof(double) + 3 * sizeof(int32_t) + sizeof(SmpRec));
     }
-    size_t out_bytes(int64_t st) const {
-        return sizeof(double) * (size_t)(st * nw * ndim + st * nw) + sizeof(int64_t) * (size_t)nw + 16;
+    size_t out_bytes(int64_t st) const {  // [chain | log p chain | acceptance counts | worst statuses (16-byte padded)]
+        return sizeof(double) * (size_t)(st * nw * ndim + st * nw) + sizeof(int64_t) * (size_t)nw + 16 * (size_t)((4 * nworst + 15) / 16);
     }
 };
 
-static void sampler_free(msx_ctx *c) {
-    SamplerRun *r = c->smp;
-    if (!r) return;
-    (void)hipSetDevice(c->device);
-    (void)hipStreamSynchronize(c->stream);
+// ---- the pipeline's pieces that the context's run (msx_sampler_*) and a target group's (msx_group_sampler_*) share ----
+// streams, events and the two slots' buffers (cap_steps, ns, nw, ndim, layout_steps and nworst set)
+static hipError_t run_open(SamplerRun *r) {
+    hipError_t e = hipStreamCreateWithFlags(&r->copy, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&r->up, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&r->s2, hipStreamNonBlocking);
+    for (auto &ev : r->hs_done)
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&r->chunk_open, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&r->s2_done, hipEventDisableTiming);
+    for (auto &sl : r->slot) {
+        if (e == hipSuccess) e = hipMalloc((void **)&sl.d_in, r->in_bytes(r->cap_steps));
+        if (e == hipSuccess) e = hipMalloc((void **)&sl.d_out, r->out_bytes(r->cap_steps));
+        if (e == hipSuccess) e = hipHostMalloc((void **)&sl.h_in, r->in_bytes(r->cap_steps), hipHostMallocDefault);
+        if (e == hipSuccess) e = hipHostMalloc((void **)&sl.h_out, r->out_bytes(r->cap_steps), hipHostMallocDefault);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.in_ready, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.kernels_done, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.out_ready, hipEventDisableTiming);
+    }
+    return e;
+}
+
+// waits for what the run queued (on `compute` and its own streams) and frees it
+static void run_close(SamplerRun *r, hipStream_t compute) {
+    (void)hipStreamSynchronize(compute);
     if (r->copy) (void)hipStreamSynchronize(r->copy);
     if (r->up) (void)hipStreamSynchronize(r->up);
     for (auto &sl : r->slot) {
@@ -1767,6 +1816,77 @@ static void sampler_free(msx_ctx *c) {
     if (r->copy) (void)hipStreamDestroy(r->copy);
     if (r->up) (void)hipStreamDestroy(r->up);
     delete r;
+}
+
+// The chunk's host randomness -- [nsteps][2][ns] each, the members' active halves side by side, indices member-local --
+// into the slot's pinned staging, laid out for lay(nsteps) iterations: [zz | zfac | logu | sidx | cidx | partner | records].
+// Every index is dereferenced on the device: checked here.  partner is resolved to the ensemble index of the
+// complementary walker, so that the kernel's proposal needs two dependent loads (record, coordinates) instead of three,
+// and the records carry ensemble indices (member offset + local index).  nullptr, or what is wrong.
+static const char *run_pack(SamplerRun *r, SamplerRun::Slot &sl, int64_t nsteps, const int32_t *sidx, const int32_t *cidx,
+                            const int32_t *partner, const double *zz, const double *zfac, const double *logu) {
+    const int64_t ns = r->ns, nh = nsteps * 2 * ns, L = r->lay(nsteps) * 2 * ns;
+    const size_t km = r->m_nw.size();
+    // pinned staging, doubles first
+    double *hz = (double *)sl.h_in;
+    int32_t *hi = (int32_t *)(hz + 3 * L);
+    memcpy(hz, zz, sizeof(double) * nh); memcpy(hz + L, zfac, sizeof(double) * nh); memcpy(hz + 2 * L, logu, sizeof(double) * nh);
+    memcpy(hi, sidx, sizeof(int32_t) * nh); memcpy(hi + L, cidx, sizeof(int32_t) * nh);
+    memcpy(hi + 2 * L, partner, sizeof(int32_t) * nh);
+    for (int64_t row = 0; row < 2 * nsteps; ++row)
+        for (size_t m = 0; m < km; ++m) {
+            const int64_t b = row * ns + r->m_astart[m];
+            const uint32_t mw = (uint32_t)r->m_nw[m], mh = mw / 2;
+            for (int64_t j = b; j < b + (int64_t)mh; ++j)
+                if ((uint32_t)hi[j] >= mw || (uint32_t)hi[L + j] >= mw || (uint32_t)hi[2 * L + j] >= mh)
+                    return "walker / partner index out of range";
+        }
+    for (int64_t row = 0; row < 2 * nsteps; ++row)
+        for (size_t m = 0; m < km; ++m) {
+            const int64_t b = row * ns + r->m_astart[m], e = b + r->m_nw[m] / 2, off = r->m_off[m];
+            for (int64_t j = b; j < e; ++j) hi[2 * L + j] = (int32_t)(off + hi[L + b + hi[2 * L + j]]);
+        }
+    if (r->overlap == 1) {
+        // the version protocol rests on every walker moving exactly once per iteration: the two half-steps' walkers must
+        // be a permutation of the ensemble (emcee's random split is; checked here because a violation would not fail
+        // until a workgroup's wait runs out on the device).  (The context's run only: one member, L = nh.)
+        std::vector<int64_t> seen((size_t)r->nw, -1);
+        for (int64_t i = 0; i < nh; ++i) {
+            const int64_t it = i / (2 * ns);
+            if (seen[(size_t)hi[i]] == it) return "a walker appears twice in one iteration's two half-steps";
+            seen[(size_t)hi[i]] = it;
+        }
+    }
+    // ... and the proposal's inputs once more as one record per walker (the kernel's first load), with the versions of
+    // the two walkers the move reads: before iteration k every walker has version k; the second half-step's partners
+    // were updated by the first
+    SmpRec *hr = (SmpRec *)(hi + 3 * L);
+    for (int64_t row = 0; row < 2 * nsteps; ++row)
+        for (size_t m = 0; m < km; ++m) {
+            const int64_t b = row * ns + r->m_astart[m], e = b + r->m_nw[m] / 2, off = r->m_off[m];
+            const int64_t k = r->steps_done + row / 2, half = row & 1;
+            for (int64_t i = b; i < e; ++i) {
+                hr[i].si = (int32_t)(off + hi[i]); hr[i].ci = hi[2 * L + i]; hr[i].zz = hz[i];
+                hr[i].ver_own = r->overlap == 1 ? (uint32_t)k : 0u;
+                hr[i].ver_partner = r->overlap == 1 ? (uint32_t)(k + half) : 0u;
+            }
+        }
+    return nullptr;
+}
+
+// the packed slot up on the upload stream; `compute` waits for it
+static hipError_t run_upload(SamplerRun *r, SamplerRun::Slot &sl, int64_t nsteps, hipStream_t compute) {
+    hipError_t e = hipMemcpyAsync(sl.d_in, sl.h_in, r->in_bytes(r->lay(nsteps)), hipMemcpyHostToDevice, r->up);
+    if (e == hipSuccess) e = hipEventRecord(sl.in_ready, r->up);
+    if (e == hipSuccess) e = hipStreamWaitEvent(compute, sl.in_ready, 0);
+    return e;
+}
+
+static void sampler_free(msx_ctx *c) {
+    SamplerRun *r = c->smp;
+    if (!r) return;
+    (void)hipSetDevice(c->device);
+    run_close(r, c->stream);
     c->smp = nullptr;
     c->P.smp_on = 0;
     c->P.smp_defer = 0;
@@ -1787,6 +1907,7 @@ int msx_sampler_begin(msx_ctx *c, int32_t mode, int64_t nw, int32_t ndim, int64_
     SamplerRun *r = new SamplerRun;
     c->smp = r;
     r->mode = mode; r->ndim = ndim; r->nw = nw; r->ns = nw / 2; r->cap_steps = max_chunk_steps;
+    r->m_nw = {nw}; r->m_off = {0}; r->m_astart = {0};
     const int64_t ns = r->ns;
     // (two coordinate buffers, two half-steps' worth of per-launch outputs: overlapped half-steps)
     const size_t gran_words = (size_t)(2 * nw * kGranPerWalker);
@@ -1795,22 +1916,7 @@ int msx_sampler_begin(msx_ctx *c, int32_t mode, int64_t nw, int32_t ndim, int64_
                                sizeof(int32_t) * (size_t)(2 * ns) + sizeof(uint32_t) * (size_t)nw + 64 + sizeof(unsigned long long) * gran_words;
     hipError_t e = hipMalloc((void **)&r->d_state, state_bytes);
     if (e == hipSuccess) e = hipMemsetAsync(r->d_state, 0, state_bytes, c->stream);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&r->copy, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&r->up, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&r->s2, hipStreamNonBlocking);
-    for (auto &ev : r->hs_done)
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&r->chunk_open, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&r->s2_done, hipEventDisableTiming);
-    for (auto &sl : r->slot) {
-        if (e == hipSuccess) e = hipMalloc((void **)&sl.d_in, r->in_bytes(max_chunk_steps));
-        if (e == hipSuccess) e = hipMalloc((void **)&sl.d_out, r->out_bytes(max_chunk_steps));
-        if (e == hipSuccess) e = hipHostMalloc((void **)&sl.h_in, r->in_bytes(max_chunk_steps), hipHostMallocDefault);
-        if (e == hipSuccess) e = hipHostMalloc((void **)&sl.h_out, r->out_bytes(max_chunk_steps), hipHostMallocDefault);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.in_ready, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.kernels_done, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.out_ready, hipEventDisableTiming);
-    }
+    if (e == hipSuccess) e = run_open(r);
     if (e == hipSuccess) {
         r->d_coords = (double *)r->d_state; r->d_logp = r->d_coords + 2 * nw * ndim; r->d_q = r->d_logp + nw;
         r->d_newlp = r->d_q + 2 * ns * ndim; r->d_nacc = (int64_t *)(r->d_newlp + 2 * ns); r->d_wst = (int32_t *)(r->d_nacc + nw);
@@ -1883,6 +1989,50 @@ struct ChunkPtrs {
     int32_t *d_worst = nullptr;
 };
 
+// where a chunk of nsteps iterations lives in its slot (SamplerRun::lay)
+static void run_chunk_ptrs(const SamplerRun *r, const SamplerRun::Slot &sl, int64_t nsteps, ChunkPtrs *cp) {
+    const int64_t L = r->lay(nsteps), nh = L * 2 * r->ns;
+    cp->nh = nsteps * 2 * r->ns;
+    cp->d_zz = (double *)sl.d_in; cp->d_zfac = cp->d_zz + nh; cp->d_logu = cp->d_zfac + nh;
+    cp->d_sidx = (int32_t *)(cp->d_logu + nh); cp->d_cidx = cp->d_sidx + nh; cp->d_partner = cp->d_cidx + nh;
+    cp->d_rec = (const SmpRec *)(cp->d_partner + nh);
+    cp->d_chain = (double *)sl.d_out; cp->d_lpchain = cp->d_chain + L * r->nw * r->ndim;
+    cp->d_nacc_snap = (int64_t *)(cp->d_lpchain + L * r->nw);
+    cp->d_worst = (int32_t *)(cp->d_nacc_snap + r->nw);
+}
+
+// the chunk's launches are queued on `compute`: snapshot the acceptance counters behind them, then bring the slot's
+// results back on the download stream
+static hipError_t run_finish(SamplerRun *r, int32_t slot, int64_t nsteps, const ChunkPtrs &cp, hipStream_t compute) {
+    SamplerRun::Slot &sl = r->slot[slot];
+    // acceptance counters keep running while this chunk's results travel: snapshot them in stream order
+    hipError_t e = hipMemcpyAsync(cp.d_nacc_snap, r->d_nacc, sizeof(int64_t) * r->nw, hipMemcpyDeviceToDevice, compute);
+    if (e == hipSuccess) e = hipEventRecord(sl.kernels_done, compute);
+    if (e == hipSuccess) e = hipStreamWaitEvent(r->copy, sl.kernels_done, 0);
+    if (e == hipSuccess) e = hipMemcpyAsync(sl.h_out, sl.d_out, r->out_bytes(r->lay(nsteps)), hipMemcpyDeviceToHost, r->copy);
+    if (e == hipSuccess) e = hipEventRecord(sl.out_ready, r->copy);
+    if (e != hipSuccess) return e;
+    sl.nsteps = nsteps;
+    sl.busy = true;
+    return hipSuccess;
+}
+
+// waits for the slot's results and copies them out: chain [nsteps][nw][ndim], log p [nsteps][nw], naccept [nw], worst [nworst]
+static hipError_t run_collect(SamplerRun *r, int32_t slot, double *chain_out, double *logp_out, int64_t *naccept, int32_t *worst) {
+    SamplerRun::Slot &sl = r->slot[slot];
+    const hipError_t e = hipEventSynchronize(sl.out_ready);
+    if (e != hipSuccess) return e;
+    const int64_t st = sl.nsteps, nw = r->nw, L = r->lay(st);
+    const double *h_chain = (const double *)sl.h_out, *h_lp = h_chain + L * nw * r->ndim;
+    const int64_t *h_nacc = (const int64_t *)(h_lp + L * nw);
+    memcpy(chain_out, h_chain, sizeof(double) * st * nw * r->ndim);
+    memcpy(logp_out, h_lp, sizeof(double) * st * nw);
+    memcpy(naccept, h_nacc, sizeof(int64_t) * nw);
+    memcpy(worst, h_nacc + nw, sizeof(int32_t) * r->nworst);
+    sl.busy = false;
+    return hipSuccess;
+}
+
 // (draw != nullptr: the chunk's randomness is drawn on the device -- sampler_draw_kernel, keyed by draw->seed and the
 // run's absolute iteration numbers -- instead of coming from the host's arrays)
 struct DeviceDraw { unsigned long long seed; double a; };
@@ -1927,53 +2077,12 @@ static int chunk_prepare(msx_ctx *c, int32_t slot, int64_t nsteps, const int32_t
                            nw, (int32_t)ndim, 1, (int32_t)(r->overlap == 1), g_sidx, g_cidx, g_partner, g_zz, g_zfac, g_logu, g_rec);
         HIP_TRY(c, hipGetLastError());
     } else {
-    // pinned staging, doubles first: [zz | zfac | logu | sidx | cidx | partner]
-    double *hz = (double *)sl.h_in;
-    int32_t *hi = (int32_t *)(hz + 3 * nh);
-    memcpy(hz, zz, sizeof(double) * nh); memcpy(hz + nh, zfac, sizeof(double) * nh); memcpy(hz + 2 * nh, logu, sizeof(double) * nh);
-    memcpy(hi, sidx, sizeof(int32_t) * nh); memcpy(hi + nh, cidx, sizeof(int32_t) * nh);
-    memcpy(hi + 2 * nh, partner, sizeof(int32_t) * nh);
-    // every index is dereferenced on the device: check them here
-    for (int64_t i = 0; i < nh; ++i)
-        if ((uint32_t)hi[i] >= (uint32_t)nw || (uint32_t)hi[nh + i] >= (uint32_t)nw || (uint32_t)hi[2 * nh + i] >= (uint32_t)ns)
-            return fail(c, MSX_ERR_INVALID, "msx_sampler_enqueue: walker / partner index out of range");
-    // resolve partner -> ensemble index of the complementary walker here, so that the kernel's proposal needs
-    // two dependent loads (index, coordinates) instead of three
-    for (int64_t i = 0; i < nh; ++i) hi[2 * nh + i] = hi[nh + (i / ns) * ns + hi[2 * nh + i]];
-    if (r->overlap == 1) {
-        // the version protocol rests on every walker moving exactly once per iteration: the two half-steps' walkers must
-        // be a permutation of the ensemble (emcee's random split is; checked here because a violation would not fail
-        // until a workgroup's wait runs out on the device)
-        std::vector<int64_t> seen((size_t)nw, -1);
-        for (int64_t i = 0; i < nh; ++i) {
-            const int64_t it = i / (2 * ns);
-            if (seen[(size_t)hi[i]] == it)
-                return fail(c, MSX_ERR_INVALID, "msx_sampler_enqueue: a walker appears twice in one iteration's two half-steps");
-            seen[(size_t)hi[i]] = it;
-        }
+        if (const char *why = run_pack(r, sl, nsteps, sidx, cidx, partner, zz, zfac, logu))
+            return fail(c, MSX_ERR_INVALID, std::string("msx_sampler_enqueue: ") + why);
+        HIP_TRY(c, run_upload(r, sl, nsteps, c->stream));
     }
-    // ... and the proposal's inputs once more as one record per walker (the kernel's first load), with the versions of
-    // the two walkers the move reads: before iteration k every walker has version k; the second half-step's partners
-    // were updated by the first
-    SmpRec *hr = (SmpRec *)(hi + 3 * nh);
-    for (int64_t i = 0; i < nh; ++i) {
-        hr[i].si = hi[i]; hr[i].ci = hi[2 * nh + i]; hr[i].zz = hz[i];
-        const int64_t k = r->steps_done + i / (2 * ns), half = (i / ns) & 1;
-        hr[i].ver_own = r->overlap == 1 ? (uint32_t)k : 0u;
-        hr[i].ver_partner = r->overlap == 1 ? (uint32_t)(k + half) : 0u;
-    }
-    HIP_TRY(c, hipMemcpyAsync(sl.d_in, sl.h_in, r->in_bytes(nsteps), hipMemcpyHostToDevice, r->up));
-    HIP_TRY(c, hipEventRecord(sl.in_ready, r->up));
-    HIP_TRY(c, hipStreamWaitEvent(c->stream, sl.in_ready, 0));
-    }
-    cp->nh = nh;
-    cp->d_zz = (double *)sl.d_in; cp->d_zfac = cp->d_zz + nh; cp->d_logu = cp->d_zfac + nh;
-    cp->d_sidx = (int32_t *)(cp->d_logu + nh); cp->d_cidx = cp->d_sidx + nh; cp->d_partner = cp->d_cidx + nh;
-    cp->d_rec = (const SmpRec *)(cp->d_partner + nh);
-    cp->d_chain = (double *)sl.d_out; cp->d_lpchain = cp->d_chain + nsteps * nw * ndim;
-    cp->d_nacc_snap = (int64_t *)(cp->d_lpchain + nsteps * nw);
-    cp->d_worst = (int32_t *)(cp->d_nacc_snap + nw);
-    HIP_TRY(c, hipMemsetAsync(cp->d_worst, 0, sizeof(int32_t), c->stream));
+    run_chunk_ptrs(r, sl, nsteps, cp);
+    HIP_TRY(c, hipMemsetAsync(cp->d_worst, 0, sizeof(int32_t) * r->nworst, c->stream));
     DevProblem &P = c->P;
     P.smp_on = 1;
     P.smp_coords = r->d_coords; P.smp_logp = r->d_logp; P.smp_q = r->d_q; P.smp_naccept = r->d_nacc; P.smp_worst = cp->d_worst;
@@ -2049,7 +2158,6 @@ static int chunk_half_apply(msx_ctx *c) {
 
 static int chunk_finish(msx_ctx *c, int32_t slot, int64_t nsteps, const ChunkPtrs &cp, int rc) {
     SamplerRun *r = c->smp;
-    SamplerRun::Slot &sl = r->slot[slot];
     DevProblem &P = c->P;
     P.smp_on = 0;
     P.smp_defer = 0;
@@ -2064,14 +2172,7 @@ static int chunk_finish(msx_ctx *c, int32_t slot, int64_t nsteps, const ChunkPtr
         HIP_TRY(c, hipStreamWaitEvent(c->stream, r->s2_done, 0));
     }
     r->steps_done += nsteps;
-    // acceptance counters keep running while this chunk's results travel: snapshot them in stream order
-    HIP_TRY(c, hipMemcpyAsync(cp.d_nacc_snap, r->d_nacc, sizeof(int64_t) * r->nw, hipMemcpyDeviceToDevice, c->stream));
-    HIP_TRY(c, hipEventRecord(sl.kernels_done, c->stream));
-    HIP_TRY(c, hipStreamWaitEvent(r->copy, sl.kernels_done, 0));
-    HIP_TRY(c, hipMemcpyAsync(sl.h_out, sl.d_out, r->out_bytes(nsteps), hipMemcpyDeviceToHost, r->copy));
-    HIP_TRY(c, hipEventRecord(sl.out_ready, r->copy));
-    sl.nsteps = nsteps;
-    sl.busy = true;
+    HIP_TRY(c, run_finish(r, slot, nsteps, cp, c->stream));
     return MSX_OK;
 }
 
@@ -2211,15 +2312,7 @@ int msx_sampler_collect(msx_ctx *c, int32_t slot, double *chain_out, double *log
         return fail(c, MSX_ERR_INVALID, "msx_sampler_collect: bad arguments");
     SamplerRun::Slot &sl = r->slot[slot];
     if (!sl.busy) return fail(c, MSX_ERR_STATE, "msx_sampler_collect: nothing enqueued in this slot");
-    HIP_TRY(c, hipEventSynchronize(sl.out_ready));
-    const int64_t st = sl.nsteps, nw = r->nw;
-    const double *h_chain = (const double *)sl.h_out, *h_lp = h_chain + st * nw * r->ndim;
-    const int64_t *h_nacc = (const int64_t *)(h_lp + st * nw);
-    memcpy(chain_out, h_chain, sizeof(double) * st * nw * r->ndim);
-    memcpy(logp_out, h_lp, sizeof(double) * st * nw);
-    memcpy(naccept, h_nacc, sizeof(int64_t) * nw);
-    *worst_status = *(const int32_t *)(h_nacc + nw);
-    sl.busy = false;
+    HIP_TRY(c, run_collect(r, slot, chain_out, logp_out, naccept, worst_status));
     return MSX_OK;
 }
 
@@ -2571,6 +2664,7 @@ int msx_group_create(msx_ctx **ctxs, int32_t k, msx_group **out) {
 
 void msx_group_destroy(msx_group *g) {
     if (!g) return;
+    group_run_free(g);  // a run still open ends here
     for (msx_ctx *c : g->members)
         if (c) c->groups.erase(std::remove(c->groups.begin(), c->groups.end(), g), c->groups.end());
     (void)hipSetDevice(g->device);
@@ -2633,7 +2727,8 @@ int msx_group_logprob_batch_dev(msx_group *g, int32_t mode, const double *d_thet
     int64_t a_n = total;
     double *a_logp = d_logp;
     int32_t *a_status = d_status;
-    void *args[] = {&a_theta, &a_members, &a_probs, &a_mode, &a_n, &st, &a_logp, &a_status};
+    const SmpRec *a_rec = nullptr;
+    void *args[] = {&a_theta, &a_members, &a_probs, &a_mode, &a_n, &st, &a_logp, &a_status, &a_rec};
     GROUP_HIP_TRY(g, hipSetDevice(g->device));
     GROUP_HIP_TRY(g, hipLaunchKernel(pl.v->fn, dim3((unsigned)total), dim3((unsigned)pl.v->threads), args, pl.dyn_lds, (hipStream_t)hip_stream));
     return MSX_OK;
@@ -2697,6 +2792,213 @@ int msx_group_launch_info(msx_group *g, int32_t mode, const int64_t *counts, int
         strncpy(name, nm.c_str(), (size_t)name_len - 1);
         name[name_len - 1] = 0;
     }
+    return MSX_OK;
+}
+
+// ---- a target group's device-resident sampler (include/msx.h, msx_group_sampler_*) -------------------------------------
+// One resident ensemble for the whole group -- the members' walkers concatenated, [sum nw_k][ndim] -- and SamplerRun's
+// pipeline (slots, upload / download streams, events, chunk packing).  Each half-step is ONE plain launch of the group
+// kernel's SMP instance over the members' active halves (sum nw_k / 2 walkers, GroupStarts over nw_k / 2).  What changes
+// from one half-step to the next (the records, zfac, log u, the chain rows) reaches the kernel without an upload: a slot's
+// buffers never move and the chunks are laid out for cap_steps iterations (SamplerRun::layout_steps), so one set of member
+// snapshots per (slot, step, half) is built at begin, and each launch passes its set as g_probs and its records as
+// g_smp_rec.  Every record's si / ci is a GROUP-level ensemble index; each member's snapshots carry its own smp_worst.
+struct GroupRun {
+    SamplerRun *r = nullptr;
+    hipStream_t stream = nullptr;  // the run's compute stream (its own: members may be destroyed while it is open)
+    DevProblem *d_snap = nullptr;  // [2 slots][cap_steps][2 halves][k members]
+    const void *fn = nullptr;      // the planned SMP instance
+    int threads = 0;
+    size_t dyn_lds = 0;
+    GroupStarts st;                // over the members' active halves
+};
+
+// a member's problem is about to go (free_problem): let the launches that read its tables finish
+static void group_run_drain(msx_group *g) {
+    if (g->run && g->run->stream) (void)hipStreamSynchronize(g->run->stream);
+}
+
+static void group_run_free(msx_group *g) {
+    GroupRun *gr = g->run;
+    if (!gr) return;
+    (void)hipSetDevice(g->device);
+    if (gr->r) run_close(gr->r, gr->stream);
+    if (gr->stream) (void)hipStreamDestroy(gr->stream);
+    if (gr->d_snap) (void)hipFree(gr->d_snap);
+    delete gr;
+    g->run = nullptr;
+}
+
+int msx_group_sampler_begin(msx_group *g, int32_t mode, const int64_t *counts, int32_t ndim, int64_t max_chunk_steps,
+                            const double *coords, const double *logp, const int64_t *naccept) {
+    if (!g) return MSX_ERR_INVALID;
+    int64_t total = 0;
+    if (int rc = group_check(g, "msx_group_sampler_begin", mode, counts, ndim, &total)) return rc;
+    if (mode != MSX_MODE_LOGPOST && mode != MSX_MODE_LOGLIKE)
+        return gfail(g, MSX_ERR_INVALID, "msx_group_sampler_begin: mode must be MSX_MODE_LOGPOST or MSX_MODE_LOGLIKE");
+    const int k = (int)g->members.size();
+    for (int m = 0; m < k; ++m)
+        if (counts[m] < 2 || (counts[m] & 1))
+            return gfail(g, MSX_ERR_INVALID, "msx_group_sampler_begin: member " + std::to_string(m) + " has " + std::to_string(counts[m]) +
+                                                 " walkers: the stretch move needs an even number, at least 2");
+    if (!coords || !logp || max_chunk_steps < 1) return gfail(g, MSX_ERR_INVALID, "msx_group_sampler_begin: bad arguments");
+    GROUP_HIP_TRY(g, hipSetDevice(g->device));
+    group_run_free(g);
+    std::vector<int64_t> half((size_t)k);
+    for (int m = 0; m < k; ++m) half[(size_t)m] = counts[m] / 2;
+    const int64_t ns = total / 2;
+    GroupPlan pl = plan_group_launch(g, half.data(), ns, 0, false);
+    if (pl.v && !pl.v->smp_fn) {  // no sampler instance of the planned entry: its neighbour without PF, then without SH
+        const GroupVariant *sub = nullptr;
+        for (int pass = 0; pass < 2 && !sub; ++pass)
+            for (const GroupVariant &v : kGroupVariants)
+                if (!sub && v.smp_fn && v.ns == pl.v->ns && v.threads == pl.v->threads && v.sh == (pass == 0 && pl.v->sh) && !v.pf && v.full == 0)
+                    sub = &v;
+        pl = sub ? group_plan_lds(g, half.data(), ns, sub) : GroupPlan();
+    }
+    if (!pl.v) return gfail(g, MSX_ERR_STATE, "msx_group_sampler_begin: no kernel variant for this group launch");
+    GroupRun *gr = new GroupRun;
+    g->run = gr;
+    gr->fn = pl.v->smp_fn; gr->threads = pl.v->threads; gr->dyn_lds = pl.dyn_lds;
+    gr->st.k = k;
+    SamplerRun *r = gr->r = new SamplerRun;
+    r->mode = mode; r->ndim = ndim; r->nw = total; r->ns = ns; r->cap_steps = max_chunk_steps;
+    r->overlap = 0;  // plain launches, one half-step after the other
+    r->layout_steps = max_chunk_steps;
+    r->nworst = k;
+    int64_t off = 0, astart = 0;
+    for (int m = 0; m < k; ++m) {
+        r->m_nw.push_back(counts[m]); r->m_off.push_back(off); r->m_astart.push_back(astart);
+        gr->st.start[m] = (int32_t)astart;
+        off += counts[m]; astart += half[(size_t)m];
+    }
+    for (int m = k; m <= MSX_MAX_GROUP; ++m) gr->st.start[m] = (int32_t)astart;
+    // [coords | logp | q | newlp | nacc | wst]
+    const size_t state_bytes = sizeof(double) * (size_t)(total * ndim + total + ns * ndim + ns) + sizeof(int64_t) * (size_t)total +
+                               sizeof(int32_t) * (size_t)ns;
+    const size_t snap_count = (size_t)(2 * max_chunk_steps * 2 * k);
+    hipError_t e = hipStreamCreateWithFlags(&gr->stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipMalloc((void **)&r->d_state, state_bytes);
+    if (e == hipSuccess) e = hipMalloc((void **)&gr->d_snap, sizeof(DevProblem) * snap_count);
+    if (e == hipSuccess) e = run_open(r);
+    std::vector<DevProblem> snaps;
+    if (e == hipSuccess) {
+        r->d_coords = (double *)r->d_state; r->d_logp = r->d_coords + total * ndim; r->d_q = r->d_logp + total;
+        r->d_newlp = r->d_q + ns * ndim; r->d_nacc = (int64_t *)(r->d_newlp + ns); r->d_wst = (int32_t *)(r->d_nacc + total);
+        // the member snapshots of every (slot, step, half): msx_group_create's, with the sampler's fields pointing at the
+        // group's ensemble and at this half-step's place in the slot
+        snaps.reserve(snap_count);
+        for (int slot = 0; slot < 2; ++slot) {
+            ChunkPtrs cp;
+            run_chunk_ptrs(r, r->slot[slot], max_chunk_steps, &cp);
+            for (int64_t st = 0; st < max_chunk_steps; ++st)
+                for (int h = 0; h < 2; ++h)
+                    for (int m = 0; m < k; ++m) {
+                        DevProblem q = g->probs[(size_t)m];
+                        const int64_t o = (st * 2 + h) * ns;
+                        q.smp_on = 1;
+                        q.smp_coords = r->d_coords; q.smp_logp = r->d_logp; q.smp_q = r->d_q; q.smp_naccept = r->d_nacc;
+                        q.smp_sidx = cp.d_sidx + o; q.smp_cidx = cp.d_cidx + o; q.smp_partner = cp.d_partner + o;
+                        q.smp_zz = cp.d_zz + o; q.smp_zfac = cp.d_zfac + o; q.smp_logu = cp.d_logu + o; q.smp_rec = cp.d_rec + o;
+                        q.smp_chain_row = cp.d_chain + st * total * ndim; q.smp_lp_row = cp.d_lpchain + st * total;
+                        q.smp_worst = cp.d_worst + m;
+                        q.smp_stride = total * ndim; q.smp_gwalkers = total;
+                        snaps.push_back(q);
+                    }
+        }
+        e = hipMemcpyAsync(gr->d_snap, snaps.data(), sizeof(DevProblem) * snap_count, hipMemcpyHostToDevice, gr->stream);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(r->d_coords, coords, sizeof(double) * total * ndim, hipMemcpyHostToDevice, gr->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(r->d_logp, logp, sizeof(double) * total, hipMemcpyHostToDevice, gr->stream);
+    if (e == hipSuccess)
+        e = naccept ? hipMemcpyAsync(r->d_nacc, naccept, sizeof(int64_t) * total, hipMemcpyHostToDevice, gr->stream)
+                    : hipMemsetAsync(r->d_nacc, 0, sizeof(int64_t) * total, gr->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(gr->stream);  // the caller's arrays (and the snapshots) are consumed on return
+    if (e != hipSuccess) {
+        group_run_free(g);
+        return gfail(g, MSX_ERR_HIP, std::string("msx_group_sampler_begin: ") + hipGetErrorString(e));
+    }
+    return MSX_OK;
+}
+
+int msx_group_sampler_enqueue(msx_group *g, int32_t slot, int64_t nsteps, const int32_t *sidx, const int32_t *cidx,
+                              const int32_t *partner, const double *zz, const double *zfac, const double *logu) {
+    if (!g) return MSX_ERR_INVALID;
+    GroupRun *gr = g->run;
+    if (!gr) return gfail(g, MSX_ERR_STATE, "msx_group_sampler_enqueue: call msx_group_sampler_begin first");
+    SamplerRun *r = gr->r;
+    if (slot < 0 || slot > 1 || nsteps < 1 || nsteps > r->cap_steps || !sidx || !cidx || !partner || !zz || !zfac || !logu)
+        return gfail(g, MSX_ERR_INVALID, "msx_group_sampler_enqueue: bad arguments");
+    if (r->failed)
+        return gfail(g, MSX_ERR_STATE, "msx_group_sampler_enqueue: the run failed; end it (msx_group_sampler_end) and begin again");
+    // a member restaged or destroyed since begin: the snapshots point at tables that are gone -- the run is over
+    int64_t total = 0;
+    std::vector<int64_t> counts(r->m_nw);
+    if (int rc = group_check(g, "msx_group_sampler_enqueue", r->mode, counts.data(), r->ndim, &total)) {
+        r->failed = true;
+        return rc;
+    }
+    SamplerRun::Slot &sl = r->slot[slot];
+    if (sl.busy) return gfail(g, MSX_ERR_STATE, "msx_group_sampler_enqueue: slot not collected yet");
+    GROUP_HIP_TRY(g, hipSetDevice(g->device));
+    if (const char *why = run_pack(r, sl, nsteps, sidx, cidx, partner, zz, zfac, logu))
+        return gfail(g, MSX_ERR_INVALID, std::string("msx_group_sampler_enqueue: ") + why);
+    ChunkPtrs cp;
+    run_chunk_ptrs(r, sl, nsteps, &cp);
+    const int k = (int)g->members.size();
+    hipError_t e = run_upload(r, sl, nsteps, gr->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(cp.d_worst, 0, sizeof(int32_t) * (size_t)k, gr->stream);
+    // the kernel's arguments, in its own order; per half-step only the snapshot set and the records move
+    const double *a_theta = r->d_coords;
+    const void *a_members = g->d_members;
+    const void *a_probs = nullptr;
+    int a_mode = r->mode;
+    int64_t a_n = r->ns;
+    double *a_logp = r->d_newlp;
+    int32_t *a_status = r->d_wst;
+    const SmpRec *a_rec = nullptr;
+    void *args[] = {&a_theta, &a_members, &a_probs, &a_mode, &a_n, &gr->st, &a_logp, &a_status, &a_rec};
+    for (int64_t st = 0; st < nsteps && e == hipSuccess; ++st)
+        for (int h = 0; h < 2 && e == hipSuccess; ++h) {
+            a_probs = gr->d_snap + (((int64_t)slot * r->cap_steps + st) * 2 + h) * k;
+            a_rec = cp.d_rec + (st * 2 + h) * r->ns;
+            e = hipLaunchKernel(gr->fn, dim3((unsigned)r->ns), dim3((unsigned)gr->threads), args, gr->dyn_lds, gr->stream);
+        }
+    if (e == hipSuccess) e = run_finish(r, slot, nsteps, cp, gr->stream);
+    if (e != hipSuccess) {
+        r->failed = true;  // some of the chunk's half-steps may be queued: only msx_group_sampler_end from here on
+        return gfail(g, MSX_ERR_HIP, std::string("msx_group_sampler_enqueue: ") + hipGetErrorString(e));
+    }
+    r->steps_done += nsteps;
+    return MSX_OK;
+}
+
+int msx_group_sampler_collect(msx_group *g, int32_t slot, double *chain_out, double *logp_out, int64_t *naccept,
+                              int32_t *worst_status) {
+    if (!g) return MSX_ERR_INVALID;
+    GroupRun *gr = g->run;
+    if (!gr) return gfail(g, MSX_ERR_STATE, "msx_group_sampler_collect: call msx_group_sampler_begin first");
+    SamplerRun *r = gr->r;
+    if (slot < 0 || slot > 1 || !chain_out || !logp_out || !naccept || !worst_status)
+        return gfail(g, MSX_ERR_INVALID, "msx_group_sampler_collect: bad arguments");
+    if (r->failed)
+        return gfail(g, MSX_ERR_STATE, "msx_group_sampler_collect: the run failed; end it (msx_group_sampler_end) and begin again");
+    if (!r->slot[slot].busy) return gfail(g, MSX_ERR_STATE, "msx_group_sampler_collect: nothing enqueued in this slot");
+    GROUP_HIP_TRY(g, run_collect(r, slot, chain_out, logp_out, naccept, worst_status));
+    return MSX_OK;
+}
+
+int msx_group_sampler_end(msx_group *g, double *coords, double *logp) {
+    if (!g) return MSX_ERR_INVALID;
+    GroupRun *gr = g->run;
+    if (!gr) return MSX_OK;
+    SamplerRun *r = gr->r;
+    hipError_t e = hipSetDevice(g->device);
+    if (e == hipSuccess) e = hipStreamSynchronize(gr->stream);
+    if (e == hipSuccess && coords) e = hipMemcpy(coords, r->d_coords, sizeof(double) * r->nw * r->ndim, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && logp) e = hipMemcpy(logp, r->d_logp, sizeof(double) * r->nw, hipMemcpyDeviceToHost);
+    group_run_free(g);
+    if (e != hipSuccess) return gfail(g, MSX_ERR_HIP, std::string("msx_group_sampler_end: ") + hipGetErrorString(e));
     return MSX_OK;
 }
 

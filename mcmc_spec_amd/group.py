@@ -8,6 +8,9 @@ workgroup per walker, each against its own target.  Walker i of target k gets th
 through ONE batched call ``f(list_of_thetas) -> list_of_logp`` (``TargetGroup.logposterior``: one launch).  Each target
 draws its randomness from its own ``EnsembleSampler`` state, so target k's chain is bit for bit the chain of
 ``EnsembleSampler(nwalkers[k], ndim, f_k, vectorize=True, seed=seeds[k])`` run alone.
+
+``DeviceGroupSampler`` walks the same chains with the ensembles resident on the GPU (``msx_group_sampler_*``): one launch
+per half-step, no host round trip between half-steps, chunks of iterations queued back to back.
 """
 from __future__ import annotations
 
@@ -197,3 +200,121 @@ class GroupSampler:
     def acceptance_fraction(self):
         """One array per target."""
         return [s.acceptance_fraction for s in self.samplers]
+
+
+class DeviceGroupSampler(GroupSampler):
+    """``GroupSampler`` with the K ensembles resident in HBM (``msx_group_sampler_*``, include/msx.h): ``chunk`` iterations
+    are queued on the GPU back to back, ONE launch of the group kernel per half-step over the active half of every
+    target's ensemble, and only the chains come back.  Each target's randomness is drawn on the host by its own
+    ``EnsembleSampler``'s generators, the calls ``GroupSampler`` makes, so target k's chain is bit for bit the chain of
+    ``GroupSampler`` and of ``EnsembleSampler(nwalkers[k], ndim, f_k, vectorize=True, seed=seeds[k])``.
+
+    ``group`` is a ``TargetGroup``; ``mode`` ``'logposterior'`` or ``'loglikelihood'``.  Drawing chunk i+1 overlaps chunk i
+    on the GPU (as ``DeviceEnsembleSampler.sample``); consecutive ``sample`` calls continue the generators.  A walker error
+    raises what ``TargetGroup`` raises, prefixed ``target k:``; the run ends there and the chain up to the last collected
+    chunk stands."""
+
+    def __init__(self, nwalkers, ndim, group, mode='logposterior', a=2.0, seeds=None, chunk=64):
+        if mode not in ('logposterior', 'loglikelihood'):
+            raise ValueError("mode must be 'logposterior' or 'loglikelihood'")
+        nwalkers = [int(n) for n in nwalkers]
+        if len(nwalkers) != len(group):
+            raise ValueError('one walker count per target ({} given, {} targets)'.format(len(nwalkers), len(group)))
+        if int(chunk) < 1:
+            raise ValueError('chunk must be at least 1')
+        self.group = group
+        self.mode = mode
+        self._mode = {'logposterior': _lib.MODE_LOGPOST, 'loglikelihood': _lib.MODE_LOGLIKE}[mode]
+        fn = group.logposterior if mode == 'logposterior' else group.loglikelihood
+        super().__init__(nwalkers, ndim, fn, a=a, seeds=seeds)
+        self.chunk = int(chunk)
+
+    def _initial(self, initial_states):
+        if len(initial_states) != len(self.samplers):
+            raise ValueError('one initial state per target')
+        coords, logp = [], []
+        for k, (st, smp) in enumerate(zip(initial_states, self.samplers)):
+            if isinstance(st, State):
+                c, lp = st.coords.copy(), st.log_prob.copy()
+            else:
+                c, lp = np.array(st, dtype=float), None
+            if c.shape != (smp.nwalkers, self.ndim):
+                raise ValueError('incompatible input dimensions (target {})'.format(k))
+            coords.append(c)
+            logp.append(lp if lp is not None and lp.shape == (smp.nwalkers,) else None)
+        missing = [k for k, lp in enumerate(logp) if lp is None]
+        if missing:  # one group launch for every target that came without its log-probabilities
+            lps = self.compute_log_prob([coords[k] if logp[k] is None else np.empty((0, self.ndim)) for k in range(len(coords))])
+            for k in missing:
+                logp[k] = lps[k]
+        return coords, logp
+
+    def _draw_split_all(self, m):
+        split = [s._draw_split(m) for s in self.samplers]
+        return [np.concatenate(x, axis=2) for x in zip(*split)]
+
+    def _draw_moves_all(self, m):
+        moves = [s._draw_moves(m) for s in self.samplers]
+        return [np.concatenate(x, axis=2) for x in zip(*moves)]
+
+    def sample(self, initial_states, iterations=1, store=True):
+        """``initial_states``: one State or coordinate array ``(nwalkers[k], ndim)`` per target.  Yields a list of K States
+        per iteration."""
+        from collections import deque
+        from concurrent.futures import ThreadPoolExecutor
+        coords, logp = self._initial(initial_states)
+        left = int(iterations)
+        if left <= 0:
+            return
+        counts = self.nwalkers
+        off = np.concatenate([[0], np.cumsum(counts)]).astype(int)
+        grp = self.group.group
+        base_acc = [s._accepted.copy() for s in self.samplers]
+
+        def submit(pool, m):
+            return (pool.submit(self._draw_split_all, m), pool.submit(self._draw_moves_all, m)) if m > 0 else None
+
+        def next_size(prev, left):  # (DeviceEnsembleSampler's ramp: the first launch does not wait for a whole chunk)
+            return min(left, self.chunk, max(8, 2 * prev))
+
+        grp.sampler_begin(self._mode, np.concatenate(coords), np.concatenate(logp), counts, self.chunk)
+        try:
+            with ThreadPoolExecutor(max_workers=2) as pool:
+                queued = deque()
+                m = next_size(4, left)
+                fut = submit(pool, m)
+                slot = 0
+                while left > 0 or queued:
+                    if left > 0:
+                        arrays = [x for f in fut for x in f.result()]
+                        left -= m
+                        m_next = next_size(m, left) if left > 0 else 0
+                        fut = submit(pool, m_next)
+                        grp.sampler_enqueue(slot, *arrays)
+                        queued.append((slot, m))
+                        slot ^= 1
+                        m = m_next
+                        if len(queued) < 2 and left > 0:
+                            continue  # keep two chunks in flight
+                    sl, mm = queued.popleft()
+                    chain, lpc, nacc, worst = grp.sampler_collect(sl, mm)
+                    for k in np.nonzero(worst > _lib.W_REJECT)[0]:
+                        try:
+                            _raise_for_status(worst[k:k + 1], chain[-1, off[k]:off[k] + 1])
+                        except (KeyError, IndexError, ValueError, RuntimeError) as e:
+                            raise type(e)('target {}: {}'.format(k, e.args[0] if e.args else e)) from None
+                    for k, s in enumerate(self.samplers):
+                        s._accepted = base_acc[k] + nacc[off[k]:off[k + 1]]
+                    for i in range(mm):
+                        states = []
+                        for k, s in enumerate(self.samplers):
+                            c, lp = chain[i, off[k]:off[k + 1]], lpc[i, off[k]:off[k + 1]]
+                            s.iteration += 1
+                            if store:
+                                s._chain.append(c)
+                                s._logp.append(lp)
+                            s._last = State(c, lp)
+                            states.append(s._last)
+                        yield states
+        finally:
+            grp.sampler_end()

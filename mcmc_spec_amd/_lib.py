@@ -415,17 +415,7 @@ class Context:
 
     def sampler_enqueue(self, slot, sidx, cidx, partner, zz, zfac, logu):
         """Queue one chunk (arrays of shape (nsteps, 2, nw/2)) without waiting for it."""
-        i32p = C.POINTER(C.c_int32)
-        arrs = [np.ascontiguousarray(a, dtype=np.int32) for a in (sidx, cidx, partner)]
-        dbl = [as_f64(a) for a in (zz, zfac, logu)]
-        nsteps = dbl[0].shape[0]
-        for a in arrs + dbl:
-            if a.shape != (nsteps, 2, self._smp_shape[0] // 2):
-                raise ValueError('sampler_enqueue: arrays must have shape (nsteps, 2, nwalkers/2)')
-        self.check(self.lib.msx_sampler_enqueue(self.h, int(slot), nsteps, arrs[0].ctypes.data_as(i32p),
-                                                arrs[1].ctypes.data_as(i32p), arrs[2].ctypes.data_as(i32p),
-                                                dptr(dbl[0]), dptr(dbl[1]), dptr(dbl[2])))
-        return nsteps
+        return _sampler_enqueue(self, self.lib.msx_sampler_enqueue, 'nwalkers/2', slot, (sidx, cidx, partner, zz, zfac, logu))
 
     def sampler_enqueue_drawn(self, slot, nsteps, seed, a=2.0):
         """Queue one chunk whose randomness the device draws itself (msx_sampler_enqueue_drawn)."""
@@ -446,21 +436,13 @@ class Context:
 
     def sampler_collect(self, slot, nsteps):
         """Wait for the chunk in `slot`: (chain [nsteps][nw][ndim], logp [nsteps][nw], naccept [nw], worst)."""
-        nw, ndim = self._smp_shape
-        chain, lpc = np.empty((nsteps, nw, ndim)), np.empty((nsteps, nw))
-        nacc = np.zeros(nw, dtype=np.int64)
+        chain, lpc, nacc = _collect_out(self._smp_shape, nsteps)
         worst = C.c_int32()
         self.check(self.lib.msx_sampler_collect(self.h, int(slot), dptr(chain), dptr(lpc), iptr(nacc), C.byref(worst)))
         return chain, lpc, nacc, worst.value
 
     def sampler_end(self, want_state=False):
-        if not want_state:
-            self.check(self.lib.msx_sampler_end(self.h, None, None))
-            return None
-        nw, ndim = self._smp_shape
-        coords, logp = np.empty((nw, ndim)), np.empty(nw)
-        self.check(self.lib.msx_sampler_end(self.h, dptr(coords), dptr(logp)))
-        return coords, logp
+        return _sampler_end(self, self.lib.msx_sampler_end, want_state)
 
     def make_composite(self, teff, logg, rad, use_distance, plx, win_n, nc, nph):
         teff, logg, rad = as_f64(teff), as_f64(logg), as_f64(rad)
@@ -621,33 +603,48 @@ class Group:
 
     def sampler_enqueue(self, slot, sidx, cidx, partner, zz, zfac, logu):
         """Queue one chunk: arrays (nsteps, 2, sum(counts)/2), the members' active halves side by side, indices member-local."""
-        i32p = C.POINTER(C.c_int32)
-        arrs = [np.ascontiguousarray(a, dtype=np.int32) for a in (sidx, cidx, partner)]
-        dbl = [as_f64(a) for a in (zz, zfac, logu)]
-        nsteps = dbl[0].shape[0]
-        for a in arrs + dbl:
-            if a.shape != (nsteps, 2, self._smp_shape[0] // 2):
-                raise ValueError('sampler_enqueue: arrays must have shape (nsteps, 2, sum(counts)/2)')
-        self.check(self.lib.msx_group_sampler_enqueue(self.h, int(slot), nsteps, arrs[0].ctypes.data_as(i32p),
-                                                      arrs[1].ctypes.data_as(i32p), arrs[2].ctypes.data_as(i32p),
-                                                      dptr(dbl[0]), dptr(dbl[1]), dptr(dbl[2])))
-        return nsteps
+        return _sampler_enqueue(self, self.lib.msx_group_sampler_enqueue, 'sum(counts)/2', slot, (sidx, cidx, partner, zz, zfac, logu))
 
     def sampler_collect(self, slot, nsteps):
         """Wait for the chunk in `slot`: (chain [nsteps][n][ndim], logp [nsteps][n], naccept [n], worst [k])."""
-        n, ndim = self._smp_shape
-        chain, lpc = np.empty((nsteps, n, ndim)), np.empty((nsteps, n))
-        nacc = np.zeros(n, dtype=np.int64)
+        chain, lpc, nacc = _collect_out(self._smp_shape, nsteps)
         worst = np.zeros(self.k, dtype=np.int32)
         self.check(self.lib.msx_group_sampler_collect(self.h, int(slot), dptr(chain), dptr(lpc), iptr(nacc),
                                                       worst.ctypes.data_as(C.POINTER(C.c_int32))))
         return chain, lpc, nacc, worst
 
     def sampler_end(self, want_state=False):
-        if not want_state:
-            self.check(self.lib.msx_group_sampler_end(self.h, None, None))
-            return None
-        n, ndim = self._smp_shape
-        coords, logp = np.empty((n, ndim)), np.empty(n)
-        self.check(self.lib.msx_group_sampler_end(self.h, dptr(coords), dptr(logp)))
-        return coords, logp
+        return _sampler_end(self, self.lib.msx_group_sampler_end, want_state)
+
+
+# ---- the device-resident samplers' marshalling, shared by Context (msx_sampler_*) and Group (msx_group_sampler_*) ----
+def _sampler_enqueue(owner, fn, half, slot, arrays):
+    """fn(h, slot, nsteps, sidx, cidx, partner, zz, zfac, logu) for one chunk of arrays (nsteps, 2, owner's walkers / 2);
+    ``half`` names that size in the error message."""
+    i32p = C.POINTER(C.c_int32)
+    arrs = [np.ascontiguousarray(a, dtype=np.int32) for a in arrays[:3]]
+    dbl = [as_f64(a) for a in arrays[3:]]
+    nsteps = dbl[0].shape[0]
+    for a in arrs + dbl:
+        if a.shape != (nsteps, 2, owner._smp_shape[0] // 2):
+            raise ValueError('sampler_enqueue: arrays must have shape (nsteps, 2, {})'.format(half))
+    owner.check(fn(owner.h, int(slot), nsteps, arrs[0].ctypes.data_as(i32p), arrs[1].ctypes.data_as(i32p),
+                   arrs[2].ctypes.data_as(i32p), dptr(dbl[0]), dptr(dbl[1]), dptr(dbl[2])))
+    return nsteps
+
+
+def _collect_out(shape, nsteps):
+    """A chunk's outputs for the run's (walkers, ndim): chain [nsteps][n][ndim], logp [nsteps][n], naccept [n]."""
+    n, ndim = shape
+    return np.empty((nsteps, n, ndim)), np.empty((nsteps, n)), np.zeros(n, dtype=np.int64)
+
+
+def _sampler_end(owner, fn, want_state):
+    """fn(h, coords, logp): end the run; its final (coords, logp) if want_state."""
+    if not want_state:
+        owner.check(fn(owner.h, None, None))
+        return None
+    n, ndim = owner._smp_shape
+    coords, logp = np.empty((n, ndim)), np.empty(n)
+    owner.check(fn(owner.h, dptr(coords), dptr(logp)))
+    return coords, logp

@@ -44,6 +44,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <array>
 #include <mutex>
 #include <type_traits>
 #include <string>
@@ -221,12 +222,17 @@ int fail(msx_ctx *c, int code, const std::string &msg) {
     if (c) c->err = msg;
     return code;
 }
+int fail(msx_group *g, int code, const std::string &msg) {
+    if (g) g->err = msg;
+    return code;
+}
 
-#define HIP_TRY(ctx, expr)                                                                         \
+// (h: an msx_ctx or an msx_group)
+#define HIP_TRY(h, expr)                                                                           \
     do {                                                                                           \
         hipError_t e__ = (expr);                                                                   \
         if (e__ != hipSuccess)                                                                     \
-            return fail(ctx, MSX_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__));     \
+            return fail(h, MSX_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__));       \
     } while (0)
 
 template <typename T>
@@ -321,6 +327,56 @@ int launch_conv(msx_ctx *c, const double *d_in, int64_t in_stride, double *d_tmp
     return MSX_OK;
 }
 
+// The host-pointer entry points' pinned (device-mapped, coherent) staging of n walkers: the kernel reads theta from, and
+// writes its n results to, the buffer itself -- 48 + 12 bytes per walker over PCIe instead of two copy commands (41 -> 38 us
+// per 256-walker call, 122 -> 111 us at 2,048).  [cap x MSX_MAX_DIM theta | cap log p | cap status]: *pin grows to cap =
+// max(n, 1024) walkers when n does not fit; the statuses follow the n log-probs.
+struct PinnedStaging {
+    double *theta, *logp;
+    int32_t *status;
+};
+hipError_t pinned_staging(void **pin, int64_t *cap, int64_t n, PinnedStaging *out) {
+    if (n > *cap) {
+        if (*pin) (void)hipHostFree(*pin);
+        *pin = nullptr; *cap = 0;
+        const int64_t want = std::max<int64_t>(n, 1024);
+        const hipError_t e = hipHostMalloc(pin, (sizeof(double) * (MSX_MAX_DIM + 1) + sizeof(int32_t)) * want, hipHostMallocDefault);
+        if (e != hipSuccess) return e;
+        *cap = want;
+    }
+    out->theta = reinterpret_cast<double *>(*pin);
+    out->logp = out->theta + *cap * MSX_MAX_DIM;
+    out->status = reinterpret_cast<int32_t *>(out->logp + n);
+    return hipSuccess;
+}
+
+// block_threads as the entry points take it: MSX_BLOCK_512_SHARED is 512 with shared512; nothing else but 0, 256, 512
+template <class H>
+int decode_block(H *h, int32_t &block_threads, bool &shared512) {
+    shared512 = block_threads == MSX_BLOCK_512_SHARED;  // 512 threads, the <= 128-VGPR variant that shares a CU with another workgroup
+    if (shared512) block_threads = 512;
+    if (block_threads != 0 && block_threads != 256 && block_threads != 512)
+        return fail(h, MSX_ERR_INVALID, "block_threads must be 0, 256, 512 or MSX_BLOCK_512_SHARED");
+    return MSX_OK;
+}
+
+// msx_launch_info's and msx_group_launch_info's answer: out8 = the plan's {form, threads, -, -, dynamic LDS, requested
+// bytes, workgroups, walkers per sub-batch} with the kernel's VGPRs and static LDS filled in, and its name
+template <class H>
+int launch_info_out(H *h, const void *fn, std::array<int64_t, 8> v, const std::string &nm, char *name, int32_t name_len,
+                    int64_t *out8) {
+    hipFuncAttributes at;
+    HIP_TRY(h, hipFuncGetAttributes(&at, fn));
+    v[2] = at.numRegs;
+    v[3] = (int64_t)at.sharedSizeBytes;
+    std::copy(v.begin(), v.end(), out8);
+    if (name && name_len > 0) {
+        strncpy(name, nm.c_str(), (size_t)name_len - 1);
+        name[name_len - 1] = 0;
+    }
+    return MSX_OK;
+}
+
 // A synchronous entry point has seen the walkers' statuses: MSX_W_HANDOVER anywhere means the linked form's flags are
 // no longer trustworthy on this context (the device-side poison word says the same to every later linked launch).
 // (The pair form's bounded wait -- a spill row's lease never granted -- reports the same status: the launch is over when a
@@ -334,19 +390,62 @@ void note_handover(msx_ctx *c, const int32_t *status, int64_t n) {
         }
 }
 
-int pick_block(const msx_ctx *c, int64_t n, int64_t npix) {
+// ---- the fused form's launch rules, over plain inputs: a context's launch (plan_launch) and a target group's
+// (plan_group_launch, over its longest member, the AND of its members' flags and its total walkers) both read them ------
+
+// The workgroup size for n walkers of npix pixels on `cus` CUs.
+int pick_block(int64_t cus, int64_t n, int64_t npix) {
     // Measured at 4096 px: up to one walker per CU, 512 threads owning the CU with the pixel statics in
     // LDS; up to 2 per CU, 512 threads sharing the CU two by two (<= 128 VGPRs); beyond, 256 threads three per CU
     // (512 / 1024 / 2048 walkers: 28.3 / 48.2 / 87.8 us shared-512 against 29.2 / 47.2 / 77.6 us with 256 threads).
     // Long spectra (model vector > half the LDS): 512 threads, one workgroup per CU.
     // The choice only affects speed: every variant sums in the same order (see phase A), so a walker's value
     // has the same bits whichever one evaluates it.
-    const int64_t cus = c->prop.multiProcessorCount > 0 ? c->prop.multiProcessorCount : 256;
     if (npix >= 8192) return 512;
     if (n <= cus) return 512;
     if (npix <= 2048) return 256;  // short spectra (512 walkers x 1194 px: 17.8 us with 256 threads, 20.2 shared-512)
     if (n <= 2 * cus) return 512;
     return 256;
+}
+
+// Which variant of `block` threads n walkers of npix pixels want: SH (two workgroups per CU) and / or PF (u and the data
+// flux staged in LDS; pf_ok / pf256_ok: its statics fit, at 512 / 256 threads).  shared512: MSX_BLOCK_512_SHARED.
+struct FusedShape {
+    bool sh = false, pf = false;
+};
+FusedShape fused_shape(int64_t cus, int64_t n, int64_t npix, int block, bool shared512, bool pf_ok, bool pf256_ok) {
+    FusedShape f;
+    if (block == 256) {
+        // at most two walkers per CU (config 5's 512 x 1194 px): the variant compiled for two workgroups per CU has the
+        // registers for quad trips (16.0 against 16.3 us); beyond, three per CU matter more.  With u and the data flux
+        // staged in LDS (PF) when two such workgroups still fit a CU.
+        f.sh = n <= 2 * cus;
+        f.pf = f.sh && pf256_ok;
+    } else {
+        // PF: 512-thread workgroups that own their CU (long spectra: one per CU anyway) and whose 3 npix doubles fit
+        // (256 walkers x 4096 px 16.7-16.9 us against 17.0-17.1 for the <= 128-VGPR variant).  Between one and two
+        // walkers per CU, or when asked for: the <= 128-VGPR variant, two workgroups per CU.
+        const bool own_cu = n <= cus || sizeof(double) * (size_t)npix > 70 * 1024;
+        f.pf = !shared512 && own_cu && pf_ok;
+        f.sh = !f.pf && (shared512 || !own_cu);
+    }
+    return f;
+}
+
+// no pad pixels, and npair a whole number of trips of `trip` elements (the fused variants' FULL entries: 2 x threads)
+bool whole_trips(const DevProblem &P, int64_t trip) { return P.npix == 2 * P.npair && P.npair % trip == 0; }
+
+// dynamic LDS of a fused variant: the model vector; PF adds u and the data flux in the tables' pair layout
+size_t fused_dyn_lds(const DevProblem &P, bool pf) {
+    return pf ? sizeof(double) * (size_t)((P.npix + 1) & ~1ll) + 2 * sizeof(double2) * (size_t)P.npair : sizeof(double) * (size_t)P.npix;
+}
+
+// bytes a fused variant requests from the memory system per walker
+//   blend: 12-B {R f64, H f32} per corner (8-B with the R table in float32) + {k_lo f64, dk f32} + data flux, u (f64) per pixel
+//   chi^2 pass: 1/err^2, and -- unless the variant kept them in LDS (PF) -- u and data flux again
+int64_t fused_bytes(const DevProblem &P, bool pf, bool r32) {
+    const int64_t per_corner = r32 ? 8 : 12;  // {R f64 | f32, H f32}
+    return P.npix * (per_corner * (int64_t)P.nspec * 4 + 12 + 16 + (pf ? 8 : 24)) + 8 * (2 * P.nspec + 2) + 12;
 }
 
 }  // namespace
@@ -363,6 +462,15 @@ struct LaunchArgs {
     hipStream_t s;
     int niso_nt, ng_mode_fast;
 };
+
+// The leading, preloaded arguments' packed words (logprob_kernel decodes them; logprob_group_kernel ORs in its launch's mode):
+// niso | nt << 16, and ng | mode << 8 | fast << 16 | smp_on << 17 | dist_fit << 18 | use_av << 19; `fast` = the recipe's
+// small tables fit the register-resident recipe.
+void pack_leading_words(const DevProblem &P, bool fast, int mode, int *niso_nt, int *ng_mode_fast) {
+    *niso_nt = (int)(std::min<int64_t>(P.niso, 0xffff) | ((int64_t)std::min<int64_t>(P.nt, 0x7fff) << 16));
+    *ng_mode_fast = (int)std::min<int64_t>(P.ng, 0xff) | (mode << 8) | ((fast ? 1 : 0) << 16) | ((P.smp_on ? 1 : 0) << 17) |
+                    ((P.dist_fit ? 1 : 0) << 18) | ((P.use_av ? 1 : 0) << 19);
+}
 
 // A copy of the staged problem whose per-walker pointers start at walker `off` of the caller's batch (sub-batches)
 DevProblem problem_at(const DevProblem &P0, int64_t off, int mode, int ndim) {
@@ -460,8 +568,6 @@ const Variant *find_variant(const Variant &want, bool whole) {
             hit = &v;
     return hit;
 }
-// no pad pixels, and npair a whole number of trips of `trip` elements
-bool whole_trips(const DevProblem &P, int64_t trip) { return P.npix == 2 * P.npair && P.npair % trip == 0; }
 
 // THE launch decision, for the launcher (per sub-batch), msx_launch_info and msx_bytes_per_eval alike: how a launch of n
 // walkers in form f with workgroups of block_threads (0: automatic; shared512: MSX_BLOCK_512_SHARED) runs.
@@ -611,11 +717,7 @@ int64_t requested_bytes_of(const msx_ctx *c, const FormChoice &f, const Variant 
     // the pair form: two walkers per set of loads -- rows, extinction terms, the fit sweep's data flux / u, the pass's three
     // vectors -- + the planner's record
     if (f.pair) return npix * (12 * 8 + 12 + 16 + 24) / 2 + (int64_t)sizeof(PairRec) + 8 * 6 + 12;
-    //   blend: 12-B {R f64, H f32} per corner + {k_lo f64, dk f32} + data flux, u (f64)        per pixel
-    //   chi^2 pass: 1/err^2, and -- unless the variant kept them in LDS (PF) -- u and data flux again
-    const bool pf = v && v->pf;
-    const int64_t per_corner = (v && v->r32) ? 8 : 12;  // {R f64 | f32, H f32}
-    int64_t b = npix * (per_corner * (int64_t)c->P.nspec * 4 + 12 + 16 + (pf ? 8 : 24)) + 8 * (2 * c->P.nspec + 2) + 12;
+    int64_t b = fused_bytes(c->P, v && v->pf, v && v->r32);
     // the linked form: every segment's workgroup reads theta and writes its partials (counters, sums, range; chi^2 sum
     // and candidates: <= 64 of them as a rule), reads the other segments' partials, and one of them their candidates
     if (f.linked) {
@@ -634,7 +736,7 @@ LaunchPlan plan_launch(const msx_ctx *c, const FormChoice &f, int64_t n, int blo
     pl.rows = f.inpath ? c->inp_rows : f.pair ? c->pair_rows : (f.linked || c->model_in_global) ? c->scratch_rows : n;
     pl.m = std::min(n, pl.rows);
     const int64_t m = pl.m;
-    pl.block = (f.linked || f.inpath) ? 512 : block_threads > 0 ? block_threads : pick_block(c, m, P.npix);
+    pl.block = (f.linked || f.inpath) ? 512 : block_threads > 0 ? block_threads : pick_block(cus, m, P.npix);
     if (f.pair) {
         // a trip of the pair kernel is NT x 512 elements
         const int nt = P.npair <= 2 * 512 ? 2 : 4;
@@ -657,20 +759,9 @@ LaunchPlan plan_launch(const msx_ctx *c, const FormChoice &f, int64_t n, int blo
     want.r32 = c->store_f32;  // (msx_stage_problem has checked that the problem has such variants: fused binaries)
     if (!want.lk && !want.given && !want.gm) {
         want.threads = B;
-        if (B == 256) {
-            // at most two walkers per CU (config 5's 512 x 1194 px): the variant compiled for two workgroups per CU has the
-            // registers for quad trips (16.0 against 16.3 us); beyond, three per CU matter more.  With u and the data flux
-            // staged in LDS (PF) when two such workgroups still fit a CU.
-            want.sh = m <= 2 * cus;
-            want.pf = want.sh && c->pf256_ok;
-        } else {
-            // PF: 512-thread workgroups that own their CU (long spectra: one per CU anyway) and whose 3 npix doubles fit
-            // (256 walkers x 4096 px 16.7-16.9 us against 17.0-17.1 for the <= 128-VGPR variant).  Between one and two
-            // walkers per CU, or when asked for: the <= 128-VGPR variant, two workgroups per CU.
-            const bool own_cu = m <= cus || sizeof(double) * (size_t)P.npix > 70 * 1024;
-            want.pf = !shared512 && own_cu && c->pf_ok;
-            want.sh = !want.pf && (shared512 || !own_cu);
-        }
+        const FusedShape fs = fused_shape(cus, m, P.npix, B, shared512, c->pf_ok, c->pf256_ok);
+        want.sh = fs.sh;
+        want.pf = fs.pf;
     }
     // 2. its entry of the table -- triples have no SH variant (twelve corners do not fit its 128 VGPRs) and take the plain
     //    one; the FULL entry when the spectrum is whole trips of 2 x threads elements
@@ -683,12 +774,10 @@ LaunchPlan plan_launch(const msx_ctx *c, const FormChoice &f, int64_t n, int blo
     if (!pl.v) return pl;
     pl.fn = pl.v->fn;
     pl.threads = pl.v->threads;
-    // dynamic LDS: the model vector (linked: one segment of it, and the segment's data flux behind it); PF adds u and the
-    // data flux in the tables' pair layout
+    // dynamic LDS: the fused variants' (linked: one segment of the model vector, and the segment's data flux behind it)
     pl.dyn_lds = pl.v->lk ? sizeof(double) * (size_t)(2 * kSegElems) + sizeof(double2) * (size_t)kSegElems
                  : pl.v->gm ? 0
-                 : pl.v->pf ? sizeof(double) * (size_t)((P.npix + 1) & ~1ll) + 2 * sizeof(double2) * (size_t)P.npair
-                            : sizeof(double) * (size_t)P.npix;
+                 : fused_dyn_lds(P, pl.v->pf);
     // (linked: block = (walker / 8) * 8 segments + segment * 8 + walker % 8, see the kernel)
     pl.grid = pl.v->lk ? ((m + 7) & ~7ll) * c->nseg : m;
     pl.bytes = requested_bytes_of(c, f, pl.v);
@@ -738,13 +827,11 @@ struct GroupPlan {
     int64_t bytes = 0;  // requested from the memory system per walker, averaged over the launch's walkers
 };
 
-// plan_launch's rules for the fused form, applied to (the launch's walkers, its longest member), restricted to the entries
-// every member with walkers can take: FULL only if every one of them is whole trips of it, PF only if every one's statics
-// fit (pf_ok / pf256_ok).  counts[m] = member m's walkers; total = their sum (> 0).
+// plan_launch's rules for the fused form (fused_shape, whole_trips), applied to the launch's walkers and its longest member,
+// restricted to the entries every member with walkers can take: FULL only if every one of them is whole trips of it, PF
+// only if every one's statics fit (pf_ok / pf256_ok).  counts[m] = member m's walkers; total = their sum (> 0).
 GroupPlan group_plan_lds(const msx_group *g, const int64_t *counts, int64_t total, const GroupVariant *v);
 GroupPlan plan_group_launch(const msx_group *g, const int64_t *counts, int64_t total, int block_threads, bool shared512) {
-    GroupPlan pl;
-    const int64_t cus = g->cus;
     const int k = (int)g->members.size();
     int64_t npix = 0;
     bool pf = true, pf256 = true;
@@ -754,48 +841,31 @@ GroupPlan plan_group_launch(const msx_group *g, const int64_t *counts, int64_t t
             pf = pf && g->pf_ok[m];
             pf256 = pf256 && g->pf256_ok[m];
         }
-    // (pick_block's rule)
-    const int B = block_threads > 0 ? block_threads
-                  : npix >= 8192 ? 512 : total <= cus ? 512 : npix <= 2048 ? 256 : total <= 2 * cus ? 512 : 256;
-    bool want_sh, want_pf;
-    if (B == 256) {
-        want_sh = total <= 2 * cus;
-        want_pf = want_sh && pf256;
-    } else {
-        const bool own_cu = total <= cus || sizeof(double) * (size_t)npix > 70 * 1024;
-        want_pf = !shared512 && own_cu && pf;
-        want_sh = !want_pf && (shared512 || !own_cu);
-    }
+    const int B = block_threads > 0 ? block_threads : pick_block(g->cus, total, npix);
+    bool whole = true;
+    for (int m = 0; m < k; ++m)
+        if (counts[m] > 0) whole = whole && whole_trips(g->probs[m], 2 * (int64_t)B);
+    FusedShape want = fused_shape(g->cus, total, npix, B, shared512, pf, pf256);
     const int ns = g->nspec == 2 ? 2 : 3;
-    for (int attempt = 0; attempt < 2 && !pl.v; ++attempt) {
-        if (attempt == 1) want_sh = want_pf = false;  // triples have no SH variant
-        bool whole = true;
-        for (int m = 0; m < k; ++m)
-            if (counts[m] > 0) whole = whole && whole_trips(g->probs[m], 2 * (int64_t)B);
+    const GroupVariant *hit = nullptr;
+    for (int attempt = 0; attempt < 2 && !hit; ++attempt) {
+        if (attempt == 1) want.sh = want.pf = false;  // triples have no SH variant
         for (const GroupVariant &v : kGroupVariants)
-            if (v.ns == ns && v.threads == B && v.sh == want_sh && v.pf == want_pf && (v.full == 0 || whole) && (!pl.v || v.full != 0))
-                pl.v = &v;
+            if (v.ns == ns && v.threads == B && v.sh == want.sh && v.pf == want.pf && (v.full == 0 || whole) && (!hit || v.full != 0))
+                hit = &v;
     }
-    if (!pl.v) return pl;
-    return group_plan_lds(g, counts, total, pl.v);
+    return hit ? group_plan_lds(g, counts, total, hit) : GroupPlan();
 }
 
-// the plan's dynamic LDS and bytes for entry v
+// the plan's dynamic LDS (the largest member's) and bytes (averaged over the walkers) for entry v
 GroupPlan group_plan_lds(const msx_group *g, const int64_t *counts, int64_t total, const GroupVariant *v) {
     GroupPlan pl;
     pl.v = v;
-    const int k = (int)g->members.size();
-    // dynamic LDS: the longest member's model vector; PF: the largest member's model vector + u and data flux in pairs
     double bytes = 0.0;
-    for (int m = 0; m < k; ++m) {
+    for (int m = 0; m < (int)g->members.size(); ++m) {
         if (counts[m] <= 0) continue;
-        const DevProblem &P = g->probs[m];
-        const size_t lds = pl.v->pf ? sizeof(double) * (size_t)((P.npix + 1) & ~1ll) + 2 * sizeof(double2) * (size_t)P.npair
-                                    : sizeof(double) * (size_t)P.npix;
-        pl.dyn_lds = std::max(pl.dyn_lds, lds);
-        // requested_bytes_of's fused-form count for this member
-        const int64_t b = P.npix * (12 * (int64_t)P.nspec * 4 + 12 + 16 + (pl.v->pf ? 8 : 24)) + 8 * (2 * P.nspec + 2) + 12;
-        bytes += (double)b * (double)counts[m];
+        pl.dyn_lds = std::max(pl.dyn_lds, fused_dyn_lds(g->probs[m], v->pf));
+        bytes += (double)fused_bytes(g->probs[m], v->pf, false) * (double)counts[m];
     }
     pl.bytes = (int64_t)(bytes / (double)total + 0.5);
     return pl;
@@ -1575,20 +1645,12 @@ int msx_logprob_batch_dev(msx_ctx *c, int32_t mode, const double *d_theta, int64
     if ((mode == MSX_MODE_OPT_STEP || mode == MSX_MODE_OPT_INIT) && !c->P.opt_flux)
         return fail(c, MSX_ERR_STATE, "optimiser modes go through msx_opt_init / msx_opt_step");
     if (n == 0) return MSX_OK;
-    const bool shared512 = block_threads == MSX_BLOCK_512_SHARED;  // 512 threads, the <= 128-VGPR variant that
-    if (shared512) block_threads = 512;                            // shares a CU with another workgroup
-    if (block_threads != 0 && block_threads != 256 && block_threads != 512)
-        return fail(c, MSX_ERR_INVALID, "block_threads must be 0, 256, 512 or MSX_BLOCK_512_SHARED");
-    hipStream_t s = (hipStream_t)hip_stream;
+    bool shared512;
+    if (int rc = decode_block(c, block_threads, shared512)) return rc;
     const DevProblem &Pc = c->P;
-    // the leading, preloaded kernel arguments (see logprob_kernel): theta, the recipe's small tables and three
-    // packed ints; `fast` = the tables fit the register-resident recipe
-    const bool fast = c->recipe_fast;
     LaunchArgs A;
-    A.ndim = ndim; A.mode = mode; A.s = s;
-    A.niso_nt = (int)(std::min<int64_t>(Pc.niso, 0xffff) | ((int64_t)std::min<int64_t>(Pc.nt, 0x7fff) << 16));
-    A.ng_mode_fast = (int)std::min<int64_t>(Pc.ng, 0xff) | (mode << 8) | ((fast ? 1 : 0) << 16) | ((Pc.smp_on ? 1 : 0) << 17) |
-                     ((Pc.dist_fit ? 1 : 0) << 18) | ((Pc.use_av ? 1 : 0) << 19);
+    A.ndim = ndim; A.mode = mode; A.s = (hipStream_t)hip_stream;
+    pack_leading_words(Pc, c->recipe_fast, mode, &A.niso_nt, &A.ng_mode_fast);
 
     // ---- which form of the path (decide_form) ---------------------------------------------------------------
     const FormChoice form = decide_form(c, n, mode, false);
@@ -1654,26 +1716,14 @@ int msx_logprob_batch(msx_ctx *c, int32_t mode, const double *theta, int64_t n, 
         return fail(c, MSX_ERR_INVALID, "P0 doesn't match what I was expecting (ndim must be 2*nspec+2)");
     if (n == 0) return MSX_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    if (n > c->cap_walkers) {
-        if (c->h_pin) (void)hipHostFree(c->h_pin);
-        c->h_pin = nullptr; c->cap_walkers = 0;
-        const int64_t cap = std::max<int64_t>(n, 1024);
-        HIP_TRY(c, hipHostMalloc((void **)&c->h_pin, (sizeof(double) * (MSX_MAX_DIM + 1) + sizeof(int32_t)) * cap, hipHostMallocDefault));
-        c->cap_walkers = cap;
-    }
-    const int64_t cap = c->cap_walkers;
-    double *h_theta = reinterpret_cast<double *>(c->h_pin);
-    double *h_out = h_theta + cap * MSX_MAX_DIM;  // [cap] log-probs followed by [cap] int32 statuses
-    memcpy(h_theta, theta, sizeof(double) * n * ndim);
-    // the kernel reads theta from, and writes its n results to, the pinned (device-mapped, coherent) staging buffer
-    // itself -- 48 + 12 bytes per walker over PCIe instead of two copy commands (41 -> 38 us per 256-walker call,
-    // 122 -> 111 us at 2,048)
-    int32_t *h_st = reinterpret_cast<int32_t *>(h_out + n);
-    int rc = msx_logprob_batch_dev(c, mode, h_theta, n, ndim, h_out, h_st, c->stream, 0);
+    PinnedStaging h;
+    HIP_TRY(c, pinned_staging(&c->h_pin, &c->cap_walkers, n, &h));
+    memcpy(h.theta, theta, sizeof(double) * n * ndim);
+    int rc = msx_logprob_batch_dev(c, mode, h.theta, n, ndim, h.logp, h.status, c->stream, 0);
     if (rc) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    memcpy(logp_out, h_out, sizeof(double) * n);
-    memcpy(status_out, h_st, sizeof(int32_t) * n);
+    memcpy(logp_out, h.logp, sizeof(double) * n);
+    memcpy(status_out, h.status, sizeof(int32_t) * n);
     note_handover(c, status_out, n);
     return MSX_OK;
 }
@@ -1882,6 +1932,18 @@ static hipError_t run_upload(SamplerRun *r, SamplerRun::Slot &sl, int64_t nsteps
     return e;
 }
 
+// begin: the run's initial state up on `s` -- coordinates, log p and the acceptance counts (naccept, or zeros) -- and `s`
+// synchronised, so the caller's arrays are consumed on return
+static hipError_t run_load_state(SamplerRun *r, hipStream_t s, const double *coords, const double *logp, const int64_t *naccept) {
+    hipError_t e = hipMemcpyAsync(r->d_coords, coords, sizeof(double) * r->nw * r->ndim, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(r->d_logp, logp, sizeof(double) * r->nw, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess)
+        e = naccept ? hipMemcpyAsync(r->d_nacc, naccept, sizeof(int64_t) * r->nw, hipMemcpyHostToDevice, s)
+                    : hipMemsetAsync(r->d_nacc, 0, sizeof(int64_t) * r->nw, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    return e;
+}
+
 static void sampler_free(msx_ctx *c) {
     SamplerRun *r = c->smp;
     if (!r) return;
@@ -1922,9 +1984,7 @@ int msx_sampler_begin(msx_ctx *c, int32_t mode, int64_t nw, int32_t ndim, int64_
         r->d_newlp = r->d_q + 2 * ns * ndim; r->d_nacc = (int64_t *)(r->d_newlp + 2 * ns); r->d_wst = (int32_t *)(r->d_nacc + nw);
         r->d_ver = (uint32_t *)(r->d_wst + 2 * ns);
         r->d_gran = (unsigned long long *)(((uintptr_t)(r->d_ver + nw) + 15) & ~(uintptr_t)15);
-        e = hipMemcpyAsync(r->d_coords, coords, sizeof(double) * nw * ndim, hipMemcpyHostToDevice, c->stream);
-    }
-    if (e == hipSuccess) {
+
         // the granules of version 0 (buffer 0); buffer 1 carries a version nobody asks for until it is written
         hg.assign(gran_words, granule(0u, 0xffffffffu));
         for (int64_t w = 0; w < nw; ++w) {
@@ -1943,11 +2003,7 @@ int msx_sampler_begin(msx_ctx *c, int32_t mode, int64_t nw, int32_t ndim, int64_
         }
         e = hipMemcpyAsync(r->d_gran, hg.data(), sizeof(unsigned long long) * gran_words, hipMemcpyHostToDevice, c->stream);  // (behind the memset)
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(r->d_logp, logp, sizeof(double) * nw, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess)
-        e = naccept ? hipMemcpyAsync(r->d_nacc, naccept, sizeof(int64_t) * nw, hipMemcpyHostToDevice, c->stream)
-                    : hipMemsetAsync(r->d_nacc, 0, sizeof(int64_t) * nw, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // the caller's arrays are consumed on return
+    if (e == hipSuccess) e = run_load_state(r, c->stream, coords, logp, naccept);
     if (e != hipSuccess) {
         sampler_free(c);
         return fail(c, MSX_ERR_HIP, std::string("msx_sampler_begin: ") + hipGetErrorString(e));
@@ -2033,6 +2089,43 @@ static hipError_t run_collect(SamplerRun *r, int32_t slot, double *chain_out, do
     return hipSuccess;
 }
 
+// The checks of an enqueue, in order: a run in flight, the slot and chunk length (args_ok: the caller's arrays), a run
+// that failed part-way, a slot not collected yet.  MSX_OK, or the code with *err set.  who / begin / end: the entry point
+// and its family's begin and end.
+static int run_enqueue_check(std::string *err, const SamplerRun *r, const char *who, const char *begin, const char *end, int32_t slot,
+                             int64_t nsteps, bool args_ok) {
+    const std::string w(who);
+    int code = MSX_OK;
+    if (!r) { code = MSX_ERR_STATE; *err = w + ": call " + begin + " first"; }
+    else if (slot < 0 || slot > 1 || nsteps < 1 || nsteps > r->cap_steps || !args_ok) { code = MSX_ERR_INVALID; *err = w + ": bad arguments"; }
+    else if (r->failed) { code = MSX_ERR_STATE; *err = w + ": an earlier enqueue failed part-way; end this run (" + end + ") and begin again"; }
+    else if (r->slot[slot].busy) { code = MSX_ERR_STATE; *err = w + ": slot not collected yet"; }
+    return code;
+}
+
+// msx_sampler_collect / msx_group_sampler_collect: the checks, then the slot's results (run_collect)
+static int run_collect_checked(std::string *err, SamplerRun *r, const char *who, const char *begin, int32_t slot, double *chain_out,
+                               double *logp_out, int64_t *naccept, int32_t *worst) {
+    const std::string w(who);
+    if (!r) { *err = w + ": call " + begin + " first"; return MSX_ERR_STATE; }
+    if (slot < 0 || slot > 1 || !chain_out || !logp_out || !naccept || !worst) { *err = w + ": bad arguments"; return MSX_ERR_INVALID; }
+    if (!r->slot[slot].busy) { *err = w + ": nothing enqueued in this slot"; return MSX_ERR_STATE; }
+    const hipError_t e = run_collect(r, slot, chain_out, logp_out, naccept, worst);
+    if (e != hipSuccess) { *err = w + ": " + hipGetErrorString(e); return MSX_ERR_HIP; }
+    return MSX_OK;
+}
+
+// end: everything the run queued on `compute` (and its second stream) done, then its state down (coords / logp: nullptr
+// for none).  The caller frees the run.
+static hipError_t run_save_state(const SamplerRun *r, int device, hipStream_t compute, double *coords, double *logp) {
+    hipError_t e = hipSetDevice(device);
+    if (e == hipSuccess) e = hipStreamSynchronize(compute);
+    if (e == hipSuccess && r->s2) e = hipStreamSynchronize(r->s2);
+    if (e == hipSuccess && coords) e = hipMemcpy(coords, r->coords_now(), sizeof(double) * r->nw * r->ndim, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && logp) e = hipMemcpy(logp, r->d_logp, sizeof(double) * r->nw, hipMemcpyDeviceToHost);
+    return e;
+}
+
 // (draw != nullptr: the chunk's randomness is drawn on the device -- sampler_draw_kernel, keyed by draw->seed and the
 // run's absolute iteration numbers -- instead of coming from the host's arrays)
 struct DeviceDraw { unsigned long long seed; double a; };
@@ -2040,15 +2133,12 @@ static int chunk_prepare(msx_ctx *c, int32_t slot, int64_t nsteps, const int32_t
                          const int32_t *partner, const double *zz, const double *zfac, const double *logu, ChunkPtrs *cp,
                          const DeviceDraw *draw = nullptr) {
     SamplerRun *r = c->smp;
-    if (!r) return fail(c, MSX_ERR_STATE, "msx_sampler_enqueue: call msx_sampler_begin first");
-    if (slot < 0 || slot > 1 || nsteps < 1 || nsteps > r->cap_steps || (!draw && (!sidx || !cidx || !partner || !zz || !zfac || !logu)))
-        return fail(c, MSX_ERR_INVALID, "msx_sampler_enqueue: bad arguments");
+    if (int rc = run_enqueue_check(&c->err, r, "msx_sampler_enqueue", "msx_sampler_begin", "msx_sampler_end", slot, nsteps,
+                                   draw || (sidx && cidx && partner && zz && zfac && logu)))
+        return rc;
     if (draw && (r->nw > kDrawMaxWalkers || !(draw->a > 1.0)))
         return fail(c, MSX_ERR_INVALID, "msx_sampler_enqueue_drawn: the device generator takes up to 4096 walkers and a stretch scale a > 1");
-    if (r->failed)
-        return fail(c, MSX_ERR_STATE, "msx_sampler_enqueue: an earlier enqueue failed part-way; end this run (msx_sampler_end) and begin again");
     SamplerRun::Slot &sl = r->slot[slot];
-    if (sl.busy) return fail(c, MSX_ERR_STATE, "msx_sampler_enqueue: slot not collected yet");
     HIP_TRY(c, hipSetDevice(c->device));
     const int64_t ns = r->ns, nw = r->nw, nh = nsteps * 2 * ns;
     const int ndim = r->ndim;
@@ -2176,17 +2266,18 @@ static int chunk_finish(msx_ctx *c, int32_t slot, int64_t nsteps, const ChunkPtr
     return MSX_OK;
 }
 
-int msx_sampler_enqueue(msx_ctx *c, int32_t slot, int64_t nsteps, const int32_t *sidx, const int32_t *cidx,
-                        const int32_t *partner, const double *zz, const double *zfac, const double *logu) {
+// msx_sampler_enqueue (draw = nullptr) and msx_sampler_enqueue_drawn
+static int sampler_enqueue(msx_ctx *c, const char *who, int32_t slot, int64_t nsteps, const int32_t *sidx, const int32_t *cidx,
+                           const int32_t *partner, const double *zz, const double *zfac, const double *logu, const DeviceDraw *draw) {
     if (!c) return MSX_ERR_INVALID;
     if (c->smp && c->smp->sharded && c->smp->world > 1) {
         if (!c->loop_peers.empty())
-            return fail(c, MSX_ERR_STATE, "msx_sampler_enqueue: the ranks of a loopback group advance together (msx_sampler_enqueue_group)");
+            return fail(c, MSX_ERR_STATE, std::string(who) + ": the ranks of a loopback group advance together (msx_sampler_enqueue_group)");
         if (!c->rccl_comm || c->comm_world != c->smp->world)
-            return fail(c, MSX_ERR_STATE, "msx_sampler_enqueue: the run is sharded over a communicator that no longer exists");
+            return fail(c, MSX_ERR_STATE, std::string(who) + ": the run is sharded over a communicator that no longer exists");
     }
     ChunkPtrs cp;
-    int rc = chunk_prepare(c, slot, nsteps, sidx, cidx, partner, zz, zfac, logu, &cp);
+    int rc = chunk_prepare(c, slot, nsteps, sidx, cidx, partner, zz, zfac, logu, &cp, draw);
     if (rc != MSX_OK) return rc;
     for (int64_t st = 0; st < nsteps && rc == MSX_OK; ++st)
         for (int half = 0; half < 2 && rc == MSX_OK; ++half) {
@@ -2197,25 +2288,14 @@ int msx_sampler_enqueue(msx_ctx *c, int32_t slot, int64_t nsteps, const int32_t 
     return chunk_finish(c, slot, nsteps, cp, rc);
 }
 
+int msx_sampler_enqueue(msx_ctx *c, int32_t slot, int64_t nsteps, const int32_t *sidx, const int32_t *cidx,
+                        const int32_t *partner, const double *zz, const double *zfac, const double *logu) {
+    return sampler_enqueue(c, "msx_sampler_enqueue", slot, nsteps, sidx, cidx, partner, zz, zfac, logu, nullptr);
+}
+
 int msx_sampler_enqueue_drawn(msx_ctx *c, int32_t slot, int64_t nsteps, uint64_t seed, double a) {
-    if (!c) return MSX_ERR_INVALID;
-    if (c->smp && c->smp->sharded && c->smp->world > 1) {
-        if (!c->loop_peers.empty())
-            return fail(c, MSX_ERR_STATE, "msx_sampler_enqueue_drawn: the ranks of a loopback group advance together (msx_sampler_enqueue_group)");
-        if (!c->rccl_comm || c->comm_world != c->smp->world)
-            return fail(c, MSX_ERR_STATE, "msx_sampler_enqueue_drawn: the run is sharded over a communicator that no longer exists");
-    }
-    ChunkPtrs cp;
     const DeviceDraw dd = {(unsigned long long)seed, a};
-    int rc = chunk_prepare(c, slot, nsteps, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &cp, &dd);
-    if (rc != MSX_OK) return rc;
-    for (int64_t st = 0; st < nsteps && rc == MSX_OK; ++st)
-        for (int half = 0; half < 2 && rc == MSX_OK; ++half) {
-            rc = chunk_half_eval(c, cp, st, half);
-            if (rc == MSX_OK && c->smp->sharded) rc = chunk_half_gather_rccl(c);
-            if (rc == MSX_OK) rc = chunk_half_apply(c);
-        }
-    return chunk_finish(c, slot, nsteps, cp, rc);
+    return sampler_enqueue(c, "msx_sampler_enqueue_drawn", slot, nsteps, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &dd);
 }
 
 int msx_sampler_draw(msx_ctx *c, uint64_t seed, double a, int64_t first_iter, int64_t nsteps, int64_t nw, int32_t ndim,
@@ -2306,25 +2386,13 @@ int msx_sampler_enqueue_group(msx_ctx **ctxs, int32_t world, int32_t slot, int64
 int msx_sampler_collect(msx_ctx *c, int32_t slot, double *chain_out, double *logp_out, int64_t *naccept,
                         int32_t *worst_status) {
     if (!c) return MSX_ERR_INVALID;
-    SamplerRun *r = c->smp;
-    if (!r) return fail(c, MSX_ERR_STATE, "msx_sampler_collect: call msx_sampler_begin first");
-    if (slot < 0 || slot > 1 || !chain_out || !logp_out || !naccept || !worst_status)
-        return fail(c, MSX_ERR_INVALID, "msx_sampler_collect: bad arguments");
-    SamplerRun::Slot &sl = r->slot[slot];
-    if (!sl.busy) return fail(c, MSX_ERR_STATE, "msx_sampler_collect: nothing enqueued in this slot");
-    HIP_TRY(c, run_collect(r, slot, chain_out, logp_out, naccept, worst_status));
-    return MSX_OK;
+    return run_collect_checked(&c->err, c->smp, "msx_sampler_collect", "msx_sampler_begin", slot, chain_out, logp_out, naccept, worst_status);
 }
 
 int msx_sampler_end(msx_ctx *c, double *coords, double *logp) {
     if (!c) return MSX_ERR_INVALID;
-    SamplerRun *r = c->smp;
-    if (!r) return MSX_OK;
-    hipError_t e = hipSetDevice(c->device);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess && r->s2) e = hipStreamSynchronize(r->s2);
-    if (e == hipSuccess && coords) e = hipMemcpy(coords, r->coords_now(), sizeof(double) * r->nw * r->ndim, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && logp) e = hipMemcpy(logp, r->d_logp, sizeof(double) * r->nw, hipMemcpyDeviceToHost);
+    if (!c->smp) return MSX_OK;
+    const hipError_t e = run_save_state(c->smp, c->device, c->stream, coords, logp);
     sampler_free(c);
     if (e != hipSuccess) return fail(c, MSX_ERR_HIP, std::string("msx_sampler_end: ") + hipGetErrorString(e));
     return MSX_OK;
@@ -2531,10 +2599,8 @@ int msx_launch_info(msx_ctx *c, int32_t mode, int64_t n, int32_t block_threads, 
     if (!c || !out8 || n < 1) return MSX_ERR_INVALID;
     if (!c->problem_staged) return fail(c, MSX_ERR_STATE, "msx_launch_info: no problem staged");
     HIP_TRY(c, hipSetDevice(c->device));
-    const bool shared512 = block_threads == MSX_BLOCK_512_SHARED;
-    if (shared512) block_threads = 512;
-    if (block_threads != 0 && block_threads != 256 && block_threads != 512)
-        return fail(c, MSX_ERR_INVALID, "block_threads must be 0, 256, 512 or MSX_BLOCK_512_SHARED");
+    bool shared512;
+    if (int rc = decode_block(c, block_threads, shared512)) return rc;
     const FormChoice f = decide_form(c, n, mode, true);
     if (f.err != MSX_OK) return fail(c, f.err, f.msg);
     // (the first sub-batch stands for the launch: sub-batches only differ in their walker count)
@@ -2550,21 +2616,8 @@ int msx_launch_info(msx_ctx *c, int32_t mode, int64_t n, int32_t block_threads, 
              (v->lk ? ", linked" : v->gm ? ", GM" : v->pf && v->sh ? ", SH, PF" : v->pf ? ", PF" : v->sh ? ", SH" : "") + (v->r32 ? ", R32" : "") + (v->full == 3 ? ", FULL" : v->full == 2 ? ", FULL(chi2 pass)" : "") + (v->given ? ", GIVEN" : "") + "> (" + v->what + ")";
         if (f.inpath) nm = "inpath_recipe_kernel + inpath_conv_kernel + inpath_resample_kernel + " + nm;
     }
-    hipFuncAttributes at;
-    HIP_TRY(c, hipFuncGetAttributes(&at, pl.fn));
-    out8[0] = f.inpath ? MSX_FORM_INPATH : f.pair ? MSX_FORM_PAIR : f.linked ? MSX_FORM_LINKED : MSX_FORM_FUSED;
-    out8[1] = pl.threads;
-    out8[2] = at.numRegs;
-    out8[3] = (int64_t)at.sharedSizeBytes;
-    out8[4] = (int64_t)pl.dyn_lds;
-    out8[5] = pl.bytes;
-    out8[6] = pl.grid;
-    out8[7] = pl.m;
-    if (name && name_len > 0) {
-        strncpy(name, nm.c_str(), (size_t)name_len - 1);
-        name[name_len - 1] = 0;
-    }
-    return MSX_OK;
+    const int form = f.inpath ? MSX_FORM_INPATH : f.pair ? MSX_FORM_PAIR : f.linked ? MSX_FORM_LINKED : MSX_FORM_FUSED;
+    return launch_info_out(c, pl.fn, {form, pl.threads, 0, 0, (int64_t)pl.dyn_lds, pl.bytes, pl.grid, pl.m}, nm, name, name_len, out8);
 }
 
 int msx_last_form(msx_ctx *c, int32_t *form) {
@@ -2586,39 +2639,28 @@ int msx_pair_stats(msx_ctx *c, int64_t *out2) {
 }
 
 // ---- target groups (include/msx.h, group_kernel.h) -------------------------------------------------------------------
-static int gfail(msx_group *g, int code, const std::string &msg) {
-    if (g) g->err = msg;
-    return code;
-}
-#define GROUP_HIP_TRY(g, expr)                                                                     \
-    do {                                                                                           \
-        hipError_t e__ = (expr);                                                                   \
-        if (e__ != hipSuccess)                                                                     \
-            return gfail(g, MSX_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__));      \
-    } while (0)
-
 int msx_group_create(msx_ctx **ctxs, int32_t k, msx_group **out) {
     if (!out) return MSX_ERR_INVALID;
     msx_group *g = new msx_group();
     *out = g;  // returned even on failure so the caller can read msx_group_last_error
-    if (!ctxs) return gfail(g, MSX_ERR_INVALID, "msx_group_create: null context list");
+    if (!ctxs) return fail(g, MSX_ERR_INVALID, "msx_group_create: null context list");
     if (k < 1 || k > MSX_MAX_GROUP)
-        return gfail(g, MSX_ERR_RANGE, "msx_group_create: 1 to " + std::to_string(MSX_MAX_GROUP) + " members, " + std::to_string(k) + " given");
+        return fail(g, MSX_ERR_RANGE, "msx_group_create: 1 to " + std::to_string(MSX_MAX_GROUP) + " members, " + std::to_string(k) + " given");
     for (int m = 0; m < k; ++m) {
         const msx_ctx *c = ctxs[m];
         const std::string who = "msx_group_create: member " + std::to_string(m);
-        if (!c) return gfail(g, MSX_ERR_INVALID, who + " is a null context");
-        if (!c->problem_staged) return gfail(g, MSX_ERR_STATE, who + ": no problem staged");
+        if (!c) return fail(g, MSX_ERR_INVALID, who + " is a null context");
+        if (!c->problem_staged) return fail(g, MSX_ERR_STATE, who + ": no problem staged");
         if (c->device != ctxs[0]->device)
-            return gfail(g, MSX_ERR_STATE, who + " is on device " + std::to_string(c->device) + ", member 0 on device " +
+            return fail(g, MSX_ERR_STATE, who + " is on device " + std::to_string(c->device) + ", member 0 on device " +
                                                std::to_string(ctxs[0]->device) + ": a group lives on one device");
         if (c->P.nspec != ctxs[0]->P.nspec)
-            return gfail(g, MSX_ERR_RANGE, who + " has nspec = " + std::to_string(c->P.nspec) + ", member 0 nspec = " +
+            return fail(g, MSX_ERR_RANGE, who + " has nspec = " + std::to_string(c->P.nspec) + ", member 0 nspec = " +
                                                std::to_string(ctxs[0]->P.nspec) + ": the members of a group share nspec (and ndim)");
         if (c->store_f32)
-            return gfail(g, MSX_ERR_STATE, who + " is staged with float32 grid storage (msx_set_grid_storage): groups take float64 tables only");
+            return fail(g, MSX_ERR_STATE, who + " is staged with float32 grid storage (msx_set_grid_storage): groups take float64 tables only");
         if (c->model_in_global)
-            return gfail(g, MSX_ERR_RANGE, who + " has " + std::to_string(c->P.npix) +
+            return fail(g, MSX_ERR_RANGE, who + " has " + std::to_string(c->P.npix) +
                                                " pixels: groups take spectra of at most 17,152 pixels (the model vector in LDS)");
     }
     g->device = ctxs[0]->device;
@@ -2645,18 +2687,15 @@ int msx_group_create(msx_ctx **ctxs, int32_t k, msx_group **out) {
         g->gen.push_back(c->prob_gen);
         GroupMember &r = recs[(size_t)m];
         r.rblk = (const unsigned char *)c->d_recipe_block;
-        // (msx_logprob_batch_dev's packing)
-        r.niso_nt = (int)(std::min<int64_t>(q.niso, 0xffff) | ((int64_t)std::min<int64_t>(q.nt, 0x7fff) << 16));
-        r.ng_fast = (int)std::min<int64_t>(q.ng, 0xff) | ((c->recipe_fast ? 1 : 0) << 16) | ((q.dist_fit ? 1 : 0) << 18) |
-                    ((q.use_av ? 1 : 0) << 19);
+        pack_leading_words(q, c->recipe_fast, 0, &r.niso_nt, &r.ng_fast);  // (q.smp_on = 0)
         r.tmin = q.tmin;
         r.tmax = q.tmax;
     }
-    GROUP_HIP_TRY(g, hipSetDevice(g->device));
-    GROUP_HIP_TRY(g, hipMalloc((void **)&g->d_probs, sizeof(DevProblem) * (size_t)k));
-    GROUP_HIP_TRY(g, hipMalloc((void **)&g->d_members, sizeof(GroupMember) * (size_t)k));
-    GROUP_HIP_TRY(g, hipMemcpy(g->d_probs, g->probs.data(), sizeof(DevProblem) * (size_t)k, hipMemcpyHostToDevice));
-    GROUP_HIP_TRY(g, hipMemcpy(g->d_members, recs.data(), sizeof(GroupMember) * (size_t)k, hipMemcpyHostToDevice));
+    HIP_TRY(g, hipSetDevice(g->device));
+    HIP_TRY(g, hipMalloc((void **)&g->d_probs, sizeof(DevProblem) * (size_t)k));
+    HIP_TRY(g, hipMalloc((void **)&g->d_members, sizeof(GroupMember) * (size_t)k));
+    HIP_TRY(g, hipMemcpy(g->d_probs, g->probs.data(), sizeof(DevProblem) * (size_t)k, hipMemcpyHostToDevice));
+    HIP_TRY(g, hipMemcpy(g->d_members, recs.data(), sizeof(GroupMember) * (size_t)k, hipMemcpyHostToDevice));
     for (msx_ctx *c : g->members)  // (back-pointers, once per context: a context may stand for several members)
         if (std::find(c->groups.begin(), c->groups.end(), g) == c->groups.end()) c->groups.push_back(g);
     return MSX_OK;
@@ -2678,25 +2717,25 @@ const char *msx_group_last_error(msx_group *g) { return g ? g->err.c_str() : "nu
 
 // Every member alive and still holding the problem the group snapshotted; the counts valid.  *total = their sum.
 static int group_check(msx_group *g, const char *who, int32_t mode, const int64_t *counts, int32_t ndim, int64_t *total) {
-    if (g->members.empty()) return gfail(g, MSX_ERR_STATE, std::string(who) + ": the group was not created");
+    if (g->members.empty()) return fail(g, MSX_ERR_STATE, std::string(who) + ": the group was not created");
     for (size_t m = 0; m < g->members.size(); ++m) {
         const msx_ctx *c = g->members[m];
         if (!c)
-            return gfail(g, MSX_ERR_STATE, std::string(who) + ": member " + std::to_string(m) + " was destroyed (msx_destroy) before its group");
+            return fail(g, MSX_ERR_STATE, std::string(who) + ": member " + std::to_string(m) + " was destroyed (msx_destroy) before its group");
         if (c->prob_gen != g->gen[m])
-            return gfail(g, MSX_ERR_STATE, std::string(who) + ": member " + std::to_string(m) +
+            return fail(g, MSX_ERR_STATE, std::string(who) + ": member " + std::to_string(m) +
                                                "'s problem was dropped or staged again since msx_group_create; create the group again");
     }
     if (mode < MSX_MODE_LOGLIKE || mode > MSX_MODE_LOGPRIOR)
-        return gfail(g, MSX_ERR_INVALID, std::string(who) + ": mode must be MSX_MODE_LOGLIKE, _LOGPOST, _CHISQ or _LOGPRIOR");
+        return fail(g, MSX_ERR_INVALID, std::string(who) + ": mode must be MSX_MODE_LOGLIKE, _LOGPOST, _CHISQ or _LOGPRIOR");
     if (ndim != 2 * g->nspec + 2)
-        return gfail(g, MSX_ERR_INVALID, "P0 doesn't match what I was expecting (ndim must be 2*nspec+2)");
-    if (!counts) return gfail(g, MSX_ERR_INVALID, std::string(who) + ": null counts");
+        return fail(g, MSX_ERR_INVALID, "P0 doesn't match what I was expecting (ndim must be 2*nspec+2)");
+    if (!counts) return fail(g, MSX_ERR_INVALID, std::string(who) + ": null counts");
     int64_t t = 0;
     for (size_t m = 0; m < g->members.size(); ++m) {
-        if (counts[m] < 0) return gfail(g, MSX_ERR_INVALID, std::string(who) + ": member " + std::to_string(m) + " has a negative walker count");
+        if (counts[m] < 0) return fail(g, MSX_ERR_INVALID, std::string(who) + ": member " + std::to_string(m) + " has a negative walker count");
         t += counts[m];
-        if (t > 0x7fffffff) return gfail(g, MSX_ERR_RANGE, std::string(who) + ": more than 2^31 - 1 walkers in one launch");
+        if (t > 0x7fffffff) return fail(g, MSX_ERR_RANGE, std::string(who) + ": more than 2^31 - 1 walkers in one launch");
     }
     *total = t;
     return MSX_OK;
@@ -2708,13 +2747,11 @@ int msx_group_logprob_batch_dev(msx_group *g, int32_t mode, const double *d_thet
     int64_t total = 0;
     if (int rc = group_check(g, "msx_group_logprob_batch", mode, counts, ndim, &total)) return rc;
     if (total == 0) return MSX_OK;
-    if (!d_theta || !d_logp || !d_status) return gfail(g, MSX_ERR_INVALID, "msx_group_logprob_batch: bad arguments");
-    const bool shared512 = block_threads == MSX_BLOCK_512_SHARED;
-    if (shared512) block_threads = 512;
-    if (block_threads != 0 && block_threads != 256 && block_threads != 512)
-        return gfail(g, MSX_ERR_INVALID, "block_threads must be 0, 256, 512 or MSX_BLOCK_512_SHARED");
+    if (!d_theta || !d_logp || !d_status) return fail(g, MSX_ERR_INVALID, "msx_group_logprob_batch: bad arguments");
+    bool shared512;
+    if (int rc = decode_block(g, block_threads, shared512)) return rc;
     const GroupPlan pl = plan_group_launch(g, counts, total, block_threads, shared512);
-    if (!pl.v) return gfail(g, MSX_ERR_STATE, "no kernel variant for this group launch");
+    if (!pl.v) return fail(g, MSX_ERR_STATE, "no kernel variant for this group launch");
     GroupStarts st;
     st.k = (int32_t)g->members.size();
     int64_t acc = 0;
@@ -2729,8 +2766,8 @@ int msx_group_logprob_batch_dev(msx_group *g, int32_t mode, const double *d_thet
     int32_t *a_status = d_status;
     const SmpRec *a_rec = nullptr;
     void *args[] = {&a_theta, &a_members, &a_probs, &a_mode, &a_n, &st, &a_logp, &a_status, &a_rec};
-    GROUP_HIP_TRY(g, hipSetDevice(g->device));
-    GROUP_HIP_TRY(g, hipLaunchKernel(pl.v->fn, dim3((unsigned)total), dim3((unsigned)pl.v->threads), args, pl.dyn_lds, (hipStream_t)hip_stream));
+    HIP_TRY(g, hipSetDevice(g->device));
+    HIP_TRY(g, hipLaunchKernel(pl.v->fn, dim3((unsigned)total), dim3((unsigned)pl.v->threads), args, pl.dyn_lds, (hipStream_t)hip_stream));
     return MSX_OK;
 }
 
@@ -2740,24 +2777,16 @@ int msx_group_logprob_batch(msx_group *g, int32_t mode, const double *theta, con
     int64_t n = 0;
     if (int rc = group_check(g, "msx_group_logprob_batch", mode, counts, ndim, &n)) return rc;
     if (n == 0) return MSX_OK;
-    if (!theta || !logp_out || !status_out) return gfail(g, MSX_ERR_INVALID, "msx_group_logprob_batch: bad arguments");
-    GROUP_HIP_TRY(g, hipSetDevice(g->device));
-    if (n > g->cap_walkers) {  // (msx_logprob_batch's pinned staging: the kernel reads theta and writes its results there)
-        if (g->h_pin) (void)hipHostFree(g->h_pin);
-        g->h_pin = nullptr; g->cap_walkers = 0;
-        const int64_t cap = std::max<int64_t>(n, 1024);
-        GROUP_HIP_TRY(g, hipHostMalloc((void **)&g->h_pin, (sizeof(double) * (MSX_MAX_DIM + 1) + sizeof(int32_t)) * cap, hipHostMallocDefault));
-        g->cap_walkers = cap;
-    }
-    double *h_theta = reinterpret_cast<double *>(g->h_pin);
-    double *h_out = h_theta + g->cap_walkers * MSX_MAX_DIM;
-    int32_t *h_st = reinterpret_cast<int32_t *>(h_out + n);
-    memcpy(h_theta, theta, sizeof(double) * n * ndim);
+    if (!theta || !logp_out || !status_out) return fail(g, MSX_ERR_INVALID, "msx_group_logprob_batch: bad arguments");
+    HIP_TRY(g, hipSetDevice(g->device));
+    PinnedStaging h;
+    HIP_TRY(g, pinned_staging(&g->h_pin, &g->cap_walkers, n, &h));
+    memcpy(h.theta, theta, sizeof(double) * n * ndim);
     hipStream_t s = g->members[0]->stream;  // member 0's stream
-    if (int rc = msx_group_logprob_batch_dev(g, mode, h_theta, counts, ndim, h_out, h_st, s, 0)) return rc;
-    GROUP_HIP_TRY(g, hipStreamSynchronize(s));
-    memcpy(logp_out, h_out, sizeof(double) * n);
-    memcpy(status_out, h_st, sizeof(int32_t) * n);
+    if (int rc = msx_group_logprob_batch_dev(g, mode, h.theta, counts, ndim, h.logp, h.status, s, 0)) return rc;
+    HIP_TRY(g, hipStreamSynchronize(s));
+    memcpy(logp_out, h.logp, sizeof(double) * n);
+    memcpy(status_out, h.status, sizeof(int32_t) * n);
     return MSX_OK;
 }
 
@@ -2766,33 +2795,17 @@ int msx_group_launch_info(msx_group *g, int32_t mode, const int64_t *counts, int
     if (!g || !out8) return MSX_ERR_INVALID;
     int64_t total = 0;
     if (int rc = group_check(g, "msx_group_launch_info", mode, counts, 2 * g->nspec + 2, &total)) return rc;
-    if (total < 1) return gfail(g, MSX_ERR_INVALID, "msx_group_launch_info: no walkers");
-    const bool shared512 = block_threads == MSX_BLOCK_512_SHARED;
-    if (shared512) block_threads = 512;
-    if (block_threads != 0 && block_threads != 256 && block_threads != 512)
-        return gfail(g, MSX_ERR_INVALID, "block_threads must be 0, 256, 512 or MSX_BLOCK_512_SHARED");
+    if (total < 1) return fail(g, MSX_ERR_INVALID, "msx_group_launch_info: no walkers");
+    bool shared512;
+    if (int rc = decode_block(g, block_threads, shared512)) return rc;
     const GroupPlan pl = plan_group_launch(g, counts, total, block_threads, shared512);
-    if (!pl.v) return gfail(g, MSX_ERR_STATE, "no kernel variant for this group launch");
+    if (!pl.v) return fail(g, MSX_ERR_STATE, "no kernel variant for this group launch");
     const GroupVariant *v = pl.v;
     const std::string nm = std::string("logprob_group_kernel<NS=") + std::to_string(v->ns) + ", " + std::to_string(v->threads) + " threads" +
                            (v->pf && v->sh ? ", SH, PF" : v->pf ? ", PF" : v->sh ? ", SH" : "") +
                            (v->full == 3 ? ", FULL" : v->full == 2 ? ", FULL(chi2 pass)" : "") + "> (" + v->what + ")";
-    GROUP_HIP_TRY(g, hipSetDevice(g->device));
-    hipFuncAttributes at;
-    GROUP_HIP_TRY(g, hipFuncGetAttributes(&at, v->fn));
-    out8[0] = MSX_FORM_FUSED;
-    out8[1] = v->threads;
-    out8[2] = at.numRegs;
-    out8[3] = (int64_t)at.sharedSizeBytes;
-    out8[4] = (int64_t)pl.dyn_lds;
-    out8[5] = pl.bytes;
-    out8[6] = total;
-    out8[7] = total;
-    if (name && name_len > 0) {
-        strncpy(name, nm.c_str(), (size_t)name_len - 1);
-        name[name_len - 1] = 0;
-    }
-    return MSX_OK;
+    HIP_TRY(g, hipSetDevice(g->device));
+    return launch_info_out(g, v->fn, {MSX_FORM_FUSED, v->threads, 0, 0, (int64_t)pl.dyn_lds, pl.bytes, total, total}, nm, name, name_len, out8);
 }
 
 // ---- a target group's device-resident sampler (include/msx.h, msx_group_sampler_*) -------------------------------------
@@ -2835,14 +2848,14 @@ int msx_group_sampler_begin(msx_group *g, int32_t mode, const int64_t *counts, i
     int64_t total = 0;
     if (int rc = group_check(g, "msx_group_sampler_begin", mode, counts, ndim, &total)) return rc;
     if (mode != MSX_MODE_LOGPOST && mode != MSX_MODE_LOGLIKE)
-        return gfail(g, MSX_ERR_INVALID, "msx_group_sampler_begin: mode must be MSX_MODE_LOGPOST or MSX_MODE_LOGLIKE");
+        return fail(g, MSX_ERR_INVALID, "msx_group_sampler_begin: mode must be MSX_MODE_LOGPOST or MSX_MODE_LOGLIKE");
     const int k = (int)g->members.size();
     for (int m = 0; m < k; ++m)
         if (counts[m] < 2 || (counts[m] & 1))
-            return gfail(g, MSX_ERR_INVALID, "msx_group_sampler_begin: member " + std::to_string(m) + " has " + std::to_string(counts[m]) +
+            return fail(g, MSX_ERR_INVALID, "msx_group_sampler_begin: member " + std::to_string(m) + " has " + std::to_string(counts[m]) +
                                                  " walkers: the stretch move needs an even number, at least 2");
-    if (!coords || !logp || max_chunk_steps < 1) return gfail(g, MSX_ERR_INVALID, "msx_group_sampler_begin: bad arguments");
-    GROUP_HIP_TRY(g, hipSetDevice(g->device));
+    if (!coords || !logp || max_chunk_steps < 1) return fail(g, MSX_ERR_INVALID, "msx_group_sampler_begin: bad arguments");
+    HIP_TRY(g, hipSetDevice(g->device));
     group_run_free(g);
     std::vector<int64_t> half((size_t)k);
     for (int m = 0; m < k; ++m) half[(size_t)m] = counts[m] / 2;
@@ -2856,7 +2869,7 @@ int msx_group_sampler_begin(msx_group *g, int32_t mode, const int64_t *counts, i
                     sub = &v;
         pl = sub ? group_plan_lds(g, half.data(), ns, sub) : GroupPlan();
     }
-    if (!pl.v) return gfail(g, MSX_ERR_STATE, "msx_group_sampler_begin: no kernel variant for this group launch");
+    if (!pl.v) return fail(g, MSX_ERR_STATE, "msx_group_sampler_begin: no kernel variant for this group launch");
     GroupRun *gr = new GroupRun;
     g->run = gr;
     gr->fn = pl.v->smp_fn; gr->threads = pl.v->threads; gr->dyn_lds = pl.dyn_lds;
@@ -2908,15 +2921,10 @@ int msx_group_sampler_begin(msx_group *g, int32_t mode, const int64_t *counts, i
         }
         e = hipMemcpyAsync(gr->d_snap, snaps.data(), sizeof(DevProblem) * snap_count, hipMemcpyHostToDevice, gr->stream);
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(r->d_coords, coords, sizeof(double) * total * ndim, hipMemcpyHostToDevice, gr->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(r->d_logp, logp, sizeof(double) * total, hipMemcpyHostToDevice, gr->stream);
-    if (e == hipSuccess)
-        e = naccept ? hipMemcpyAsync(r->d_nacc, naccept, sizeof(int64_t) * total, hipMemcpyHostToDevice, gr->stream)
-                    : hipMemsetAsync(r->d_nacc, 0, sizeof(int64_t) * total, gr->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(gr->stream);  // the caller's arrays (and the snapshots) are consumed on return
+    if (e == hipSuccess) e = run_load_state(r, gr->stream, coords, logp, naccept);  // (the snapshots, too, are consumed on return)
     if (e != hipSuccess) {
         group_run_free(g);
-        return gfail(g, MSX_ERR_HIP, std::string("msx_group_sampler_begin: ") + hipGetErrorString(e));
+        return fail(g, MSX_ERR_HIP, std::string("msx_group_sampler_begin: ") + hipGetErrorString(e));
     }
     return MSX_OK;
 }
@@ -2925,12 +2933,10 @@ int msx_group_sampler_enqueue(msx_group *g, int32_t slot, int64_t nsteps, const 
                               const int32_t *partner, const double *zz, const double *zfac, const double *logu) {
     if (!g) return MSX_ERR_INVALID;
     GroupRun *gr = g->run;
-    if (!gr) return gfail(g, MSX_ERR_STATE, "msx_group_sampler_enqueue: call msx_group_sampler_begin first");
+    if (int rc = run_enqueue_check(&g->err, gr ? gr->r : nullptr, "msx_group_sampler_enqueue", "msx_group_sampler_begin",
+                                   "msx_group_sampler_end", slot, nsteps, sidx && cidx && partner && zz && zfac && logu))
+        return rc;
     SamplerRun *r = gr->r;
-    if (slot < 0 || slot > 1 || nsteps < 1 || nsteps > r->cap_steps || !sidx || !cidx || !partner || !zz || !zfac || !logu)
-        return gfail(g, MSX_ERR_INVALID, "msx_group_sampler_enqueue: bad arguments");
-    if (r->failed)
-        return gfail(g, MSX_ERR_STATE, "msx_group_sampler_enqueue: the run failed; end it (msx_group_sampler_end) and begin again");
     // a member restaged or destroyed since begin: the snapshots point at tables that are gone -- the run is over
     int64_t total = 0;
     std::vector<int64_t> counts(r->m_nw);
@@ -2939,10 +2945,9 @@ int msx_group_sampler_enqueue(msx_group *g, int32_t slot, int64_t nsteps, const 
         return rc;
     }
     SamplerRun::Slot &sl = r->slot[slot];
-    if (sl.busy) return gfail(g, MSX_ERR_STATE, "msx_group_sampler_enqueue: slot not collected yet");
-    GROUP_HIP_TRY(g, hipSetDevice(g->device));
+    HIP_TRY(g, hipSetDevice(g->device));
     if (const char *why = run_pack(r, sl, nsteps, sidx, cidx, partner, zz, zfac, logu))
-        return gfail(g, MSX_ERR_INVALID, std::string("msx_group_sampler_enqueue: ") + why);
+        return fail(g, MSX_ERR_INVALID, std::string("msx_group_sampler_enqueue: ") + why);
     ChunkPtrs cp;
     run_chunk_ptrs(r, sl, nsteps, &cp);
     const int k = (int)g->members.size();
@@ -2967,7 +2972,7 @@ int msx_group_sampler_enqueue(msx_group *g, int32_t slot, int64_t nsteps, const 
     if (e == hipSuccess) e = run_finish(r, slot, nsteps, cp, gr->stream);
     if (e != hipSuccess) {
         r->failed = true;  // some of the chunk's half-steps may be queued: only msx_group_sampler_end from here on
-        return gfail(g, MSX_ERR_HIP, std::string("msx_group_sampler_enqueue: ") + hipGetErrorString(e));
+        return fail(g, MSX_ERR_HIP, std::string("msx_group_sampler_enqueue: ") + hipGetErrorString(e));
     }
     r->steps_done += nsteps;
     return MSX_OK;
@@ -2976,29 +2981,18 @@ int msx_group_sampler_enqueue(msx_group *g, int32_t slot, int64_t nsteps, const 
 int msx_group_sampler_collect(msx_group *g, int32_t slot, double *chain_out, double *logp_out, int64_t *naccept,
                               int32_t *worst_status) {
     if (!g) return MSX_ERR_INVALID;
-    GroupRun *gr = g->run;
-    if (!gr) return gfail(g, MSX_ERR_STATE, "msx_group_sampler_collect: call msx_group_sampler_begin first");
-    SamplerRun *r = gr->r;
-    if (slot < 0 || slot > 1 || !chain_out || !logp_out || !naccept || !worst_status)
-        return gfail(g, MSX_ERR_INVALID, "msx_group_sampler_collect: bad arguments");
-    if (r->failed)
-        return gfail(g, MSX_ERR_STATE, "msx_group_sampler_collect: the run failed; end it (msx_group_sampler_end) and begin again");
-    if (!r->slot[slot].busy) return gfail(g, MSX_ERR_STATE, "msx_group_sampler_collect: nothing enqueued in this slot");
-    GROUP_HIP_TRY(g, run_collect(r, slot, chain_out, logp_out, naccept, worst_status));
-    return MSX_OK;
+    if (g->run && g->run->r->failed)
+        return fail(g, MSX_ERR_STATE, "msx_group_sampler_collect: the run failed; end it (msx_group_sampler_end) and begin again");
+    return run_collect_checked(&g->err, g->run ? g->run->r : nullptr, "msx_group_sampler_collect", "msx_group_sampler_begin", slot,
+                               chain_out, logp_out, naccept, worst_status);
 }
 
 int msx_group_sampler_end(msx_group *g, double *coords, double *logp) {
     if (!g) return MSX_ERR_INVALID;
-    GroupRun *gr = g->run;
-    if (!gr) return MSX_OK;
-    SamplerRun *r = gr->r;
-    hipError_t e = hipSetDevice(g->device);
-    if (e == hipSuccess) e = hipStreamSynchronize(gr->stream);
-    if (e == hipSuccess && coords) e = hipMemcpy(coords, r->d_coords, sizeof(double) * r->nw * r->ndim, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && logp) e = hipMemcpy(logp, r->d_logp, sizeof(double) * r->nw, hipMemcpyDeviceToHost);
+    if (!g->run) return MSX_OK;
+    const hipError_t e = run_save_state(g->run->r, g->device, g->run->stream, coords, logp);
     group_run_free(g);
-    if (e != hipSuccess) return gfail(g, MSX_ERR_HIP, std::string("msx_group_sampler_end: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(g, MSX_ERR_HIP, std::string("msx_group_sampler_end: ") + hipGetErrorString(e));
     return MSX_OK;
 }
 

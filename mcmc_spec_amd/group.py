@@ -14,11 +14,13 @@ per half-step, no host round trip between half-steps, chunks of iterations queue
 """
 from __future__ import annotations
 
+from contextlib import closing
+
 import numpy as np
 
 from . import _lib
 from .engine import _raise_for_status
-from .sampler import EnsembleSampler, State
+from .sampler import EnsembleSampler, State, _accept, _propose, _pump
 
 
 class TargetGroup:
@@ -129,33 +131,21 @@ class GroupSampler:
         return out
 
     def _stretch_step(self, coords, logp):
-        """One iteration of every target: EnsembleSampler._stretch_step's arithmetic, the K targets' half-steps batched."""
+        """One iteration of every target: the stretch move's half-steps (_propose, _accept), the K targets' evaluations batched."""
         draws = [s._draw_split(1) + s._draw_moves(1) for s in self.samplers]
         accepted = [np.zeros(s.nwalkers, dtype=bool) for s in self.samplers]
         for h in (0, 1):
-            qs, moves = [], []
-            for k, (sidx, cidx, part, zz_, zfac_, logu_) in enumerate(draws):
-                s_idx, c_idx, zz, partner_idx = sidx[0, h], cidx[0, h], zz_[0, h], part[0, h]
-                s, c = coords[k][s_idx], coords[k][c_idx]
-                partner = c[partner_idx]
-                qs.append(partner - (partner - s) * zz[:, None])
-                moves.append((s_idx, zfac_[0, h], logu_[0, h]))
-            new_lps = self.compute_log_prob(qs)
-            for k, ((s_idx, zfac, logu), q, new_lp) in enumerate(zip(moves, qs, new_lps)):
-                with np.errstate(invalid='ignore'):  # -inf - -inf = nan -> compares False -> rejected
-                    lnpdiff = zfac + new_lp - logp[k][s_idx]
-                acc = logu < lnpdiff
-                coords[k][s_idx[acc]] = q[acc]
-                logp[k][s_idx[acc]] = new_lp[acc]
-                accepted[k][s_idx[acc]] = True
+            qs = [_propose(coords[k], d, h) for k, d in enumerate(draws)]
+            for k, (d, q, new_lp) in enumerate(zip(draws, qs, self.compute_log_prob(qs))):
+                _accept(coords[k], logp[k], accepted[k], d, h, q, new_lp)
         return accepted
 
-    def sample(self, initial_states, iterations=1, store=True):
-        """``initial_states``: one State or coordinate array ``(nwalkers[k], ndim)`` per target.  Yields a list of K States
-        per iteration."""
+    def _initial(self, initial_states):
+        """Coordinates and log-probabilities per target from one State or coordinate array per target.  The targets that
+        come without their log-probabilities are evaluated in one batched call of K arrays, the others' left empty."""
         if len(initial_states) != len(self.samplers):
             raise ValueError('one initial state per target')
-        coords, logp, missing = [], [], []
+        coords, logp = [], []
         for k, (st, smp) in enumerate(zip(initial_states, self.samplers)):
             if isinstance(st, State):
                 c, lp = st.coords.copy(), st.log_prob.copy()
@@ -163,13 +153,19 @@ class GroupSampler:
                 c, lp = np.array(st, dtype=float), None
             if c.shape != (smp.nwalkers, self.ndim):
                 raise ValueError('incompatible input dimensions (target {})'.format(k))
-            if lp is None or lp.shape != (smp.nwalkers,):
-                missing.append(k)
             coords.append(c)
-            logp.append(lp)
-        if missing:  # (one batched call for every target that came without its log-probabilities)
-            for k, lp in zip(missing, self.compute_log_prob([coords[k] for k in missing])):
-                logp[k] = lp
+            logp.append(lp if lp is not None and lp.shape == (smp.nwalkers,) else None)
+        missing = [k for k, lp in enumerate(logp) if lp is None]
+        if missing:
+            lps = self.compute_log_prob([coords[k] if logp[k] is None else np.empty((0, self.ndim)) for k in range(len(coords))])
+            for k in missing:
+                logp[k] = lps[k]
+        return coords, logp
+
+    def sample(self, initial_states, iterations=1, store=True):
+        """``initial_states``: one State or coordinate array ``(nwalkers[k], ndim)`` per target.  Yields a list of K States
+        per iteration."""
+        coords, logp = self._initial(initial_states)
         for _ in range(int(iterations)):
             acc = self._stretch_step(coords, logp)
             states = []
@@ -210,9 +206,9 @@ class DeviceGroupSampler(GroupSampler):
     ``GroupSampler`` and of ``EnsembleSampler(nwalkers[k], ndim, f_k, vectorize=True, seed=seeds[k])``.
 
     ``group`` is a ``TargetGroup``; ``mode`` ``'logposterior'`` or ``'loglikelihood'``.  Drawing chunk i+1 overlaps chunk i
-    on the GPU (as ``DeviceEnsembleSampler.sample``); consecutive ``sample`` calls continue the generators.  A walker error
-    raises what ``TargetGroup`` raises, prefixed ``target k:``; the run ends there and the chain up to the last collected
-    chunk stands."""
+    on the GPU (``DeviceEnsembleSampler``'s chunk pipeline, ``sampler._pump``); consecutive ``sample`` calls continue the
+    generators.  A walker error raises what ``TargetGroup`` raises, prefixed ``target k:``; the run ends there and the
+    chain up to the last collected chunk stands."""
 
     def __init__(self, nwalkers, ndim, group, mode='logposterior', a=2.0, seeds=None, chunk=64):
         if mode not in ('logposterior', 'loglikelihood'):
@@ -229,26 +225,6 @@ class DeviceGroupSampler(GroupSampler):
         super().__init__(nwalkers, ndim, fn, a=a, seeds=seeds)
         self.chunk = int(chunk)
 
-    def _initial(self, initial_states):
-        if len(initial_states) != len(self.samplers):
-            raise ValueError('one initial state per target')
-        coords, logp = [], []
-        for k, (st, smp) in enumerate(zip(initial_states, self.samplers)):
-            if isinstance(st, State):
-                c, lp = st.coords.copy(), st.log_prob.copy()
-            else:
-                c, lp = np.array(st, dtype=float), None
-            if c.shape != (smp.nwalkers, self.ndim):
-                raise ValueError('incompatible input dimensions (target {})'.format(k))
-            coords.append(c)
-            logp.append(lp if lp is not None and lp.shape == (smp.nwalkers,) else None)
-        missing = [k for k, lp in enumerate(logp) if lp is None]
-        if missing:  # one group launch for every target that came without its log-probabilities
-            lps = self.compute_log_prob([coords[k] if logp[k] is None else np.empty((0, self.ndim)) for k in range(len(coords))])
-            for k in missing:
-                logp[k] = lps[k]
-        return coords, logp
-
     def _draw_split_all(self, m):
         split = [s._draw_split(m) for s in self.samplers]
         return [np.concatenate(x, axis=2) for x in zip(*split)]
@@ -260,61 +236,33 @@ class DeviceGroupSampler(GroupSampler):
     def sample(self, initial_states, iterations=1, store=True):
         """``initial_states``: one State or coordinate array ``(nwalkers[k], ndim)`` per target.  Yields a list of K States
         per iteration."""
-        from collections import deque
-        from concurrent.futures import ThreadPoolExecutor
         coords, logp = self._initial(initial_states)
-        left = int(iterations)
-        if left <= 0:
+        if int(iterations) <= 0:
             return
         counts = self.nwalkers
         off = np.concatenate([[0], np.cumsum(counts)]).astype(int)
         grp = self.group.group
         base_acc = [s._accepted.copy() for s in self.samplers]
-
-        def submit(pool, m):
-            return (pool.submit(self._draw_split_all, m), pool.submit(self._draw_moves_all, m)) if m > 0 else None
-
-        def next_size(prev, left):  # (DeviceEnsembleSampler's ramp: the first launch does not wait for a whole chunk)
-            return min(left, self.chunk, max(8, 2 * prev))
-
         grp.sampler_begin(self._mode, np.concatenate(coords), np.concatenate(logp), counts, self.chunk)
-        try:
-            with ThreadPoolExecutor(max_workers=2) as pool:
-                queued = deque()
-                m = next_size(4, left)
-                fut = submit(pool, m)
-                slot = 0
-                while left > 0 or queued:
-                    if left > 0:
-                        arrays = [x for f in fut for x in f.result()]
-                        left -= m
-                        m_next = next_size(m, left) if left > 0 else 0
-                        fut = submit(pool, m_next)
-                        grp.sampler_enqueue(slot, *arrays)
-                        queued.append((slot, m))
-                        slot ^= 1
-                        m = m_next
-                        if len(queued) < 2 and left > 0:
-                            continue  # keep two chunks in flight
-                    sl, mm = queued.popleft()
-                    chain, lpc, nacc, worst = grp.sampler_collect(sl, mm)
-                    for k in np.nonzero(worst > _lib.W_REJECT)[0]:
-                        try:
-                            _raise_for_status(worst[k:k + 1], chain[-1, off[k]:off[k] + 1])
-                        except (KeyError, IndexError, ValueError, RuntimeError) as e:
-                            raise type(e)('target {}: {}'.format(k, e.args[0] if e.args else e)) from None
+        with closing(_pump(iterations, self.chunk, (self._draw_split_all, self._draw_moves_all),
+                           lambda slot, m, arrays: grp.sampler_enqueue(slot, *arrays), grp.sampler_collect,
+                           grp.sampler_end)) as chunks:
+            for mm, (chain, lpc, nacc, worst) in chunks:
+                for k in np.nonzero(worst > _lib.W_REJECT)[0]:
+                    try:
+                        _raise_for_status(worst[k:k + 1], chain[-1, off[k]:off[k] + 1])
+                    except (KeyError, IndexError, ValueError, RuntimeError) as e:
+                        raise type(e)('target {}: {}'.format(k, e.args[0] if e.args else e)) from None
+                for k, s in enumerate(self.samplers):
+                    s._accepted = base_acc[k] + nacc[off[k]:off[k + 1]]
+                for i in range(mm):
+                    states = []
                     for k, s in enumerate(self.samplers):
-                        s._accepted = base_acc[k] + nacc[off[k]:off[k + 1]]
-                    for i in range(mm):
-                        states = []
-                        for k, s in enumerate(self.samplers):
-                            c, lp = chain[i, off[k]:off[k + 1]], lpc[i, off[k]:off[k + 1]]
-                            s.iteration += 1
-                            if store:
-                                s._chain.append(c)
-                                s._logp.append(lp)
-                            s._last = State(c, lp)
-                            states.append(s._last)
-                        yield states
-        finally:
-            grp.sampler_end()
+                        c, lp = chain[i, off[k]:off[k + 1]], lpc[i, off[k]:off[k + 1]]
+                        s.iteration += 1
+                        if store:
+                            s._chain.append(c)
+                            s._logp.append(lp)
+                        s._last = State(c, lp)
+                        states.append(s._last)
+                    yield states

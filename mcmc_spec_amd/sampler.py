@@ -15,6 +15,9 @@ With ``vectorize=True`` the log-probability function receives the whole half-ens
 from __future__ import annotations
 
 import warnings
+from collections import deque
+from contextlib import closing
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
@@ -179,21 +182,11 @@ class EnsembleSampler:
         return partner, zz, zfac, logu
 
     def _stretch_step(self, coords, logp):
-        nw, nd = self.nwalkers, self.ndim
-        accepted = np.zeros(nw, dtype=bool)
-        sidx, cidx, part, zz_, zfac_, logu_ = self._draw_steps(1)
-        for k in (0, 1):
-            s_idx, c_idx, zz, partner_idx, logu, zfac = sidx[0, k], cidx[0, k], zz_[0, k], part[0, k], logu_[0, k], zfac_[0, k]
-            s, c = coords[s_idx], coords[c_idx]
-            partner = c[partner_idx]
-            q = partner - (partner - s) * zz[:, None]
-            new_lp = self.compute_log_prob(q)
-            with np.errstate(invalid='ignore'):  # -inf - -inf = nan -> compares False -> rejected
-                lnpdiff = zfac + new_lp - logp[s_idx]
-            acc = logu < lnpdiff
-            coords[s_idx[acc]] = q[acc]
-            logp[s_idx[acc]] = new_lp[acc]
-            accepted[s_idx[acc]] = True
+        accepted = np.zeros(self.nwalkers, dtype=bool)
+        draws = self._draw_steps(1)
+        for h in (0, 1):
+            q = _propose(coords, draws, h)
+            _accept(coords, logp, accepted, draws, h, q, self.compute_log_prob(q))
         return accepted
 
     def sample(self, initial_state, iterations=1, store=True):
@@ -248,6 +241,69 @@ class EnsembleSampler:
         return tau
 
 
+# One half-step of the stretch move, in two parts around the evaluation of the proposals (EnsembleSampler, and
+# GroupSampler for each of its targets).  draws: _draw_steps' six arrays for one iteration; h: the half.
+def _propose(coords, draws, h):
+    """The proposals q of half h: each active walker s stretched towards its partner in the other half."""
+    sidx, cidx, part, zz = (d[0, h] for d in draws[:4])
+    s, c = coords[sidx], coords[cidx]
+    partner = c[part]
+    return partner - (partner - s) * zz[:, None]
+
+
+def _accept(coords, logp, accepted, draws, h, q, new_lp):
+    """The accept rule of half h, in place: walkers whose ln u < (ndim-1) ln z + ln p(q) - ln p(s) move to q."""
+    s_idx, zfac, logu = draws[0][0, h], draws[4][0, h], draws[5][0, h]
+    with np.errstate(invalid='ignore'):  # -inf - -inf = nan -> compares False -> rejected
+        lnpdiff = zfac + new_lp - logp[s_idx]
+    acc = logu < lnpdiff
+    coords[s_idx[acc]] = q[acc]
+    logp[s_idx[acc]] = new_lp[acc]
+    accepted[s_idx[acc]] = True
+
+
+def _pump(iterations, chunk, draws, enqueue, collect, end):
+    """The device-resident samplers' chunk pipeline: yields ``(m, collect(slot, m))`` per chunk of m iterations, in order.
+
+    ``draws = (split, moves)``: callables of m that draw a chunk's randomness on the host (two threads; NumPy's
+    generators and the ctypes calls release the GIL), or None for chunks the device draws itself.  The randomness of
+    chunk i+1 is drawn and QUEUED on the GPU (``enqueue(slot, m, arrays)``, arrays None for device draws) while chunk i
+    runs; chunk i is collected only after chunk i+1 has been queued, so the GPU never waits for the host between chunks.
+    Host-drawn chunk sizes ramp up from 8 so the first launch does not wait for a whole chunk of randomness.  The run
+    begun by the caller ends (``end()``) when the generator finishes, raises or is closed."""
+    def submit(pool, m):
+        return (pool.submit(draws[0], m), pool.submit(draws[1], m)) if draws is not None and m > 0 else None
+
+    def next_size(prev, left):
+        if draws is None:   # (nothing to wait for on the host: whole chunks from the start)
+            return min(left, chunk)
+        return min(left, chunk, max(8, 2 * prev))
+
+    left = int(iterations)
+    try:
+        with ThreadPoolExecutor(max_workers=2) as pool:
+            queued = deque()
+            m = next_size(4, left)
+            fut = submit(pool, m)
+            slot = 0
+            while left > 0 or queued:
+                if left > 0:
+                    arrays = None if fut is None else [x for f in fut for x in f.result()]
+                    left -= m
+                    m_next = next_size(m, left) if left > 0 else 0
+                    fut = submit(pool, m_next)
+                    enqueue(slot, m, arrays)
+                    queued.append((slot, m))
+                    slot ^= 1
+                    m = m_next
+                    if len(queued) < 2 and left > 0:
+                        continue  # keep two chunks in flight
+                sl, mm = queued.popleft()
+                yield mm, collect(sl, mm)
+    finally:
+        end()
+
+
 class DeviceEnsembleSampler(EnsembleSampler):
     """The same sampler with the walker state resident in HBM: ``chunk`` iterations are queued on the GPU
     back to back (per half-step: proposal kernel, fused log-probability launch, accept kernel;
@@ -300,72 +356,35 @@ class DeviceEnsembleSampler(EnsembleSampler):
             logp = self.compute_log_prob(coords)
         coords = np.ascontiguousarray(coords)
         logp = np.ascontiguousarray(logp)
-        nd, ns = self.ndim, self.nwalkers // 2
-
-        # Pipeline: the randomness of chunk i+1 is drawn (two streams, one thread each; NumPy's generators and
-        # the ctypes calls release the GIL) and QUEUED on the GPU while chunk i runs; chunk i is collected only
-        # after chunk i+1 has been queued, so the GPU never waits for the host between chunks.  Chunk sizes ramp
-        # up from 8 so the first launch does not wait for a whole chunk of randomness.
-        from collections import deque
-        from concurrent.futures import ThreadPoolExecutor
-
-        device_rng = self.rng_mode == 'device'
-
-        def submit(pool, m):
-            if device_rng:
-                return None
-            return (pool.submit(self._draw_split, m), pool.submit(self._draw_moves, m)) if m > 0 else None
-
-        def next_size(prev, left):
-            if self.rng_mode == 'device':   # (nothing to wait for on the host: whole chunks from the start)
-                return min(left, self.chunk)
-            return min(left, self.chunk, max(8, 2 * prev))
-
         ctx = self.engine.ctx
-        left = int(iterations)
-        if left <= 0:
+        if int(iterations) <= 0:
             return
         base_acc = self._accepted.copy()
+
+        def enqueue(slot, m, arrays):
+            if arrays is None:
+                ctx.sampler_enqueue_drawn(slot, m, self.device_seed, self.a)
+            else:
+                ctx.sampler_enqueue(slot, *arrays)
+            self.overlapped = ctx.sampler_overlapped() == 1   # (half-steps on two streams: include/msx.h)
+
         ctx.sampler_policy(self.overlap_policy)
         ctx.sampler_begin(self._mode, coords, logp, self.chunk)
         if self.shard is not None:
             ctx.sampler_shard(*self.shard)
-        try:
-            with ThreadPoolExecutor(max_workers=2) as pool:
-                queued = deque()
-                m = next_size(4, left)
-                fut = submit(pool, m)
-                slot = 0
-                while left > 0 or queued:
-                    if left > 0:
-                        arrays = None if device_rng else [x for f in fut for x in f.result()]
-                        left -= m
-                        m_next = next_size(m, left) if left > 0 else 0
-                        fut = submit(pool, m_next)
-                        if device_rng:
-                            ctx.sampler_enqueue_drawn(slot, m, self.device_seed, self.a)
-                        else:
-                            ctx.sampler_enqueue(slot, *arrays)
-                        self.overlapped = ctx.sampler_overlapped() == 1   # (half-steps on two streams: include/msx.h)
-                        queued.append((slot, m))
-                        slot ^= 1
-                        m = m_next
-                        if len(queued) < 2 and left > 0:
-                            continue  # keep two chunks in flight
-                    sl, mm = queued.popleft()
-                    chain, lpc, nacc, worst = ctx.sampler_collect(sl, mm)
-                    if worst:
-                        _raise_for_status(np.array([worst]), chain[-1][:1])
-                    self._accepted = base_acc + nacc
-                    for i in range(mm):
-                        self.iteration += 1
-                        if store:
-                            self._chain.append(chain[i])
-                            self._logp.append(lpc[i])
-                        self._last = State(chain[i], lpc[i])
-                        yield self._last
-        finally:
-            ctx.sampler_end()
+        draws = None if self.rng_mode == 'device' else (self._draw_split, self._draw_moves)
+        with closing(_pump(iterations, self.chunk, draws, enqueue, ctx.sampler_collect, ctx.sampler_end)) as chunks:
+            for mm, (chain, lpc, nacc, worst) in chunks:
+                if worst:
+                    _raise_for_status(np.array([worst]), chain[-1][:1])
+                self._accepted = base_acc + nacc
+                for i in range(mm):
+                    self.iteration += 1
+                    if store:
+                        self._chain.append(chain[i])
+                        self._logp.append(lpc[i])
+                    self._last = State(chain[i], lpc[i])
+                    yield self._last
 
     @property
     def acceptance_fraction(self):

@@ -3,10 +3,12 @@
 problems, walker counts, workgroup sizes and paths.  The plan only depends on the problem's shape (pixels, stars, the R
 table's storage), never on its values, so the problems are staged from ``mcmc_spec_amd/synth.py`` with flat data.
 
-    python tests/golden/make_launch_plans.py [out.json]      # on a GPU (the answers include the kernels' resources)
+    python tests/golden/make_launch_plans.py [out.json [group_out.json]]   # on a GPU (the answers include the kernels' resources)
 
-``tests/test_gpu_launch_plans.py`` runs the same matrix against the library under test and compares it with the
-committed ``launch_plans.json``."""
+The group matrix asks ``msx_group_launch_info`` the same of target groups: members that mix pixel counts (whole trips of
+a variant or not, LDS-staged statics that fit or not), walker layouts around one and two walkers per CU with empty
+members, and every workgroup size.  ``tests/test_gpu_launch_plans.py`` runs both matrices against the library under test
+and compares them with the committed ``launch_plans.json`` and ``group_launch_plans.json``."""
 import json
 import os
 import sys
@@ -18,10 +20,16 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 
 OUT = os.path.join(HERE, 'launch_plans.json')
+GROUP_OUT = os.path.join(HERE, 'group_launch_plans.json')
 BINARY_PIX = (1194, 2048, 4000, 4096, 16384, 20000)
 TRIPLE_PIX = (4096, 16384, 20000)
 WALKERS = (16, 128, 256, 384, 512, 1024, 2048, 4096)
 INPATH_PIX = 4096
+# target groups: (nspec, member pixel counts).  At 256 / 512 threads a binary is whole trips at multiples of 1024 / 2048
+# pixels; the PF statics fit two 256-thread workgroups per CU up to ~3,400 pixels and one 512-thread one up to ~6,800.
+GROUPS = ((2, (1194, 2048)), (2, (1194, 4096)), (2, (2048, 4096)), (2, (4096, 5120)), (2, (4096, 16384)),
+          (2, (5120, 1194, 2048)), (3, (4096, 5120)), (3, (4096, 16384)))
+GROUP_TOTALS = (16, 200, 256, 257, 400, 512, 513, 1024, 4096)
 
 
 def problems():
@@ -32,6 +40,26 @@ def problems():
     for npix in TRIPLE_PIX:
         yield 'triple', 3, npix, 'f64', 'staging'
     yield 'binary', 2, INPATH_PIX, 'f64', 'in_path'
+
+
+def _layouts(k):
+    """Walker counts per member: every total split evenly, all in the first member, all in the last, one walker in each
+    but the last; and no walkers at all."""
+    out = []
+    for t in GROUP_TOTALS:
+        even = [t // k] * k
+        even[0] += t - sum(even)
+        for c in (even, [t] + [0] * (k - 1), [0] * (k - 1) + [t], [1] * (k - 1) + [t - (k - 1)]):
+            if c not in out:
+                out.append(c)
+    return out + [[0] * k]
+
+
+def _grid():
+    from mcmc_spec_amd import synth
+    teffs, loggs = np.arange(3000, 5600, 100), np.array([4.0, 4.5, 5.0, 5.5])
+    wl = np.arange(3000, 30000, 0.2)
+    return wl, teffs, loggs, synth.make_grid(teffs, loggs, wl)
 
 
 def _stage(eng, grid, nspec, npix, store, placement):
@@ -62,11 +90,9 @@ def _ask(fn):
 
 def collect():
     """Every case of the matrix, in a fixed order: a list of dicts."""
-    from mcmc_spec_amd import _lib, synth
+    from mcmc_spec_amd import _lib
     from mcmc_spec_amd.engine import Engine
-    teffs, loggs = np.arange(3000, 5600, 100), np.array([4.0, 4.5, 5.0, 5.5])
-    wl = np.arange(3000, 30000, 0.2)
-    grid = (wl, teffs, loggs, synth.make_grid(teffs, loggs, wl))
+    grid = _grid()
     paths = {'auto': _lib.PATH_AUTO, 'fused': _lib.PATH_FUSED, 'inpath': _lib.PATH_INPATH}
     blocks = (0, 256, 512, _lib.BLOCK_512_SHARED)
     out = []
@@ -86,6 +112,30 @@ def collect():
                     out.append(dict(head, path=path, walkers=n, block=block,
                                     launch_info=_ask(lambda: eng.ctx.launch_info(n, _lib.MODE_LOGPOST, block)),
                                     bytes_per_eval=_ask(lambda: eng.ctx.bytes_per_eval(n))))
+        eng.ctx.close()
+    return out
+
+
+def collect_groups():
+    """Every case of the group matrix, in a fixed order: a list of dicts."""
+    from mcmc_spec_amd import _lib
+    from mcmc_spec_amd.engine import Engine
+    grid = _grid()
+    engines = {}
+    for nspec, pix in GROUPS:
+        for npix in pix:
+            if (nspec, npix) not in engines:
+                engines[nspec, npix] = Engine(0)
+                _stage(engines[nspec, npix], grid, nspec, npix, 'f64', 'staging')
+    out = []
+    for nspec, pix in GROUPS:
+        grp = _lib.Group([engines[nspec, npix].ctx for npix in pix])
+        for counts in _layouts(len(pix)):
+            for block in (0, 256, 512, _lib.BLOCK_512_SHARED):
+                out.append({'nspec': nspec, 'npix': list(pix), 'counts': counts, 'block': block,
+                            'launch_info': _ask(lambda: grp.launch_info(counts, _lib.MODE_LOGPOST, block))})
+        grp.close()
+    for eng in engines.values():
         eng.ctx.close()
     return out
 
@@ -141,12 +191,58 @@ def load(path=OUT):
     return out
 
 
+GROUP_HEAD = ('nspec', 'npix')
+
+
+def save_groups(cases, path):
+    """One line per group: its cases as rows [counts, block, kernel, dynamic LDS, requested bytes, workgroups, walkers per
+    sub-batch] (the form is always the fused one); kernels as in save()."""
+    kernels, groups = [], {}
+    for c in cases:
+        g = groups.setdefault(json.dumps([c[k] for k in GROUP_HEAD]), dict({k: c[k] for k in GROUP_HEAD}, rows=[]))
+        li = c['launch_info']
+        if 'error' in li:
+            info = [li]
+        else:
+            assert li['form'] == 'fused'
+            kern = [li[k] for k in PER_KERNEL]
+            if kern not in kernels:
+                kernels.append(kern)
+            info = [kernels.index(kern)] + [li[k] for k in PER_CASE[1:]]
+        g['rows'].append([c['counts'], c['block']] + info)
+    with open(path, 'w') as f:
+        f.write('{"kernels": [\n' + ',\n'.join(json.dumps(k) for k in kernels) + '\n],\n"groups": [\n' +
+                ',\n'.join(json.dumps(g) for g in groups.values()) + '\n]}\n')
+
+
+def load_groups(path=GROUP_OUT):
+    """The cases of a file save_groups() wrote, in the form collect_groups() returns them."""
+    from mcmc_spec_amd import _lib
+    with open(path) as f:
+        j = json.load(f)
+    out = []
+    for g in j['groups']:
+        for r in g['rows']:
+            if isinstance(r[2], dict):
+                li = r[2]
+            else:
+                li = dict(zip(PER_KERNEL, j['kernels'][r[2]]), form='fused', form_id=_lib.FORM_FUSED,
+                          **dict(zip(PER_CASE[1:], r[3:7])))
+            out.append({'nspec': g['nspec'], 'npix': g['npix'], 'counts': r[0], 'block': r[1], 'launch_info': li})
+    return out
+
+
 def main():
     out = sys.argv[1] if len(sys.argv) > 1 else OUT
+    group_out = sys.argv[2] if len(sys.argv) > 2 else GROUP_OUT
     cases = collect()
     save(cases, out)
     assert load(out) == cases
     print(f'{len(cases)} cases -> {out}')
+    groups = collect_groups()
+    save_groups(groups, group_out)
+    assert load_groups(group_out) == groups
+    print(f'{len(groups)} group cases -> {group_out}')
 
 
 if __name__ == '__main__':

@@ -1,6 +1,8 @@
 """The launch plan pinned: which variant, block, dynamic LDS, grid, sub-batch and requested bytes the library's
 ``msx_launch_info`` / ``msx_bytes_per_eval`` report, over the matrix of ``tests/golden/make_launch_plans.py``, against
-``tests/golden/launch_plans.json`` (generated with the library before the launch decision was gathered into one plan)."""
+``tests/golden/launch_plans.json`` (generated with the library before the launch decision was gathered into one plan);
+and what ``msx_group_launch_info`` reports for the group matrix, against ``tests/golden/group_launch_plans.json``
+(generated with the library before the group planner was made to share the fused form's rules)."""
 import os
 import re
 import sys
@@ -33,6 +35,27 @@ def test_fixture_covers_every_variant():
     for nt, full in pairs:
         assert any(k.startswith(f'pair_plan_kernel + logprob_pair_kernel<512 threads, {nt} element trips per lane'
                                 + (', FULL>' if full else '>')) for k in kernels), (nt, full)
+
+
+def test_group_fixture_covers_every_group_variant():
+    """Every entry of kGroupVariants is some group case's kernel."""
+    kernels = {c['launch_info']['kernel'] for c in mlp.load_groups() if 'kernel' in c['launch_info']}
+    entries = re.findall(r'group_variant<(\d), (\d+), (true|false), (true|false)(?:, (\d))?[^>]*>\("([^"]*)"\)',
+                         _table(('GroupVariant', 'kGroupVariants')))
+    assert len(entries) == 13 and len(set(entries)) == len(entries)
+    for ns, threads, sh, pf, full, what in entries:
+        flags = {('true', 'true'): ', SH, PF', ('false', 'true'): ', PF', ('true', 'false'): ', SH'}.get((sh, pf), '')
+        flags += {'3': ', FULL', '2': ', FULL(chi2 pass)'}.get(full, '')
+        assert f'logprob_group_kernel<NS={ns}, {threads} threads{flags}> ({what})' in kernels, (ns, threads, sh, pf, full)
+
+
+@pytest.mark.gpu
+def test_group_launch_plans_match_the_fixture():
+    want = mlp.load_groups()
+    got = mlp.collect_groups()
+    assert len(got) == len(want)
+    for g, w in zip(got, want):
+        assert g == w
 
 
 @pytest.mark.gpu

@@ -83,3 +83,31 @@ def test_nan_and_bad_shapes_raise():
         gs.run_mcmc([np.zeros((12, NDIM)), np.zeros((10, NDIM))], 1)
     with pytest.raises(ValueError):
         GroupSampler([12, 12], NDIM, None, seeds=[0])
+
+
+def test_resumes_from_mixed_states_with_one_array_per_target():
+    """Resumed from a State for some targets and bare coordinates for others: log_prob_fn still receives K arrays (the
+    complete targets' empty), as TargetGroup.logposterior requires, and each target walks its EnsembleSampler chain."""
+    nws, seeds = [12, 12, 16], [4, 5, 6]
+    fns = [make_target(k) for k in range(3)]
+    p0s = [np.random.default_rng(20 + k).normal(size=(nw, NDIM)) for k, nw in enumerate(nws)]
+    calls = []
+
+    def batched(thetas):
+        if len(thetas) != len(fns):
+            raise ValueError('one array of walkers per target')
+        calls.append([len(t) for t in thetas])
+        return [f(np.reshape(t, (-1, NDIM))) for f, t in zip(fns, thetas)]
+    gs = GroupSampler(nws, NDIM, batched, seeds=seeds)
+    st = gs.run_mcmc(p0s, 4)
+    gs.reset()
+    calls.clear()
+    gs.run_mcmc([st[0], st[1].coords, st[2]], 6)
+    assert calls[0] == [0, nws[1], 0]
+    for k in range(3):
+        es = EnsembleSampler(nws[k], NDIM, fns[k], vectorize=True, seed=seeds[k])
+        s = es.run_mcmc(p0s[k], 4)
+        es.reset()
+        es.run_mcmc(s if k != 1 else s.coords, 6)
+        assert np.array_equal(gs.get_chain(k), es.get_chain())
+        assert np.array_equal(gs.get_log_prob(k), es.get_log_prob())

@@ -97,6 +97,8 @@ __device__ void build_desc(const DevProblem &P, const double *teff, const double
 
 // The hard gates of logprior (a value of -inf, not an error) for theta = [T.., A_V, R1, ratios.., plx]:
 //   dist_fit, binary   : T box, every radius entry >= 0.05, R1 <= 1.5, 1/3000 <= plx <= 1/4   mft6.py:1227
+//     (without extinction the reference's "radii" are theta[NS..2NS) = [A_V, R1], mft6.py:1219-1221: A_V in
+//     [0.05, 1.5], R1 >= 0.05 and the ratio untested -- prior_radii below, for the gates and the radius prior alike)
 //   dist_fit, triple   : T box, every radius entry >= 0.05, 1/1000 <= plx <= 1/4               mft6.py:1347
 //   no dist_fit, binary: T box, both radius entries >= 0.05                                    mft6.py:1286
 //   no dist_fit, triple: T box, the two RATIOS >= 0.05 (R1 is not tested), plx >= 0            mft6.py:1411
@@ -108,17 +110,31 @@ struct GateArgs {
     bool dist_fit, use_av;
 };
 __device__ __forceinline__ GateArgs gates_of(const DevProblem &P) { return GateArgs{P.tmin, P.tmax, P.dist_fit != 0, P.use_av != 0}; }
+// where the prior's radius entries start in theta: R1 on (NS + 1), except for a binary with dist_fit and no extinction,
+// whose reference reads rad = p0[nspec:2*nspec] (mft6.py:1219-1221) -- the likelihood keeps R1 at NS + 1 (mft6.py:1143)
+template <int NS>
+__device__ __forceinline__ int prior_radii(bool dist_fit, bool use_av) { return (NS == 2 && dist_fit && !use_av) ? NS : NS + 1; }
+// The dist_fit radius gates on rad = t + R (mft6.py:1227 / :1347).  Theta lives in registers: the two offsets are two
+// instances with constant indices, not a dynamic index into it.
+template <int NS, int R>
+__device__ __forceinline__ bool dist_radius_gates(const double *t) {
+    bool ok = true;
+#pragma unroll
+    for (int s = 0; s < NS; ++s) ok = ok && !(t[R + s] < 0.05);
+    if (NS == 2) ok = ok && !(t[R] > 1.5);
+    return ok;
+}
 template <int NS>
 __device__ __forceinline__ bool prior_gates(const GateArgs &P, const double *t) {
     const double a_v = t[NS], plx = t[2 * NS + 1];
-    const double *rad = t + NS + 1;
+    const double *rad = t + NS + 1;  // (the branches without dist_fit; those with it: dist_radius_gates)
     bool ok = true;
 #pragma unroll
     for (int s = 0; s < NS; ++s) ok = ok && !(t[s] > P.tmax) && !(t[s] < P.tmin);
     if (P.dist_fit) {
-#pragma unroll
-        for (int s = 0; s < NS; ++s) ok = ok && !(rad[s] < 0.05);
-        if (NS == 2) ok = ok && !(rad[0] > 1.5) && !(plx < 1.0 / 3000) && !(plx > 1.0 / 4);
+        const bool rad_ok = prior_radii<NS>(true, P.use_av) == NS ? dist_radius_gates<NS, NS>(t) : dist_radius_gates<NS, NS + 1>(t);
+        ok = ok && rad_ok;
+        if (NS == 2) ok = ok && !(plx < 1.0 / 3000) && !(plx > 1.0 / 4);
         else ok = ok && !(plx < 1.0 / 1000) && !(plx > 1.0 / 4);
     } else if (NS == 2) {
         ok = ok && !(rad[0] < 0.05) && !(rad[1] < 0.05);
@@ -201,7 +217,7 @@ __device__ __forceinline__ void build_recipe_wave(const DevProblem &P, const Rec
     }
     const double a_v = t[NS];
     const double plx = t[2 * NS + 1];
-    const double *rad = &t[NS + 1];
+    const double *rad = &t[NS + 1];  // the likelihood's radii (the prior's: prior_gates / prior_radii)
     int st = MSX_W_OK;
     double lp = 0.0;
     if (alive && (mode == MSX_MODE_LOGPOST || mode == MSX_MODE_LOGPRIOR)) {
@@ -237,10 +253,13 @@ __device__ __forceinline__ void build_recipe_wave(const DevProblem &P, const Rec
                 const double t2 = t[s] * t[s];
                 mr[s] = sqrt(lum * lsun / (4 * M_PI * sigma_sb * (t2 * t2))) / kRsunCm;  // mft6.py:83
             }
+            // (the radii re-read from theta's row at their offset: selecting among the registers that hold it costs the
+            // kernels that carry this form two VGPRs)
+            const double *prad = th + prior_radii<NS>(P.dist_fit != 0, P.use_av != 0);
 #pragma unroll
             for (int s = 0; s < NS; ++s) {
                 const double target = (s == 0) ? mr[0] : mr[s] / mr[0];
-                const double z = (rad[s] - target) / (0.02 * target);
+                const double z = (prad[s] - target) / (0.02 * target);
                 lp += -0.5 * (z * z);
             }
         }
@@ -388,6 +407,18 @@ __device__ __forceinline__ double model_radius(double lum, double teff) {  // ge
 __device__ __forceinline__ double radius_term(double lp, double rad, double target) {  // mft6.py:1262-1269
     const double z = (rad - target) / (0.02 * target);
     return lp + -0.5 * (z * z);
+}
+// The radius prior's terms on rad = t + R (mft6.py:1262-1269 / :1383-1390), mr: the model radii
+template <int NS, int R>
+__device__ __forceinline__ double radius_terms(double lp, const double *t, const double (&mr)[NS]) {
+#pragma unroll
+    for (int s = 0; s < NS; ++s) lp = radius_term(lp, t[R + s], (s == 0) ? mr[0] : mr[s] / mr[0]);
+    return lp;
+}
+template <int NS>
+__device__ __forceinline__ double prior_radius_terms(double lp, bool dist_fit, bool use_av, const double *t, const double (&mr)[NS]) {
+    if (prior_radii<NS>(dist_fit, use_av) == NS) return radius_terms<NS, NS>(lp, t, mr);
+    return radius_terms<NS, NS + 1>(lp, t, mr);
 }
 // magnitude of one "job" of the band terms: job < nc NS = (contrast filter f, star s), else photometric band f
 template <int NS>
@@ -565,8 +596,9 @@ __device__ __forceinline__ void recipe_part1_regs(const DevProblem &P, const Gat
             if (lane < NS) { lo = G.tmin; hi = G.tmax; }
             if (lane == NS && G.use_av) lo = 0.0;
             if (G.dist_fit) {
-                if (lane > NS && lane <= 2 * NS) lo = 0.05;
-                if (NS == 2 && lane == NS + 1) hi = 1.5;
+                const int r0 = prior_radii<NS>(true, G.use_av);  // the first radius entry: R1, or A_V (binary, no A_V fit)
+                if (lane >= r0 && lane < r0 + NS) lo = 0.05;
+                if (NS == 2 && lane == r0) hi = 1.5;
                 if (lane == 2 * NS + 1) { lo = NS == 2 ? 1.0 / 3000 : 1.0 / 1000; hi = 1.0 / 4; }
             } else if (NS == 2) {
                 if (lane > NS && lane <= 2 * NS) lo = 0.05;
@@ -823,7 +855,6 @@ __device__ __forceinline__ void recipe_prior_terms(const DevProblem &P, int mode
     for (int k = 0; k < 2 * NS + 2; ++k) t[k] = th[k];
     const double a_v = t[NS];
     const double plx = t[2 * NS + 1];
-    const double *rad = &t[NS + 1];
     double lp = 0.0;
     int st = MSX_W_OK;
     if (mode == MSX_MODE_LOGPOST || mode == MSX_MODE_LOGPRIOR) {
@@ -865,8 +896,7 @@ __device__ __forceinline__ void recipe_prior_terms(const DevProblem &P, int mode
                 if (!(t[s] >= iso_lo) || !(t[s] <= iso_hi)) { st = MSX_W_VALUEERROR; mr[s] = 1.0; continue; }
                 mr[s] = model_radius(iso_interp_regs(isot, isol, P.niso, t[s]), t[s]);
             }
-#pragma unroll
-            for (int s = 0; s < NS; ++s) lp = radius_term(lp, rad[s], (s == 0) ? mr[0] : mr[s] / mr[0]);
+            lp = prior_radius_terms<NS>(lp, P.dist_fit != 0, P.use_av != 0, t, mr);
         }
     }
     if (lane == 0) {
@@ -914,7 +944,6 @@ __device__ __forceinline__ double prior_terms_scalar2(const DevProblem &P, const
                                                       int av_bin, const int (&iso_lo)[2]) {
     constexpr int NS = 2;
     const double a_v = t[NS];
-    const double *rad = &t[NS + 1];
     double lp = 0.0;
     if (!(mode == MSX_MODE_LOGPOST || mode == MSX_MODE_LOGPRIOR)) return lp;
     if (P.use_av && P.nav > 0) {
@@ -945,8 +974,7 @@ __device__ __forceinline__ double prior_terms_scalar2(const DevProblem &P, const
             const double lum = j >= P.niso - 1 ? lum_last : seg;
             mr[s] = inside ? model_radius(lum, t[s]) : 1.0;
         }
-#pragma unroll
-        for (int s = 0; s < NS; ++s) lp = radius_term(lp, rad[s], (s == 0) ? mr[0] : mr[s] / mr[0]);
+        lp = prior_radius_terms<NS>(lp, P.dist_fit != 0, P.use_av != 0, t, mr);
     }
     return lp;
 }

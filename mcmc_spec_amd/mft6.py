@@ -152,13 +152,35 @@ def _check_p0(p0, nspec):
     return p
 
 
+def _prior_falls_through(nspec, dist_fit, rad_prior):
+    """The triple with ``dist_fit`` and without ``rad_prior``: the reference's ``return`` sits inside
+    ``if rad_prior == True`` (mft6.py:1383-1393), so its logprior returns None once the gates pass and logposterior
+    raises TypeError on ``np.isfinite(None)`` (:1465).  The drop-ins do the same; Engine, TargetGroup and the
+    samplers give the prior's value instead."""
+    return int(nspec) == 3 and dist_fit == True and not rad_prior == True  # noqa: E712 (the reference's tests)
+
+
+def _fall_through_prior(lp):
+    """logprior's result there: None for a walker that passes the gates (an object array for a batch), -inf else."""
+    if np.ndim(lp) == 0:
+        return None if np.isfinite(lp) else lp
+    out = np.empty(len(lp), dtype=object)
+    for i, v in enumerate(lp):
+        out[i] = None if np.isfinite(v) else float(v)
+    return out
+
+
 def logposterior(p0, fr, nspec, ndust, data, err, broadening, r, specs, ctm, ptm, tmi, tma, vs, tmin, tmax, matrix,
                  ra, dec, wu='aa', dust=False, norm=True, prior=0, a=True, models='btsettl', dist_fit=True,
                  rad_prior=False):
-    """mft6.py:1459-1470: log prior + log likelihood, ``-inf`` outside the prior box.  emcee's ``log_prob_fn``."""
+    """mft6.py:1459-1470: log prior + log likelihood, ``-inf`` outside the prior box.  emcee's ``log_prob_fn``.
+    TypeError where the reference's logprior returns None (``_prior_falls_through``) for any walker."""
     p = _check_p0(p0, nspec)
     eng = _staged(specs, fr, nspec, data, err, r, ctm, ptm, tmi, tma, matrix, tmin, tmax, prior, a, dist_fit,
                   rad_prior, need_prior=True)
+    if _prior_falls_through(nspec, dist_fit, rad_prior) and np.any(np.isfinite(eng.logprior(p))):
+        raise TypeError("ufunc 'isfinite' not supported for the input types: logprior returned None (mft6.py:1393, "
+                        "ndim 8 with dist_fit=True and rad_prior=False)")
     return eng.logposterior(p)
 
 
@@ -187,6 +209,9 @@ def device_sampler(nwalkers, ndim, args, kwargs=None, a=2.0, seed=None, chunk=64
     g = given.get
     if 2 * int(g('nspec')) + 2 != int(ndim):
         raise ValueError("P0 doesn't match what I was expecting")
+    if _prior_falls_through(g('nspec'), g('dist_fit', True), g('rad_prior', False)):
+        raise TypeError('device_sampler: logposterior raises TypeError for ndim 8 with dist_fit=True and rad_prior=False '
+                        '(the reference\'s logprior returns None there, mft6.py:1393)')
     eng = _staged(g('specs'), g('fr'), g('nspec'), g('data'), g('err'), g('r'), g('ctm'), g('ptm'), g('tmi'), g('tma'),
                   g('matrix'), g('tmin'), g('tmax'), g('prior', 0), g('a', True), g('dist_fit', True),
                   g('rad_prior', False), need_prior=True)
@@ -206,7 +231,8 @@ def logprior(p0, nspec, ndust, tmin, tmax, matrix, ra, dec, prior=0, ext=True, d
     """mft6.py:1207-1272.  The value depends on ``p0`` and on the arguments above only; the reference signature
     carries neither grid nor dataset, but the device evaluates priors inside a staged problem, so one is needed:
     the dataset of the LAST ``logposterior`` / ``loglikelihood`` call (recorded explicitly, not "whichever engine
-    was touched last"), or -- with ``specs=`` -- the last dataset staged on that grid."""
+    was touched last"), or -- with ``specs=`` -- the last dataset staged on that grid.  None (an object array of them
+    for a batch) where the reference returns None (``_prior_falls_through``)."""
     p = _check_p0(p0, nspec)
     last = _LAST_DATASET
     if specs is not None and (last is None or last[0] is not specs):
@@ -222,6 +248,8 @@ def logprior(p0, nspec, ndust, tmin, tmax, matrix, ra, dec, prior=0, ext=True, d
     sp, fr, data, err, r, ctm, ptm, tmi, tma = last
     eng = _staged(sp, fr, nspec, data, err, r, ctm, ptm, tmi, tma, matrix, tmin, tmax, prior, ext, dist_fit, rad_prior,
                   need_prior=True)
+    if _prior_falls_through(nspec, dist_fit, rad_prior):
+        return _fall_through_prior(eng.logprior(p))
     return eng.logprior(p)
 
 

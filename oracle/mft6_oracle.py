@@ -369,6 +369,10 @@ def loglikelihood(p0, fr, nspec, data, err, r, specs, ctm, ptm, tmi, tma, matrix
 def logprior(p0, nspec, tmin, tmax, matrix, av_prior, prior=0, ext=True, dist_fit=True, rad_prior=False):
     """mft6.py:1207-1272 (len 6, dist_fit) and :1329-1393 (len 8, dist_fit).
 
+    As in the reference: a binary without extinction (``ext=False``) gates and radius-priors ``p0[nspec:2*nspec]``
+    = [A_V, R1] (the ratio is not tested), and a triple without ``rad_prior`` returns ``None`` once the gates pass
+    (``logposterior`` then raises ``TypeError`` like ``np.isfinite(None)``).
+
     ``av_prior(distance_pc) -> (mu, sigma)`` stands in for
     ``bayestar(SkyCoord(ra, dec, 1/plx pc), mode='samples') * 3.1 * 0.884`` mean/std (mft6.py:1233-1238);
     sigma == 0 is replaced by 0.05 as in the reference.
@@ -379,6 +383,8 @@ def logprior(p0, nspec, tmin, tmax, matrix, av_prior, prior=0, ext=True, dist_fi
     a_v = p0[nspec]
     rad = list(p0[nspec + 1:2 * nspec + 1])
     dist = p0[2 * nspec + 1]
+    if len(p0) == 6 and not ext:  # mft6.py:1219-1221: without extinction the binary reads rad = [A_V, R1]
+        rad = list(p0[nspec:2 * nspec])
     if len(p0) == 6:
         if (any(t > tmax for t in temps) or any(t < tmin for t in temps) or any(x < 0.05 for x in rad)
                 or rad[0] > 1.5 or dist < 1 / 3000 or dist > 1 / 4):  # mft6.py:1227
@@ -407,6 +413,8 @@ def logprior(p0, nspec, tmin, tmax, matrix, av_prior, prior=0, ext=True, dist_fi
         targets = [mr[0]] + [m / mr[0] for m in mr[1:]]
         for k, p in enumerate(targets):
             pp.append(-0.5 * ((rad[k] - p) / (0.02 * p)) ** 2)
+    elif len(p0) != 6:
+        return None  # mft6.py:1383-1393: the triple's `return` sits inside `if rad_prior == True`
     return np.sum(pp)
 
 

@@ -28,6 +28,8 @@ def main():
     ap.add_argument('--nburn', type=int, default=50)
     ap.add_argument('--nsteps', type=int, default=300)
     ap.add_argument('--seed', type=int, default=1)
+    ap.add_argument('--autocorr', choices=('host', 'device'), default='host',
+                    help="where the protocol's convergence checks compute tau ('device': from the chain kept on the GPU)")
     args = ap.parse_args()
 
     import mcmc_spec_amd.mft6 as gpu
@@ -86,7 +88,7 @@ def main():
     prior = [*np.zeros(10), plx, plx_err]  # mft6.py:3689
     eng = gpu._staged(specs, fr, 2, data, err, [wl_um.min(), wl_um.max()], ctm, ptm, tmi, tma, matrix, 3000.0, 4200.0, prior,
                       True, True, False, need_prior=True)
-    sampler = DeviceEnsembleSampler(len(p0), 6, eng, seed=args.seed, chunk=50)
+    sampler = DeviceEnsembleSampler(len(p0), 6, eng, seed=args.seed, chunk=50, autocorr=args.autocorr)
     samples = run_reference_protocol(sampler, p0, args.nburn, args.nsteps, nthin=50, dirname=args.out, fname='synthetic')
     print('sampler: {} walkers, {} + {} iterations in {:.2f} s; acceptance {:.2f}'.format(
         len(p0), args.nburn, sampler.iteration, time.time() - t2, sampler.acceptance_fraction.mean()))

@@ -7,6 +7,10 @@ Every target gets its own data spectrum (a binary at its own truth, its own pixe
 Target k's chain is the chain a separate EnsembleSampler with target k's seed would walk.
 
     python examples/fit_target_group.py --targets 4 --nwalkers 32 --nsteps 200 [--device]
+
+With --protocol DIR the targets are fitted the way the reference's driver fits one (run_group_protocol: burn-in, then
+production with every target's own convergence check every --nthin iterations; a converged target stops there) and
+each target's dumps and samples.txt go to DIR/target<k>/; with --device the checks run on the GPU (autocorr='device').
 """
 import argparse
 import os
@@ -25,12 +29,15 @@ def main():
     ap.add_argument('--nsteps', type=int, default=200)
     ap.add_argument('--seed', type=int, default=1)
     ap.add_argument('--device', action='store_true', help='keep the ensembles on the GPU (DeviceGroupSampler)')
+    ap.add_argument('--protocol', default=None, metavar='DIR', help="run the reference's driver per target (run_group_protocol)")
+    ap.add_argument('--nburn', type=int, default=100)
+    ap.add_argument('--nthin', type=int, default=50)
     args = ap.parse_args()
 
     from scipy.interpolate import interp1d
     from mcmc_spec_amd import bands, synth
     from mcmc_spec_amd.engine import Engine
-    from mcmc_spec_amd.group import DeviceGroupSampler, GroupSampler, TargetGroup
+    from mcmc_spec_amd.group import DeviceGroupSampler, GroupSampler, TargetGroup, run_group_protocol
     from oracle import mft6_oracle as orc
 
     rng = np.random.default_rng(args.seed)
@@ -71,10 +78,20 @@ def main():
     p0s = [truths[k] + 1e-3 * np.abs(truths[k]) * rng.normal(size=(args.nwalkers, 6)) for k in range(args.targets)]
     seeds = [args.seed + k for k in range(args.targets)]
     if args.device:
-        sampler = DeviceGroupSampler([args.nwalkers] * args.targets, 6, group, seeds=seeds)
+        sampler = DeviceGroupSampler([args.nwalkers] * args.targets, 6, group, seeds=seeds,
+                                     autocorr='device' if args.protocol else 'host')
     else:
         sampler = GroupSampler([args.nwalkers] * args.targets, 6, group.logposterior, seeds=seeds)
     t0 = time.time()
+    if args.protocol:
+        out = run_group_protocol(sampler, p0s, args.nburn, args.nsteps, nthin=args.nthin, dirname=args.protocol,
+                                 fnames=['target{}'.format(k) for k in range(args.targets)])
+        print('protocol: {} targets, production iterations per target {} in {:.2f} s (files under {})'.format(
+            args.targets, [len(x) // args.nwalkers for x in out], time.time() - t0, args.protocol))
+        for k in range(args.targets):
+            print('target {}: Teff {:.0f} / {:.0f} (truth {:.0f} / {:.0f})'.format(k, *np.median(out[k][:, :2], axis=0), *truths[k][:2]))
+        group.close()
+        return sampler
     sampler.run_mcmc(p0s, args.nsteps)
     dt = time.time() - t0
     print('{} targets x {} walkers x {} steps in {:.2f} s ({:.0f} evaluations/s)'.format(

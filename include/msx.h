@@ -424,6 +424,41 @@ int msx_group_sampler_collect(msx_group *group, int32_t slot, double *chain_out,
 /* ends the run (waits for it); coords / logp (may be NULL) receive the final state.  msx_group_destroy also ends it.  */
 int msx_group_sampler_end(msx_group *group, double *coords, double *logp);
 
+/* ---- device chain series: a chain kept on the device, and its autocorrelation -------------------
+ * A series holds rows of nw walkers x ndim, laid out [ndim][nw][cap] so that each walker-dimension series is contiguous,
+ * and belongs to whoever created it -- not to the context, whose device it lives on: it outlives runs, and two samplers
+ * on one context keep two series.  k members of counts[m] walkers (sum = nw), in a group's member order; 1 member for a
+ * plain run.  cap_hint: rows to allocate up front (0: on first use; the buffer grows by doubling).                      */
+typedef struct msx_series msx_series;
+int msx_series_create(msx_ctx *ctx, int64_t nw, int32_t ndim, int32_t k, const int64_t *counts, int64_t cap_hint,
+                      msx_series **out);
+/* waits for what a run attached to it still queues (the whole device), then frees it                                    */
+void msx_series_destroy(msx_series *s);
+const char *msx_series_last_error(msx_series *s);
+/* rows held: written, or queued by an attached run's enqueues (a chunk's rows are in place once it is collected)         */
+int msx_series_rows(msx_series *s, int64_t *out);
+/* Attach `s` to the run begun on ctx / group, once, between *_begin and the first enqueue: every chunk of the run then
+ * appends its iterations at rows at_row, at_row + 1, ... (a transpose queued on the run's compute stream before the
+ * chunk's results are downloaded; every rank of a sharded run keeps its own identical series).  Rows at or after at_row
+ * (0 <= at_row <= rows) are dropped.  The series must match the run: nw, ndim and the members' walker counts.  When the
+ * run outgrows the buffer it is reallocated and copied at enqueue time, in compute-stream order (readers wait for that
+ * copy).  The run detaches at its end (msx_sampler_end / msx_group_sampler_end, or destruction).                        */
+int msx_sampler_attach_series(msx_ctx *ctx, msx_series *s, int64_t at_row);
+int msx_group_sampler_attach_series(msx_group *group, msx_series *s, int64_t at_row);
+/* host rows [nrows][nw][ndim] appended (synchronous; refused while a run is attached)                                    */
+int msx_series_append(msx_series *s, const double *rows, int64_t nrows);
+/* rows row0 .. row0 + nrows - 1 back as [nrows][nw][ndim] (synchronous)                                                */
+int msx_series_read(msx_series *s, int64_t row0, int64_t nrows, double *out);
+/* The normalised autocorrelation of x = rows[0:n][discard::thin] (n' rows), for member m and each dimension d named in
+ * dim_mask (bit d):  f_out[(m * ndim + d) * nlag + j] = (1/W_m) sum_{walkers k of m} acov_k(lag0 + j) / acov_k(0),
+ * acov_k(tau) = sum_{t < n' - tau} y_k[t] y_k[t + tau], y = x - mean(x), by direct sums in an order fixed by n' alone
+ * (the bits do not depend on the lags asked for, the launch or how the rows arrived).  A series with acov_k(0) == 0
+ * contributes ones.  Entries of dimensions not in dim_mask are left as they are.  Needs n <= rows and
+ * lag0 + nlag <= n'.  Runs on the series' own stream and waits for nothing but the latest growth copy: rows < n must be
+ * in place (collected chunks, appended rows).  Synchronous.                                                              */
+int msx_series_acf(msx_series *s, int64_t n, int64_t discard, int64_t thin, int64_t lag0, int64_t nlag, uint32_t dim_mask,
+                   double *f_out);
+
 /* ---- test hooks (used by tests/ only) ------------------------------------------------------------ */
 /* MSX_HOOK_LINKED_FAULT: value != 0 makes the workgroups of the linked form skip their signal -- and the walkers of an
  * overlapped sampler run the publication of their new version -- so that every in-kernel wait runs into its bound;

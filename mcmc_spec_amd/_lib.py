@@ -151,6 +151,15 @@ def load():
                                                 C.POINTER(C.c_int32), _dp, _dp, _dp]),
         'msx_group_sampler_collect': (C.c_int, [vp, C.c_int32, _dp, _dp, _ip, C.POINTER(C.c_int32)]),
         'msx_group_sampler_end': (C.c_int, [vp, _dp, _dp]),
+        'msx_series_create': (C.c_int, [vp, C.c_int64, C.c_int32, C.c_int32, _ip, C.c_int64, C.POINTER(vp)]),
+        'msx_series_destroy': (None, [vp]),
+        'msx_series_last_error': (C.c_char_p, [vp]),
+        'msx_series_rows': (C.c_int, [vp, _ip]),
+        'msx_sampler_attach_series': (C.c_int, [vp, vp, C.c_int64]),
+        'msx_group_sampler_attach_series': (C.c_int, [vp, vp, C.c_int64]),
+        'msx_series_append': (C.c_int, [vp, _dp, C.c_int64]),
+        'msx_series_read': (C.c_int, [vp, C.c_int64, C.c_int64, _dp]),
+        'msx_series_acf': (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_uint32, _dp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = header/library skew, fail loudly
@@ -170,7 +179,9 @@ EXPORTED = ['msx_create', 'msx_destroy', 'msx_last_error', 'msx_device_info', 'm
             'msx_stream_copy_gbps', 'msx_bytes_per_eval', 'msx_launch_info', 'msx_last_form', 'msx_test_hook', 'msx_pair_stats', 'msx_sampler_overlapped', 'msx_sampler_policy',
             'msx_group_create', 'msx_group_destroy', 'msx_group_last_error', 'msx_group_logprob_batch',
             'msx_group_logprob_batch_dev', 'msx_group_launch_info', 'msx_group_sampler_begin', 'msx_group_sampler_enqueue',
-            'msx_group_sampler_collect', 'msx_group_sampler_end']
+            'msx_group_sampler_collect', 'msx_group_sampler_end',
+            'msx_series_create', 'msx_series_destroy', 'msx_series_last_error', 'msx_series_rows', 'msx_sampler_attach_series',
+            'msx_group_sampler_attach_series', 'msx_series_append', 'msx_series_read', 'msx_series_acf']
 
 
 def as_f64(a):
@@ -444,6 +455,10 @@ class Context:
     def sampler_end(self, want_state=False):
         return _sampler_end(self, self.lib.msx_sampler_end, want_state)
 
+    def sampler_attach_series(self, series, at_row):
+        """Append every chunk of the run begun by sampler_begin to ``series`` from row ``at_row`` on (msx_sampler_attach_series)."""
+        self.check(self.lib.msx_sampler_attach_series(self.h, series.h, int(at_row)))
+
     def make_composite(self, teff, logg, rad, use_distance, plx, win_n, nc, nph):
         teff, logg, rad = as_f64(teff), as_f64(logg), as_f64(rad)
         spec = np.empty(win_n)
@@ -615,6 +630,73 @@ class Group:
 
     def sampler_end(self, want_state=False):
         return _sampler_end(self, self.lib.msx_group_sampler_end, want_state)
+
+    def sampler_attach_series(self, series, at_row):
+        """Append every chunk of the group's run to ``series`` from row ``at_row`` on (msx_group_sampler_attach_series)."""
+        self.check(self.lib.msx_group_sampler_attach_series(self.h, series.h, int(at_row)))
+
+
+class Series:
+    """One ``msx_series`` (include/msx.h): a chain of ``nw`` walkers x ``ndim`` kept on the device of ``ctx``, and its
+    normalised autocorrelation.  ``counts``: the members' walker counts (a target group's, in member order); None for one."""
+
+    def __init__(self, ctx, nw, ndim, counts=None, cap_hint=0):
+        self.lib = load()
+        counts = np.ascontiguousarray([nw] if counts is None else counts, dtype=np.int64)
+        h = C.c_void_p()
+        ctx.check(self.lib.msx_series_create(ctx.h, int(nw), int(ndim), counts.size, iptr(counts), int(cap_hint), C.byref(h)))
+        self.h = h
+        self.nw, self.ndim, self.k = int(nw), int(ndim), int(counts.size)
+
+    def close(self):
+        if getattr(self, 'h', None):
+            self.lib.msx_series_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def check(self, rc):
+        if rc != MSX_OK:
+            raise MsxError(rc, self.lib.msx_series_last_error(self.h).decode())
+
+    @property
+    def rows(self):
+        out = C.c_int64()
+        self.check(self.lib.msx_series_rows(self.h, C.byref(out)))
+        return out.value
+
+    def append(self, rows):
+        """Host rows (nrows, nw, ndim) appended."""
+        rows = as_f64(rows)
+        if rows.ndim != 3 or rows.shape[1:] != (self.nw, self.ndim):
+            raise ValueError('append: rows must have shape (nrows, {}, {})'.format(self.nw, self.ndim))
+        if rows.shape[0]:
+            self.check(self.lib.msx_series_append(self.h, dptr(rows), rows.shape[0]))
+
+    def read(self, row0=0, nrows=None):
+        """Rows row0 .. row0 + nrows - 1 as (nrows, nw, ndim)."""
+        nrows = self.rows - int(row0) if nrows is None else int(nrows)
+        out = np.empty((nrows, self.nw, self.ndim))
+        if nrows:
+            self.check(self.lib.msx_series_read(self.h, int(row0), nrows, dptr(out)))
+        return out
+
+    def acf(self, n, discard=0, thin=1, lag0=0, nlag=None, dims=None):
+        """f (k, ndim, nlag): the members' walker-averaged normalised autocorrelation at lags lag0 .. lag0 + nlag - 1 of
+        rows[0:n][discard::thin] (msx_series_acf).  ``dims``: the dimensions to compute (others are NaN); None for all."""
+        n_eff = len(range(int(discard), int(n), int(thin)))
+        nlag = n_eff - int(lag0) if nlag is None else int(nlag)
+        dims = range(self.ndim) if dims is None else dims
+        mask = 0
+        for d in dims:
+            mask |= 1 << int(d)
+        f = np.full((self.k, self.ndim, nlag), np.nan)
+        self.check(self.lib.msx_series_acf(self.h, int(n), int(discard), int(thin), int(lag0), nlag, mask, dptr(f)))
+        return f
 
 
 # ---- the device-resident samplers' marshalling, shared by Context (msx_sampler_*) and Group (msx_group_sampler_*) ----

@@ -63,6 +63,7 @@
 #include "pair_kernel.h"
 #include "staging_kernels.h"
 #include "inpath_kernels.h"
+#include "autocorr_kernels.h"
 
 // ================================================================================================
 // host side: context + C ABI
@@ -182,6 +183,31 @@ struct msx_group {
 static void group_run_drain(msx_group *g);
 static void group_run_free(msx_group *g);
 
+// A DEVICE CHAIN SERIES (include/msx.h, msx_series_*): a chain kept on the device as
+// [ndim][nw][cap] doubles, filled by the runs it is attached to (run_finish) or from the host, read by the
+// autocorrelation kernels (autocorr_kernels.h) on its own stream.  It belongs to whoever created it, not to a context:
+// it outlives runs, and at most one run at a time appends to it.
+struct msx_series {
+    int device = 0;
+    std::string err;
+    hipStream_t stream = nullptr;        // append / read / acf
+    int64_t nw = 0;
+    int32_t ndim = 0;
+    std::vector<int64_t> off;            // [k + 1] the members' walker offsets
+    int64_t *d_off = nullptr;
+    double *d_rows = nullptr;
+    int64_t cap = 0, rows = 0;           // rows: written or queued to be written
+    // growth while a run is attached happens at enqueue time, in the run's compute-stream order: the copy into the new
+    // buffer sits behind the chunks already queued.  Readers wait for `grown` (recorded after the latest copy); the
+    // buffers it replaced are freed when no run is attached (hipFree would wait for the whole device)
+    hipEvent_t grown = nullptr;
+    bool grown_set = false;
+    std::vector<void *> retired;
+    char *d_scratch = nullptr;           // acf's partial sums and results, append's / read's staging
+    size_t scratch_bytes = 0;
+    struct SamplerRun *run = nullptr;    // the run appending to it (msx_*sampler_attach_series .. the run's end)
+};
+
 namespace {
 
 // RCCL is resolved at run time from the copy PyTorch-ROCm already mapped (same SONAME librccl.so.1 as
@@ -224,6 +250,10 @@ int fail(msx_ctx *c, int code, const std::string &msg) {
 }
 int fail(msx_group *g, int code, const std::string &msg) {
     if (g) g->err = msg;
+    return code;
+}
+int fail(msx_series *sr, int code, const std::string &msg) {
+    if (sr) sr->err = msg;
     return code;
 }
 
@@ -1809,6 +1839,9 @@ struct SamplerRun {
     // length: the group's launches read their per-half-step pointers from snapshots built once, at begin.
     int64_t layout_steps = 0;
     int32_t nworst = 1;  // worst statuses behind a chunk's acceptance counts (the group's run: one per member)
+    // the device chain series the run appends its chunks to (msx_sampler_attach_series), and the row its next chunk starts at
+    struct msx_series *series = nullptr;
+    int64_t series_row = 0;
     int64_t lay(int64_t st) const { return layout_steps > 0 ? layout_steps : st; }
     double *coords_now() const { return d_coords + (overlap == 1 ? (steps_done & 1) * nw * ndim : 0); }
     size_t in_bytes(int64_t st) const {  // [zz | zfac | logu | sidx | cidx | partner | records]
@@ -1818,6 +1851,47 @@ struct SamplerRun {
         return sizeof(double) * (size_t)(st * nw * ndim + st * nw) + sizeof(int64_t) * (size_t)nw + 16 * (size_t)((4 * nworst + 15) / 16);
     }
 };
+
+// A series' buffer holds at least `need` rows; its first `keep` rows carry over, copied on `st` (a buffer it replaces is
+// retired: freed when no run is attached).  `grown` is recorded on `st` after the copy.
+static hipError_t series_reserve(msx_series *sr, int64_t need, int64_t keep, hipStream_t st) {
+    if (need <= sr->cap) return hipSuccess;
+    const int64_t cap = std::max<int64_t>(need, std::max<int64_t>(2 * sr->cap, 256));
+    double *d = nullptr;
+    hipError_t e = hipMalloc((void **)&d, sizeof(double) * (size_t)(cap * sr->nw * sr->ndim));
+    if (e != hipSuccess) return e;
+    if (keep > 0)
+        e = hipMemcpy2DAsync(d, sizeof(double) * (size_t)cap, sr->d_rows, sizeof(double) * (size_t)sr->cap, sizeof(double) * (size_t)keep,
+                             (size_t)(sr->nw * sr->ndim), hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess) e = hipEventRecord(sr->grown, st);
+    if (e != hipSuccess) {
+        (void)hipFree(d);
+        return e;
+    }
+    sr->grown_set = true;
+    if (sr->d_rows) sr->retired.push_back(sr->d_rows);
+    sr->d_rows = d;
+    sr->cap = cap;
+    return hipSuccess;
+}
+
+// the chunk's rows [nsteps][nw][ndim] at `chain` appended to the run's series, on the compute stream (before the chunk's
+// kernels_done event, so a collected chunk's rows are in the series)
+static hipError_t series_put_chunk(SamplerRun *r, const double *chain, int64_t nsteps, hipStream_t compute) {
+    msx_series *sr = r->series;
+    if (!sr) return hipSuccess;
+    const int64_t row0 = r->series_row;
+    hipError_t e = series_reserve(sr, row0 + nsteps, row0, compute);
+    if (e != hipSuccess) return e;
+    const int64_t total = nsteps * r->nw * r->ndim;
+    hipLaunchKernelGGL(series_put_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, compute, chain, nsteps, r->nw,
+                       (int32_t)r->ndim, sr->d_rows, sr->cap, row0);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    r->series_row = row0 + nsteps;
+    sr->rows = r->series_row;
+    return hipSuccess;
+}
 
 // ---- the pipeline's pieces that the context's run (msx_sampler_*) and a target group's (msx_group_sampler_*) share ----
 // streams, events and the two slots' buffers (cap_steps, ns, nw, ndim, layout_steps and nworst set)
@@ -1863,6 +1937,7 @@ static void run_close(SamplerRun *r, hipStream_t compute) {
     if (r->s2) (void)hipStreamDestroy(r->s2);
     if (r->d_state) (void)hipFree(r->d_state);
     if (r->d_newlp_all) (void)hipFree(r->d_newlp_all);
+    if (r->series) r->series->run = nullptr;  // (the series outlives the run)
     if (r->copy) (void)hipStreamDestroy(r->copy);
     if (r->up) (void)hipStreamDestroy(r->up);
     delete r;
@@ -2061,8 +2136,10 @@ static void run_chunk_ptrs(const SamplerRun *r, const SamplerRun::Slot &sl, int6
 // results back on the download stream
 static hipError_t run_finish(SamplerRun *r, int32_t slot, int64_t nsteps, const ChunkPtrs &cp, hipStream_t compute) {
     SamplerRun::Slot &sl = r->slot[slot];
-    // acceptance counters keep running while this chunk's results travel: snapshot them in stream order
-    hipError_t e = hipMemcpyAsync(cp.d_nacc_snap, r->d_nacc, sizeof(int64_t) * r->nw, hipMemcpyDeviceToDevice, compute);
+    // the chunk's rows into the attached series, then: acceptance counters keep running while this chunk's results
+    // travel -- snapshot them in stream order
+    hipError_t e = series_put_chunk(r, cp.d_chain, nsteps, compute);
+    if (e == hipSuccess) e = hipMemcpyAsync(cp.d_nacc_snap, r->d_nacc, sizeof(int64_t) * r->nw, hipMemcpyDeviceToDevice, compute);
     if (e == hipSuccess) e = hipEventRecord(sl.kernels_done, compute);
     if (e == hipSuccess) e = hipStreamWaitEvent(r->copy, sl.kernels_done, 0);
     if (e == hipSuccess) e = hipMemcpyAsync(sl.h_out, sl.d_out, r->out_bytes(r->lay(nsteps)), hipMemcpyDeviceToHost, r->copy);
@@ -2993,6 +3070,228 @@ int msx_group_sampler_end(msx_group *g, double *coords, double *logp) {
     const hipError_t e = run_save_state(g->run->r, g->device, g->run->stream, coords, logp);
     group_run_free(g);
     if (e != hipSuccess) return fail(g, MSX_ERR_HIP, std::string("msx_group_sampler_end: ") + hipGetErrorString(e));
+    return MSX_OK;
+}
+
+// ---- device chain series ------------------------------------------------------------------------
+static constexpr size_t kSeriesStageBytes = (size_t)64 << 20;   // append / read move rows through 64 MB pieces
+static constexpr size_t kAcfPartBudget = (size_t)256 << 20;     // acf's partial sums per launch (lag ranges cut to fit)
+
+// a scratch block of at least `bytes` (a smaller one is retired while a run is attached, freed otherwise)
+static hipError_t series_scratch(msx_series *sr, size_t bytes) {
+    if (bytes <= sr->scratch_bytes) return hipSuccess;
+    if (sr->d_scratch) {
+        if (sr->run) sr->retired.push_back(sr->d_scratch);
+        else {
+            (void)hipStreamSynchronize(sr->stream);
+            (void)hipFree(sr->d_scratch);
+        }
+    }
+    sr->d_scratch = nullptr;
+    sr->scratch_bytes = 0;
+    hipError_t e = hipMalloc((void **)&sr->d_scratch, bytes);
+    if (e == hipSuccess) sr->scratch_bytes = bytes;
+    return e;
+}
+
+// readers of the rows: behind the latest growth copy (queued on a run's compute stream, possibly behind chunks in flight)
+static hipError_t series_wait_growth(msx_series *sr) {
+    return sr->grown_set ? hipStreamWaitEvent(sr->stream, sr->grown, 0) : hipSuccess;
+}
+
+// frees what growth retired (no run attached: nothing queued reads it; the series' stream and the growth copy are done)
+static void series_release(msx_series *sr) {
+    if (sr->retired.empty()) return;
+    (void)hipStreamSynchronize(sr->stream);
+    if (sr->grown_set) (void)hipEventSynchronize(sr->grown);
+    for (void *p : sr->retired) (void)hipFree(p);
+    sr->retired.clear();
+}
+
+int msx_series_create(msx_ctx *c, int64_t nw, int32_t ndim, int32_t k, const int64_t *counts, int64_t cap_hint, msx_series **out) {
+    if (!out) return MSX_ERR_INVALID;
+    *out = nullptr;
+    if (!c) return MSX_ERR_INVALID;
+    if (nw < 1 || ndim < 1 || ndim > MSX_MAX_DIM || k < 1 || k > MSX_MAX_GROUP || !counts || cap_hint < 0)
+        return fail(c, MSX_ERR_INVALID, "msx_series_create: bad arguments");
+    int64_t tot = 0;
+    for (int m = 0; m < k; ++m) {
+        if (counts[m] < 1) return fail(c, MSX_ERR_INVALID, "msx_series_create: every member needs at least one walker");
+        tot += counts[m];
+    }
+    if (tot != nw) return fail(c, MSX_ERR_INVALID, "msx_series_create: the members' walker counts do not add up to nw");
+    HIP_TRY(c, hipSetDevice(c->device));
+    msx_series *sr = new msx_series;
+    sr->device = c->device; sr->nw = nw; sr->ndim = ndim;
+    sr->off.assign(1, 0);
+    for (int m = 0; m < k; ++m) sr->off.push_back(sr->off.back() + counts[m]);
+    hipError_t e = hipStreamCreateWithFlags(&sr->stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&sr->grown, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipMalloc((void **)&sr->d_off, sizeof(int64_t) * sr->off.size());
+    if (e == hipSuccess) e = hipMemcpy(sr->d_off, sr->off.data(), sizeof(int64_t) * sr->off.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess && cap_hint > 0) {
+        e = series_reserve(sr, cap_hint, 0, sr->stream);
+        sr->grown_set = false;
+    }
+    if (e != hipSuccess) {
+        msx_series_destroy(sr);
+        return fail(c, MSX_ERR_HIP, std::string("msx_series_create: ") + hipGetErrorString(e));
+    }
+    *out = sr;
+    return MSX_OK;
+}
+
+void msx_series_destroy(msx_series *sr) {
+    if (!sr) return;
+    (void)hipSetDevice(sr->device);
+    if (sr->run) {  // a run still appends to it: let what it queued finish, and detach it
+        SamplerRun *r = sr->run;
+        if (r->series == sr) r->series = nullptr;
+        (void)hipDeviceSynchronize();
+    }
+    if (sr->stream) (void)hipStreamSynchronize(sr->stream);
+    if (sr->grown_set) (void)hipEventSynchronize(sr->grown);
+    for (void *p : sr->retired) (void)hipFree(p);
+    if (sr->d_rows) (void)hipFree(sr->d_rows);
+    if (sr->d_scratch) (void)hipFree(sr->d_scratch);
+    if (sr->d_off) (void)hipFree(sr->d_off);
+    if (sr->grown) (void)hipEventDestroy(sr->grown);
+    if (sr->stream) (void)hipStreamDestroy(sr->stream);
+    delete sr;
+}
+
+const char *msx_series_last_error(msx_series *sr) { return sr ? sr->err.c_str() : "null series"; }
+
+int msx_series_rows(msx_series *sr, int64_t *out) {
+    if (!sr || !out) return MSX_ERR_INVALID;
+    *out = sr->rows;
+    return MSX_OK;
+}
+
+// the attach checks and the attach itself, for msx_sampler_attach_series and msx_group_sampler_attach_series
+static int series_attach(std::string *err, msx_series *sr, SamplerRun *r, int device, int64_t at_row, const char *who, const char *begin) {
+    const std::string w(who);
+    if (!sr) { *err = w + ": bad arguments"; return MSX_ERR_INVALID; }
+    if (!r) { *err = w + ": call " + begin + " first"; return MSX_ERR_STATE; }
+    if (r->steps_done > 0 || r->slot[0].busy || r->slot[1].busy || r->series) {
+        *err = w + ": attach once, between " + begin + " and the run's first enqueue";
+        return MSX_ERR_STATE;
+    }
+    if (sr->run) { *err = w + ": the series is attached to another run in flight"; return MSX_ERR_STATE; }
+    if (sr->device != device) { *err = w + ": the series lives on another device"; return MSX_ERR_INVALID; }
+    bool same = sr->nw == r->nw && sr->ndim == r->ndim && sr->off.size() == r->m_nw.size() + 1;
+    for (size_t m = 0; same && m < r->m_nw.size(); ++m) same = sr->off[m + 1] - sr->off[m] == r->m_nw[m];
+    if (!same) { *err = w + ": the series' walkers, members or dimensions differ from the run's"; return MSX_ERR_INVALID; }
+    if (at_row < 0 || at_row > sr->rows) { *err = w + ": at_row must lie in 0 .. the rows the series holds"; return MSX_ERR_INVALID; }
+    series_release(sr);
+    sr->rows = at_row;   // (rows at or after at_row are dropped: the run overwrites them)
+    sr->run = r;
+    r->series = sr;
+    r->series_row = at_row;
+    return MSX_OK;
+}
+
+int msx_sampler_attach_series(msx_ctx *c, msx_series *sr, int64_t at_row) {
+    if (!c) return MSX_ERR_INVALID;
+    HIP_TRY(c, hipSetDevice(c->device));
+    return series_attach(&c->err, sr, c->smp, c->device, at_row, "msx_sampler_attach_series", "msx_sampler_begin");
+}
+
+int msx_group_sampler_attach_series(msx_group *g, msx_series *sr, int64_t at_row) {
+    if (!g) return MSX_ERR_INVALID;
+    HIP_TRY(g, hipSetDevice(g->device));
+    return series_attach(&g->err, sr, g->run ? g->run->r : nullptr, g->device, at_row, "msx_group_sampler_attach_series",
+                         "msx_group_sampler_begin");
+}
+
+int msx_series_append(msx_series *sr, const double *rows, int64_t nrows) {
+    if (!sr) return MSX_ERR_INVALID;
+    if (!rows || nrows < 1) return fail(sr, MSX_ERR_INVALID, "msx_series_append: bad arguments");
+    if (sr->run) return fail(sr, MSX_ERR_STATE, "msx_series_append: a run in flight appends to this series");
+    HIP_TRY(sr, hipSetDevice(sr->device));
+    const int64_t per = sr->nw * sr->ndim;
+    const int64_t piece = std::max<int64_t>(1, (int64_t)(kSeriesStageBytes / (sizeof(double) * (size_t)per)));
+    HIP_TRY(sr, series_reserve(sr, sr->rows + nrows, sr->rows, sr->stream));
+    HIP_TRY(sr, series_scratch(sr, sizeof(double) * (size_t)(std::min(piece, nrows) * per)));
+    for (int64_t p = 0; p < nrows; p += piece) {
+        const int64_t cnt = std::min(piece, nrows - p), total = cnt * per;
+        HIP_TRY(sr, hipMemcpyAsync(sr->d_scratch, rows + p * per, sizeof(double) * (size_t)total, hipMemcpyHostToDevice, sr->stream));
+        hipLaunchKernelGGL(series_put_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, sr->stream, (const double *)sr->d_scratch,
+                           cnt, sr->nw, sr->ndim, sr->d_rows, sr->cap, sr->rows + p);
+        HIP_TRY(sr, hipGetLastError());
+    }
+    HIP_TRY(sr, hipStreamSynchronize(sr->stream));
+    sr->rows += nrows;
+    return MSX_OK;
+}
+
+int msx_series_read(msx_series *sr, int64_t row0, int64_t nrows, double *out) {
+    if (!sr) return MSX_ERR_INVALID;
+    if (!out || row0 < 0 || nrows < 1 || row0 + nrows > sr->rows) return fail(sr, MSX_ERR_INVALID, "msx_series_read: bad arguments (rows past the series)");
+    HIP_TRY(sr, hipSetDevice(sr->device));
+    const int64_t per = sr->nw * sr->ndim;
+    const int64_t piece = std::max<int64_t>(1, (int64_t)(kSeriesStageBytes / (sizeof(double) * (size_t)per)));
+    HIP_TRY(sr, series_scratch(sr, sizeof(double) * (size_t)(std::min(piece, nrows) * per)));
+    HIP_TRY(sr, series_wait_growth(sr));
+    for (int64_t p = 0; p < nrows; p += piece) {
+        const int64_t cnt = std::min(piece, nrows - p), total = cnt * per;
+        hipLaunchKernelGGL(series_get_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, sr->stream, (const double *)sr->d_rows,
+                           sr->cap, row0 + p, cnt, sr->nw, sr->ndim, (double *)sr->d_scratch);
+        HIP_TRY(sr, hipGetLastError());
+        HIP_TRY(sr, hipMemcpyAsync(out + p * per, sr->d_scratch, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, sr->stream));
+        HIP_TRY(sr, hipStreamSynchronize(sr->stream));
+    }
+    return MSX_OK;
+}
+
+int msx_series_acf(msx_series *sr, int64_t n, int64_t discard, int64_t thin, int64_t lag0, int64_t nlag, uint32_t dim_mask,
+                   double *f_out) {
+    if (!sr) return MSX_ERR_INVALID;
+    if (!f_out || n < 1 || n > sr->rows || discard < 0 || thin < 1 || lag0 < 0 || nlag < 1)
+        return fail(sr, MSX_ERR_INVALID, "msx_series_acf: bad arguments (n must lie in 1 .. the rows the series holds)");
+    const int64_t np = n > discard ? (n - discard + thin - 1) / thin : 0;
+    if (lag0 + nlag > np) return fail(sr, MSX_ERR_INVALID, "msx_series_acf: lags past the thinned chain's length");
+    AcfDims dims = {};
+    for (int d = 0; d < sr->ndim; ++d)
+        if (dim_mask >> d & 1u) dims.d[dims.nd++] = d;
+    if (dims.nd == 0 || (dim_mask >> sr->ndim) != 0) return fail(sr, MSX_ERR_INVALID, "msx_series_acf: dim_mask names no dimension, or one past ndim");
+    HIP_TRY(sr, hipSetDevice(sr->device));
+    const int k = (int)sr->off.size() - 1, nd = dims.nd;
+    const int64_t nser = (int64_t)nd * sr->nw, nsuper = (np + kAcfSuper - 1) / kAcfSuper;
+    // lags per launch: whole tiles, as many as the partial sums' budget allows
+    const int64_t per_lag = nser * nsuper * (int64_t)sizeof(double);
+    int64_t sub = std::max<int64_t>(1, (int64_t)kAcfPartBudget / per_lag / kAcfLagTile) * kAcfLagTile;
+    sub = std::min(sub, nlag);
+    // scratch: [mean nser | part0 nser * nsuper | part nser * nsuper * sub | f k * nd * sub]
+    const size_t doubles = (size_t)(nser + nser * nsuper + nser * nsuper * sub + (int64_t)k * nd * sub);
+    HIP_TRY(sr, series_scratch(sr, sizeof(double) * doubles));
+    double *d_mean = (double *)sr->d_scratch, *d_part0 = d_mean + nser, *d_part = d_part0 + nser * nsuper;
+    double *d_f = d_part + nser * nsuper * sub;
+    HIP_TRY(sr, series_wait_growth(sr));
+    hipStream_t st = sr->stream;
+    hipLaunchKernelGGL(acf_mean_kernel, dim3((unsigned)nser), dim3(kAcfMeanThreads), 0, st, (const double *)sr->d_rows, sr->cap,
+                       sr->nw, dims, np, discard, thin, d_mean);
+    HIP_TRY(sr, hipGetLastError());
+    hipLaunchKernelGGL(acf_lag_kernel, dim3((unsigned)nser, 1u, (unsigned)nsuper), dim3(kAcfThreads), 0, st, (const double *)sr->d_rows,
+                       sr->cap, sr->nw, dims, np, discard, thin, (const double *)d_mean, (int64_t)0, (int64_t)1, d_part0, nsuper, (int64_t)1);
+    HIP_TRY(sr, hipGetLastError());
+    std::vector<double> h((size_t)((int64_t)k * nd * sub));
+    for (int64_t lb = lag0; lb < lag0 + nlag; lb += sub) {
+        const int64_t cnt = std::min(sub, lag0 + nlag - lb), nout = (int64_t)k * nd * cnt;
+        hipLaunchKernelGGL(acf_lag_kernel, dim3((unsigned)nser, (unsigned)((cnt + kAcfLagTile - 1) / kAcfLagTile), (unsigned)nsuper),
+                           dim3(kAcfThreads), 0, st, (const double *)sr->d_rows, sr->cap, sr->nw, dims, np, discard, thin,
+                           (const double *)d_mean, lb, cnt, d_part, nsuper, cnt);
+        HIP_TRY(sr, hipGetLastError());
+        hipLaunchKernelGGL(acf_reduce_kernel, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, st, (const double *)d_part,
+                           (const double *)d_part0, nsuper, cnt, sr->nw, (int32_t)nd, (const int64_t *)sr->d_off, (int32_t)k, cnt, d_f);
+        HIP_TRY(sr, hipGetLastError());
+        HIP_TRY(sr, hipMemcpyAsync(h.data(), d_f, sizeof(double) * (size_t)nout, hipMemcpyDeviceToHost, st));
+        HIP_TRY(sr, hipStreamSynchronize(st));
+        for (int m = 0; m < k; ++m)
+            for (int q = 0; q < nd; ++q)
+                memcpy(f_out + ((int64_t)m * sr->ndim + dims.d[q]) * nlag + (lb - lag0), h.data() + ((int64_t)m * nd + q) * cnt,
+                       sizeof(double) * (size_t)cnt);
+    }
     return MSX_OK;
 }
 

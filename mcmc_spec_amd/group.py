@@ -20,7 +20,7 @@ import numpy as np
 
 from . import _lib
 from .engine import _raise_for_status
-from .sampler import EnsembleSampler, State, _accept, _propose, _pump
+from .sampler import EnsembleSampler, State, _accept, _check_tau, _device_integrated_time, _propose, _pump
 
 
 class TargetGroup:
@@ -197,6 +197,14 @@ class GroupSampler:
         """One array per target."""
         return [s.acceptance_fraction for s in self.samplers]
 
+    def get_autocorr_time(self, k=None, quiet=False, c=5.0, tol=50.0, discard=0, thin=1):
+        """Target k's integrated autocorrelation time (ndim,), or every target's (K, ndim) for k None: each from the
+        target's own EnsembleSampler (EnsembleSampler.get_autocorr_time's keywords and rules)."""
+        kw = dict(quiet=quiet, c=c, tol=tol, discard=discard, thin=thin)
+        if k is not None:
+            return self.samplers[k].get_autocorr_time(**kw)
+        return np.array([s.get_autocorr_time(**kw) for s in self.samplers])
+
 
 class DeviceGroupSampler(GroupSampler):
     """``GroupSampler`` with the K ensembles resident in HBM (``msx_group_sampler_*``, include/msx.h): ``chunk`` iterations
@@ -210,7 +218,7 @@ class DeviceGroupSampler(GroupSampler):
     generators.  A walker error raises what ``TargetGroup`` raises, prefixed ``target k:``; the run ends there and the
     chain up to the last collected chunk stands."""
 
-    def __init__(self, nwalkers, ndim, group, mode='logposterior', a=2.0, seeds=None, chunk=64):
+    def __init__(self, nwalkers, ndim, group, mode='logposterior', a=2.0, seeds=None, chunk=64, autocorr='host'):
         if mode not in ('logposterior', 'loglikelihood'):
             raise ValueError("mode must be 'logposterior' or 'loglikelihood'")
         nwalkers = [int(n) for n in nwalkers]
@@ -222,8 +230,15 @@ class DeviceGroupSampler(GroupSampler):
         self.mode = mode
         self._mode = {'logposterior': _lib.MODE_LOGPOST, 'loglikelihood': _lib.MODE_LOGLIKE}[mode]
         fn = group.logposterior if mode == 'logposterior' else group.loglikelihood
+        if autocorr not in ('host', 'device'):
+            raise ValueError("autocorr must be 'host' or 'device'")
         super().__init__(nwalkers, ndim, fn, a=a, seeds=seeds)
         self.chunk = int(chunk)
+        # autocorr='device': the targets' stored chains are kept on the device too (one _lib.Series of K members, appended
+        # by every sample(store=True) run) and get_autocorr_time computes all targets' autocorrelation there, one
+        # msx_series_acf call per lag tile; 'host': GroupSampler's, per target
+        self.autocorr = autocorr
+        self._series = _lib.Series(group.engines[0].ctx, sum(nwalkers), self.ndim, nwalkers) if autocorr == 'device' else None
 
     def _draw_split_all(self, m):
         split = [s._draw_split(m) for s in self.samplers]
@@ -244,6 +259,12 @@ class DeviceGroupSampler(GroupSampler):
         grp = self.group.group
         base_acc = [s._accepted.copy() for s in self.samplers]
         grp.sampler_begin(self._mode, np.concatenate(coords), np.concatenate(logp), counts, self.chunk)
+        if store and self._series is not None:
+            try:
+                grp.sampler_attach_series(self._series, len(self.samplers[0]._chain))
+            except Exception:
+                grp.sampler_end()
+                raise
         with closing(_pump(iterations, self.chunk, (self._draw_split_all, self._draw_moves_all),
                            lambda slot, m, arrays: grp.sampler_enqueue(slot, *arrays), grp.sampler_collect,
                            grp.sampler_end)) as chunks:
@@ -266,3 +287,96 @@ class DeviceGroupSampler(GroupSampler):
                         s._last = State(c, lp)
                         states.append(s._last)
                     yield states
+
+    def get_autocorr_time(self, k=None, quiet=False, c=5.0, tol=50.0, discard=0, thin=1):
+        """GroupSampler.get_autocorr_time; with autocorr='device' every target's from the chains on the device, ONE
+        msx_series_acf call per lag tile over all targets (the targets step together: their chains have one length)."""
+        if self._series is None:
+            return super().get_autocorr_time(k, quiet=quiet, c=c, tol=tol, discard=discard, thin=thin)
+        n_total = len(self.samplers[0]._chain)
+        n = len(range(discard, n_total, thin))
+        shape = (self.ndim,) if k is not None else (len(self.samplers), self.ndim)
+        if n < 4:
+            if quiet:
+                return np.full(shape, np.nan)
+            raise ValueError('chain too short')
+        tau = _device_integrated_time(self._series, n_total, c, discard, thin) * thin
+        return _check_tau(tau if k is None else tau[k], n, thin, tol, quiet)
+
+
+def run_group_protocol(sampler, pos, nburn, nsteps, nthin=10, dirname=None, fnames=None):
+    """``sampler.run_reference_protocol`` (run_emcee's driver, mft6.py:1494-1529) applied to every target of a group
+    sampler (GroupSampler or DeviceGroupSampler) stepped in lock-step: burn-in, reset, then production with one tau
+    computation for all targets every ``nthin`` iterations.  Each target keeps its own ``old_acl``; a target that meets
+    ``acl * 50 < n`` and the 10 % rule is finished at that n -- its samples, its results dumps and its autocorr lines stop
+    there -- and the group keeps stepping until every target has finished or ``nsteps`` runs out.
+
+    ``pos``: one initial state per target.  ``dirname``: one directory per target (a sequence), or one directory under
+    which target k writes into ``dirname/fnames[k]/``; ``fnames``: the targets' file prefixes (default ``run0``, ``run1``,
+    ...).  Target k's files are those ``run_reference_protocol(dirname=<its directory>, fname=fnames[k])`` writes.
+    Returns the K targets' flattened samples; target k's are exactly ``run_reference_protocol``'s on target k alone with
+    k's seed (its chain in the group is its own chain, bit for bit)."""
+    import os
+    K, ndim = len(sampler.samplers), sampler.ndim
+    fnames = ['run{}'.format(k) for k in range(K)] if fnames is None else [str(f) for f in fnames]
+    if len(fnames) != K:
+        raise ValueError('one file prefix per target')
+    dirs = None
+    if dirname is not None:
+        if isinstance(dirname, (str, bytes, os.PathLike)):
+            dirs = [os.path.join(dirname, f) for f in fnames]
+            for d in dirs:
+                os.makedirs(d, exist_ok=True)
+        else:
+            dirs = list(dirname)
+            if len(dirs) != K:
+                raise ValueError('one directory per target')
+
+    def dump(k, what, coords):
+        with open('{}/{}_{}.txt'.format(dirs[k], fnames[k], what), 'ab') as f:
+            f.write(b'\n')
+            np.savetxt(f, coords)
+
+    for n, states in enumerate(sampler.sample(pos, iterations=nburn)):
+        if dirs and n % nthin == 0:
+            for k in range(K):
+                dump(k, '{}_burnin'.format(n), states[k].coords)
+    state = [s.get_last_sample() for s in sampler.samplers]
+    sampler.reset()
+    old_acl = [np.inf] * K
+    stop = [None] * K   # the production iteration at which target k finished
+    at_once = getattr(sampler, '_series', None) is not None
+    for n, states in enumerate(sampler.sample(state, iterations=nsteps)):
+        if n % nthin:
+            continue
+        active = [k for k in range(K) if stop[k] is None]
+        if dirs:
+            for k in active:
+                dump(k, '{}_results'.format(n), states[k].coords)
+        if at_once:   # (one device computation for all targets)
+            acls = sampler.get_autocorr_time(quiet=True)
+        else:
+            acls = {k: sampler.get_autocorr_time(k, quiet=True) for k in active}
+        for k in active:
+            acl = acls[k]
+            macl = np.mean(acl)
+            if dirs:
+                with open('{}/{}_autocorr.txt'.format(dirs[k], fnames[k]), 'a') as f:
+                    f.write(str(macl) + '\n')
+            if not np.isnan(macl):
+                converged = np.all(acl * 50 < n)
+                converged &= np.all((np.abs(old_acl[k] - acl) / acl) < 0.1)
+                if converged:
+                    stop[k] = n
+                    continue
+            old_acl[k] = acl
+        if all(st is not None for st in stop):
+            break
+    out = []
+    for k, s in enumerate(sampler.samplers):
+        nk = len(s._chain) if stop[k] is None else stop[k] + 1
+        samples = s.chain[:, :nk, :].reshape((-1, ndim))
+        if dirs:
+            np.savetxt(os.path.join(dirs[k], 'samples.txt'), samples)
+        out.append(samples)
+    return out

@@ -223,22 +223,70 @@ class EnsembleSampler:
                 return np.full(self.ndim, np.nan)
             raise ValueError('chain too short')
         n = x.shape[0]
-        tau = np.empty(self.ndim)
+        f = np.empty((self.ndim, n))
         for d in range(self.ndim):
-            f = np.zeros(n)
+            f[d] = 0.0
             for k in range(self.nwalkers):
-                f += _autocorr_1d(x[:, k, d])
-            f /= self.nwalkers
-            taus = 2.0 * np.cumsum(f) - 1.0
-            m = np.arange(len(taus)) < c * taus
-            win = int(np.argmin(m)) if np.any(~m) else len(taus) - 1
-            tau[d] = taus[win]
-        tau *= thin
-        if np.any(tol * tau > n * thin):
-            msg = 'The chain is shorter than {} times the integrated autocorrelation time'.format(tol)
-            if not quiet:
-                raise RuntimeError(msg)
-        return tau
+                f[d] += _autocorr_1d(x[:, k, d])
+            f[d] /= self.nwalkers
+        return _check_tau(_integrated_time(f, c) * thin, n, thin, tol, quiet)
+
+
+def _window(f, c):
+    """The Sokal window over the lags f[:L] of one dimension: (the first index idx with idx >= c * taus[idx], or None if
+    no index of the prefix qualifies; taus = 2 cumsum(f) - 1).  cumsum is sequential, so the taus of a prefix are those
+    of the full length: an index found in a prefix is the index the full length gives."""
+    taus = 2.0 * np.cumsum(f) - 1.0
+    m = np.arange(len(taus)) < c * taus
+    return (int(np.argmin(m)) if np.any(~m) else None), taus
+
+
+def _integrated_time(f, c):
+    """tau per dimension from the whole normalised autocorrelation f (ndim, L): taus at the Sokal window, or at the last
+    lag when no window is found (what get_autocorr_time has always done)."""
+    tau = np.empty(len(f))
+    for d in range(len(f)):
+        win, taus = _window(f[d], c)
+        tau[d] = taus[len(taus) - 1 if win is None else win]
+    return tau
+
+
+def _check_tau(tau, n, thin, tol, quiet):
+    """get_autocorr_time's tol rule: a chain shorter than tol taus raises unless quiet.  (n: rows after discard / thin.)"""
+    if np.any(tol * tau > n * thin):
+        msg = 'The chain is shorter than {} times the integrated autocorrelation time'.format(tol)
+        if not quiet:
+            raise RuntimeError(msg)
+    return tau
+
+
+ACF_TILE = 320  # the first lag tile of a device window search (autocorr_kernels.h: one workgroup's lags); then doubling
+
+
+def _device_integrated_time(series, n_total, c, discard, thin):
+    """tau (k, ndim) of the chain a ``_lib.Series`` holds in its first n_total rows, thinned x = rows[discard::thin]
+    (n' >= 4 rows), before ``*= thin``: lag tiles of growing length (ACF_TILE, 2 ACF_TILE, ... up to n') are requested
+    for the dimensions whose window some member has not found yet, one msx_series_acf call per tile over all members.  A
+    window found in the prefix is the one the full length gives (_window); none by n' -> the last lag, as on the host."""
+    n = len(range(discard, n_total, thin))
+    k, ndim = series.k, series.ndim
+    tau = np.full((k, ndim), np.nan)
+    pending = {(m, d) for m in range(k) for d in range(ndim)}
+    prefix = np.empty((k, ndim, 0))
+    lag0, tile = 0, ACF_TILE
+    while pending:
+        nlag = min(tile, n - lag0)
+        f = series.acf(n_total, discard, thin, lag0, nlag, sorted({d for _, d in pending}))
+        prefix = np.concatenate([prefix, f], axis=2)
+        lag0 += nlag
+        tile *= 2
+        for m, d in sorted(pending):
+            win, taus = _window(prefix[m, d], c)
+            if win is None and lag0 < n:
+                continue
+            tau[m, d] = taus[n - 1 if win is None else win]
+            pending.discard((m, d))
+    return tau
 
 
 # One half-step of the stretch move, in two parts around the evaluation of the proposals (EnsembleSampler, and
@@ -313,7 +361,8 @@ class DeviceEnsembleSampler(EnsembleSampler):
     ``engine`` is a staged ``mcmc_spec_amd.engine.Engine``; ``mode`` selects ``'logposterior'`` or
     ``'loglikelihood'`` as the target density."""
 
-    def __init__(self, nwalkers, ndim, engine, mode='logposterior', a=2.0, seed=None, chunk=64, shard=None, rng='host', overlap=None):
+    def __init__(self, nwalkers, ndim, engine, mode='logposterior', a=2.0, seed=None, chunk=64, shard=None, rng='host', overlap=None,
+                 autocorr='host'):
         """``shard = (rank, world)`` runs the SHARDED form: every rank holds the whole ensemble on
         its GPU, evaluates block ``rank`` of each half-step's proposals, one RCCL all-gather of the new
         log-probabilities crosses xGMI and every rank applies the accept rule for all walkers on the device.
@@ -330,6 +379,14 @@ class DeviceEnsembleSampler(EnsembleSampler):
         # half-steps fit the chip together: include/msx.h, msx_sampler_policy); False: plain launches -- the choice for a
         # GPU shared with other work, where a waiting workgroup's producer may not get a CU (the chunk then fails with
         # MSX_W_HANDOVER after a bounded wait, a RuntimeError here, and the run has to be started again).
+        # autocorr = 'host' (default): get_autocorr_time is EnsembleSampler's (the chain on the host, one FFT per walker and
+        # dimension).  'device': the sampler keeps its stored chain on the device as well (a _lib.Series that every
+        # sample(store=True) run appends to, from row len(self._chain) on) and get_autocorr_time computes the
+        # autocorrelation there (msx_series_acf).  Same tau up to roundoff, same window.
+        if autocorr not in ('host', 'device'):
+            raise ValueError("autocorr must be 'host' or 'device'")
+        self.autocorr = autocorr
+        self._series = None
         self.overlap_policy = -1 if overlap is None or overlap else 0
         if rng not in ('host', 'device'):
             raise ValueError("rng must be 'host' or 'device'")
@@ -343,6 +400,8 @@ class DeviceEnsembleSampler(EnsembleSampler):
         fn = engine.logposterior if mode == 'logposterior' else engine.loglikelihood
         super().__init__(nwalkers, ndim, fn, a=a, vectorize=True, seed=seed)
         self.chunk = int(chunk)
+        if autocorr == 'device':
+            self._series = _lib.Series(engine.ctx, self.nwalkers, self.ndim)
 
     def sample(self, initial_state, iterations=1, store=True):
         from .engine import _raise_for_status
@@ -372,6 +431,12 @@ class DeviceEnsembleSampler(EnsembleSampler):
         ctx.sampler_begin(self._mode, coords, logp, self.chunk)
         if self.shard is not None:
             ctx.sampler_shard(*self.shard)
+        if store and self._series is not None:
+            try:
+                ctx.sampler_attach_series(self._series, len(self._chain))   # (rows a consumer never saw are overwritten)
+            except Exception:
+                ctx.sampler_end()
+                raise
         draws = None if self.rng_mode == 'device' else (self._draw_split, self._draw_moves)
         with closing(_pump(iterations, self.chunk, draws, enqueue, ctx.sampler_collect, ctx.sampler_end)) as chunks:
             for mm, (chain, lpc, nacc, worst) in chunks:
@@ -389,6 +454,20 @@ class DeviceEnsembleSampler(EnsembleSampler):
     @property
     def acceptance_fraction(self):
         return self._accepted / max(self.iteration, 1)
+
+    def get_autocorr_time(self, quiet=False, c=5.0, tol=50.0, discard=0, thin=1):
+        """EnsembleSampler.get_autocorr_time; with autocorr='device' from the chain on the device (msx_series_acf).
+        Rows the device holds past len(self._chain) -- queued chunks not consumed yet -- are not part of it."""
+        if self._series is None:
+            return super().get_autocorr_time(quiet=quiet, c=c, tol=tol, discard=discard, thin=thin)
+        n_total = len(self._chain)
+        n = len(range(discard, n_total, thin))
+        if n < 4:
+            if quiet:
+                return np.full(self.ndim, np.nan)
+            raise ValueError('chain too short')
+        tau = _device_integrated_time(self._series, n_total, c, discard, thin)[0]
+        return _check_tau(tau * thin, n, thin, tol, quiet)
 
 
 def _autocorr_1d(x):

@@ -30,6 +30,8 @@ def main():
     ap.add_argument('--seed', type=int, default=1)
     ap.add_argument('--autocorr', choices=('host', 'device'), default='host',
                     help="where the protocol's convergence checks compute tau ('device': from the chain kept on the GPU)")
+    ap.add_argument('--resident-optimiser', action='store_true',
+                    help="the optimiser's chains live on the GPU (optimizer.fit_spec_device): same chains, no host round trip per proposal")
     args = ap.parse_args()
 
     import mcmc_spec_amd.mft6 as gpu
@@ -73,7 +75,7 @@ def main():
     t1 = time.time()
     optimizer.optimize_fit(args.out, data, err, specs, args.nwalk, fr, [plx, plx_err], [0.106, 0.01], res, ctm, ptm, tmi,
                            tma, None, matrix, 288.456, 45.802, nspec=2, nstep=args.nstep, dist_fit=True, rad_prior=False,
-                           seed=args.seed)
+                           seed=args.seed, resident=args.resident_optimiser)
     chisqs, pars = np.genfromtxt(os.path.join(args.out, 'optimize_cs.txt')), np.genfromtxt(
         os.path.join(args.out, 'optimize_res.txt'))
     best = np.argsort(chisqs)[: int(len(chisqs) / 3)]  # mft6.py:3670-3674

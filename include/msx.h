@@ -225,6 +225,41 @@ int msx_opt_init(msx_ctx *ctx, const double *theta0, int64_t nchains, int32_t nd
 int msx_opt_step(msx_ctx *ctx, const double *theta, const int32_t *chain, int64_t n, int32_t ndim,
                  double *chi2_out, int32_t *status_out);
 
+/* ---- f4 on the device: fit_spec's random-walk descent with the chains' state in HBM ----------
+ * After msx_opt_init, one chain per row of its theta0.  A TRIP is ONE draw of every chain (the body of fit_spec's while
+ * loop, mft6.py:935-1103): step sizes from the chain's phase, proposal gi + si * z (rounded multiply, rounded add), the
+ * bounds test; out of bounds -> the seven repair loops advance total_n and nothing is evaluated; in bounds -> the
+ * proposal's chi^2 in MSX_MODE_OPT_STEP against the chain's stored data vector, the opt_prior terms (A_V against the
+ * table's bin of 1 / plx; the parallax if dist_fit; the radii against the isochrone's if rad_prior, sigma = the radius
+ * step sizes) and the accept rule test < chi.  A chain is finished when n >= steps or total_n >= 50 * steps.
+ * begin: gi0 [nchains][ndim] the start points (rows [T.., A_V, rad.., plx]: msx_opt_init's theta0), chi0 [nchains] their
+ * chi^2 INCLUDING the prior terms (the host adds them as fit_spec does, mft6.py:909-929); tmin / tmax the Teff box;
+ * av_edges [nedges] ascending, av_mu / av_sig [nav] the A_V(distance) table of THIS run (bin = #{edges <= 1 / plx} - 1,
+ * clipped to [0, nav - 1]; sigma 0 reads 0.05); iso_teff / iso_lum [niso] the isochrone sorted by Teff (read only with
+ * rad_prior).  Argument errors are reported before any device work.  A run still open ends; so does msx_opt_init,
+ * restaging the problem or destroying the ctx.                                                                        */
+#define MSX_OPT_TRIP_IDLE 0      /* the chain was finished before this trip                                  */
+#define MSX_OPT_TRIP_OOB 1       /* the draw was out of bounds: repair loops counted, nothing evaluated      */
+#define MSX_OPT_TRIP_REJECTED 2  /* evaluated, test >= chi                                                   */
+#define MSX_OPT_TRIP_ACCEPTED 3  /* evaluated, test < chi: the record's gi is the proposal                   */
+#define MSX_OPT_TRIP_ERROR 4     /* evaluated with a walker error: flag = 4 | MSX_W_* << 8, the record's gi slot names
+                                  * the PROPOSAL, its test is NaN, and the chain stops                              */
+int msx_opt_run_begin(msx_ctx *ctx, int64_t nchains, int32_t ndim, const double *gi0, const double *chi0, int64_t steps,
+                      double tmin, double tmax, int32_t dist_fit, int32_t rad_prior, double plx_prior, double plx_sigma,
+                      int32_t nedges, const double *av_edges, int32_t nav, const double *av_mu, const double *av_sig,
+                      int32_t niso, const double *iso_teff, const double *iso_lum, int64_t max_chunk_trips);
+/* one chunk of ntrips <= max_chunk_trips trips into slot 0|1 without waiting for it: z [ntrips][nchains][ndim] standard
+ * normals (chain c's k-th draw of the run is its slice of the run's k-th trip), uploaded on a stream of its own;
+ * 2 * ntrips + 1 launches on the compute stream and no host round trip between them.                                   */
+int msx_opt_run_enqueue(msx_ctx *ctx, int32_t slot, int64_t ntrips, const double *z);
+/* waits for the chunk in `slot`: records [ntrips][nchains][ndim + 2] = {gi[ndim], chi, test} of every chain AFTER each
+ * trip (test: NaN unless evaluated), flags [ntrips][nchains] MSX_OPT_TRIP_*, *live = chains that would draw again after
+ * the chunk (0: the run is over), *worst_status = the worst walker status above MSX_W_REJECT of the chunk's evaluations. */
+int msx_opt_run_collect(msx_ctx *ctx, int32_t slot, double *records, int32_t *flags, int64_t *live, int32_t *worst_status);
+/* ends the run (waits for it); any of gi [nchains][ndim], chi, n [nchains] (a double: steps / 2 + 1 is fractional for
+ * odd steps), total_n [nchains] may be NULL.                                                                           */
+int msx_opt_run_end(msx_ctx *ctx, double *gi, double *chi, double *n, int64_t *total_n);
+
 /* ---- f2 on the device: nsteps iterations of the affine-invariant stretch move (Goodman & Weare 2010, the
  * default move of emcee 3; the loop the reference drives at mft6.py:1494-1524) with the walker state resident in
  * HBM.  Per half-step there is ONE launch of the fused log-probability kernel: its first lines build each active

@@ -111,6 +111,11 @@ def load():
         'msx_set_broadening': (C.c_int, [vp, C.c_int32]),
         'msx_opt_init': (C.c_int, [vp, _dp, C.c_int64, C.c_int32, _dp, C.POINTER(C.c_int32)]),
         'msx_opt_step': (C.c_int, [vp, _dp, C.POINTER(C.c_int32), C.c_int64, C.c_int32, _dp, C.POINTER(C.c_int32)]),
+        'msx_opt_run_begin': (C.c_int, [vp, C.c_int64, C.c_int32, _dp, _dp, C.c_int64, C.c_double, C.c_double, C.c_int32, C.c_int32,
+                                        C.c_double, C.c_double, C.c_int32, _dp, C.c_int32, _dp, _dp, C.c_int32, _dp, _dp, C.c_int64]),
+        'msx_opt_run_enqueue': (C.c_int, [vp, C.c_int32, C.c_int64, _dp]),
+        'msx_opt_run_collect': (C.c_int, [vp, C.c_int32, _dp, C.POINTER(C.c_int32), _ip, C.POINTER(C.c_int32)]),
+        'msx_opt_run_end': (C.c_int, [vp, _dp, _dp, _dp, _ip]),
         'msx_sampler_run': (C.c_int, [vp, C.c_int32, C.c_int64, C.c_int32, C.c_int64, _dp, _dp, C.POINTER(C.c_int32),
                                       C.POINTER(C.c_int32), C.POINTER(C.c_int32), _dp, _dp, _dp, _dp, _dp, _ip,
                                       C.POINTER(C.c_int32)]),
@@ -173,7 +178,8 @@ EXPORTED = ['msx_create', 'msx_destroy', 'msx_last_error', 'msx_device_info', 'm
             'msx_resample_linear',
             'msx_broaden', 'msx_broaden_grid', 'msx_rot_broaden', 'msx_rot_broaden_grid', 'msx_split_components',
             'msx_stage_grid_components', 'msx_rot_broaden_grid_component', 'msx_read_node_component', 'msx_read_node', 'msx_stage_problem', 'msx_logprob_batch',
-            'msx_logprob_batch_dev', 'msx_probe_launch', 'msx_set_path', 'msx_set_grid_storage', 'msx_set_broadening', 'msx_opt_init', 'msx_opt_step', 'msx_sampler_run', 'msx_sampler_begin',
+            'msx_logprob_batch_dev', 'msx_probe_launch', 'msx_set_path', 'msx_set_grid_storage', 'msx_set_broadening', 'msx_opt_init', 'msx_opt_step', 'msx_opt_run_begin', 'msx_opt_run_enqueue',
+            'msx_opt_run_collect', 'msx_opt_run_end', 'msx_sampler_run', 'msx_sampler_begin',
             'msx_sampler_shard', 'msx_sampler_enqueue', 'msx_sampler_enqueue_drawn', 'msx_sampler_draw', 'msx_sampler_collect', 'msx_sampler_end', 'msx_make_composite', 'msx_comm_unique_id', 'msx_comm_init', 'msx_comm_allgather_dev', 'msx_comm_wait_slot',
             'msx_comm_init_loopback', 'msx_sampler_enqueue_group',
             'msx_stream_copy_gbps', 'msx_bytes_per_eval', 'msx_launch_info', 'msx_last_form', 'msx_test_hook', 'msx_pair_stats', 'msx_sampler_overlapped', 'msx_sampler_policy',
@@ -382,6 +388,52 @@ class Context:
         self.check(self.lib.msx_opt_step(self.h, dptr(theta), chain.ctypes.data_as(C.POINTER(C.c_int32)), n, ndim,
                                          dptr(chi), status.ctypes.data_as(C.POINTER(C.c_int32))))
         return chi, status
+
+    def opt_run_begin(self, gi0, chi0, steps, tlim, dist_fit, rad_prior, dist_prior, av_table, iso, max_chunk_trips):
+        """Start a device-resident pre-optimiser run (msx_opt_run_begin) over the chains of the last opt_init: gi0
+        [nchains][ndim] the start points, chi0 their chi^2 with the prior terms; av_table = (edges, mu, sigma);
+        iso = (teff, luminosity) sorted by Teff, or None without rad_prior."""
+        gi0, chi0 = as_f64(gi0), as_f64(chi0)
+        nch, ndim = gi0.shape
+        if chi0.shape != (nch,):
+            raise ValueError('opt_run_begin: one chi^2 per start point')
+        edges, mu, sig = [as_f64(a) for a in av_table]
+        if mu.shape != sig.shape or mu.ndim != 1 or edges.ndim != 1:
+            raise ValueError('opt_run_begin: av_table = (edges, mu, sigma), mu and sigma of one length')
+        it, il = (None, None) if iso is None else (as_f64(iso[0]), as_f64(iso[1]))
+        if it is not None and it.shape != il.shape:
+            raise ValueError('opt_run_begin: iso = (teff, luminosity) of one length')
+        self.check(self.lib.msx_opt_run_begin(self.h, nch, ndim, dptr(gi0), dptr(chi0), int(steps), float(min(tlim)), float(max(tlim)),
+                                              int(bool(dist_fit)), int(bool(rad_prior)), float(dist_prior[0]), float(dist_prior[1]),
+                                              edges.size, dptr(edges), mu.size, dptr(mu), dptr(sig),
+                                              0 if it is None else it.size, None if it is None else dptr(it),
+                                              None if il is None else dptr(il), int(max_chunk_trips)))
+        self._opt_shape = (nch, ndim)
+
+    def opt_run_enqueue(self, slot, z):
+        """Queue one chunk of trips without waiting for it: z [ntrips][nchains][ndim] standard normals."""
+        z = as_f64(z)
+        if z.ndim != 3 or z.shape[1:] != self._opt_shape:
+            raise ValueError('opt_run_enqueue: z must be [ntrips][nchains][ndim]')
+        self.check(self.lib.msx_opt_run_enqueue(self.h, int(slot), z.shape[0], dptr(z)))
+        return z.shape[0]
+
+    def opt_run_collect(self, slot, ntrips):
+        """Wait for the chunk in `slot`: (records [ntrips][nchains][ndim + 2], flags [ntrips][nchains], live, worst)."""
+        nch, ndim = self._opt_shape
+        rec = np.empty((int(ntrips), nch, ndim + 2))
+        flags = np.empty((int(ntrips), nch), dtype=np.int32)
+        live, worst = C.c_int64(), C.c_int32()
+        self.check(self.lib.msx_opt_run_collect(self.h, int(slot), dptr(rec), flags.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                C.cast(C.byref(live), _ip), C.byref(worst)))
+        return rec, flags, live.value, worst.value
+
+    def opt_run_end(self):
+        """End the run: (gi [nchains][ndim], chi, n, total_n)."""
+        nch, ndim = self._opt_shape
+        gi, chi, n, tot = np.empty((nch, ndim)), np.empty(nch), np.empty(nch), np.empty(nch, dtype=np.int64)
+        self.check(self.lib.msx_opt_run_end(self.h, dptr(gi), dptr(chi), dptr(n), iptr(tot)))
+        return gi, chi, n, tot
 
     def sampler_run(self, mode, coords, logp, sidx, cidx, partner, zz, zfac, logu):
         """Run len(zz) stretch-move steps on the device.  coords [nw][ndim] and logp [nw] are updated in place;

@@ -23,6 +23,7 @@
 //   logprob_body.h     the fused kernel's body, included as text by logprob_kernel and logprob_group_kernel
 //   group_kernel.h     target groups: the fused body over the walkers of several staged problems in one launch
 //   pair_kernel.h      the pair form: two walkers of one grid cell per workgroup, one set of row loads
+//   opt_run_kernels.h  the device-resident pre-optimiser: fit_spec's per-chain state machine, one thread per chain
 //   staging_kernels.h  CCM89, pair gather, band integrals, broadening, resample, composite, stream copy
 //   msx.hip            host context + the C ABI of include/msx.h
 //
@@ -64,6 +65,7 @@
 #include "staging_kernels.h"
 #include "inpath_kernels.h"
 #include "autocorr_kernels.h"
+#include "opt_run_kernels.h"
 
 // ================================================================================================
 // host side: context + C ABI
@@ -148,6 +150,7 @@ struct msx_ctx {
     bool recipe_fast = false;       // the register-resident recipe applies (small tables)
     unsigned char *d_recipe_block = nullptr;  // ... and its tables in one block (dev_types.h), freed with the problem
     struct SamplerRun *smp = nullptr;  // device-resident sampler in flight (msx_sampler_begin .. _end)
+    struct OptRun *opt_run = nullptr;  // device-resident pre-optimiser in flight (msx_opt_run_begin .. _end)
     bool smp_overlap_launch = false;   // the launch being queued is a half-step of an overlapped run: fused form, bit 20
     bool probe_launch = false;         // ... is msx_probe_launch's: the kernel leaves clock stamps (bit 21)
     int32_t last_form = 0;             // MSX_FORM_* of the last launch queued (msx_last_form)
@@ -161,6 +164,7 @@ struct msx_ctx {
     std::vector<struct msx_group *> groups;
 };
 static void sampler_free(msx_ctx *c);
+static void opt_run_free(msx_ctx *c);
 
 // A TARGET GROUP (include/msx.h): 1..MSX_MAX_GROUP staged contexts on one device whose walkers one launch of
 // logprob_group_kernel evaluates, each against its own member's problem.  The group owns snapshots of the members'
@@ -282,6 +286,7 @@ int dev_alloc_copy(msx_ctx *c, std::vector<void *> *track, const T *host, int64_
 
 void free_problem(msx_ctx *c) {
     sampler_free(c);  // a sampler in flight holds pointers into the problem's tables
+    opt_run_free(c);  // ... and a pre-optimiser run into the chains' data vectors
     for (msx_group *g : c->groups) group_run_drain(g);  // ... and so does a group's (its next enqueue is refused)
     ++c->prob_gen;    // (target groups holding a snapshot of the problem refuse this member from now on)
     for (void *p : c->prob_allocs) (void)hipFree(p);
@@ -1764,6 +1769,7 @@ int msx_opt_init(msx_ctx *c, const double *theta0, int64_t nchains, int32_t ndim
     if (!c->problem_staged) return fail(c, MSX_ERR_STATE, "msx_opt_init: no problem staged");
     if (!theta0 || !chi2_out || !status_out || nchains < 1) return fail(c, MSX_ERR_INVALID, "msx_opt_init: bad arguments");
     HIP_TRY(c, hipSetDevice(c->device));
+    opt_run_free(c);  // (a run in flight reads the data vectors freed below)
     if (c->d_opt_flux) (void)hipFree(c->d_opt_flux);
     if (c->d_opt_med) (void)hipFree(c->d_opt_med);
     c->d_opt_flux = c->d_opt_med = nullptr; c->opt_chains = 0;
@@ -1793,6 +1799,243 @@ int msx_opt_step(msx_ctx *c, const double *theta, const int32_t *chain, int64_t 
     HIP_TRY(c, hipMemcpyAsync(c->d_opt_chain, chain, sizeof(int32_t) * n, hipMemcpyHostToDevice, c->stream));
     c->P.opt_chain = c->d_opt_chain;
     return msx_logprob_batch(c, MSX_MODE_OPT_STEP, theta, n, ndim, chi2_out, status_out);
+}
+
+// ---- device-resident pre-optimiser ---------------------------------------------------
+// fit_spec's chains (mft6.py:856-1137) with their state in HBM.  A TRIP is one draw of every chain: the chain's thread
+// (opt_run_kernels.h) proposes, the UNCHANGED hot kernel evaluates the in-bounds proposals in MSX_MODE_OPT_STEP (one
+// workgroup per chain; chains with nothing to evaluate hand it a row of NaNs and their workgroup leaves after its
+// recipe), and the chain's thread applies the prior terms and the accept rule -- fused with the next trip's proposal,
+// so a chunk of k trips is 2 k + 1 launches on the compute stream and nothing returns to the host in between.  Two
+// slots, pipelined like the sampler's: chunk i + 1 is uploaded and queued while chunk i runs.
+struct OptRun {
+    OptRunDev R;
+    int64_t nch = 0, cap_trips = 0;
+    int32_t ndim = 0;
+    bool failed = false;
+    char *d_state = nullptr;
+    int32_t *d_ident = nullptr;  // [nch] 0, 1, ...: chain of walker c (DevProblem::opt_chain)
+    hipStream_t copy = nullptr, up = nullptr;
+    struct Slot {
+        char *d_in = nullptr, *d_out = nullptr, *h_in = nullptr, *h_out = nullptr;
+        hipEvent_t in_ready = nullptr, kernels_done = nullptr, out_ready = nullptr;
+        int64_t ntrips = 0;
+        bool busy = false;
+    } slot[2];
+    size_t in_bytes(int64_t t) const { return sizeof(double) * (size_t)(t * nch * ndim); }
+    size_t rec_count(int64_t t) const { return (size_t)(t * nch * (ndim + 2)); }
+    size_t out_bytes(int64_t t) const {  // [records | flags | live, worst]
+        return sizeof(double) * rec_count(t) + sizeof(int32_t) * (size_t)(t * nch + 2);
+    }
+};
+
+static void opt_run_free(msx_ctx *c) {
+    OptRun *r = c->opt_run;
+    if (!r) return;
+    (void)hipSetDevice(c->device);
+    (void)hipStreamSynchronize(c->stream);
+    if (r->copy) (void)hipStreamSynchronize(r->copy);
+    if (r->up) (void)hipStreamSynchronize(r->up);
+    for (auto &sl : r->slot) {
+        if (sl.d_in) (void)hipFree(sl.d_in);
+        if (sl.d_out) (void)hipFree(sl.d_out);
+        if (sl.h_in) (void)hipHostFree(sl.h_in);
+        if (sl.h_out) (void)hipHostFree(sl.h_out);
+        if (sl.in_ready) (void)hipEventDestroy(sl.in_ready);
+        if (sl.kernels_done) (void)hipEventDestroy(sl.kernels_done);
+        if (sl.out_ready) (void)hipEventDestroy(sl.out_ready);
+    }
+    if (r->d_state) (void)hipFree(r->d_state);
+    if (r->copy) (void)hipStreamDestroy(r->copy);
+    if (r->up) (void)hipStreamDestroy(r->up);
+    delete r;
+    c->opt_run = nullptr;
+    c->P.opt_chain = nullptr;
+}
+
+int msx_opt_run_begin(msx_ctx *c, int64_t nchains, int32_t ndim, const double *gi0, const double *chi0, int64_t steps,
+                      double tmin, double tmax, int32_t dist_fit, int32_t rad_prior, double plx_prior, double plx_sigma,
+                      int32_t nedges, const double *av_edges, int32_t nav, const double *av_mu, const double *av_sig,
+                      int32_t niso, const double *iso_teff, const double *iso_lum, int64_t max_chunk_trips) {
+    if (!c) return MSX_ERR_INVALID;
+    if (!c->problem_staged || !c->P.opt_flux) return fail(c, MSX_ERR_STATE, "msx_opt_run_begin: call msx_opt_init first");
+    if (!gi0 || !chi0 || !av_edges || !av_mu || !av_sig || nedges < 1 || nav < 1 || steps < 1 || steps > (1ll << 40) ||
+        max_chunk_trips < 1)
+        return fail(c, MSX_ERR_INVALID, "msx_opt_run_begin: bad arguments");
+    if (nchains != c->opt_chains) return fail(c, MSX_ERR_INVALID, "msx_opt_run_begin: one chain per row of msx_opt_init's theta0");
+    if (ndim != 2 * c->P.nspec + 2 || ndim > MSX_MAX_DIM) return fail(c, MSX_ERR_INVALID, "P0 doesn't match what I was expecting");
+    if (rad_prior && (!iso_teff || !iso_lum || niso < 2)) return fail(c, MSX_ERR_INVALID, "msx_opt_run_begin: rad_prior needs the isochrone");
+    if (!rad_prior) niso = 0;
+    for (int32_t i = 1; i < nedges; ++i)
+        if (!(av_edges[i - 1] <= av_edges[i])) return fail(c, MSX_ERR_INVALID, "msx_opt_run_begin: av_edges must ascend");
+    for (int32_t i = 1; i < niso; ++i)
+        if (!(iso_teff[i - 1] <= iso_teff[i])) return fail(c, MSX_ERR_INVALID, "msx_opt_run_begin: iso_teff must ascend");
+    HIP_TRY(c, hipSetDevice(c->device));
+    opt_run_free(c);
+    OptRun *r = new OptRun;
+    c->opt_run = r;
+    const int64_t nch = nchains;
+    const int ns = c->P.nspec;
+    r->nch = nch; r->ndim = ndim; r->cap_trips = max_chunk_trips;
+    // state: doubles first [gi | chi | n | rad0 | dist0 | theta | like | tables], then int64 total_n, then the int32 arrays
+    const size_t ntab = (size_t)nedges + 2 * (size_t)nav + 2 * (size_t)niso;
+    const size_t ndbl = (size_t)(nch * ndim) * 2 + (size_t)nch * 4 + (size_t)(nch * ns) + ntab;
+    const size_t state_bytes = sizeof(double) * ndbl + sizeof(int64_t) * (size_t)nch + sizeof(int32_t) * (size_t)(4 * nch);
+    std::vector<double> h(ndbl, 0.0);
+    hipError_t e = hipMalloc((void **)&r->d_state, state_bytes);
+    if (e == hipSuccess) e = hipMemsetAsync(r->d_state, 0, state_bytes, c->stream);
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&r->copy, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&r->up, hipStreamNonBlocking);
+    for (auto &sl : r->slot) {
+        if (e == hipSuccess) e = hipMalloc((void **)&sl.d_in, r->in_bytes(r->cap_trips));
+        if (e == hipSuccess) e = hipMalloc((void **)&sl.d_out, r->out_bytes(r->cap_trips));
+        if (e == hipSuccess) e = hipHostMalloc((void **)&sl.h_in, r->in_bytes(r->cap_trips), hipHostMallocDefault);
+        if (e == hipSuccess) e = hipHostMalloc((void **)&sl.h_out, r->out_bytes(r->cap_trips), hipHostMallocDefault);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.in_ready, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.kernels_done, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.out_ready, hipEventDisableTiming);
+    }
+    if (e == hipSuccess) {
+        OptRunDev &R = r->R;
+        double *d = (double *)r->d_state;
+        size_t o = 0;
+        auto take = [&](size_t cnt) { double *p = d + o; o += cnt; return p; };
+        R.gi = take((size_t)(nch * ndim));
+        R.chi = take((size_t)nch);
+        R.n = take((size_t)nch);
+        R.rad0 = take((size_t)(nch * ns));
+        R.dist0 = take((size_t)nch);
+        R.theta = take((size_t)(nch * ndim));
+        double *like = take((size_t)nch);
+        R.like = like;
+        double *t_edges = take((size_t)nedges), *t_mu = take((size_t)nav), *t_sig = take((size_t)nav);
+        double *t_isot = take((size_t)niso), *t_isol = take((size_t)niso);
+        R.av_edges = t_edges; R.av_mu = t_mu; R.av_sig = t_sig; R.iso_t = t_isot; R.iso_l = t_isol;
+        R.total_n = (int64_t *)(d + ndbl);
+        R.done = (int32_t *)(R.total_n + nch);
+        R.tflag = R.done + nch;
+        int32_t *status = R.tflag + nch;
+        R.status = status;
+        r->d_ident = status + nch;
+        R.nch = (int32_t)nch; R.ndim = ndim; R.nspec = ns; R.dist_fit = dist_fit != 0; R.rad_prior = rad_prior != 0;
+        R.nedges = nedges; R.nmu = nav; R.niso = niso;
+        R.steps = (double)steps; R.cap = 50 * steps;
+        R.tmin = tmin; R.tmax = tmax; R.pprior = plx_prior; R.psig = plx_sigma;
+        // the host image of the doubles: the start points, their chi^2, n = 0, the step sizes' scales, the tables
+        memcpy(h.data() + (R.gi - d), gi0, sizeof(double) * (size_t)(nch * ndim));
+        memcpy(h.data() + (R.chi - d), chi0, sizeof(double) * (size_t)nch);
+        for (int64_t k = 0; k < nch; ++k) {
+            for (int s = 0; s < ns; ++s) h[(size_t)((R.rad0 - d) + k * ns + s)] = gi0[k * ndim + ns + 1 + s];
+            h[(size_t)((R.dist0 - d) + k)] = gi0[k * ndim + 2 * ns + 1];
+        }
+        memcpy(h.data() + (t_edges - d), av_edges, sizeof(double) * (size_t)nedges);
+        memcpy(h.data() + (t_mu - d), av_mu, sizeof(double) * (size_t)nav);
+        memcpy(h.data() + (t_sig - d), av_sig, sizeof(double) * (size_t)nav);
+        if (niso > 0) {
+            memcpy(h.data() + (t_isot - d), iso_teff, sizeof(double) * (size_t)niso);
+            memcpy(h.data() + (t_isol - d), iso_lum, sizeof(double) * (size_t)niso);
+        }
+        e = hipMemcpyAsync(d, h.data(), sizeof(double) * ndbl, hipMemcpyHostToDevice, c->stream);  // (behind the memset)
+    }
+    std::vector<int32_t> ident((size_t)nch);
+    for (int64_t k = 0; k < nch; ++k) ident[(size_t)k] = (int32_t)k;
+    if (e == hipSuccess) e = hipMemcpyAsync(r->d_ident, ident.data(), sizeof(int32_t) * (size_t)nch, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // (the host images above are consumed)
+    if (e != hipSuccess) {
+        opt_run_free(c);
+        return fail(c, MSX_ERR_HIP, std::string("msx_opt_run_begin: ") + hipGetErrorString(e));
+    }
+    return MSX_OK;
+}
+
+static hipError_t opt_run_trip_launch(msx_ctx *c, const OptRun *r, const double *z, double *rec, int32_t *flags, int32_t *worst,
+                                      int32_t *live) {
+    const dim3 grid((unsigned int)((r->nch + kOptRunThreads - 1) / kOptRunThreads)), block(kOptRunThreads);
+    if (r->R.nspec == 2)
+        hipLaunchKernelGGL(opt_run_trip_kernel<2>, grid, block, 0, c->stream, r->R, z, rec, flags, worst, live);
+    else
+        hipLaunchKernelGGL(opt_run_trip_kernel<3>, grid, block, 0, c->stream, r->R, z, rec, flags, worst, live);
+    return hipGetLastError();
+}
+
+int msx_opt_run_enqueue(msx_ctx *c, int32_t slot, int64_t ntrips, const double *z) {
+    if (!c) return MSX_ERR_INVALID;
+    OptRun *r = c->opt_run;
+    if (!r) return fail(c, MSX_ERR_STATE, "msx_opt_run_enqueue: call msx_opt_run_begin first");
+    if (r->failed) return fail(c, MSX_ERR_STATE, "msx_opt_run_enqueue: an earlier chunk failed while it was queued; call msx_opt_run_end");
+    if (slot < 0 || slot > 1 || !z || ntrips < 1 || ntrips > r->cap_trips)
+        return fail(c, MSX_ERR_INVALID, "msx_opt_run_enqueue: bad arguments (slot 0|1, 1 <= ntrips <= max_chunk_trips)");
+    OptRun::Slot &sl = r->slot[slot];
+    if (sl.busy) return fail(c, MSX_ERR_STATE, "msx_opt_run_enqueue: the slot holds a chunk that was not collected");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int64_t nch = r->nch;
+    const int32_t ndim = r->ndim;
+    memcpy(sl.h_in, z, r->in_bytes(ntrips));
+    HIP_TRY(c, hipMemcpyAsync(sl.d_in, sl.h_in, r->in_bytes(ntrips), hipMemcpyHostToDevice, r->up));
+    HIP_TRY(c, hipEventRecord(sl.in_ready, r->up));
+    HIP_TRY(c, hipStreamWaitEvent(c->stream, sl.in_ready, 0));
+    double *rec = (double *)sl.d_out;
+    int32_t *flags = (int32_t *)(rec + r->rec_count(ntrips));
+    int32_t *live = flags + ntrips * nch, *worst = live + 1;
+    r->failed = true;  // (until every launch of the chunk is queued)
+    HIP_TRY(c, hipMemsetAsync(live, 0, 2 * sizeof(int32_t), c->stream));
+    c->P.opt_chain = r->d_ident;
+    const double *dz = (const double *)sl.d_in;
+    for (int64_t t = 0; t <= ntrips; ++t) {
+        // the last lines of trip t - 1 and the first lines of trip t, then trip t's evaluation
+        const bool prev = t > 0, next = t < ntrips;
+        HIP_TRY(c, opt_run_trip_launch(c, r, next ? dz + t * nch * ndim : nullptr, prev ? rec + (t - 1) * nch * (ndim + 2) : nullptr,
+                                       prev ? flags + (t - 1) * nch : nullptr, worst, next ? nullptr : live));
+        if (next) {
+            const int rc = msx_logprob_batch_dev(c, MSX_MODE_OPT_STEP, r->R.theta, nch, ndim, const_cast<double *>(r->R.like),
+                                                 const_cast<int32_t *>(r->R.status), c->stream, 0);
+            if (rc != MSX_OK) return rc;
+        }
+    }
+    r->failed = false;
+    HIP_TRY(c, hipEventRecord(sl.kernels_done, c->stream));
+    HIP_TRY(c, hipStreamWaitEvent(r->copy, sl.kernels_done, 0));
+    HIP_TRY(c, hipMemcpyAsync(sl.h_out, sl.d_out, r->out_bytes(ntrips), hipMemcpyDeviceToHost, r->copy));
+    HIP_TRY(c, hipEventRecord(sl.out_ready, r->copy));
+    sl.ntrips = ntrips;
+    sl.busy = true;
+    return MSX_OK;
+}
+
+int msx_opt_run_collect(msx_ctx *c, int32_t slot, double *records, int32_t *flags, int64_t *live, int32_t *worst_status) {
+    if (!c) return MSX_ERR_INVALID;
+    OptRun *r = c->opt_run;
+    if (!r) return fail(c, MSX_ERR_STATE, "msx_opt_run_collect: call msx_opt_run_begin first");
+    if (slot < 0 || slot > 1 || !records || !flags || !live || !worst_status) return fail(c, MSX_ERR_INVALID, "msx_opt_run_collect: bad arguments");
+    OptRun::Slot &sl = r->slot[slot];
+    if (!sl.busy) return fail(c, MSX_ERR_STATE, "msx_opt_run_collect: no chunk queued in this slot");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipEventSynchronize(sl.out_ready));
+    sl.busy = false;
+    const double *hr = (const double *)sl.h_out;
+    const int32_t *hf = (const int32_t *)(hr + r->rec_count(sl.ntrips));
+    memcpy(records, hr, sizeof(double) * r->rec_count(sl.ntrips));
+    memcpy(flags, hf, sizeof(int32_t) * (size_t)(sl.ntrips * r->nch));
+    *live = hf[sl.ntrips * r->nch];
+    *worst_status = hf[sl.ntrips * r->nch + 1];
+    if (*worst_status == MSX_W_HANDOVER) c->linked_poisoned = true;
+    return MSX_OK;
+}
+
+int msx_opt_run_end(msx_ctx *c, double *gi, double *chi, double *n, int64_t *total_n) {
+    if (!c) return MSX_ERR_INVALID;
+    OptRun *r = c->opt_run;
+    if (!r) return fail(c, MSX_ERR_STATE, "msx_opt_run_end: no run in flight");
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipError_t e = hipStreamSynchronize(c->stream);
+    const size_t nch = (size_t)r->nch;
+    if (e == hipSuccess && gi) e = hipMemcpy(gi, r->R.gi, sizeof(double) * nch * (size_t)r->ndim, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && chi) e = hipMemcpy(chi, r->R.chi, sizeof(double) * nch, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && n) e = hipMemcpy(n, r->R.n, sizeof(double) * nch, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && total_n) e = hipMemcpy(total_n, r->R.total_n, sizeof(int64_t) * nch, hipMemcpyDeviceToHost);
+    opt_run_free(c);
+    if (e != hipSuccess) return fail(c, MSX_ERR_HIP, std::string("msx_opt_run_end: ") + hipGetErrorString(e));
+    return MSX_OK;
 }
 
 // ---- device-resident sampler, pipelined -------------------------------------------------------------------

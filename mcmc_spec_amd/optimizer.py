@@ -196,11 +196,193 @@ def fit_spec_batch(engine, starts, tlim, dist_prior, matrix, av_table, nspec=2, 
     return out
 
 
+# ---- device-resident run ---------------------------------------------------------------------
+# One TRIP = the body of fit_spec_batch's ``while`` loop for exactly ONE draw of one chain.  The HIP kernel
+# (csrc/opt_run_kernels.h), ``trip_numpy`` below and the tests share this definition.
+TRIP_IDLE, TRIP_OOB, TRIP_REJECTED, TRIP_ACCEPTED, TRIP_ERROR = 0, 1, 2, 3, 4
+
+
+class TripState:
+    """One chain's state between trips: ``gi`` (flat row ``[T.., A_V, rad.., plx]``), ``chi``, ``n``, ``total_n``,
+    the start point's ``rad0`` / ``dist0`` (the step sizes' scale) and ``done``."""
+
+    def __init__(self, start, chi, nspec):
+        self.gi = np.array(start, dtype=float)
+        self.chi = chi
+        self.n, self.total_n = 0, 0
+        self.rad0 = [float(r) for r in self.gi[nspec + 1:2 * nspec + 1]]
+        self.dist0 = float(self.gi[2 * nspec + 1])
+        self.done = False
+
+
+def _groups(row, nspec):
+    """A flat row as the four groups ``default_propose`` returns (arrays of nspec, 1, nspec, 1 entries)."""
+    row = np.asarray(row, dtype=float)
+    return [row[:nspec].copy(), row[nspec:nspec + 1].copy(), row[nspec + 1:2 * nspec + 1].copy(), row[2 * nspec + 1:].copy()]
+
+
+def trip_numpy(st, z, chi2, tlim, dist_prior, matrix, av_table, nspec=2, steps=200, dist_fit=True, rad_prior=False):
+    """One trip of one chain in NumPy: ``st`` (a ``TripState``) is advanced in place by the draw ``z`` (``ndim``
+    standard normals); ``chi2(row)`` returns the likelihood chi^2 of an in-bounds proposal (what ``msx_opt_step``
+    returns for this chain).  Returns ``(flag, test, proposal)``: flag one of TRIP_IDLE / TRIP_OOB / TRIP_REJECTED /
+    TRIP_ACCEPTED, ``test`` NaN unless evaluated, ``proposal`` the flat row drawn (None for an idle trip)."""
+    cap = 50 * steps
+    ndim = 2 * nspec + 2
+    if st.done:
+        return TRIP_IDLE, np.nan, None
+    if not (st.n < steps and st.total_n < cap):
+        st.done = True
+        return TRIP_IDLE, np.nan, None
+    si = _step_sizes(nspec, st.rad0, st.dist0, st.n > steps / 2)
+    sflat = np.array(si[0] + si[1] + si[2] + si[3], dtype=float)
+    row = st.gi + sflat * np.asarray(z, dtype=float)[:ndim]  # a rounded multiply, then a rounded add
+    var = _groups(row, nspec)
+    if not _in_bounds(var, tlim):
+        st.total_n = _repair_count(var, tlim, st.total_n, cap)
+        return TRIP_OOB, np.nan, row
+    if nspec == 3:
+        while var[2][2] >= var[2][1] or var[2][2] < 0:  # mft6.py:984-985
+            var[2][2] = var[2][1] * 0.9
+        row = np.concatenate(var)
+    st.total_n += 1
+    st.n += 1
+    like = chi2(row)
+    plx, av = float(var[3][0]), float(var[1][0])
+    mu, sg = _av_lookup(av_table, 1.0 / plx)
+    test = like + opt_prior_one(av, mu, sg)
+    if dist_fit:
+        test = test + opt_prior_one(plx, dist_prior[0], dist_prior[1])
+    if rad_prior:
+        mr = staging.isochrone_radius(np.asarray(var[0], dtype=float), matrix)
+        test = test + opt_prior_sum(var[2], [mr[0]] + [m / mr[0] for m in mr[1:]], np.array(si[2]))
+    if test < st.chi:
+        st.gi = row.copy()
+        st.chi = test
+        st.n = steps / 2 + 1 if st.n > steps / 2 else 0
+        return TRIP_ACCEPTED, test, row
+    return TRIP_REJECTED, test, row
+
+
+def _initial_chi(like0, start, dist_prior, matrix, av_table, nspec, dist_fit, rad_prior):
+    """The start point's chi^2 with its prior terms (mft6.py:909-929), as fit_spec_batch forms it."""
+    T, av, rad, plx = list(start[:nspec]), float(start[nspec]), list(start[nspec + 1:2 * nspec + 1]), float(start[2 * nspec + 1])
+    cs = like0
+    if dist_fit:
+        cs = cs + opt_prior_one(plx, dist_prior[0], dist_prior[1])
+    if rad_prior:
+        mr = staging.isochrone_radius(np.array(T), matrix)
+        cs = cs + opt_prior_sum(rad, [mr[0]] + [m / mr[0] for m in mr[1:]], [0.05 * r for r in rad])
+    mu, sg = _av_lookup(av_table, 1.0 / plx)
+    return cs + opt_prior_one(av, mu, sg)
+
+
+def _row_text(g, nspec):
+    ndim = 2 * nspec + 2
+    vals = list(np.ravel(g[0])) + [float(np.ravel(g[1])[0])] + list(np.ravel(g[2])) + [float(np.ravel(g[3])[0])]
+    return ' '.join(str(v) for v in vals[:nspec]) + ' ' + str(float(vals[nspec])) + ' ' + \
+        ' '.join(str(v) for v in vals[nspec + 1:2 * nspec + 1]) + ' ' + str(float(vals[ndim - 1]))
+
+
+def fit_spec_device(engine, starts, tlim, dist_prior, matrix, av_table, nspec=2, steps=200, dist_fit=True,
+                    rad_prior=False, rngs=None, dirname=None, first_index=0, chunk=128, timings=None):
+    """``fit_spec_batch`` with the chains' state machine on the device (``msx_opt_run_*``): the host draws the
+    standard normals of ``chunk`` trips per chain (``rngs[c].standard_normal``: chain c walks exactly the trajectory
+    ``fit_spec_batch`` gives it with the same ``rngs``), queues the chunk -- one evaluation launch per trip, nothing
+    returns in between -- and rebuilds the chains from the records of the evaluated trips.  Same return value and the
+    same ``params{n}.txt`` / ``chisq{n}.txt`` as ``fit_spec_batch``; each chain also carries ``flags`` (TRIP_REJECTED /
+    TRIP_ACCEPTED per evaluated trip) and ``trips`` (its draws).  ``timings`` (a dict) receives the wall seconds of the run's
+    three parts: ``init`` (start points' chi^2, upload), ``run`` (draw, queue, collect) and ``rebuild`` (chains, files).  Walker errors raise what the host loop raises, naming the proposal."""
+    import time
+    from .engine import _raise_for_status
+    t_begin = time.perf_counter()
+    starts = np.atleast_2d(np.asarray(starts, dtype=float))
+    nch = len(starts)
+    ndim = 2 * nspec + 2
+    if rngs is None:
+        rngs = [np.random.default_rng() for _ in range(nch)]
+    chunk = int(chunk)
+    if chunk < 1:
+        raise ValueError('fit_spec_device: chunk must be at least one trip')
+    ctx = engine.ctx
+    like0, status = ctx.opt_init(starts)
+    _raise_for_status(status, starts)
+    chi0 = np.array([_initial_chi(like0[c], starts[c], dist_prior, matrix, av_table, nspec, dist_fit, rad_prior)
+                     for c in range(nch)])
+    iso = None
+    if rad_prior:
+        x, _, lum = staging.sorted_isochrone(np.asarray(matrix))
+        iso = (x, lum)
+    ctx.opt_run_begin(starts, chi0, steps, tlim, dist_fit, rad_prior, dist_prior, av_table, iso, chunk)
+    recs, flgs = [], []
+    t_run = time.perf_counter()
+    try:
+        def draw():
+            z = np.empty((chunk, nch, ndim))
+            for c in range(nch):
+                z[:, c, :] = rngs[c].standard_normal((chunk, ndim))
+            return z
+
+        def collect(slot):
+            rec, fl, live, worst = ctx.opt_run_collect(slot, chunk)
+            if worst > 1:  # above MSX_W_REJECT: the first failed evaluation, in trip order
+                t, c = np.argwhere((fl & 0xff) == TRIP_ERROR)[0]
+                _raise_for_status(np.array([int(fl[t, c]) >> 8]), rec[t, c, :ndim][None, :])
+            recs.append(rec)
+            flgs.append(fl)
+            return live
+
+        # two slots: chunk i + 1 is drawn, uploaded and queued while chunk i runs
+        ctx.opt_run_enqueue(0, draw())
+        slot = 0
+        while True:
+            ctx.opt_run_enqueue(1 - slot, draw())
+            if collect(slot) == 0:
+                break
+            slot = 1 - slot
+    finally:
+        gi, chi, n_end, tot_end = ctx.opt_run_end()
+    t_rebuild = time.perf_counter()
+    rec = np.concatenate(recs)
+    fl = np.concatenate(flgs)
+    out = []
+    for c in range(nch):
+        ev = np.nonzero(fl[:, c] >= TRIP_REJECTED)[0]
+        rows = rec[ev, c, :]  # (one copy per chain; the rows of ``sp`` are views of it, in default_propose's four groups)
+        ch = _Chain()
+        ch.sp = [[starts[c, :nspec].copy(), float(starts[c, nspec]), starts[c, nspec + 1:2 * nspec + 1].copy(),
+                  float(starts[c, 2 * nspec + 1])]] + \
+            [list(g) for g in zip(rows[:, :nspec], rows[:, nspec:nspec + 1], rows[:, nspec + 1:2 * nspec + 1],
+                                  rows[:, 2 * nspec + 1:ndim])]
+        ch.savechi = [chi0[c]] + list(rows[:, ndim])
+        ch.savetest = list(rows[:, ndim + 1])
+        ch.flags = fl[ev, c].tolist()
+        ch.trips = int(np.count_nonzero(fl[:, c] != TRIP_IDLE))  # draws: evaluated or out of bounds
+        ch.gi = ch.sp[-1]
+        ch.chi = ch.savechi[-1]
+        ch.n, ch.total_n = float(n_end[c]), int(tot_end[c])
+        ch.rad0, ch.dist0 = list(starts[c, nspec + 1:2 * nspec + 1]), float(starts[c, 2 * nspec + 1])
+        ch.done = True
+        line = _row_text(ch.gi, nspec) + '\n'
+        if dirname:
+            with open(os.path.join(dirname, 'params{}.txt'.format(first_index + c)), 'a') as f:
+                for row in ch.sp[1:]:
+                    f.write(_row_text(row, nspec) + '\n')
+            with open(os.path.join(dirname, 'chisq{}.txt'.format(first_index + c)), 'a') as f:
+                for k in range(1, len(ch.savechi)):
+                    f.write('{} {}\n'.format(ch.savechi[k], ch.savetest[k - 1]))
+        out.append((line, ch.savechi[-1], ch))
+    if timings is not None:
+        timings.update(init=t_run - t_begin, run=t_rebuild - t_run, rebuild=time.perf_counter() - t_rebuild)
+    return out
+
+
 def optimize_fit(dirname, data, err, specs, nwalk, fr, dist_arr, av, res, ctm, ptm, tmi, tma, vs, matrix, ra, dec,
                  cutoff=2, nspec=2, nstep=200, nburn=20, con=True, models='btsettl', err2=0, dist_fit=True,
-                 rad_prior=False, seed=None, av_table=None, bands=None):
+                 rad_prior=False, seed=None, av_table=None, bands=None, resident=False):
     """``optimize_fit`` (mft6.py:1686-1765): random start points, ``fit_spec`` on each, results appended to
-    ``optimize_res.txt`` / ``optimize_cs.txt``.  All ``nwalk`` chains run as one batch on the GPU."""
+    ``optimize_res.txt`` / ``optimize_cs.txt``.  All ``nwalk`` chains run as one batch on the GPU; with
+    ``resident=True`` their state machine runs there too (``fit_spec_device``: the same chains, no host round trip
+    between proposals)."""
     from . import mft6 as api
     rng = np.random.default_rng(seed)
     t = [float(k.split(', ')[0]) for k in specs.keys() if k != 'wl']
@@ -227,7 +409,7 @@ def optimize_fit(dirname, data, err, specs, nwalk, fr, dist_arr, av, res, ctm, p
     if table is None:
         raise RuntimeError('optimize_fit needs the A_V(distance) table (mcmc_spec_amd.mft6.set_av_prior)')
     rngs = [np.random.default_rng(rng.integers(1 << 62)) for _ in range(nwalk)]
-    res_ = fit_spec_batch(eng, starts, [tmin, tmax], (dist_arr[0], dist_arr[1]), matrix, table, nspec=nspec,
+    res_ = (fit_spec_device if resident else fit_spec_batch)(eng, starts, [tmin, tmax], (dist_arr[0], dist_arr[1]), matrix, table, nspec=nspec,
                           steps=nstep, dist_fit=dist_fit, rad_prior=rad_prior, rngs=rngs, dirname=dirname)
     with open(os.path.join(dirname, 'optimize_res.txt'), 'a') as f:  # mft6.py:1757-1763
         for line, cs, _ in res_:

@@ -6,7 +6,7 @@ the ensembles stay on the GPU, DeviceGroupSampler: no host round trip between ha
 Every target gets its own data spectrum (a binary at its own truth, its own pixel count and noise) on one synthetic grid.
 Target k's chain is the chain a separate EnsembleSampler with target k's seed would walk.
 
-    python examples/fit_target_group.py --targets 4 --nwalkers 32 --nsteps 200 [--device]
+    python examples/fit_target_group.py --targets 4 --nwalkers 32 --nsteps 200 [--device [--rng device]]
 
 With --protocol DIR the targets are fitted the way the reference's driver fits one (run_group_protocol: burn-in, then
 production with every target's own convergence check every --nthin iterations; a converged target stops there) and
@@ -29,10 +29,15 @@ def main():
     ap.add_argument('--nsteps', type=int, default=200)
     ap.add_argument('--seed', type=int, default=1)
     ap.add_argument('--device', action='store_true', help='keep the ensembles on the GPU (DeviceGroupSampler)')
+    ap.add_argument('--rng', choices=('host', 'device'), default='host',
+                    help="with --device: who draws the stretch move's randomness -- the host's generators (default), or the GPU "
+                         "itself, one launch per chunk and nothing uploaded (another stream: other chains, same posterior)")
     ap.add_argument('--protocol', default=None, metavar='DIR', help="run the reference's driver per target (run_group_protocol)")
     ap.add_argument('--nburn', type=int, default=100)
     ap.add_argument('--nthin', type=int, default=50)
     args = ap.parse_args()
+    if args.rng == 'device' and not args.device:
+        ap.error('--rng device needs --device (the device draws for the resident sampler)')
 
     from scipy.interpolate import interp1d
     from mcmc_spec_amd import bands, synth
@@ -78,7 +83,7 @@ def main():
     p0s = [truths[k] + 1e-3 * np.abs(truths[k]) * rng.normal(size=(args.nwalkers, 6)) for k in range(args.targets)]
     seeds = [args.seed + k for k in range(args.targets)]
     if args.device:
-        sampler = DeviceGroupSampler([args.nwalkers] * args.targets, 6, group, seeds=seeds,
+        sampler = DeviceGroupSampler([args.nwalkers] * args.targets, 6, group, seeds=seeds, rng=args.rng,
                                      autocorr='device' if args.protocol else 'host')
     else:
         sampler = GroupSampler([args.nwalkers] * args.targets, 6, group.logposterior, seeds=seeds)

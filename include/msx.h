@@ -452,6 +452,15 @@ int msx_group_sampler_begin(msx_group *group, int32_t mode, const int64_t *count
  * msx_group_sampler_end is accepted.                                                                                   */
 int msx_group_sampler_enqueue(msx_group *group, int32_t slot, int64_t nsteps, const int32_t *sidx, const int32_t *cidx,
                               const int32_t *partner, const double *zz, const double *zfac, const double *logu);
+/* the same chunk with its randomness DRAWN ON THE DEVICE: one launch of the counter-based generator (msx_sampler_draw's)
+ * on the run's stream ahead of the chunk's half-steps, nothing packed or uploaded.  Member m draws from seeds[m] (seeds
+ * [k]) with its own counts[m]: exactly the numbers msx_sampler_draw(seeds[m], a, first_iter, nsteps, counts[m], ndim) gives
+ * that target alone, so member m's chain is the one its context walks fed that stream.  first_iter is the ABSOLUTE iteration
+ * of the chunk's first step -- the caller's to carry from chunk to chunk and from run to run (msx_group_sampler_begin starts
+ * no stream over).  seeds NULL, a not > 1, first_iter < 0 or a member of more than 4096 walkers (the generator's sort):
+ * MSX_ERR_INVALID, nothing queued.  Otherwise as msx_group_sampler_enqueue, with which it may alternate within a run.   */
+int msx_group_sampler_enqueue_drawn(msx_group *group, int32_t slot, int64_t nsteps, const uint64_t *seeds /* [k] */, double a,
+                                    int64_t first_iter);
 /* waits for the chunk in `slot`: chain_out [nsteps][sum counts][ndim], logp_out [nsteps][sum counts], naccept [sum counts]
  * (cumulative over the run), worst_status [k] (the worst walker status of each member's walkers in the chunk)          */
 int msx_group_sampler_collect(msx_group *group, int32_t slot, double *chain_out, double *logp_out, int64_t *naccept,

@@ -154,6 +154,7 @@ def load():
         'msx_group_sampler_begin': (C.c_int, [vp, C.c_int32, _ip, C.c_int32, C.c_int64, _dp, _dp, _ip]),
         'msx_group_sampler_enqueue': (C.c_int, [vp, C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                                 C.POINTER(C.c_int32), _dp, _dp, _dp]),
+        'msx_group_sampler_enqueue_drawn': (C.c_int, [vp, C.c_int32, C.c_int64, C.POINTER(C.c_uint64), C.c_double, C.c_int64]),
         'msx_group_sampler_collect': (C.c_int, [vp, C.c_int32, _dp, _dp, _ip, C.POINTER(C.c_int32)]),
         'msx_group_sampler_end': (C.c_int, [vp, _dp, _dp]),
         'msx_series_create': (C.c_int, [vp, C.c_int64, C.c_int32, C.c_int32, _ip, C.c_int64, C.POINTER(vp)]),
@@ -185,7 +186,7 @@ EXPORTED = ['msx_create', 'msx_destroy', 'msx_last_error', 'msx_device_info', 'm
             'msx_stream_copy_gbps', 'msx_bytes_per_eval', 'msx_launch_info', 'msx_last_form', 'msx_test_hook', 'msx_pair_stats', 'msx_sampler_overlapped', 'msx_sampler_policy',
             'msx_group_create', 'msx_group_destroy', 'msx_group_last_error', 'msx_group_logprob_batch',
             'msx_group_logprob_batch_dev', 'msx_group_launch_info', 'msx_group_sampler_begin', 'msx_group_sampler_enqueue',
-            'msx_group_sampler_collect', 'msx_group_sampler_end',
+            'msx_group_sampler_enqueue_drawn', 'msx_group_sampler_collect', 'msx_group_sampler_end',
             'msx_series_create', 'msx_series_destroy', 'msx_series_last_error', 'msx_series_rows', 'msx_sampler_attach_series',
             'msx_group_sampler_attach_series', 'msx_series_append', 'msx_series_read', 'msx_series_acf']
 
@@ -671,6 +672,16 @@ class Group:
     def sampler_enqueue(self, slot, sidx, cidx, partner, zz, zfac, logu):
         """Queue one chunk: arrays (nsteps, 2, sum(counts)/2), the members' active halves side by side, indices member-local."""
         return _sampler_enqueue(self, self.lib.msx_group_sampler_enqueue, 'sum(counts)/2', slot, (sidx, cidx, partner, zz, zfac, logu))
+
+    def sampler_enqueue_drawn(self, slot, nsteps, seeds, a, first_iter):
+        """Queue one chunk whose randomness the device draws itself (msx_group_sampler_enqueue_drawn): member m from
+        ``seeds[m]``, the chunk's first step the ABSOLUTE iteration ``first_iter`` of every member's stream."""
+        seeds = np.ascontiguousarray([int(s) & 0xffffffffffffffff for s in seeds], dtype=np.uint64)
+        if seeds.shape != (self.k,):
+            raise ValueError('one seed per member ({} given, {} members)'.format(seeds.size, self.k))
+        self.check(self.lib.msx_group_sampler_enqueue_drawn(self.h, int(slot), int(nsteps), seeds.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                            float(a), int(first_iter)))
+        return int(nsteps)
 
     def sampler_collect(self, slot, nsteps):
         """Wait for the chunk in `slot`: (chain [nsteps][n][ndim], logp [nsteps][n], naccept [n], worst [k])."""

@@ -372,17 +372,19 @@ __host__ __device__ inline double counter_uniform(unsigned long long seed, unsig
 }
 constexpr int kDrawMaxWalkers = 4096;  // (key, index) pairs of one iteration sorted in LDS: 48 KB
 constexpr int kDrawThreads = 256;
+// One iteration `it` of one ensemble of nw walkers keyed by `seed`, by the whole workgroup (kDrawThreads threads): the keys,
+// the LDS sort, and per half-step h and position j the entry o0 + h * hstride + j of the chunk's arrays.  sidx and cidx
+// stay the ensemble's own indices; the resolved partner and the records' si / ci -- what the kernels dereference -- are
+// woff + the ensemble's own index (a target group's member: its offset in the group's ensemble), as run_pack leaves them.
 // resolve != 0: `partner` receives cidx[partner] (the ensemble index of the complementary walker: what the kernels read);
 // 0: the raw index into the complementary half (what the host loop consumes)
-__global__ void __launch_bounds__(kDrawThreads)
-sampler_draw_kernel(unsigned long long seed, double a, int64_t first_iter, int64_t nw, int32_t ndim, int32_t resolve, int32_t overlap,
-                    int32_t *__restrict__ sidx, int32_t *__restrict__ cidx, int32_t *__restrict__ partner, double *__restrict__ zz,
-                    double *__restrict__ zfac, double *__restrict__ logu, SmpRec *__restrict__ rec) {
+__device__ __forceinline__ void draw_iteration(unsigned long long seed, double a, unsigned long long it, int nw, int32_t ndim, int32_t resolve,
+                                               int32_t overlap, int32_t woff, int64_t o0, int64_t hstride, int32_t *__restrict__ sidx,
+                                               int32_t *__restrict__ cidx, int32_t *__restrict__ partner, double *__restrict__ zz,
+                                               double *__restrict__ zfac, double *__restrict__ logu, SmpRec *__restrict__ rec) {
     __shared__ unsigned long long key[kDrawMaxWalkers];
     __shared__ int32_t idx[kDrawMaxWalkers];
-    const int64_t st = blockIdx.x;  // iteration of the chunk
-    const unsigned long long it = (unsigned long long)(first_iter + st);
-    const int ns = (int)(nw / 2);
+    const int ns = nw / 2;
     int npad = 1;
     while (npad < nw) npad <<= 1;
     for (int i = threadIdx.x; i < npad; i += kDrawThreads) {
@@ -407,7 +409,6 @@ sampler_draw_kernel(unsigned long long seed, double a, int64_t first_iter, int64
         }
     }
     // the two half-steps of this iteration
-    const int64_t base = st * 2 * ns;
     for (int t = threadIdx.x; t < 2 * ns; t += kDrawThreads) {
 #pragma clang fp contract(off)
         const int h = t / ns, j = t - h * ns;
@@ -420,21 +421,51 @@ sampler_draw_kernel(unsigned long long seed, double a, int64_t first_iter, int64
         const double z = (t1 * t1) / a;                         // emcee: ((a - 1) u + 1)^2 / a
         int pj = (int)(up * (double)ns);
         pj = pj < ns - 1 ? pj : ns - 1;
-        const int64_t o = base + t;
+        const int64_t o = o0 + h * hstride + j;
         sidx[o] = s_w;
         cidx[o] = comp[j];
-        partner[o] = resolve ? comp[pj] : pj;
+        partner[o] = resolve ? woff + comp[pj] : pj;
         zz[o] = z;
         zfac[o] = ((double)ndim - 1.0) * log(z);
         logu[o] = log(ua);                                      // (u = 0: -inf, accepted by nothing -- like log(random()))
         if (rec) {
             SmpRec r;
-            r.si = s_w; r.ci = comp[pj]; r.zz = z;
+            r.si = woff + s_w; r.ci = woff + comp[pj]; r.zz = z;
             r.ver_own = overlap ? (uint32_t)it : 0u;
             r.ver_partner = overlap ? (uint32_t)(it + (unsigned long long)h) : 0u;
             rec[o] = r;
         }
     }
+}
+
+// one workgroup per iteration of the chunk; the arrays [nsteps][2][nw / 2]
+__global__ void __launch_bounds__(kDrawThreads)
+sampler_draw_kernel(unsigned long long seed, double a, int64_t first_iter, int64_t nw, int32_t ndim, int32_t resolve, int32_t overlap,
+                    int32_t *__restrict__ sidx, int32_t *__restrict__ cidx, int32_t *__restrict__ partner, double *__restrict__ zz,
+                    double *__restrict__ zfac, double *__restrict__ logu, SmpRec *__restrict__ rec) {
+    const int64_t st = blockIdx.x;  // iteration of the chunk
+    const int64_t ns = nw / 2;
+    draw_iteration(seed, a, (unsigned long long)(first_iter + st), (int)nw, ndim, resolve, overlap, 0, st * 2 * ns, ns, sidx, cidx, partner,
+                   zz, zfac, logu, rec);
+}
+
+// The same for a target group's run (msx_group_sampler_enqueue_drawn): grid (nsteps, k), one workgroup per iteration of the
+// chunk and MEMBER.  Member m draws from its own seed with its own walker count -- the numbers sampler_draw_kernel gives
+// that target alone -- and writes them where the host-fed chunk carries them: entry astart[m] + j of each half-step's
+// ns_total, sidx / cidx member-local, the resolved partner and the records' si / ci the group's (off[m] + the member's own),
+// versions 0 (plain launches).
+struct GroupDrawTable {  // by value: a drawn chunk uploads nothing
+    unsigned long long seed[MSX_MAX_GROUP];
+    int32_t nw[MSX_MAX_GROUP], off[MSX_MAX_GROUP], astart[MSX_MAX_GROUP];
+};
+__global__ void __launch_bounds__(kDrawThreads)
+group_draw_kernel(GroupDrawTable T, double a, int64_t first_iter, int32_t ndim, int64_t ns_total, int32_t *__restrict__ sidx,
+                  int32_t *__restrict__ cidx, int32_t *__restrict__ partner, double *__restrict__ zz, double *__restrict__ zfac,
+                  double *__restrict__ logu, SmpRec *__restrict__ rec) {
+    const int64_t st = blockIdx.x;
+    const int m = blockIdx.y;
+    draw_iteration(T.seed[m], a, (unsigned long long)(first_iter + st), T.nw[m], ndim, 1, 0, T.off[m], st * 2 * ns_total + T.astart[m],
+                   ns_total, sidx, cidx, partner, zz, zfac, logu, rec);
 }
 
 }  // namespace

@@ -3249,29 +3249,58 @@ int msx_group_sampler_begin(msx_group *g, int32_t mode, const int64_t *counts, i
     return MSX_OK;
 }
 
-int msx_group_sampler_enqueue(msx_group *g, int32_t slot, int64_t nsteps, const int32_t *sidx, const int32_t *cidx,
-                              const int32_t *partner, const double *zz, const double *zfac, const double *logu) {
+// (draw != nullptr: the chunk's randomness is drawn on the device -- ONE group_draw_kernel launch on the run's stream, ahead
+// of the chunk's half-steps, member m keyed by draw->seeds[m] and the absolute iteration numbers from draw->first_iter --
+// instead of coming from the host's arrays: nothing is packed, nothing uploaded)
+struct GroupDeviceDraw { const uint64_t *seeds; double a; int64_t first_iter; };
+static int group_sampler_enqueue(msx_group *g, const char *who, int32_t slot, int64_t nsteps, const int32_t *sidx, const int32_t *cidx,
+                                 const int32_t *partner, const double *zz, const double *zfac, const double *logu,
+                                 const GroupDeviceDraw *draw) {
     if (!g) return MSX_ERR_INVALID;
+    const std::string w(who);
     GroupRun *gr = g->run;
-    if (int rc = run_enqueue_check(&g->err, gr ? gr->r : nullptr, "msx_group_sampler_enqueue", "msx_group_sampler_begin",
-                                   "msx_group_sampler_end", slot, nsteps, sidx && cidx && partner && zz && zfac && logu))
+    if (int rc = run_enqueue_check(&g->err, gr ? gr->r : nullptr, who, "msx_group_sampler_begin", "msx_group_sampler_end", slot, nsteps,
+                                   draw ? draw->seeds != nullptr : (sidx && cidx && partner && zz && zfac && logu)))
         return rc;
     SamplerRun *r = gr->r;
+    if (draw) {
+        if (!(draw->a > 1.0) || draw->first_iter < 0)
+            return fail(g, MSX_ERR_INVALID, w + ": the device generator takes a stretch scale a > 1 and a first iteration >= 0");
+        for (size_t m = 0; m < r->m_nw.size(); ++m)
+            if (r->m_nw[m] > kDrawMaxWalkers)
+                return fail(g, MSX_ERR_INVALID, w + ": member " + std::to_string(m) + " has " + std::to_string(r->m_nw[m]) +
+                                                    " walkers; the device generator takes up to 4096 per member");
+    }
     // a member restaged or destroyed since begin: the snapshots point at tables that are gone -- the run is over
     int64_t total = 0;
     std::vector<int64_t> counts(r->m_nw);
-    if (int rc = group_check(g, "msx_group_sampler_enqueue", r->mode, counts.data(), r->ndim, &total)) {
+    if (int rc = group_check(g, who, r->mode, counts.data(), r->ndim, &total)) {
         r->failed = true;
         return rc;
     }
     SamplerRun::Slot &sl = r->slot[slot];
     HIP_TRY(g, hipSetDevice(g->device));
-    if (const char *why = run_pack(r, sl, nsteps, sidx, cidx, partner, zz, zfac, logu))
-        return fail(g, MSX_ERR_INVALID, std::string("msx_group_sampler_enqueue: ") + why);
+    if (!draw)
+        if (const char *why = run_pack(r, sl, nsteps, sidx, cidx, partner, zz, zfac, logu)) return fail(g, MSX_ERR_INVALID, w + ": " + why);
     ChunkPtrs cp;
     run_chunk_ptrs(r, sl, nsteps, &cp);
     const int k = (int)g->members.size();
-    hipError_t e = run_upload(r, sl, nsteps, gr->stream);
+    hipError_t e = hipSuccess;
+    if (draw) {
+        GroupDrawTable T;
+        memset(&T, 0, sizeof(T));
+        for (int m = 0; m < k; ++m) {
+            T.seed[m] = (unsigned long long)draw->seeds[m];
+            T.nw[m] = (int32_t)r->m_nw[(size_t)m]; T.off[m] = (int32_t)r->m_off[(size_t)m]; T.astart[m] = (int32_t)r->m_astart[(size_t)m];
+        }
+        // (the slot was collected: no launch still reads its arrays, and the run's stream orders this one before the half-steps)
+        hipLaunchKernelGGL(group_draw_kernel, dim3((unsigned)nsteps, (unsigned)k), dim3(kDrawThreads), 0, gr->stream, T, draw->a,
+                           draw->first_iter, (int32_t)r->ndim, r->ns, cp.d_sidx, cp.d_cidx, cp.d_partner, cp.d_zz, cp.d_zfac, cp.d_logu,
+                           const_cast<SmpRec *>(cp.d_rec));
+        e = hipGetLastError();
+    } else {
+        e = run_upload(r, sl, nsteps, gr->stream);
+    }
     if (e == hipSuccess) e = hipMemsetAsync(cp.d_worst, 0, sizeof(int32_t) * (size_t)k, gr->stream);
     // the kernel's arguments, in its own order; per half-step only the snapshot set and the records move
     const double *a_theta = r->d_coords;
@@ -3292,10 +3321,20 @@ int msx_group_sampler_enqueue(msx_group *g, int32_t slot, int64_t nsteps, const 
     if (e == hipSuccess) e = run_finish(r, slot, nsteps, cp, gr->stream);
     if (e != hipSuccess) {
         r->failed = true;  // some of the chunk's half-steps may be queued: only msx_group_sampler_end from here on
-        return fail(g, MSX_ERR_HIP, std::string("msx_group_sampler_enqueue: ") + hipGetErrorString(e));
+        return fail(g, MSX_ERR_HIP, w + ": " + hipGetErrorString(e));
     }
     r->steps_done += nsteps;
     return MSX_OK;
+}
+
+int msx_group_sampler_enqueue(msx_group *g, int32_t slot, int64_t nsteps, const int32_t *sidx, const int32_t *cidx,
+                              const int32_t *partner, const double *zz, const double *zfac, const double *logu) {
+    return group_sampler_enqueue(g, "msx_group_sampler_enqueue", slot, nsteps, sidx, cidx, partner, zz, zfac, logu, nullptr);
+}
+
+int msx_group_sampler_enqueue_drawn(msx_group *g, int32_t slot, int64_t nsteps, const uint64_t *seeds, double a, int64_t first_iter) {
+    const GroupDeviceDraw dd = {seeds, a, first_iter};
+    return group_sampler_enqueue(g, "msx_group_sampler_enqueue_drawn", slot, nsteps, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &dd);
 }
 
 int msx_group_sampler_collect(msx_group *g, int32_t slot, double *chain_out, double *logp_out, int64_t *naccept,

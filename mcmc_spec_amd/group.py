@@ -91,17 +91,23 @@ class GroupSampler:
     """K stretch-move ensembles stepped in lock-step, one batched call per half-step.
 
     ``nwalkers`` and ``seeds``: one entry per target.  ``log_prob_fn(list_of_thetas) -> list_of_logp`` evaluates K arrays
-    ``(n_k, ndim)`` at once (``TargetGroup.logposterior``, or any host function for tests)."""
+    ``(n_k, ndim)`` at once (``TargetGroup.logposterior``, or any host function for tests).  ``draws`` (optional): one
+    ``draws(first_iteration, m)`` callable per target, handed to the target's ``EnsembleSampler(draws=...)`` in place of its
+    generators -- with ``ctx.sampler_draw`` of target k's device seed, the host twin of ``DeviceGroupSampler(rng='device')``."""
 
-    def __init__(self, nwalkers, ndim, log_prob_fn, a=2.0, seeds=None):
+    def __init__(self, nwalkers, ndim, log_prob_fn, a=2.0, seeds=None, draws=None):
         nwalkers = [int(n) for n in nwalkers]
         seeds = [None] * len(nwalkers) if seeds is None else list(seeds)
         if len(seeds) != len(nwalkers):
             raise ValueError('one seed per target')
+        draws = [None] * len(nwalkers) if draws is None else list(draws)
+        if len(draws) != len(nwalkers):
+            raise ValueError('one draws callable per target')
         self.ndim = int(ndim)
         self.log_prob_fn = log_prob_fn
         # one EnsembleSampler per target holds its generators and its bookkeeping; its own log_prob_fn is never called
-        self.samplers = [EnsembleSampler(n, ndim, None, a=a, vectorize=True, seed=s) for n, s in zip(nwalkers, seeds)]
+        self.samplers = [EnsembleSampler(n, ndim, None, a=a, vectorize=True, seed=s, draws=d)
+                         for n, s, d in zip(nwalkers, seeds, draws)]
 
     @property
     def nwalkers(self):
@@ -132,7 +138,7 @@ class GroupSampler:
 
     def _stretch_step(self, coords, logp):
         """One iteration of every target: the stretch move's half-steps (_propose, _accept), the K targets' evaluations batched."""
-        draws = [s._draw_split(1) + s._draw_moves(1) for s in self.samplers]
+        draws = [s._draw_steps(1) for s in self.samplers]
         accepted = [np.zeros(s.nwalkers, dtype=bool) for s in self.samplers]
         for h in (0, 1):
             qs = [_propose(coords[k], d, h) for k, d in enumerate(draws)]
@@ -206,22 +212,54 @@ class GroupSampler:
         return np.array([s.get_autocorr_time(**kw) for s in self.samplers])
 
 
+def _device_seed(seed):
+    """The device generator's 64-bit key for one target's ``seed``, as ``DeviceEnsembleSampler.device_seed``: an int as
+    itself (masked to 64 bits), None or a SeedSequence through ``generate_state``."""
+    if seed is None or isinstance(seed, np.random.SeedSequence):
+        ss = seed if seed is not None else np.random.SeedSequence(None)
+        return int(ss.generate_state(1, dtype=np.uint64)[0]) & 0xffffffffffffffff
+    return int(seed) & 0xffffffffffffffff
+
+
 class DeviceGroupSampler(GroupSampler):
     """``GroupSampler`` with the K ensembles resident in HBM (``msx_group_sampler_*``, include/msx.h): ``chunk`` iterations
     are queued on the GPU back to back, ONE launch of the group kernel per half-step over the active half of every
-    target's ensemble, and only the chains come back.  Each target's randomness is drawn on the host by its own
-    ``EnsembleSampler``'s generators, the calls ``GroupSampler`` makes, so target k's chain is bit for bit the chain of
-    ``GroupSampler`` and of ``EnsembleSampler(nwalkers[k], ndim, f_k, vectorize=True, seed=seeds[k])``.
+    target's ensemble, and only the chains come back.
+
+    ``rng='host'`` (default): each target's randomness is drawn on the host by its own ``EnsembleSampler``'s generators, the
+    calls ``GroupSampler`` makes, so target k's chain is bit for bit the chain of ``GroupSampler`` and of
+    ``EnsembleSampler(nwalkers[k], ndim, f_k, vectorize=True, seed=seeds[k])``.  ``rng='device'``: the library draws every
+    chunk on the GPU (``msx_group_sampler_enqueue_drawn``: one launch per chunk, nothing drawn, concatenated or uploaded by
+    the host), target k from ``device_seeds[k]`` -- ``seeds[k]`` as ``DeviceEnsembleSampler.device_seed`` derives it -- and
+    the ABSOLUTE iteration number, which every chunk queued advances and ``reset()`` leaves alone
+    (``self.samplers[k]._drawn``, as ``EnsembleSampler(draws=...)`` counts on the host).  Target k's chain is then the one
+    ``EnsembleSampler(draws=lambda i, m: ctx.sampler_draw(device_seeds[k], a, i, m, nwalkers[k], ndim))`` walks, and
+    ``GroupSampler(draws=[...])`` with those callables.  Up to 4096 walkers per target.
 
     ``group`` is a ``TargetGroup``; ``mode`` ``'logposterior'`` or ``'loglikelihood'``.  Drawing chunk i+1 overlaps chunk i
     on the GPU (``DeviceEnsembleSampler``'s chunk pipeline, ``sampler._pump``); consecutive ``sample`` calls continue the
     generators.  A walker error raises what ``TargetGroup`` raises, prefixed ``target k:``; the run ends there and the
-    chain up to the last collected chunk stands."""
+    chain up to the last collected chunk stands.
 
-    def __init__(self, nwalkers, ndim, group, mode='logposterior', a=2.0, seeds=None, chunk=64, autocorr='host'):
+    With ``rng='device'`` the stream position counts iterations QUEUED, not consumed: a ``sample()`` loop left early (a
+    ``break``, as ``run_group_protocol`` does once every target has converged, or a walker error) leaves ``_drawn`` past the
+    last iteration yielded -- by the chunks already queued -- while the host twin ``GroupSampler(draws=...)`` stops at the
+    last iteration it stepped.  Both remain valid chains; a later run on the same sampler then no longer matches the twin
+    number for number."""
+
+    DEVICE_RNG_MAX_WALKERS = 4096   # csrc/logprob_kernel.h, kDrawMaxWalkers: one ensemble's (key, index) sort in LDS
+
+    def __init__(self, nwalkers, ndim, group, mode='logposterior', a=2.0, seeds=None, chunk=64, autocorr='host', rng='host'):
         if mode not in ('logposterior', 'loglikelihood'):
             raise ValueError("mode must be 'logposterior' or 'loglikelihood'")
+        if rng not in ('host', 'device'):
+            raise ValueError("rng must be 'host' or 'device'")
         nwalkers = [int(n) for n in nwalkers]
+        if rng == 'device':
+            for k, n in enumerate(nwalkers):
+                if n > self.DEVICE_RNG_MAX_WALKERS:
+                    raise ValueError("rng='device' takes up to {} walkers per target (target {} has {})".format(
+                        self.DEVICE_RNG_MAX_WALKERS, k, n))
         if len(nwalkers) != len(group):
             raise ValueError('one walker count per target ({} given, {} targets)'.format(len(nwalkers), len(group)))
         if int(chunk) < 1:
@@ -234,6 +272,9 @@ class DeviceGroupSampler(GroupSampler):
             raise ValueError("autocorr must be 'host' or 'device'")
         super().__init__(nwalkers, ndim, fn, a=a, seeds=seeds)
         self.chunk = int(chunk)
+        self.rng_mode = rng
+        seeds = [None] * len(nwalkers) if seeds is None else list(seeds)
+        self.device_seeds = [_device_seed(s) for s in seeds] if rng == 'device' else None
         # autocorr='device': the targets' stored chains are kept on the device too (one _lib.Series of K members, appended
         # by every sample(store=True) run) and get_autocorr_time computes all targets' autocorrelation there, one
         # msx_series_acf call per lag tile; 'host': GroupSampler's, per target
@@ -248,12 +289,21 @@ class DeviceGroupSampler(GroupSampler):
         moves = [s._draw_moves(m) for s in self.samplers]
         return [np.concatenate(x, axis=2) for x in zip(*moves)]
 
-    def sample(self, initial_states, iterations=1, store=True):
-        """``initial_states``: one State or coordinate array ``(nwalkers[k], ndim)`` per target.  Yields a list of K States
-        per iteration."""
-        coords, logp = self._initial(initial_states)
-        if int(iterations) <= 0:
-            return
+    def _enqueue(self, slot, m, arrays):
+        grp = self.group.group
+        if arrays is not None:
+            return grp.sampler_enqueue(slot, *arrays)
+        # the device draws: every target's stream at its absolute iteration (equal for all targets), which only a queued
+        # chunk advances
+        grp.sampler_enqueue_drawn(slot, m, self.device_seeds, self.samplers[0].a, self.samplers[0]._drawn)
+        for s in self.samplers:
+            s._drawn += m
+        return m
+
+    def _chunks(self, coords, logp, iterations, store):
+        """One run of ``iterations`` over the group: yields ``(m, chain, logp_chain, off)`` per collected chunk of m
+        iterations -- rows [m][sum nwalkers] with target k's walkers at ``off[k]:off[k + 1]`` -- after raising the chunk's
+        walker errors and setting every target's acceptance counts."""
         counts = self.nwalkers
         off = np.concatenate([[0], np.cumsum(counts)]).astype(int)
         grp = self.group.group
@@ -265,9 +315,8 @@ class DeviceGroupSampler(GroupSampler):
             except Exception:
                 grp.sampler_end()
                 raise
-        with closing(_pump(iterations, self.chunk, (self._draw_split_all, self._draw_moves_all),
-                           lambda slot, m, arrays: grp.sampler_enqueue(slot, *arrays), grp.sampler_collect,
-                           grp.sampler_end)) as chunks:
+        draws = None if self.rng_mode == 'device' else (self._draw_split_all, self._draw_moves_all)
+        with closing(_pump(iterations, self.chunk, draws, self._enqueue, grp.sampler_collect, grp.sampler_end)) as chunks:
             for mm, (chain, lpc, nacc, worst) in chunks:
                 for k in np.nonzero(worst > _lib.W_REJECT)[0]:
                     try:
@@ -276,6 +325,16 @@ class DeviceGroupSampler(GroupSampler):
                         raise type(e)('target {}: {}'.format(k, e.args[0] if e.args else e)) from None
                 for k, s in enumerate(self.samplers):
                     s._accepted = base_acc[k] + nacc[off[k]:off[k + 1]]
+                yield mm, chain, lpc, off
+
+    def sample(self, initial_states, iterations=1, store=True):
+        """``initial_states``: one State or coordinate array ``(nwalkers[k], ndim)`` per target.  Yields a list of K States
+        per iteration."""
+        coords, logp = self._initial(initial_states)
+        if int(iterations) <= 0:
+            return
+        with closing(self._chunks(coords, logp, iterations, store)) as chunks:
+            for mm, chain, lpc, off in chunks:
                 for i in range(mm):
                     states = []
                     for k, s in enumerate(self.samplers):
@@ -287,6 +346,31 @@ class DeviceGroupSampler(GroupSampler):
                         s._last = State(c, lp)
                         states.append(s._last)
                     yield states
+
+    def run_mcmc(self, initial_states, nsteps, store=True):
+        """``sample`` consumed by whole chunks: each chunk's rows go to the targets' chains at once and the K States are
+        built for the last iteration only (building K States per iteration is host time the GPU waits for: DESIGN.md
+        section 11.2).  Chains, log-probabilities, acceptance counts and the returned States are those of
+        ``for states in sample(initial_states, nsteps): pass``, bit for bit."""
+        coords, logp = self._initial(initial_states)
+        if int(nsteps) <= 0:
+            return None
+        last = None
+        try:
+            with closing(self._chunks(coords, logp, nsteps, store)) as chunks:
+                for mm, chain, lpc, off in chunks:
+                    for k, s in enumerate(self.samplers):
+                        s.iteration += mm
+                        if store:
+                            s._chain.extend(chain[:, off[k]:off[k + 1]])
+                            s._logp.extend(lpc[:, off[k]:off[k + 1]])
+                    last = (chain[mm - 1], lpc[mm - 1], off)
+        finally:   # (also when a chunk raised: the last collected iteration is every target's last sample, as in sample())
+            if last is not None:
+                c, lp, off = last
+                for k, s in enumerate(self.samplers):
+                    s._last = State(c[off[k]:off[k + 1]], lp[off[k]:off[k + 1]])
+        return [s._last for s in self.samplers]
 
     def get_autocorr_time(self, k=None, quiet=False, c=5.0, tol=50.0, discard=0, thin=1):
         """GroupSampler.get_autocorr_time; with autocorr='device' every target's from the chains on the device, ONE

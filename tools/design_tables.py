@@ -3,9 +3,11 @@
 typed twice).
 
     python tools/design_tables.py            # prints the block
-    python tools/design_tables.py --write    # rewrites the block between the markers in DESIGN.md
+    python tools/design_tables.py --write    # rewrites the blocks between the markers in DESIGN.md
+    python tools/design_tables.py --group-rng  # ... and prints section 11.2's block too
 
-tests/test_design_tables.py checks that DESIGN.md holds exactly what this prints.
+tests/test_design_tables.py checks that DESIGN.md holds exactly the first block (what this prints without flags);
+tests/test_group_rng_abi.py checks section 11.2's block (--group-rng) and that its no-regression condition holds.
 """
 import csv
 import glob
@@ -17,6 +19,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PROF = os.path.join(ROOT, 'profiles')
 TAG = 'r4'
 BEGIN, END = '<!-- BEGIN GENERATED TABLES (tools/design_tables.py) -->', '<!-- END GENERATED TABLES -->'
+# section 11.2's tables (build_group_rng), a block of their own
+GROUP_RNG_BEGIN, GROUP_RNG_END = '<!-- BEGIN GENERATED GROUP RNG TABLES (tools/design_tables.py) -->', '<!-- END GENERATED GROUP RNG TABLES -->'
 
 
 def jload(name):
@@ -167,15 +171,53 @@ def build():
     return '\n'.join(o).rstrip() + '\n'
 
 
+def build_group_rng():
+    """Section 11.2: host-drawn against device-drawn DeviceGroupSampler (profiles/group_chains_rng.jsonl, written by
+    tools/group_chain_bench.py), and the host's own time per chunk by phase."""
+    rows = [r for r in jlines('group_chains_rng.jsonl') if r.get('what') == 'chain_us_per_iter' and 'device_rng' in r]
+    if not rows:
+        return ''
+    o = []
+
+    def span(r, d):
+        v = r[d + '_rounds']
+        return '%s (%s … %s)' % (f(r[d], 1), f(min(v), 1), f(max(v), 1))
+    o.append('| targets × walkers | host-drawn, µs/iter: median of %d (min … max) | device-drawn, µs/iter | device-drawn − host-drawn | '
+             'host-drawn spread (max − min) | no regression |' % len(rows[0]['device_rounds']))
+    o.append('|---|---|---|---|---|---|')
+    for r in rows:
+        o.append('| %d × %d | %s | %s | %s | %s | %s |' % (r['targets'], r['walkers_per_target'], span(r, 'device'), span(r, 'device_rng'),
+                                                        f(r['device_rng'] - r['device'], 1), f(r['device_spread'], 1),
+                                                        'holds' if r['no_regression'] else '**fails**'))
+    o.append('')
+    o.append('Host thread, ms per run of %d iterations (medians; host-drawn chunks ramp up from 8, so a run has more of them):' % rows[0]['iters'])
+    o.append('')
+    o.append('| targets × walkers | randomness | chunks | construct | begin | waiting for draws | enqueue | collect | chain rows, States, pump | end | '
+             '`get_chain` | per chunk, µs: draws / enqueue / collect / rows |')
+    o.append('|---|---|---|---|---|---|---|---|---|---|---|---|')
+    for r in rows:
+        for d, lab in (('device', 'host'), ('device_rng', 'device')):
+            h, c = r[d + '_host_ms_per_run'], r[d + '_host_us_per_chunk']
+            o.append('| %d × %d | %s | %d | %s | %s | %s | %s | %s | %s | %s | %s | %s / %s / %s / %s |' % (
+                r['targets'], r['walkers_per_target'], lab, r[d + '_chunks'], f(h['construct'], 2), f(h['begin'], 2), f(h['draw_wait'], 2),
+                f(h['enqueue'], 2), f(h['collect'], 2), f(h['states'], 2), f(h['end'], 2), f(h['get_chain'], 2),
+                f(c['draw_wait'], 0), f(c['enqueue'], 0), f(c['collect'], 0), f(c['states'], 0)))
+    return '\n'.join(o).rstrip() + '\n'
+
+
 def main():
-    block = build()
+    blocks = [(BEGIN, END, build()), (GROUP_RNG_BEGIN, GROUP_RNG_END, build_group_rng())]
     if '--write' in sys.argv:
         p = os.path.join(ROOT, 'DESIGN.md')
         s = open(p).read()
-        a, b = s.index(BEGIN) + len(BEGIN), s.index(END)
-        open(p, 'w').write(s[:a] + '\n' + block + s[b:])
+        for begin, end, block in blocks:
+            a, b = s.index(begin) + len(begin), s.index(end)
+            s = s[:a] + '\n' + block + s[b:]
+        open(p, 'w').write(s)
     else:
-        sys.stdout.write(block)
+        sys.stdout.write(blocks[0][2])
+        if '--group-rng' in sys.argv:
+            sys.stdout.write(blocks[1][2])
 
 
 if __name__ == '__main__':

@@ -97,6 +97,10 @@ def main():
     med = np.median(samples, axis=0)
     print('truth   :', truth)
     print('median  :', np.round(med, 5))
+    summ = sampler.get_summary()   # (the stored production chain's, selected on the GPU)
+    print('posterior 16 / 50 / 84 ({} samples):'.format(int(summ['count'])))
+    for nm, (lo, mid, hi) in zip(['T1', 'T2', 'Av', 'R1', 'R2', 'plx'], summ['quantiles']):
+        print('  {:4s} {:.6g} / {:.6g} / {:.6g}'.format(nm, lo, mid, hi))
     print('wrote', os.path.join(args.out, 'samples.txt'), samples.shape)
     return truth, med, samples
 

@@ -22,6 +22,15 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
+def print_summary(summ, targets):
+    """The 16 / 50 / 84 percentiles of every target's stored chain (sampler.get_summary: selected on the GPU)."""
+    names = ['T1', 'T2', 'Av', 'R1', 'R2', 'plx']
+    print('posterior 16 / 50 / 84 per target ({} samples each):'.format(', '.join(str(int(c)) for c in summ['count'])))
+    for k in range(targets):
+        print('target {}: '.format(k) + '  '.join('{} {:.5g} / {:.5g} / {:.5g}'.format(nm, *summ['quantiles'][k, j])
+                                                   for j, nm in enumerate(names)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--targets', type=int, default=4)
@@ -95,6 +104,8 @@ def main():
             args.targets, [len(x) // args.nwalkers for x in out], time.time() - t0, args.protocol))
         for k in range(args.targets):
             print('target {}: Teff {:.0f} / {:.0f} (truth {:.0f} / {:.0f})'.format(k, *np.median(out[k][:, :2], axis=0), *truths[k][:2]))
+        if args.device:
+            print_summary(sampler.get_summary(), args.targets)
         group.close()
         return sampler
     sampler.run_mcmc(p0s, args.nsteps)
@@ -105,6 +116,8 @@ def main():
         flat = sampler.get_chain(k, discard=args.nsteps // 2, flat=True)
         print('target {}: Teff {:.0f} / {:.0f} (truth {:.0f} / {:.0f}), acceptance {:.2f}'.format(
             k, *np.median(flat[:, :2], axis=0), *truths[k][:2], sampler.acceptance_fraction[k].mean()))
+    if args.device:
+        print_summary(sampler.get_summary(discard=args.nsteps // 2), args.targets)
     group.close()
     return sampler
 

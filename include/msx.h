@@ -503,6 +503,39 @@ int msx_series_read(msx_series *s, int64_t row0, int64_t nrows, double *out);
 int msx_series_acf(msx_series *s, int64_t n, int64_t discard, int64_t thin, int64_t lag0, int64_t nlag, uint32_t dim_mask,
                    double *f_out);
 
+/* ---- posterior summaries of a series: exact order statistics and binned marginals -------------
+ * What the reference makes of a finished chain before it draws anything: np.median(sample, axis=0) (mft6.py:2025, :2730),
+ * the 16 / 50 / 84 percentiles of corner's titles (:1554, :1595, :1636, :1662), the 75-edge marginal counts of T1, T2, R1,
+ * R2 and R2 / R1 (:2033-2073) and corner's 50-bin 1-D and 2-D counts.  All three calls name their data the same way:
+ *   - the selection x = rows[0:n][discard::thin] (n' rows), msx_series_acf's; member m contributes its W_m walkers, so its
+ *     flat sample has N_m = n' W_m values per column;
+ *   - a COLUMN is a 32-bit code: c < ndim is coordinate c, MSX_COL_RATIO(a, b) the value x[a] / x[b] (the correctly rounded
+ *     IEEE quotient: the reference's ratio = r2 / r1, NumPy's bits).
+ * They are synchronous, run on the series' own stream, wait for nothing but the latest growth copy and need n <= rows.
+ * Results are integer counts and selected elements: exact, whatever the launch.  MSX_ERR_RANGE: n past the rows held, an
+ * empty selection, an unknown column, and what each call names below.                                                     */
+#define MSX_COL_RATIO(a, b) (0x80000000u | ((uint32_t)(a) << 8) | (uint32_t)(b))
+/* out[(m * ncols + j) * nranks + r] = the element of zero-based rank ranks[m * nranks + r] in ascending order of member m's
+ * flat sample of column cols[j]; count_out[m] (may be NULL) = N_m.  Order: -inf < finite < +inf < NaN (np.sort's); -0 and
+ * +0 are equal and either may come back.  By radix selection on order-preserving keys: no sort.  MSX_ERR_RANGE: a rank
+ * outside 0 .. N_m - 1.                                                                                                   */
+int msx_series_order_stats(msx_series *s, int64_t n, int64_t discard, int64_t thin, const uint32_t *cols, int32_t ncols,
+                           const int64_t *ranks, int32_t nranks, double *out, int64_t *count_out);
+/* counts_out[(m * ncols + j) * (nedges - 1) + b] = the values of member m's column cols[j] with e[b] <= x < e[b + 1],
+ * e = edges[(m * ncols + j) * nedges ..] ascending.  closed_last != 0: values equal to the last edge count in the last bin
+ * (np.histogram); 0: nowhere (the reference's loop, mft6.py:2046-2049).  Values below e[0], above the last edge and NaN
+ * count nowhere.  Placement is by comparison with the edge values.  MSX_ERR_RANGE: nedges outside 2 .. 4097, edges that
+ * do not ascend.                                                                                                          */
+int msx_series_hist(msx_series *s, int64_t n, int64_t discard, int64_t thin, const uint32_t *cols, int32_t ncols,
+                    const double *edges, int32_t nedges, int32_t closed_last, int64_t *counts_out);
+/* The same for column pairs (pairs[2 p], pairs[2 p + 1]) = (cx, cy): counts_out[((m * npairs + p) * (nx - 1) + bx) * (ny - 1)
+ * + by], with xedges [k][npairs][nx] and yedges [k][npairs][ny] and the same edge rule on both axes (np.histogram2d with
+ * closed_last != 0).  MSX_ERR_RANGE: more than 128 bins (129 edges) on an axis, fewer than 2 edges, edges that do not
+ * ascend.                                                                                                                 */
+int msx_series_hist2d(msx_series *s, int64_t n, int64_t discard, int64_t thin, const uint32_t *pairs, int32_t npairs,
+                      const double *xedges, int32_t nx, const double *yedges, int32_t ny, int32_t closed_last,
+                      int64_t *counts_out);
+
 /* ---- test hooks (used by tests/ only) ------------------------------------------------------------ */
 /* MSX_HOOK_LINKED_FAULT: value != 0 makes the workgroups of the linked form skip their signal -- and the walkers of an
  * overlapped sampler run the publication of their new version -- so that every in-kernel wait runs into its bound;

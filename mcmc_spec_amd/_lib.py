@@ -31,6 +31,7 @@ MAX_GROUP = 64  # include/msx.h MSX_MAX_GROUP: members of a target group
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int64)
+_up = C.POINTER(C.c_uint32)
 
 
 class MsxProblem(C.Structure):
@@ -166,6 +167,10 @@ def load():
         'msx_series_append': (C.c_int, [vp, _dp, C.c_int64]),
         'msx_series_read': (C.c_int, [vp, C.c_int64, C.c_int64, _dp]),
         'msx_series_acf': (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_uint32, _dp]),
+        'msx_series_order_stats': (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, _up, C.c_int32, _ip, C.c_int32, _dp, _ip]),
+        'msx_series_hist': (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, _up, C.c_int32, _dp, C.c_int32, C.c_int32, _ip]),
+        'msx_series_hist2d': (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, _up, C.c_int32, _dp, C.c_int32, _dp, C.c_int32,
+                                        C.c_int32, _ip]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = header/library skew, fail loudly
@@ -188,7 +193,8 @@ EXPORTED = ['msx_create', 'msx_destroy', 'msx_last_error', 'msx_device_info', 'm
             'msx_group_logprob_batch_dev', 'msx_group_launch_info', 'msx_group_sampler_begin', 'msx_group_sampler_enqueue',
             'msx_group_sampler_enqueue_drawn', 'msx_group_sampler_collect', 'msx_group_sampler_end',
             'msx_series_create', 'msx_series_destroy', 'msx_series_last_error', 'msx_series_rows', 'msx_sampler_attach_series',
-            'msx_group_sampler_attach_series', 'msx_series_append', 'msx_series_read', 'msx_series_acf']
+            'msx_group_sampler_attach_series', 'msx_series_append', 'msx_series_read', 'msx_series_acf',
+            'msx_series_order_stats', 'msx_series_hist', 'msx_series_hist2d']
 
 
 def as_f64(a):
@@ -201,6 +207,22 @@ def dptr(a):
 
 def iptr(a):
     return a.ctypes.data_as(_ip)
+
+
+def uptr(a):
+    return a.ctypes.data_as(_up)
+
+
+def col_ratio(a, b):
+    """The column code of the derived value x[a] / x[b] (include/msx.h, MSX_COL_RATIO)."""
+    a, b = int(a), int(b)
+    if not (0 <= a < 256 and 0 <= b < 256):
+        raise ValueError('col_ratio: coordinates must lie in 0 .. 255')
+    return 0x80000000 | (a << 8) | b
+
+
+def _col_codes(cols):
+    return np.ascontiguousarray(np.asarray(cols, dtype=np.int64).ravel().astype(np.uint32))
 
 
 class Context:
@@ -710,6 +732,7 @@ class Series:
         ctx.check(self.lib.msx_series_create(ctx.h, int(nw), int(ndim), counts.size, iptr(counts), int(cap_hint), C.byref(h)))
         self.h = h
         self.nw, self.ndim, self.k = int(nw), int(ndim), int(counts.size)
+        self.counts = counts
 
     def close(self):
         if getattr(self, 'h', None):
@@ -724,7 +747,8 @@ class Series:
 
     def check(self, rc):
         if rc != MSX_OK:
-            raise MsxError(rc, self.lib.msx_series_last_error(self.h).decode())
+            msg = self.lib.msx_series_last_error(self.h).decode()
+            raise ValueError(msg) if rc == MSX_ERR_RANGE else MsxError(rc, msg)
 
     @property
     def rows(self):
@@ -760,6 +784,48 @@ class Series:
         f = np.full((self.k, self.ndim, nlag), np.nan)
         self.check(self.lib.msx_series_acf(self.h, int(n), int(discard), int(thin), int(lag0), nlag, mask, dptr(f)))
         return f
+
+    def order_stats(self, n, discard, thin, cols, ranks):
+        """(values (k, ncols, nranks), counts (k,)): the elements of zero-based ranks ``ranks`` (k, nranks; one row is
+        used for every member) in ascending order of each member's flat sample rows[0:n][discard::thin] of each column
+        (msx_series_order_stats; np.sort's order, NaN last).  ``cols``: coordinates or ``col_ratio(a, b)`` codes."""
+        cols = _col_codes(cols)
+        ranks = np.atleast_2d(np.asarray(ranks, dtype=np.int64))
+        if ranks.ndim != 2 or ranks.shape[0] not in (1, self.k) or ranks.shape[1] < 1 or cols.size < 1:
+            raise ValueError('order_stats: ranks must have shape (k, nranks), nranks >= 1, and cols must name a column')
+        ranks = np.ascontiguousarray(np.broadcast_to(ranks, (self.k, ranks.shape[1])))
+        out = np.empty((self.k, cols.size, ranks.shape[1]))
+        count = np.zeros(self.k, dtype=np.int64)
+        self.check(self.lib.msx_series_order_stats(self.h, int(n), int(discard), int(thin), uptr(cols), cols.size, iptr(ranks),
+                                                   ranks.shape[1], dptr(out), iptr(count)))
+        return out, count
+
+    def hist(self, n, discard, thin, cols, edges, closed_last=True):
+        """int64 counts (k, ncols, nedges - 1) of each member's column against its own ascending edge vector, ``edges``
+        (k, ncols, nedges): bin b holds edges[b] <= x < edges[b + 1]; the last edge itself counts in the last bin when
+        ``closed_last`` (np.histogram) and nowhere otherwise (the reference's loop).  msx_series_hist."""
+        cols = _col_codes(cols)
+        edges = as_f64(edges)
+        if edges.ndim != 3 or edges.shape[:2] != (self.k, cols.size):
+            raise ValueError('hist: edges must have shape (k, ncols, nedges)')
+        counts = np.zeros((self.k, cols.size, max(edges.shape[2] - 1, 0)), dtype=np.int64)
+        self.check(self.lib.msx_series_hist(self.h, int(n), int(discard), int(thin), uptr(cols), cols.size, dptr(edges),
+                                            edges.shape[2], int(bool(closed_last)), iptr(counts)))
+        return counts
+
+    def hist2d(self, n, discard, thin, pairs, xedges, yedges, closed_last=True):
+        """int64 counts (k, npairs, nx - 1, ny - 1) for the column pairs ``pairs`` (npairs, 2) = (cx, cy), with ``xedges``
+        (k, npairs, nx) and ``yedges`` (k, npairs, ny); hist's edge rule on both axes, at most 128 bins each
+        (msx_series_hist2d; np.histogram2d with closed_last)."""
+        pairs = np.ascontiguousarray(np.asarray(pairs, dtype=np.int64).reshape(-1, 2).astype(np.uint32))
+        xedges, yedges = as_f64(xedges), as_f64(yedges)
+        npairs = pairs.shape[0]
+        if xedges.ndim != 3 or yedges.ndim != 3 or xedges.shape[:2] != (self.k, npairs) or yedges.shape[:2] != (self.k, npairs):
+            raise ValueError('hist2d: xedges and yedges must have shape (k, npairs, nedges)')
+        counts = np.zeros((self.k, npairs, max(xedges.shape[2] - 1, 0), max(yedges.shape[2] - 1, 0)), dtype=np.int64)
+        self.check(self.lib.msx_series_hist2d(self.h, int(n), int(discard), int(thin), uptr(pairs), npairs, dptr(xedges),
+                                              xedges.shape[2], dptr(yedges), yedges.shape[2], int(bool(closed_last)), iptr(counts)))
+        return counts
 
 
 # ---- the device-resident samplers' marshalling, shared by Context (msx_sampler_*) and Group (msx_group_sampler_*) ----

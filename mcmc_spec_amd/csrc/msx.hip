@@ -25,6 +25,7 @@
 //   pair_kernel.h      the pair form: two walkers of one grid cell per workgroup, one set of row loads
 //   opt_run_kernels.h  the device-resident pre-optimiser: fit_spec's per-chain state machine, one thread per chain
 //   staging_kernels.h  CCM89, pair gather, band integrals, broadening, resample, composite, stream copy
+//   summary_kernels.h  order statistics and binned marginals of a device chain series
 //   msx.hip            host context + the C ABI of include/msx.h
 //
 // Design notes (details in DESIGN.md):
@@ -65,6 +66,7 @@
 #include "staging_kernels.h"
 #include "inpath_kernels.h"
 #include "autocorr_kernels.h"
+#include "summary_kernels.h"
 #include "opt_run_kernels.h"
 
 // ================================================================================================
@@ -3573,6 +3575,212 @@ int msx_series_acf(msx_series *sr, int64_t n, int64_t discard, int64_t thin, int
             for (int q = 0; q < nd; ++q)
                 memcpy(f_out + ((int64_t)m * sr->ndim + dims.d[q]) * nlag + (lb - lag0), h.data() + ((int64_t)m * nd + q) * cnt,
                        sizeof(double) * (size_t)cnt);
+    }
+    return MSX_OK;
+}
+
+// ---- order statistics and binned marginals of a series (summary_kernels.h) --------------------------
+static constexpr size_t kSummaryTableBudget = (size_t)64 << 20;   // global count tables per launch (columns cut to fit)
+
+// the selection rows[0:n][discard::thin] -> n' (MSX_ERR_RANGE when n lies past the rows held or nothing is selected)
+static int summary_selection(msx_series *sr, const char *who, int64_t n, int64_t discard, int64_t thin, int64_t *np_out) {
+    const std::string w(who);
+    if (discard < 0 || thin < 1) return fail(sr, MSX_ERR_INVALID, w + ": bad arguments (discard >= 0, thin >= 1)");
+    if (n < 1 || n > sr->rows) return fail(sr, MSX_ERR_RANGE, w + ": n must lie in 1 .. the rows the series holds");
+    const int64_t np = n > discard ? (n - discard + thin - 1) / thin : 0;
+    if (np < 1) return fail(sr, MSX_ERR_RANGE, w + ": the selection rows[0:n][discard::thin] is empty");
+    if ((np + kSumTile - 1) / kSumTile > 65535) return fail(sr, MSX_ERR_RANGE, w + ": more rows than one launch covers");
+    *np_out = np;
+    return MSX_OK;
+}
+
+static int summary_columns(msx_series *sr, const char *who, const uint32_t *cols, int64_t count) {
+    for (int64_t j = 0; j < count; ++j) {
+        const uint32_t c = cols[j];
+        const bool ok = c & kColRatioBit ? (c & 0x7fff0000u) == 0 && (int)((c >> 8) & 0xffu) < sr->ndim && (int)(c & 0xffu) < sr->ndim
+                                         : (int64_t)c < sr->ndim;
+        if (!ok) return fail(sr, MSX_ERR_RANGE, std::string(who) + ": unknown column (a coordinate < ndim or MSX_COL_RATIO(a, b))");
+    }
+    return MSX_OK;
+}
+
+// edge vectors [count][ne]: ascending (equal neighbours allowed, as np.histogram allows them), no NaN
+static int summary_edges(msx_series *sr, const char *who, const double *edges, int64_t count, int32_t ne) {
+    for (int64_t v = 0; v < count; ++v)
+        for (int32_t i = 0; i + 1 < ne; ++i)
+            if (!(edges[v * ne + i] <= edges[v * ne + i + 1]))
+                return fail(sr, MSX_ERR_RANGE, std::string(who) + ": every edge vector must ascend");
+    return MSX_OK;
+}
+
+int msx_series_order_stats(msx_series *sr, int64_t n, int64_t discard, int64_t thin, const uint32_t *cols, int32_t ncols,
+                           const int64_t *ranks, int32_t nranks, double *out, int64_t *count_out) {
+    if (!sr) return MSX_ERR_INVALID;
+    if (!cols || ncols < 1 || !ranks || nranks < 1 || !out) return fail(sr, MSX_ERR_INVALID, "msx_series_order_stats: bad arguments");
+    int64_t np = 0;
+    int rc = summary_selection(sr, "msx_series_order_stats", n, discard, thin, &np);
+    if (rc == MSX_OK) rc = summary_columns(sr, "msx_series_order_stats", cols, ncols);
+    if (rc != MSX_OK) return rc;
+    const int k = (int)sr->off.size() - 1;
+    for (int m = 0; m < k; ++m) {
+        const int64_t N = np * (sr->off[m + 1] - sr->off[m]);
+        for (int32_t r = 0; r < nranks; ++r)
+            if (ranks[(int64_t)m * nranks + r] < 0 || ranks[(int64_t)m * nranks + r] >= N)
+                return fail(sr, MSX_ERR_RANGE, "msx_series_order_stats: a rank outside 0 .. N_m - 1");
+        if (count_out) count_out[m] = N;
+    }
+    HIP_TRY(sr, hipSetDevice(sr->device));
+    // columns per launch: the digit histograms of k x columns jobs within the budget
+    const size_t job_hist = sizeof(unsigned long long) * kSelRanks * kSelDigits;
+    const int32_t ncl_max = (int32_t)std::min<size_t>(65535, std::max<size_t>(1, kSummaryTableBudget / (job_hist * (size_t)k)));
+    const int32_t ncl_cap = std::min(ncols, ncl_max);
+    const int64_t jobs_cap = (int64_t)k * ncl_cap;
+    HIP_TRY(sr, series_scratch(sr, (job_hist + sizeof(SelState)) * (size_t)jobs_cap + sizeof(uint32_t) * (size_t)ncl_cap));
+    unsigned long long *d_hist = (unsigned long long *)sr->d_scratch;
+    SelState *d_state = (SelState *)(d_hist + jobs_cap * kSelRanks * kSelDigits);
+    uint32_t *d_cols = (uint32_t *)(d_state + jobs_cap);
+    HIP_TRY(sr, series_wait_growth(sr));
+    hipStream_t st = sr->stream;
+    const dim3 grid_rows((unsigned)sr->nw, (unsigned)((np + kSumTile - 1) / kSumTile), 1u);
+    std::vector<SelState> h;
+    for (int32_t c0 = 0; c0 < ncols; c0 += ncl_cap) {
+        const int32_t ncl = std::min(ncl_cap, ncols - c0);
+        const int64_t jobs = (int64_t)k * ncl;
+        HIP_TRY(sr, hipMemcpyAsync(d_cols, cols + c0, sizeof(uint32_t) * (size_t)ncl, hipMemcpyHostToDevice, st));
+        for (int32_t r0 = 0; r0 < nranks; r0 += kSelRanks) {
+            const int32_t nr = std::min<int32_t>(kSelRanks, nranks - r0);
+            h.assign((size_t)jobs, SelState());
+            for (int64_t j = 0; j < jobs; ++j) {
+                SelState &s = h[(size_t)j];
+                memset(&s, 0, sizeof(s));
+                s.nranks = nr;
+                s.nslots = 1;   // every rank starts from the empty prefix
+                for (int32_t r = 0; r < nr; ++r) s.rem[r] = ranks[(j / ncl) * nranks + r0 + r];
+            }
+            HIP_TRY(sr, hipMemcpyAsync(d_state, h.data(), sizeof(SelState) * (size_t)jobs, hipMemcpyHostToDevice, st));
+            HIP_TRY(sr, hipMemsetAsync(d_hist, 0, job_hist * (size_t)jobs, st));
+            for (int p = 0; p < kSelPasses; ++p) {
+                const int32_t shift = 64 - kSelDigitBits * (p + 1);
+                hipLaunchKernelGGL(sel_pass_kernel, dim3(grid_rows.x, grid_rows.y, (unsigned)ncl), dim3(kSumThreads), 0, st,
+                                   (const double *)sr->d_rows, sr->cap, sr->nw, np, discard, thin, (const int64_t *)sr->d_off,
+                                   (int32_t)k, (const uint32_t *)d_cols, ncl, shift, (const SelState *)d_state, d_hist);
+                HIP_TRY(sr, hipGetLastError());
+                hipLaunchKernelGGL(sel_pick_kernel, dim3((unsigned)jobs), dim3(64), 0, st, d_state, d_hist, shift);
+                HIP_TRY(sr, hipGetLastError());
+            }
+            HIP_TRY(sr, hipMemcpyAsync(h.data(), d_state, sizeof(SelState) * (size_t)jobs, hipMemcpyDeviceToHost, st));
+            HIP_TRY(sr, hipStreamSynchronize(st));
+            for (int64_t j = 0; j < jobs; ++j)
+                for (int32_t r = 0; r < nr; ++r) {
+                    const unsigned long long key = h[(size_t)j].prefix[r];
+                    const unsigned long long b = (key >> 63) ? (key & 0x7fffffffffffffffull) : ~key;   // (val_of, on the host)
+                    memcpy(out + ((j / ncl) * ncols + c0 + j % ncl) * nranks + r0 + r, &b, sizeof(double));
+                }
+        }
+    }
+    return MSX_OK;
+}
+
+int msx_series_hist(msx_series *sr, int64_t n, int64_t discard, int64_t thin, const uint32_t *cols, int32_t ncols,
+                    const double *edges, int32_t nedges, int32_t closed_last, int64_t *counts_out) {
+    if (!sr) return MSX_ERR_INVALID;
+    if (!cols || ncols < 1 || !edges || !counts_out) return fail(sr, MSX_ERR_INVALID, "msx_series_hist: bad arguments");
+    if (nedges < 2 || nedges > kHistMaxEdges) return fail(sr, MSX_ERR_RANGE, "msx_series_hist: nedges must lie in 2 .. 4097");
+    const int k = (int)sr->off.size() - 1;
+    int64_t np = 0;
+    int rc = summary_selection(sr, "msx_series_hist", n, discard, thin, &np);
+    if (rc == MSX_OK) rc = summary_columns(sr, "msx_series_hist", cols, ncols);
+    if (rc == MSX_OK) rc = summary_edges(sr, "msx_series_hist", edges, (int64_t)k * ncols, nedges);
+    if (rc != MSX_OK) return rc;
+    HIP_TRY(sr, hipSetDevice(sr->device));
+    const int64_t nb = nedges - 1;
+    const size_t job_bytes = sizeof(double) * (size_t)nedges + sizeof(unsigned long long) * (size_t)nb;
+    const int32_t ncl_cap = std::min<int32_t>(ncols, (int32_t)std::min<size_t>(65535, std::max<size_t>(1, kSummaryTableBudget / (job_bytes * (size_t)k))));
+    const int64_t jobs_cap = (int64_t)k * ncl_cap;
+    HIP_TRY(sr, series_scratch(sr, job_bytes * (size_t)jobs_cap + sizeof(uint32_t) * (size_t)ncl_cap));
+    unsigned long long *d_counts = (unsigned long long *)sr->d_scratch;
+    double *d_edges = (double *)(d_counts + jobs_cap * nb);
+    uint32_t *d_cols = (uint32_t *)(d_edges + jobs_cap * nedges);
+    const size_t lds = sizeof(double) * (size_t)nedges + sizeof(unsigned int) * (size_t)nb;
+    if (lds > 48 * 1024) HIP_TRY(sr, hipFuncSetAttribute((const void *)hist_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+    HIP_TRY(sr, series_wait_growth(sr));
+    hipStream_t st = sr->stream;
+    std::vector<double> he;
+    std::vector<unsigned long long> hc;
+    for (int32_t c0 = 0; c0 < ncols; c0 += ncl_cap) {
+        const int32_t ncl = std::min(ncl_cap, ncols - c0);
+        const int64_t jobs = (int64_t)k * ncl;
+        he.resize((size_t)(jobs * nedges));
+        hc.resize((size_t)(jobs * nb));
+        for (int64_t j = 0; j < jobs; ++j)
+            memcpy(he.data() + j * nedges, edges + ((j / ncl) * ncols + c0 + j % ncl) * nedges, sizeof(double) * (size_t)nedges);
+        HIP_TRY(sr, hipMemcpyAsync(d_cols, cols + c0, sizeof(uint32_t) * (size_t)ncl, hipMemcpyHostToDevice, st));
+        HIP_TRY(sr, hipMemcpyAsync(d_edges, he.data(), sizeof(double) * he.size(), hipMemcpyHostToDevice, st));
+        HIP_TRY(sr, hipMemsetAsync(d_counts, 0, sizeof(unsigned long long) * hc.size(), st));
+        hipLaunchKernelGGL(hist_kernel, dim3((unsigned)sr->nw, (unsigned)((np + kSumTile - 1) / kSumTile), (unsigned)ncl), dim3(kSumThreads),
+                           lds, st, (const double *)sr->d_rows, sr->cap, sr->nw, np, discard, thin, (const int64_t *)sr->d_off, (int32_t)k,
+                           (const uint32_t *)d_cols, ncl, (const double *)d_edges, nedges, (int32_t)(closed_last != 0), d_counts);
+        HIP_TRY(sr, hipGetLastError());
+        HIP_TRY(sr, hipMemcpyAsync(hc.data(), d_counts, sizeof(unsigned long long) * hc.size(), hipMemcpyDeviceToHost, st));
+        HIP_TRY(sr, hipStreamSynchronize(st));
+        for (int64_t j = 0; j < jobs; ++j)
+            memcpy(counts_out + ((j / ncl) * ncols + c0 + j % ncl) * nb, hc.data() + j * nb, sizeof(int64_t) * (size_t)nb);
+    }
+    return MSX_OK;
+}
+
+int msx_series_hist2d(msx_series *sr, int64_t n, int64_t discard, int64_t thin, const uint32_t *pairs, int32_t npairs,
+                      const double *xedges, int32_t nx, const double *yedges, int32_t ny, int32_t closed_last, int64_t *counts_out) {
+    if (!sr) return MSX_ERR_INVALID;
+    if (!pairs || npairs < 1 || !xedges || !yedges || !counts_out) return fail(sr, MSX_ERR_INVALID, "msx_series_hist2d: bad arguments");
+    if (nx < 2 || ny < 2 || nx > kHist2dMaxBins + 1 || ny > kHist2dMaxBins + 1)
+        return fail(sr, MSX_ERR_RANGE, "msx_series_hist2d: 1 .. 128 bins (2 .. 129 edges) per axis");
+    const int k = (int)sr->off.size() - 1;
+    int64_t np = 0;
+    int rc = summary_selection(sr, "msx_series_hist2d", n, discard, thin, &np);
+    if (rc == MSX_OK) rc = summary_columns(sr, "msx_series_hist2d", pairs, 2 * (int64_t)npairs);
+    if (rc == MSX_OK) rc = summary_edges(sr, "msx_series_hist2d", xedges, (int64_t)k * npairs, nx);
+    if (rc == MSX_OK) rc = summary_edges(sr, "msx_series_hist2d", yedges, (int64_t)k * npairs, ny);
+    if (rc != MSX_OK) return rc;
+    HIP_TRY(sr, hipSetDevice(sr->device));
+    const int64_t nb = (int64_t)(nx - 1) * (ny - 1);
+    const size_t job_bytes = sizeof(double) * (size_t)(nx + ny) + sizeof(unsigned long long) * (size_t)nb;
+    const int32_t npl_cap = std::min<int32_t>(npairs, (int32_t)std::min<size_t>(65535, std::max<size_t>(1, kSummaryTableBudget / (job_bytes * (size_t)k))));
+    const int64_t jobs_cap = (int64_t)k * npl_cap;
+    HIP_TRY(sr, series_scratch(sr, job_bytes * (size_t)jobs_cap + sizeof(uint32_t) * 2 * (size_t)npl_cap));
+    unsigned long long *d_counts = (unsigned long long *)sr->d_scratch;
+    double *d_ex = (double *)(d_counts + jobs_cap * nb), *d_ey = d_ex + jobs_cap * nx;
+    uint32_t *d_cols = (uint32_t *)(d_ey + jobs_cap * ny);
+    const size_t lds = sizeof(double) * (size_t)(nx + ny) + sizeof(unsigned int) * (size_t)nb;
+    if (lds > 48 * 1024) HIP_TRY(sr, hipFuncSetAttribute((const void *)hist2d_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024));
+    HIP_TRY(sr, series_wait_growth(sr));
+    hipStream_t st = sr->stream;
+    std::vector<double> hx, hy;
+    std::vector<unsigned long long> hc;
+    for (int32_t p0 = 0; p0 < npairs; p0 += npl_cap) {
+        const int32_t npl = std::min(npl_cap, npairs - p0);
+        const int64_t jobs = (int64_t)k * npl;
+        hx.resize((size_t)(jobs * nx));
+        hy.resize((size_t)(jobs * ny));
+        hc.resize((size_t)(jobs * nb));
+        for (int64_t j = 0; j < jobs; ++j) {
+            const int64_t src = (j / npl) * npairs + p0 + j % npl;
+            memcpy(hx.data() + j * nx, xedges + src * nx, sizeof(double) * (size_t)nx);
+            memcpy(hy.data() + j * ny, yedges + src * ny, sizeof(double) * (size_t)ny);
+        }
+        HIP_TRY(sr, hipMemcpyAsync(d_cols, pairs + 2 * (int64_t)p0, sizeof(uint32_t) * 2 * (size_t)npl, hipMemcpyHostToDevice, st));
+        HIP_TRY(sr, hipMemcpyAsync(d_ex, hx.data(), sizeof(double) * hx.size(), hipMemcpyHostToDevice, st));
+        HIP_TRY(sr, hipMemcpyAsync(d_ey, hy.data(), sizeof(double) * hy.size(), hipMemcpyHostToDevice, st));
+        HIP_TRY(sr, hipMemsetAsync(d_counts, 0, sizeof(unsigned long long) * hc.size(), st));
+        hipLaunchKernelGGL(hist2d_kernel, dim3((unsigned)sr->nw, (unsigned)((np + kSumTile2d - 1) / kSumTile2d), (unsigned)npl),
+                           dim3(kSumThreads), lds, st, (const double *)sr->d_rows, sr->cap, sr->nw, np, discard, thin,
+                           (const int64_t *)sr->d_off, (int32_t)k, (const uint32_t *)d_cols, npl, (const double *)d_ex, nx,
+                           (const double *)d_ey, ny, (int32_t)(closed_last != 0), d_counts);
+        HIP_TRY(sr, hipGetLastError());
+        HIP_TRY(sr, hipMemcpyAsync(hc.data(), d_counts, sizeof(unsigned long long) * hc.size(), hipMemcpyDeviceToHost, st));
+        HIP_TRY(sr, hipStreamSynchronize(st));
+        for (int64_t j = 0; j < jobs; ++j)
+            memcpy(counts_out + ((j / npl) * npairs + p0 + j % npl) * nb, hc.data() + j * nb, sizeof(int64_t) * (size_t)nb);
     }
     return MSX_OK;
 }

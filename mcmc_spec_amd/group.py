@@ -387,6 +387,24 @@ class DeviceGroupSampler(GroupSampler):
         tau = _device_integrated_time(self._series, n_total, c, discard, thin) * thin
         return _check_tau(tau if k is None else tau[k], n, thin, tol, quiet)
 
+    def get_summary(self, k=None, q=(0.16, 0.5, 0.84), discard=0, thin=1, cols=None):
+        """Every target's posterior summary from its stored chain, flattened over its walkers: {'count' (K,), 'min', 'max'
+        (K, ncols), 'quantiles' (K, ncols, len(q))}, ``np.quantile``'s numbers exactly; for one target with ``k`` (the
+        arrays lose their first axis).  One set of device calls covers all targets (mcmc_spec_amd.summary; DESIGN.md
+        section 14): with autocorr='device' on the chains held there -- the rows of the stored chains; rows queued past
+        them are not part of it -- otherwise the host chains are uploaded first.  ``cols``: coordinates or
+        ``summary.col_ratio(a, b)``; None for all coordinates."""
+        from . import summary
+        n_total = len(self.samplers[0]._chain)
+        if self._series is not None:
+            out = summary.summary_of(self._series, n_total, q, cols, discard, thin)
+        else:
+            if n_total < 1:
+                raise ValueError('the selection rows[0:n][discard::thin] is empty')
+            chain = np.concatenate([np.array(s._chain) for s in self.samplers], axis=1)
+            out = summary.summarize(chain, self.group.engines[0].ctx, self.nwalkers, q, cols, discard, thin)
+        return out if k is None else {name: v[k] for name, v in out.items()}
+
 
 def run_group_protocol(sampler, pos, nburn, nsteps, nthin=10, dirname=None, fnames=None):
     """``sampler.run_reference_protocol`` (run_emcee's driver, mft6.py:1494-1529) applied to every target of a group

@@ -469,6 +469,22 @@ class DeviceEnsembleSampler(EnsembleSampler):
         tau = _device_integrated_time(self._series, n_total, c, discard, thin)[0]
         return _check_tau(tau * thin, n, thin, tol, quiet)
 
+    def get_summary(self, q=(0.16, 0.5, 0.84), discard=0, thin=1, cols=None):
+        """The posterior summary of the stored chain, flattened over the walkers: {'count': N, 'min', 'max' (ncols,),
+        'quantiles' (ncols, len(q))} -- ``np.quantile(get_chain(discard=, thin=, flat=True), q, axis=0).T`` exactly, from
+        elements the device selects (mcmc_spec_amd.summary).  With autocorr='device' from the chain
+        held there (rows past len(self._chain) -- queued chunks not consumed yet -- are not part of it); otherwise the
+        host chain is uploaded first.  ``cols``: coordinates or ``summary.col_ratio(a, b)``; None for all coordinates."""
+        from . import summary
+        n_total = len(self._chain)
+        if self._series is not None:
+            out = summary.summary_of(self._series, n_total, q, cols, discard, thin)
+        else:
+            if n_total < 1:
+                raise ValueError('the selection rows[0:n][discard::thin] is empty')
+            out = summary.summarize(np.array(self._chain), self.engine.ctx, None, q, cols, discard, thin)
+        return {name: v[0] for name, v in out.items()}
+
 
 def _autocorr_1d(x):
     x = np.asarray(x, dtype=float)

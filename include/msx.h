@@ -296,15 +296,20 @@ int msx_sampler_shard(msx_ctx *ctx, int32_t rank, int32_t world);
 int msx_sampler_enqueue(msx_ctx *ctx, int32_t slot /* 0|1 */, int64_t nsteps, const int32_t *sidx, const int32_t *cidx,
                         const int32_t *partner, const double *zz, const double *zfac, const double *logu);
 /* The chunk's randomness drawn ON THE DEVICE instead of coming from the host: a counter-based generator (SplitMix64's
- * output function over counters made of (seed, absolute iteration of the run, stream, index)) yields, per iteration, the
+ * output function over counters made of (seed, absolute iteration of the stream, stream, index)) yields, per iteration, the
  * random split of the ensemble into two halves (walkers sorted by a 64-bit key) and, per half-step and walker, the stretch
  * factor z = ((a - 1) u + 1)^2 / a, the partner floor(u ns) in the complementary half and ln u of the accept draw -- the
  * quantities msx_sampler_enqueue takes from the host (emcee's stretch move; mft6.py:1491-1494 drives it).  One launch per
  * chunk, no upload; every rank of a sharded run draws the same numbers from the same seed.  Up to 4096 walkers.
  * msx_sampler_draw returns the same stream to the host (arrays [nsteps][2][nw/2] as for msx_sampler_enqueue; `partner`
  * indexes the complementary half): the host loop fed with it reproduces the device-drawn chain bit for bit
- * (tests/test_gpu_overlap.py), and mcmc_spec_amd/sampler.py::counter_draws restates the generator in NumPy.           */
-int msx_sampler_enqueue_drawn(msx_ctx *ctx, int32_t slot, int64_t nsteps, uint64_t seed, double a);
+ * (tests/test_gpu_overlap.py), and mcmc_spec_amd/sampler.py::counter_draws restates the generator in NumPy.
+ * first_iter is the ABSOLUTE iteration of the chunk's first step in the seed's stream, as msx_sampler_draw takes it: the
+ * caller carries it from chunk to chunk and ACROSS runs (a run begun after burn-in goes on where the burn-in's last queued
+ * chunk stopped; the run's own count of steps starts at 0 again and plays no part in the stream -- it numbers only the
+ * hand-over versions of an overlapped run).  a not > 1, first_iter < 0 or more than 4096 walkers: MSX_ERR_INVALID, and
+ * nothing is queued (tests/test_gpu_sampler_runs.py).                                                                  */
+int msx_sampler_enqueue_drawn(msx_ctx *ctx, int32_t slot, int64_t nsteps, uint64_t seed, double a, int64_t first_iter);
 int msx_sampler_draw(msx_ctx *ctx, uint64_t seed, double a, int64_t first_iter, int64_t nsteps, int64_t nw, int32_t ndim,
                      int32_t *sidx, int32_t *cidx, int32_t *partner, double *zz, double *zfac, double *logu);
 int msx_sampler_collect(msx_ctx *ctx, int32_t slot, double *chain_out, double *logp_out, int64_t *naccept,

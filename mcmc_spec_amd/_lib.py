@@ -125,7 +125,7 @@ def load():
         'msx_sampler_enqueue': (C.c_int, [vp, C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                           C.POINTER(C.c_int32), _dp, _dp, _dp]),
         'msx_sampler_collect': (C.c_int, [vp, C.c_int32, _dp, _dp, _ip, C.POINTER(C.c_int32)]),
-        'msx_sampler_enqueue_drawn': (C.c_int, [vp, C.c_int32, C.c_int64, C.c_uint64, C.c_double]),
+        'msx_sampler_enqueue_drawn': (C.c_int, [vp, C.c_int32, C.c_int64, C.c_uint64, C.c_double, C.c_int64]),
         'msx_sampler_draw': (C.c_int, [vp, C.c_uint64, C.c_double, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_int32),
                                        C.POINTER(C.c_int32), C.POINTER(C.c_int32), _dp, _dp, _dp]),
         'msx_sampler_end': (C.c_int, [vp, _dp, _dp]),
@@ -503,9 +503,11 @@ class Context:
         """Queue one chunk (arrays of shape (nsteps, 2, nw/2)) without waiting for it."""
         return _sampler_enqueue(self, self.lib.msx_sampler_enqueue, 'nwalkers/2', slot, (sidx, cidx, partner, zz, zfac, logu))
 
-    def sampler_enqueue_drawn(self, slot, nsteps, seed, a=2.0):
-        """Queue one chunk whose randomness the device draws itself (msx_sampler_enqueue_drawn)."""
-        self.check(self.lib.msx_sampler_enqueue_drawn(self.h, int(slot), int(nsteps), int(seed) & 0xffffffffffffffff, float(a)))
+    def sampler_enqueue_drawn(self, slot, nsteps, seed, a, first_iter):
+        """Queue one chunk whose randomness the device draws itself (msx_sampler_enqueue_drawn): the chunk's first step is
+        the ABSOLUTE iteration ``first_iter`` of the seed's stream, which the caller carries across chunks and runs."""
+        self.check(self.lib.msx_sampler_enqueue_drawn(self.h, int(slot), int(nsteps), int(seed) & 0xffffffffffffffff, float(a),
+                                                      int(first_iter)))
         return int(nsteps)
 
     def sampler_draw(self, seed, a, first_iter, nsteps, nw, ndim):

@@ -373,13 +373,16 @@ __host__ __device__ inline double counter_uniform(unsigned long long seed, unsig
 constexpr int kDrawMaxWalkers = 4096;  // (key, index) pairs of one iteration sorted in LDS: 48 KB
 constexpr int kDrawThreads = 256;
 // One iteration `it` of one ensemble of nw walkers keyed by `seed`, by the whole workgroup (kDrawThreads threads): the keys,
-// the LDS sort, and per half-step h and position j the entry o0 + h * hstride + j of the chunk's arrays.  sidx and cidx
-// stay the ensemble's own indices; the resolved partner and the records' si / ci -- what the kernels dereference -- are
-// woff + the ensemble's own index (a target group's member: its offset in the group's ensemble), as run_pack leaves them.
-// resolve != 0: `partner` receives cidx[partner] (the ensemble index of the complementary walker: what the kernels read);
-// 0: the raw index into the complementary half (what the host loop consumes)
-__device__ __forceinline__ void draw_iteration(unsigned long long seed, double a, unsigned long long it, int nw, int32_t ndim, int32_t resolve,
-                                               int32_t overlap, int32_t woff, int64_t o0, int64_t hstride, int32_t *__restrict__ sidx,
+// the LDS sort, and per half-step h and position j the entry o0 + h * hstride + j of the chunk's arrays.  `it` is the
+// generator's counter only -- the ABSOLUTE iteration of the stream, which goes on across runs; the records' hand-over
+// versions of an overlapped run count from the RUN's start (msx_sampler_begin zeroes the walkers' versions) and come from
+// `ver_it`, the iteration's number within the run (run_pack's k).  sidx and cidx stay the ensemble's own indices; the
+// resolved partner and the records' si / ci -- what the kernels dereference -- are woff + the ensemble's own index (a
+// target group's member: its offset in the group's ensemble), as run_pack leaves them.  resolve != 0: `partner` receives
+// cidx[partner] (the ensemble index of the complementary walker: what the kernels read); 0: the raw index into the
+// complementary half (what the host loop consumes)
+__device__ __forceinline__ void draw_iteration(unsigned long long seed, double a, unsigned long long it, unsigned long long ver_it, int nw, int32_t ndim,
+                                               int32_t resolve, int32_t overlap, int32_t woff, int64_t o0, int64_t hstride, int32_t *__restrict__ sidx,
                                                int32_t *__restrict__ cidx, int32_t *__restrict__ partner, double *__restrict__ zz,
                                                double *__restrict__ zfac, double *__restrict__ logu, SmpRec *__restrict__ rec) {
     __shared__ unsigned long long key[kDrawMaxWalkers];
@@ -431,22 +434,23 @@ __device__ __forceinline__ void draw_iteration(unsigned long long seed, double a
         if (rec) {
             SmpRec r;
             r.si = woff + s_w; r.ci = woff + comp[pj]; r.zz = z;
-            r.ver_own = overlap ? (uint32_t)it : 0u;
-            r.ver_partner = overlap ? (uint32_t)(it + (unsigned long long)h) : 0u;
+            r.ver_own = overlap ? (uint32_t)ver_it : 0u;
+            r.ver_partner = overlap ? (uint32_t)(ver_it + (unsigned long long)h) : 0u;
             rec[o] = r;
         }
     }
 }
 
-// one workgroup per iteration of the chunk; the arrays [nsteps][2][nw / 2]
+// one workgroup per iteration of the chunk; the arrays [nsteps][2][nw / 2].  first_iter: the stream's (absolute) iteration of
+// the chunk's first step; ver_first: that step's number within the run (the versions' base; unused unless overlap)
 __global__ void __launch_bounds__(kDrawThreads)
-sampler_draw_kernel(unsigned long long seed, double a, int64_t first_iter, int64_t nw, int32_t ndim, int32_t resolve, int32_t overlap,
+sampler_draw_kernel(unsigned long long seed, double a, int64_t first_iter, int64_t ver_first, int64_t nw, int32_t ndim, int32_t resolve, int32_t overlap,
                     int32_t *__restrict__ sidx, int32_t *__restrict__ cidx, int32_t *__restrict__ partner, double *__restrict__ zz,
                     double *__restrict__ zfac, double *__restrict__ logu, SmpRec *__restrict__ rec) {
     const int64_t st = blockIdx.x;  // iteration of the chunk
     const int64_t ns = nw / 2;
-    draw_iteration(seed, a, (unsigned long long)(first_iter + st), (int)nw, ndim, resolve, overlap, 0, st * 2 * ns, ns, sidx, cidx, partner,
-                   zz, zfac, logu, rec);
+    draw_iteration(seed, a, (unsigned long long)(first_iter + st), (unsigned long long)(ver_first + st), (int)nw, ndim, resolve, overlap, 0,
+                   st * 2 * ns, ns, sidx, cidx, partner, zz, zfac, logu, rec);
 }
 
 // The same for a target group's run (msx_group_sampler_enqueue_drawn): grid (nsteps, k), one workgroup per iteration of the
@@ -464,7 +468,7 @@ group_draw_kernel(GroupDrawTable T, double a, int64_t first_iter, int32_t ndim, 
                   double *__restrict__ logu, SmpRec *__restrict__ rec) {
     const int64_t st = blockIdx.x;
     const int m = blockIdx.y;
-    draw_iteration(T.seed[m], a, (unsigned long long)(first_iter + st), T.nw[m], ndim, 1, 0, T.off[m], st * 2 * ns_total + T.astart[m],
+    draw_iteration(T.seed[m], a, (unsigned long long)(first_iter + st), 0ull, T.nw[m], ndim, 1, 0, T.off[m], st * 2 * ns_total + T.astart[m],
                    ns_total, sidx, cidx, partner, zz, zfac, logu, rec);
 }
 

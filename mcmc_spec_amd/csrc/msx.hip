@@ -2449,8 +2449,9 @@ static hipError_t run_save_state(const SamplerRun *r, int device, hipStream_t co
 }
 
 // (draw != nullptr: the chunk's randomness is drawn on the device -- sampler_draw_kernel, keyed by draw->seed and the
-// run's absolute iteration numbers -- instead of coming from the host's arrays)
-struct DeviceDraw { unsigned long long seed; double a; };
+// stream's ABSOLUTE iteration numbers from draw->first_iter, which the caller carries across runs -- instead of coming from
+// the host's arrays.  The records' versions stay the RUN's: r->steps_done, as run_pack counts them.)
+struct DeviceDraw { unsigned long long seed; double a; int64_t first_iter; };
 static int chunk_prepare(msx_ctx *c, int32_t slot, int64_t nsteps, const int32_t *sidx, const int32_t *cidx,
                          const int32_t *partner, const double *zz, const double *zfac, const double *logu, ChunkPtrs *cp,
                          const DeviceDraw *draw = nullptr) {
@@ -2458,8 +2459,8 @@ static int chunk_prepare(msx_ctx *c, int32_t slot, int64_t nsteps, const int32_t
     if (int rc = run_enqueue_check(&c->err, r, "msx_sampler_enqueue", "msx_sampler_begin", "msx_sampler_end", slot, nsteps,
                                    draw || (sidx && cidx && partner && zz && zfac && logu)))
         return rc;
-    if (draw && (r->nw > kDrawMaxWalkers || !(draw->a > 1.0)))
-        return fail(c, MSX_ERR_INVALID, "msx_sampler_enqueue_drawn: the device generator takes up to 4096 walkers and a stretch scale a > 1");
+    if (draw && (r->nw > kDrawMaxWalkers || !(draw->a > 1.0) || draw->first_iter < 0))
+        return fail(c, MSX_ERR_INVALID, "msx_sampler_enqueue_drawn: the device generator takes up to 4096 walkers, a stretch scale a > 1 and a first iteration >= 0");
     SamplerRun::Slot &sl = r->slot[slot];
     HIP_TRY(c, hipSetDevice(c->device));
     const int64_t ns = r->ns, nw = r->nw, nh = nsteps * 2 * ns;
@@ -2485,8 +2486,8 @@ static int chunk_prepare(msx_ctx *c, int32_t slot, int64_t nsteps, const int32_t
         double *g_zz = (double *)sl.d_in, *g_zfac = g_zz + nh, *g_logu = g_zfac + nh;
         int32_t *g_sidx = (int32_t *)(g_logu + nh), *g_cidx = g_sidx + nh, *g_partner = g_cidx + nh;
         SmpRec *g_rec = (SmpRec *)(g_partner + nh);
-        hipLaunchKernelGGL(sampler_draw_kernel, dim3((unsigned)nsteps), dim3(kDrawThreads), 0, c->stream, draw->seed, draw->a, r->steps_done,
-                           nw, (int32_t)ndim, 1, (int32_t)(r->overlap == 1), g_sidx, g_cidx, g_partner, g_zz, g_zfac, g_logu, g_rec);
+        hipLaunchKernelGGL(sampler_draw_kernel, dim3((unsigned)nsteps), dim3(kDrawThreads), 0, c->stream, draw->seed, draw->a, draw->first_iter,
+                           r->steps_done, nw, (int32_t)ndim, 1, (int32_t)(r->overlap == 1), g_sidx, g_cidx, g_partner, g_zz, g_zfac, g_logu, g_rec);
         HIP_TRY(c, hipGetLastError());
     } else {
         if (const char *why = run_pack(r, sl, nsteps, sidx, cidx, partner, zz, zfac, logu))
@@ -2615,8 +2616,8 @@ int msx_sampler_enqueue(msx_ctx *c, int32_t slot, int64_t nsteps, const int32_t 
     return sampler_enqueue(c, "msx_sampler_enqueue", slot, nsteps, sidx, cidx, partner, zz, zfac, logu, nullptr);
 }
 
-int msx_sampler_enqueue_drawn(msx_ctx *c, int32_t slot, int64_t nsteps, uint64_t seed, double a) {
-    const DeviceDraw dd = {(unsigned long long)seed, a};
+int msx_sampler_enqueue_drawn(msx_ctx *c, int32_t slot, int64_t nsteps, uint64_t seed, double a, int64_t first_iter) {
+    const DeviceDraw dd = {(unsigned long long)seed, a, first_iter};
     return sampler_enqueue(c, "msx_sampler_enqueue_drawn", slot, nsteps, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &dd);
 }
 
@@ -2631,8 +2632,8 @@ int msx_sampler_draw(msx_ctx *c, uint64_t seed, double a, int64_t first_iter, in
     HIP_TRY(c, hipMalloc((void **)&d, (size_t)nh * (3 * sizeof(double) + 3 * sizeof(int32_t))));
     double *g_zz = (double *)d, *g_zfac = g_zz + nh, *g_logu = g_zfac + nh;
     int32_t *g_sidx = (int32_t *)(g_logu + nh), *g_cidx = g_sidx + nh, *g_partner = g_cidx + nh;
-    hipLaunchKernelGGL(sampler_draw_kernel, dim3((unsigned)nsteps), dim3(kDrawThreads), 0, c->stream, (unsigned long long)seed, a, first_iter, nw,
-                       ndim, 0, 0, g_sidx, g_cidx, g_partner, g_zz, g_zfac, g_logu, (SmpRec *)nullptr);
+    hipLaunchKernelGGL(sampler_draw_kernel, dim3((unsigned)nsteps), dim3(kDrawThreads), 0, c->stream, (unsigned long long)seed, a, first_iter,
+                       (int64_t)0, nw, ndim, 0, 0, g_sidx, g_cidx, g_partner, g_zz, g_zfac, g_logu, (SmpRec *)nullptr);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess) e = hipMemcpy(zz, g_zz, sizeof(double) * nh, hipMemcpyDeviceToHost);

@@ -20,7 +20,7 @@ import numpy as np
 
 from . import _lib
 from .engine import _raise_for_status
-from .sampler import EnsembleSampler, State, _accept, _check_tau, _device_integrated_time, _propose, _pump
+from .sampler import EnsembleSampler, State, _accept, _check_tau, _device_integrated_time, _propose, _pump, device_seed
 
 
 class TargetGroup:
@@ -212,15 +212,6 @@ class GroupSampler:
         return np.array([s.get_autocorr_time(**kw) for s in self.samplers])
 
 
-def _device_seed(seed):
-    """The device generator's 64-bit key for one target's ``seed``, as ``DeviceEnsembleSampler.device_seed``: an int as
-    itself (masked to 64 bits), None or a SeedSequence through ``generate_state``."""
-    if seed is None or isinstance(seed, np.random.SeedSequence):
-        ss = seed if seed is not None else np.random.SeedSequence(None)
-        return int(ss.generate_state(1, dtype=np.uint64)[0]) & 0xffffffffffffffff
-    return int(seed) & 0xffffffffffffffff
-
-
 class DeviceGroupSampler(GroupSampler):
     """``GroupSampler`` with the K ensembles resident in HBM (``msx_group_sampler_*``, include/msx.h): ``chunk`` iterations
     are queued on the GPU back to back, ONE launch of the group kernel per half-step over the active half of every
@@ -274,7 +265,7 @@ class DeviceGroupSampler(GroupSampler):
         self.chunk = int(chunk)
         self.rng_mode = rng
         seeds = [None] * len(nwalkers) if seeds is None else list(seeds)
-        self.device_seeds = [_device_seed(s) for s in seeds] if rng == 'device' else None
+        self.device_seeds = [device_seed(s) for s in seeds] if rng == 'device' else None
         # autocorr='device': the targets' stored chains are kept on the device too (one _lib.Series of K members, appended
         # by every sample(store=True) run) and get_autocorr_time computes all targets' autocorrelation there, one
         # msx_series_acf call per lag tile; 'host': GroupSampler's, per target

@@ -73,6 +73,17 @@ def counter_draws(seed, a, ndim, first_iter, m, nwalkers):
     return np.ascontiguousarray(sidx), np.ascontiguousarray(cidx), partner, zz, zfac, logu
 
 
+def device_seed(seed):
+    """The device generator's 64-bit key for a sampler's ``seed`` (``DeviceEnsembleSampler.device_seed``, one per target in
+    ``DeviceGroupSampler.device_seeds``): an int as itself, masked to 64 bits; None (fresh entropy), a ``SeedSequence`` or a
+    sequence of ints -- whatever ``EnsembleSampler`` takes for its own generators -- through
+    ``SeedSequence.generate_state(1, uint64)``."""
+    if isinstance(seed, (int, np.integer)):
+        return int(seed) & 0xffffffffffffffff
+    ss = seed if isinstance(seed, np.random.SeedSequence) else np.random.SeedSequence(seed)
+    return int(ss.generate_state(1, dtype=np.uint64)[0]) & 0xffffffffffffffff
+
+
 class EnsembleSampler:
     def __init__(self, nwalkers, ndim, log_prob_fn, args=None, kwargs=None, a=2.0, vectorize=False, pool=None,
                  threads=None, seed=None, draws=None):
@@ -359,7 +370,18 @@ class DeviceEnsembleSampler(EnsembleSampler):
     calls of ``EnsembleSampler``, so for the same seed both samplers produce the same chain, bit for bit.
 
     ``engine`` is a staged ``mcmc_spec_amd.engine.Engine``; ``mode`` selects ``'logposterior'`` or
-    ``'loglikelihood'`` as the target density."""
+    ``'loglikelihood'`` as the target density.
+
+    With ``rng='device'`` the library draws every chunk on the GPU from ``device_seed`` and the ABSOLUTE iteration number
+    ``_drawn``, which every chunk queued advances and ``reset()`` leaves alone -- as ``EnsembleSampler(draws=...)`` counts
+    on the host.  Consecutive ``sample()`` / ``run_mcmc()`` calls therefore continue ONE stream (burn-in, ``reset()``,
+    production: ``run_reference_protocol``), and the chain is the one
+    ``EnsembleSampler(draws=lambda i, m: ctx.sampler_draw(device_seed, a, i, m, nwalkers, ndim))`` walks over the same
+    calls (tests/test_gpu_sampler_runs.py).  The position counts iterations QUEUED, not consumed: a ``sample()`` loop
+    left early (a ``break``, as ``run_reference_protocol`` does on convergence, or a walker error) leaves ``_drawn`` past
+    the last iteration yielded -- by the chunks already queued -- while the host twin stops at the last iteration it
+    stepped.  Both remain valid chains; a later run on the same sampler then matches a twin whose ``_drawn`` is set to
+    this sampler's."""
 
     def __init__(self, nwalkers, ndim, engine, mode='logposterior', a=2.0, seed=None, chunk=64, shard=None, rng='host', overlap=None,
                  autocorr='host'):
@@ -373,8 +395,9 @@ class DeviceEnsembleSampler(EnsembleSampler):
         # rng = 'host' (default): the randomness is drawn by this object's NumPy generators, exactly the calls of
         # EnsembleSampler -- same seed, same chain as the host loop.  rng = 'device': the library draws it on the GPU with a
         # counter-based generator keyed by `seed` (msx_sampler_enqueue_drawn: one launch per chunk, nothing uploaded, every
-        # rank of a sharded run draws the same numbers); the chain is then the one the host loop walks when it is fed
-        # `ctx.sampler_draw(seed, a, first_iteration, m, nwalkers, ndim)` (EnsembleSampler(draws=...)).  Up to 4096 walkers.
+        # rank of a sharded run draws the same numbers -- so a sharded run over world > 1 needs an explicit seed); the chain
+        # is then the one the host loop walks when it is fed `ctx.sampler_draw(device_seed, a, first_iteration, m, nwalkers,
+        # ndim)` (EnsembleSampler(draws=...)), across runs and reset() (the class docstring).  Up to 4096 walkers.
         # overlap = None: consecutive half-steps run concurrently when the library's rule allows (an unsharded run whose two
         # half-steps fit the chip together: include/msx.h, msx_sampler_policy); False: plain launches -- the choice for a
         # GPU shared with other work, where a waiting workgroup's producer may not get a CU (the chunk then fails with
@@ -391,9 +414,11 @@ class DeviceEnsembleSampler(EnsembleSampler):
         if rng not in ('host', 'device'):
             raise ValueError("rng must be 'host' or 'device'")
         self.rng_mode = rng
-        self.device_seed = int(seed if seed is not None and not isinstance(seed, np.random.SeedSequence) else
-                               np.random.SeedSequence(seed).generate_state(1, dtype=np.uint64)[0]) & 0xffffffffffffffff
         self.shard = None if shard is None else (int(shard[0]), int(shard[1]))
+        if rng == 'device' and seed is None and self.shard is not None and self.shard[1] > 1:
+            # (every rank would draw its own entropy and propose its own moves while gathering the others' log-probabilities)
+            raise ValueError("rng='device' with shard=(rank, world > 1) needs a seed: every rank must draw the same stream")
+        self.device_seed = device_seed(seed) if rng == 'device' else None   # (the generator's key; None: the host draws)
         self.overlapped = None   # set by the first chunk of a run: did its half-steps overlap (include/msx.h)?
         self.engine = engine
         self._mode = {'logposterior': _lib.MODE_LOGPOST, 'loglikelihood': _lib.MODE_LOGLIKE}[mode]
@@ -422,7 +447,9 @@ class DeviceEnsembleSampler(EnsembleSampler):
 
         def enqueue(slot, m, arrays):
             if arrays is None:
-                ctx.sampler_enqueue_drawn(slot, m, self.device_seed, self.a)
+                # the device draws: the stream at its absolute iteration, which only a queued chunk advances
+                ctx.sampler_enqueue_drawn(slot, m, self.device_seed, self.a, self._drawn)
+                self._drawn += m
             else:
                 ctx.sampler_enqueue(slot, *arrays)
             self.overlapped = ctx.sampler_overlapped() == 1   # (half-steps on two streams: include/msx.h)

@@ -101,6 +101,13 @@ def main():
     print('posterior 16 / 50 / 84 ({} samples):'.format(int(summ['count'])))
     for nm, (lo, mid, hi) in zip(['T1', 'T2', 'Av', 'R1', 'R2', 'plx'], summ['quantiles']):
         print('  {:4s} {:.6g} / {:.6g} / {:.6g}'.format(nm, lo, mid, hi))
+    # ---- derived posteriors (mft6.py:2486-2593): the Kepler contrast and the planet-radius correction factors ----
+    kep_wl = np.linspace(4200.0, 9000.0, 200)   # a stand-in for bps/Kepler_Kepler.K.dat (get_transmission('kepler', res))
+    kep_tm = np.exp(-0.5 * ((kep_wl - 6400.0) / 1100.0) ** 2)
+    eng.stage_products((kep_wl, kep_tm), matrix=matrix)
+    prod = sampler.get_products(['kep_contrast', 'pri_corr', 'sec_corr'])
+    for nm, (lo, mid, hi) in zip(['dKep', 'f_pri', 'f_sec'], prod['quantiles']):
+        print('  {:5s} {:.6g} / {:.6g} / {:.6g}'.format(nm, lo, mid, hi))
     print('wrote', os.path.join(args.out, 'samples.txt'), samples.shape)
     return truth, med, samples
 

@@ -31,6 +31,14 @@ def print_summary(summ, targets):
                                                    for j, nm in enumerate(names)))
 
 
+def print_products(prod, targets):
+    """The Kepler contrast and the planet-radius correction factors of every target (mft6.py:2505, :2544-2545), 16 / 50 / 84:
+    sampler.get_products, every stored sample through the products kernel with its own target's tables."""
+    for k in range(targets):
+        print('target {}: '.format(k) + '  '.join('{} {:.5g} / {:.5g} / {:.5g}'.format(nm, *prod['quantiles'][k, j])
+                                                   for j, nm in enumerate(['dKep', 'f_pri', 'f_sec'])))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--targets', type=int, default=4)
@@ -69,6 +77,8 @@ def main():
     bl = bands.make_bands(tabs, vw, vf)
     tmin, tmax = 3000.0, 4200.0
 
+    kep_wl = np.linspace(4200.0, 9000.0, 200)   # a stand-in for bps/Kepler_Kepler.K.dat (get_transmission('kepler', res))
+    kep_tm = np.exp(-0.5 * ((kep_wl - 6400.0) / 1100.0) ** 2)
     engines, truths = [], []
     for k in range(args.targets):
         truth = synth.TRUTH_THETA.copy()
@@ -84,6 +94,7 @@ def main():
         eng.stage_specs(specs)
         eng.stage_problem([wl_um, d / np.median(d)], 0.01 * f / np.median(d), fr, r, ctm, ptm, tmi, tma, matrix, nspec=2,
                           bands=bl, tmin=tmin, tmax=tmax)
+        eng.stage_products((kep_wl, kep_tm), matrix=matrix)
         engines.append(eng)
         truths.append(truth)
 
@@ -106,6 +117,7 @@ def main():
             print('target {}: Teff {:.0f} / {:.0f} (truth {:.0f} / {:.0f})'.format(k, *np.median(out[k][:, :2], axis=0), *truths[k][:2]))
         if args.device:
             print_summary(sampler.get_summary(), args.targets)
+            print_products(sampler.get_products(['kep_contrast', 'pri_corr', 'sec_corr']), args.targets)
         group.close()
         return sampler
     sampler.run_mcmc(p0s, args.nsteps)
@@ -118,6 +130,7 @@ def main():
             k, *np.median(flat[:, :2], axis=0), *truths[k][:2], sampler.acceptance_fraction[k].mean()))
     if args.device:
         print_summary(sampler.get_summary(discard=args.nsteps // 2), args.targets)
+        print_products(sampler.get_products(['kep_contrast', 'pri_corr', 'sec_corr'], discard=args.nsteps // 2), args.targets)
     group.close()
     return sampler
 

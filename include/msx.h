@@ -541,6 +541,87 @@ int msx_series_hist2d(msx_series *s, int64_t n, int64_t discard, int64_t thin, c
                       const double *xedges, int32_t nx, const double *yedges, int32_t ny, int32_t closed_last,
                       int64_t *counts_out);
 
+/* ---- derived posteriors: product bands and derived columns of samples -------------------------
+ * What the reference makes of chain samples after the run: make_composite(..., plot=True) (mft6.py:786-828) gives each
+ * star's Kepler-band and Gaia G magnitude, from which plot_results derives the Kepler contrast and the planet-radius
+ * correction factors (mft6.py:2505, :2544-2545), and the isochrone gives masses and luminosities (mft6.py:2679-2690).
+ * Band integrals are linear in the node spectra, so a product band is a per-node table built once at staging, as the
+ * staged problem's own bands are; a sample then costs one thread a recipe and a few table look-ups.                     */
+#define MSX_PB_TRAPZ 0 /* sum w S = np.trapz(S[mask] * interp1d(ran, tm)(wl[mask]), wl[mask])         mft6.py:792-799 */
+#define MSX_PB_SUM 1   /* sum w S = np.sum(S[mask] * interp1d(ran, tm)(wl[mask])): the triple's        mft6.py:820-822 */
+#define MSX_PB_MEAN 2  /* photon-counting mean flux (pyphot get_flux); magnitudes minus zero_mag       mft6.py:811-814 */
+typedef struct msx_products {
+    int32_t struct_size;      /* sizeof(msx_products), ABI check                                                         */
+    int32_t nbands;           /* 1 .. MSX_MAX_BANDS product bands                                                        */
+    const int32_t *band_kind; /* [nbands] MSX_PB_*                                                                       */
+    const int64_t *band_i0;   /* [nbands] first grid sample of each band: the layout of msx_problem's band_w             */
+    const int64_t *band_len;
+    const double *band_w;     /* concatenated weights                                                                    */
+    const double *band_zero_mag; /* [nbands] the zero-point magnitude subtracted from an MSX_PB_MEAN magnitude (others: unused) */
+    /* the product isochrone, sorted by Teff as interp1d sorts it: the first 200 rows of age 9.0     mft6.py:2604-2605,:2650,:2679 */
+    int32_t niso;
+    const double *iso_teff, *iso_mass, *iso_lum;
+} msx_products;
+/* Valid after msx_stage_problem; builds the per-node table of the product bands (once per copy of a component grid).
+ * Whatever drops the staged problem (staging it again, grid staging, broadening, rotation, splitting) drops the products.
+ * MSX_ERR_STATE: no problem staged.  MSX_ERR_RANGE: a band outside the staged grid, an unknown kind.                    */
+int msx_stage_products(msx_ctx *ctx, const msx_products *p);
+
+/* A derived COLUMN is a 32-bit code (kind << 24 | band << 8 | star); codes below ndim are the sample's own coordinates.
+ * b: a product band, s: a star (0 = primary), f / p: a contrast filter / photometric band of the staged problem.        */
+#define MSX_PCOL_BANDMAG(b, s) (0x01000000u | ((uint32_t)(b) << 8) | (uint32_t)(s)) /* -2.5 log10(star s's integral in band b), minus zero_mag for MSX_PB_MEAN  mft6.py:802,:813-814,:825 */
+#define MSX_PCOL_BANDMAG_SUM(b) (0x02000000u | ((uint32_t)(b) << 8))                /* the same of the stars' integrals summed in star order                     mft6.py:812 */
+#define MSX_PCOL_DMAG(b, s) (0x03000000u | ((uint32_t)(b) << 8) | (uint32_t)(s))    /* BANDMAG(b, s) - BANDMAG(b, 0): the Kepler contrast for s = 1              mft6.py:2505 */
+#define MSX_PCOL_PRI_CORR(b) (0x04000000u | ((uint32_t)(b) << 8))                   /* sqrt(1 + 10**(-0.4 DMAG(b, 1)))                                           mft6.py:2544 */
+#define MSX_PCOL_SEC_CORR(b) (0x05000000u | ((uint32_t)(b) << 8))                   /* ratio sqrt(1 + 10**(0.4 DMAG(b, 1))), ratio = the sample's R2 / R1 coordinate  mft6.py:2504,:2545 */
+#define MSX_PCOL_CONTRAST(f) (0x06000000u | (uint32_t)(f))                          /* the model contrast in the staged problem's filter f                       mft6.py:741,:747-749 */
+#define MSX_PCOL_PHOT(p) (0x07000000u | (uint32_t)(p))                              /* the unreddened model magnitude in its photometric band p                  mft6.py:780-783 */
+#define MSX_PCOL_LOGG(s) (0x08000000u | (uint32_t)(s))                              /* the isochrone's log g at T_s                                              mft6.py:95 */
+#define MSX_PCOL_MASS(s) (0x09000000u | (uint32_t)(s))                              /* the product isochrone's mass at T_s                                       mft6.py:2685-2686 */
+#define MSX_PCOL_LUM(s) (0x0a000000u | (uint32_t)(s))                               /* ... and luminosity                                                        mft6.py:2689-2690 */
+#define MSX_MAX_PCOLS 64 /* columns of one msx_products_batch call (msx_series_derive: MSX_MAX_DIM, a series' width) */
+/* theta [n][ndim] (ndim = 2 nspec + 2, the sampler's rows [T.., A_V, R1, ratios.., plx]) -> out [n][ncols], status [n]
+ * (MSX_W_*).  One thread per sample: the isochrone's log g per star, the Teff and log g brackets, the bilinear weights
+ * and the (R/d)^2 scale -- or, for a problem staged with dist_fit = 0, the ratio^2 scale of `distance=False`
+ * (mft6.py:698-703) -- then the columns from the per-node tables.  No prior is applied.  A sample whose status is not
+ * MSX_W_OK has NaN in every column: non-finite coordinates (MSX_W_REJECT), a Teff outside the isochrone -- the product
+ * isochrone too when a MASS or LUM column is asked for -- (MSX_W_VALUEERROR), a missing node or a bracket past the grid.
+ * MSX_ERR_STATE: no products staged.  MSX_ERR_RANGE: more than MSX_MAX_PCOLS columns, an unknown code, a band, star,
+ * filter or coordinate the staged tables do not have.                                                                  */
+int msx_products_batch(msx_ctx *ctx, const double *theta, int64_t n, int32_t ndim, const uint32_t *cols, int32_t ncols,
+                       double *out, int32_t *status);
+/* the same with device pointers (cols too) on a caller stream; does not synchronise; the codes are NOT checked        */
+int msx_products_batch_dev(msx_ctx *ctx, const double *d_theta, int64_t n, int32_t ndim, const uint32_t *d_cols, int32_t ncols,
+                           double *d_out, int32_t *d_status, void *hip_stream);
+/* The same map over rows of a series: rows row0 .. row0 + nrows - 1 of src (ndim = 2 nspec + 2) become rows row0 .. of
+ * dst, a series created with ndim = ncols and src's members; member m's walkers are evaluated with ctxs[m]'s problem and
+ * products (k = the series' member count; the contexts live on the series' device and share nspec).  A derived row
+ * carries the bits msx_products_batch gives that row.  dst grows as msx_series_append grows it and must hold at least
+ * row0 rows; rows from row0 on are overwritten and dst then holds max(rows, row0 + nrows) rows.  Synchronous, on src's
+ * stream; waits for nothing but the two series' latest growth copies: the rows read must be in place.  worst_status [k]
+ * (may be NULL): the worst sample status per member.  Afterwards msx_series_order_stats / _hist / _hist2d / _acf work on
+ * dst as on any series.  MSX_ERR_STATE: a member without staged products, a run attached to dst.  MSX_ERR_RANGE: ncols
+ * over MSX_MAX_DIM, a bad code, rows past src.  MSX_ERR_INVALID: series that do not match.                              */
+int msx_series_derive(msx_series *src, msx_ctx **ctxs, const uint32_t *cols, int32_t ncols, int64_t row0, int64_t nrows,
+                      msx_series *dst, int32_t *worst_status);
+
+/* The spectra of samples on the data pixels (mft6.py:2374-2415): out [n][1 + nspec][npix] in PIXEL order.  Rows 1 .. nspec
+ * hold each star's spectrum, scaled as in make_composite, reddened by the sample's A_V on the model grid and resampled to
+ * the staged problem's data pixels (:2394-2402); row 0 is their sum in star order (:744, :751).  With
+ * MSX_SPEC_MEDIAN_SCALE in flags row 0 is multiplied by median(data) / median(row 0) (:2409; the exact median, median.h's
+ * radix selection) and scale_out [n] receives the factor (1 without the flag).  A_V <= 0, or a problem staged without
+ * extinction, follows the likelihood's rule: no reddening (:1161).  One workgroup per sample; status [n] as for
+ * msx_products_batch (NaN rows and factor unless MSX_W_OK).  MSX_ERR_STATE: no products staged.                        */
+#define MSX_SPEC_MEDIAN_SCALE 1
+int msx_products_spectra(msx_ctx *ctx, const double *theta, int64_t n, int32_t ndim, int32_t flags, double *out, double *scale_out,
+                         int32_t *status);
+/* composite_kernel generalised (mft6.py:684-707): one row per star of the blend over grid samples [j0, j0 + n), scaled as
+ * msx_make_composite scales it -- comp_out [nspec][n]; the composite is the rows' sum in star order.  teff / logg / rad
+ * [nspec] and use_distance as for msx_make_composite.  Needs a staged problem (its nspec, its grid).  MSX_ERR_RANGE: a
+ * window outside the staged grid.                                                                                      */
+int msx_composite_parts(msx_ctx *ctx, const double *teff, const double *logg, const double *rad, int32_t use_distance, double plx,
+                        int64_t j0, int64_t n, double *comp_out, int32_t *status);
+
 /* ---- test hooks (used by tests/ only) ------------------------------------------------------------ */
 /* MSX_HOOK_LINKED_FAULT: value != 0 makes the workgroups of the linked form skip their signal -- and the walkers of an
  * overlapped sampler run the publication of their new version -- so that every in-kernel wait runs into its bound;

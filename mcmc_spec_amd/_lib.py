@@ -28,6 +28,9 @@ FORM_NAMES = {0: 'fused', 1: 'pair (planner + two walkers of one grid cell per w
 HOOK_LINKED_FAULT, HOOK_PAIR_LEASES = 1, 2  # include/msx.h MSX_HOOK_*
 MAX_SPEC, MAX_BANDS, MAX_DIM = 3, 8, 8
 MAX_GROUP = 64  # include/msx.h MSX_MAX_GROUP: members of a target group
+PB_TRAPZ, PB_SUM, PB_MEAN = 0, 1, 2  # include/msx.h MSX_PB_*: the kinds of a product band
+SPEC_MEDIAN_SCALE = 1  # include/msx.h MSX_SPEC_MEDIAN_SCALE
+MAX_PCOLS = 64  # include/msx.h MSX_MAX_PCOLS: derived columns of one products_batch call
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int64)
@@ -50,6 +53,15 @@ class MsxProblem(C.Structure):
         ('prior_mean', C.c_double * MAX_DIM), ('prior_sig', C.c_double * MAX_DIM),
         ('use_av', C.c_int32), ('dist_fit', C.c_int32), ('rad_prior', C.c_int32), ('has_prior_list', C.c_int32),
         ('no_spectrum', C.c_int32),
+    ]
+
+
+class MsxProducts(C.Structure):
+    """Mirror of ``struct msx_products`` (include/msx.h) -- keep the field order identical."""
+    _fields_ = [
+        ('struct_size', C.c_int32), ('nbands', C.c_int32),
+        ('band_kind', C.POINTER(C.c_int32)), ('band_i0', _ip), ('band_len', _ip), ('band_w', _dp), ('band_zero_mag', _dp),
+        ('niso', C.c_int32), ('iso_teff', _dp), ('iso_mass', _dp), ('iso_lum', _dp),
     ]
 
 
@@ -171,6 +183,12 @@ def load():
         'msx_series_hist': (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, _up, C.c_int32, _dp, C.c_int32, C.c_int32, _ip]),
         'msx_series_hist2d': (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, _up, C.c_int32, _dp, C.c_int32, _dp, C.c_int32,
                                         C.c_int32, _ip]),
+        'msx_stage_products': (C.c_int, [vp, C.POINTER(MsxProducts)]),
+        'msx_products_batch': (C.c_int, [vp, _dp, C.c_int64, C.c_int32, _up, C.c_int32, _dp, C.POINTER(C.c_int32)]),
+        'msx_products_batch_dev': (C.c_int, [vp, vp, C.c_int64, C.c_int32, vp, C.c_int32, vp, vp, vp]),
+        'msx_products_spectra': (C.c_int, [vp, _dp, C.c_int64, C.c_int32, C.c_int32, _dp, _dp, C.POINTER(C.c_int32)]),
+        'msx_composite_parts': (C.c_int, [vp, _dp, _dp, _dp, C.c_int32, C.c_double, C.c_int64, C.c_int64, _dp, C.POINTER(C.c_int32)]),
+        'msx_series_derive': (C.c_int, [vp, C.POINTER(vp), _up, C.c_int32, C.c_int64, C.c_int64, vp, C.POINTER(C.c_int32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = header/library skew, fail loudly
@@ -194,7 +212,9 @@ EXPORTED = ['msx_create', 'msx_destroy', 'msx_last_error', 'msx_device_info', 'm
             'msx_group_sampler_enqueue_drawn', 'msx_group_sampler_collect', 'msx_group_sampler_end',
             'msx_series_create', 'msx_series_destroy', 'msx_series_last_error', 'msx_series_rows', 'msx_sampler_attach_series',
             'msx_group_sampler_attach_series', 'msx_series_append', 'msx_series_read', 'msx_series_acf',
-            'msx_series_order_stats', 'msx_series_hist', 'msx_series_hist2d']
+            'msx_series_order_stats', 'msx_series_hist', 'msx_series_hist2d',
+            'msx_stage_products', 'msx_products_batch', 'msx_products_batch_dev', 'msx_series_derive',
+            'msx_products_spectra', 'msx_composite_parts']
 
 
 def as_f64(a):
@@ -219,6 +239,60 @@ def col_ratio(a, b):
     if not (0 <= a < 256 and 0 <= b < 256):
         raise ValueError('col_ratio: coordinates must lie in 0 .. 255')
     return 0x80000000 | (a << 8) | b
+
+
+def _pcol(kind, b=0, s=0):
+    b, s = int(b), int(s)
+    if not (0 <= b < 256 and 0 <= s < 256):
+        raise ValueError('derived column: band and star / filter indices must lie in 0 .. 255')
+    return (kind << 24) | (b << 8) | s
+
+
+# the codes of derived columns (include/msx.h, MSX_PCOL_*): b a product band, s a star, f / p a filter / band of the problem
+def pcol_bandmag(b, s):
+    return _pcol(1, b, s)
+
+
+def pcol_bandmag_sum(b):
+    return _pcol(2, b)
+
+
+def pcol_dmag(b, s=1):
+    return _pcol(3, b, s)
+
+
+def pcol_pri_corr(b):
+    return _pcol(4, b)
+
+
+def pcol_sec_corr(b):
+    return _pcol(5, b)
+
+
+def pcol_contrast(f):
+    return _pcol(6, 0, f)
+
+
+def pcol_phot(p):
+    return _pcol(7, 0, p)
+
+
+def pcol_logg(s):
+    return _pcol(8, 0, s)
+
+
+def pcol_mass(s):
+    return _pcol(9, 0, s)
+
+
+def pcol_lum(s):
+    return _pcol(10, 0, s)
+
+
+def pcol_decode(code):
+    """(kind, band, index) of a derived column's code; kind 0 is a coordinate."""
+    code = int(code)
+    return code >> 24, (code >> 8) & 0xff, code & 0xff
 
 
 def _col_codes(cols):
@@ -356,6 +430,47 @@ class Context:
     # ---- problem + hot path -----------------------------------------------------------------------
     def stage_problem(self, prob: MsxProblem):
         self.check(self.lib.msx_stage_problem(self.h, C.byref(prob)))
+
+    def stage_products(self, prod: MsxProducts):
+        self.check(self.lib.msx_stage_products(self.h, C.byref(prod)))
+
+    def products_batch(self, theta, cols):
+        """(values (n, ncols), status (n,)): the derived columns ``cols`` (codes) of the samples theta (n, ndim)
+        (msx_products_batch); NaN where the status is not W_OK."""
+        theta = as_f64(theta)
+        cols = _col_codes(cols)
+        n, ndim = theta.shape
+        out = np.empty((n, cols.size))
+        status = np.zeros(n, dtype=np.int32)
+        self.check(self.lib.msx_products_batch(self.h, dptr(theta), n, ndim, uptr(cols), cols.size, dptr(out),
+                                               status.ctypes.data_as(C.POINTER(C.c_int32))))
+        return out, status
+
+    def products_spectra(self, theta, nspec, npix, median_scale=True):
+        """(spectra (n, 1 + nspec, npix) in pixel order, scale (n,), status (n,)): msx_products_spectra."""
+        theta = as_f64(theta)
+        n, ndim = theta.shape
+        out = np.empty((n, 1 + int(nspec), int(npix)))
+        scale = np.empty(n)
+        status = np.zeros(n, dtype=np.int32)
+        self.check(self.lib.msx_products_spectra(self.h, dptr(theta), n, ndim, SPEC_MEDIAN_SCALE if median_scale else 0, dptr(out),
+                                                 dptr(scale), status.ctypes.data_as(C.POINTER(C.c_int32))))
+        return out, scale, status
+
+    def composite_parts(self, teff, logg, rad, use_distance, plx, j0, n):
+        """(parts (nspec, n), status): each star's scaled blend over grid samples [j0, j0 + n) (msx_composite_parts)."""
+        teff, logg = as_f64(teff), as_f64(logg)
+        r = np.zeros(len(teff))
+        r[:len(rad)] = rad
+        out = np.empty((len(teff), int(n)))
+        status = C.c_int32(0)
+        self.check(self.lib.msx_composite_parts(self.h, dptr(teff), dptr(logg), dptr(r), int(bool(use_distance)), float(plx),
+                                                int(j0), int(n), dptr(out), C.byref(status)))
+        return out, status.value
+
+    def products_batch_dev(self, d_theta_ptr, n, ndim, d_cols_ptr, ncols, d_out_ptr, d_status_ptr, stream_ptr):
+        self.check(self.lib.msx_products_batch_dev(self.h, d_theta_ptr, int(n), int(ndim), d_cols_ptr, int(ncols), d_out_ptr,
+                                                   d_status_ptr, stream_ptr))
 
     def logprob_batch(self, theta, mode=MODE_LOGPOST):
         theta = as_f64(theta)
@@ -786,6 +901,21 @@ class Series:
         f = np.full((self.k, self.ndim, nlag), np.nan)
         self.check(self.lib.msx_series_acf(self.h, int(n), int(discard), int(thin), int(lag0), nlag, mask, dptr(f)))
         return f
+
+    def derive(self, contexts, cols, dst, row0=0, nrows=None):
+        """Rows row0 .. row0 + nrows - 1 of this series mapped to the derived columns ``cols`` (codes) and written to the
+        same rows of ``dst`` (ndim = len(cols), the same members); member m is evaluated with ``contexts[m]``
+        (msx_series_derive).  Returns the members' worst sample status (k,)."""
+        cols = _col_codes(cols)
+        contexts = list(contexts)
+        if len(contexts) != self.k:
+            raise ValueError('derive: one context per member ({} members, {} contexts)'.format(self.k, len(contexts)))
+        nrows = self.rows - int(row0) if nrows is None else int(nrows)
+        arr = (C.c_void_p * self.k)(*[c.h for c in contexts])
+        worst = np.zeros(self.k, dtype=np.int32)
+        self.check(self.lib.msx_series_derive(self.h, arr, uptr(cols), cols.size, int(row0), nrows, dst.h,
+                                              worst.ctypes.data_as(C.POINTER(C.c_int32))))
+        return worst
 
     def order_stats(self, n, discard, thin, cols, ranks):
         """(values (k, ncols, nranks), counts (k,)): the elements of zero-based ranks ``ranks`` (k, nranks; one row is

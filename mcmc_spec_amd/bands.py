@@ -85,7 +85,11 @@ def from_pyphot(lib, names=BAND_NAMES_6):
     for n in names:
         f = lib[n]
         w = np.asarray(getattr(f.wavelength, 'magnitude', f.wavelength), dtype=float)
-        zero = f.Vega_zero_flux if '2MASS' in n else f.AB_zero_flux
+        vega = '2MASS' in n or n.startswith('Gaia')  # (Gaia_G: the band of make_composite(plot=True), mft6.py:811-814)
+        zero = f.Vega_zero_flux if vega else f.AB_zero_flux
         zero = float(getattr(zero, 'magnitude', getattr(zero, 'value', zero)))
         out[n] = Band(n, w, np.asarray(f.transmit, dtype=float), zero)
+        if n.startswith('Gaia'):
+            zm = f.Vega_zero_mag
+            out[n].zero_mag = float(getattr(zm, 'magnitude', getattr(zm, 'value', zm)))
     return out

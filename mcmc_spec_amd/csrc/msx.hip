@@ -67,6 +67,7 @@
 #include "inpath_kernels.h"
 #include "autocorr_kernels.h"
 #include "summary_kernels.h"
+#include "product_kernels.h"
 #include "opt_run_kernels.h"
 
 // ================================================================================================
@@ -164,6 +165,15 @@ struct msx_ctx {
     // the groups this context belongs to (back-pointers: msx_destroy clears its slots in them, msx_group_destroy leaves)
     uint64_t prob_gen = 0;
     std::vector<struct msx_group *> groups;
+    // derived posteriors (msx_stage_products; product_kernels.h): the product bands' per-node table and the product
+    // isochrone (prod_allocs), this context's record for the kernels (host copy + device copy), the window of plot=True,
+    // and the device buffer the host-pointer batches go through.  Dropped with the problem (free_problem).
+    bool products_staged = false;
+    ProdMember PM;
+    ProdMember *d_prod_member = nullptr;
+    std::vector<void *> prod_allocs;
+    char *d_prod_buf = nullptr;
+    size_t prod_buf_bytes = 0;
 };
 static void sampler_free(msx_ctx *c);
 static void opt_run_free(msx_ctx *c);
@@ -294,6 +304,12 @@ void free_problem(msx_ctx *c) {
     for (void *p : c->prob_allocs) (void)hipFree(p);
     c->prob_allocs.clear();
     c->problem_staged = false;
+    for (void *p : c->prod_allocs) (void)hipFree(p);  // the products read the problem's tables: they go with it
+    c->prod_allocs.clear();
+    if (c->d_prod_buf) (void)hipFree(c->d_prod_buf);
+    c->d_prod_buf = nullptr; c->prod_buf_bytes = 0;
+    c->d_prod_member = nullptr;
+    c->products_staged = false;
     if (c->d_opt_flux) (void)hipFree(c->d_opt_flux);
     if (c->d_opt_med) (void)hipFree(c->d_opt_med);
     c->d_opt_flux = c->d_opt_med = nullptr;
@@ -3783,6 +3799,286 @@ int msx_series_hist2d(msx_series *sr, int64_t n, int64_t discard, int64_t thin, 
         for (int64_t j = 0; j < jobs; ++j)
             memcpy(counts_out + ((j / npl) * npairs + p0 + j % npl) * nb, hc.data() + j * nb, sizeof(int64_t) * (size_t)nb);
     }
+    return MSX_OK;
+}
+
+// ---- derived posteriors ---------------------------------------------------------------------------
+int msx_stage_products(msx_ctx *c, const msx_products *p) {
+    if (!c || !p) return MSX_ERR_INVALID;
+    if (p->struct_size != (int32_t)sizeof(msx_products))
+        return fail(c, MSX_ERR_INVALID, "msx_stage_products: struct_size mismatch (header/library skew)");
+    if (!c->problem_staged) return fail(c, MSX_ERR_STATE, "msx_stage_products: stage the problem first");
+    if (p->nbands < 1 || p->nbands > MSX_MAX_BANDS || !p->band_kind || !p->band_i0 || !p->band_len || !p->band_w || !p->band_zero_mag)
+        return fail(c, MSX_ERR_INVALID, "msx_stage_products: 1 .. MSX_MAX_BANDS product bands");
+    if (p->niso < 2 || !p->iso_teff || !p->iso_mass || !p->iso_lum)
+        return fail(c, MSX_ERR_INVALID, "msx_stage_products: the product isochrone needs >= 2 rows");
+    for (int32_t i = 0; i + 1 < p->niso; ++i)
+        if (!(p->iso_teff[i] <= p->iso_teff[i + 1])) return fail(c, MSX_ERR_INVALID, "msx_stage_products: the product isochrone must be sorted by Teff");
+    const int nb = p->nbands;
+    std::vector<int64_t> woff((size_t)nb);
+    int64_t tot = 0;
+    for (int b = 0; b < nb; ++b) {
+        if (p->band_kind[b] != MSX_PB_TRAPZ && p->band_kind[b] != MSX_PB_SUM && p->band_kind[b] != MSX_PB_MEAN)
+            return fail(c, MSX_ERR_RANGE, "msx_stage_products: unknown band kind");
+        if (p->band_i0[b] < 0 || p->band_len[b] < 1 || p->band_i0[b] + p->band_len[b] > c->nwl)
+            return fail(c, MSX_ERR_RANGE, "msx_stage_products: band weights run outside the staged grid");
+        woff[(size_t)b] = tot;
+        tot += p->band_len[b];
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    for (void *q : c->prod_allocs) (void)hipFree(q);
+    c->prod_allocs.clear();
+    c->d_prod_member = nullptr;  // (a restage that fails below leaves no products and no pointer to the freed record)
+    c->products_staged = false;
+    std::vector<void *> &tr = c->prod_allocs;
+    const int64_t nn = grid_rows(c);
+    int rc;
+    double *d_w = nullptr, *d_tab = nullptr, *d_t = nullptr, *d_m = nullptr, *d_l = nullptr;
+    int64_t *d_woff = nullptr, *d_i0 = nullptr, *d_len = nullptr;
+    if ((rc = dev_alloc_copy(c, &tr, p->band_w, tot, &d_w))) return rc;
+    if ((rc = dev_alloc_copy(c, &tr, woff.data(), (int64_t)nb, &d_woff))) return rc;
+    if ((rc = dev_alloc_copy(c, &tr, p->band_i0, (int64_t)nb, &d_i0))) return rc;
+    if ((rc = dev_alloc_copy(c, &tr, p->band_len, (int64_t)nb, &d_len))) return rc;
+    HIP_TRY(c, hipMalloc((void **)&d_tab, sizeof(double) * (size_t)(nn * nb))); tr.push_back(d_tab);
+    // one row of integrals per node and per copy of a component grid: the staged problem's own band kernel
+    hipLaunchKernelGGL(band_integral_kernel, dim3((unsigned)nb, (unsigned)nn), dim3(256), 0, c->stream, c->d_grid, c->nwl, d_w, d_woff,
+                       d_i0, d_len, nb, d_tab);
+    HIP_TRY(c, hipGetLastError());
+    if ((rc = dev_alloc_copy(c, &tr, p->iso_teff, (int64_t)p->niso, &d_t))) return rc;
+    if ((rc = dev_alloc_copy(c, &tr, p->iso_mass, (int64_t)p->niso, &d_m))) return rc;
+    if ((rc = dev_alloc_copy(c, &tr, p->iso_lum, (int64_t)p->niso, &d_l))) return rc;
+    ProdMember &M = c->PM;
+    memset(&M, 0, sizeof(M));
+    const DevProblem &P = c->P;
+    M.teff_nodes = P.teff_nodes; M.logg_nodes = P.logg_nodes; M.present = P.present;
+    M.iso_t = P.iso_t; M.iso_g = P.iso_g; M.piso_t = d_t; M.piso_m = d_m; M.piso_l = d_l;
+    M.band_tab = P.band_tab; M.prod_tab = d_tab;
+    for (int i = 0; i < MSX_MAX_BANDS; ++i) M.pzero[i] = i < P.np ? P.pzero[i] : 1.0;
+    for (int b = 0; b < nb; ++b) { M.kind[b] = p->band_kind[b]; M.zero_mag[b] = p->band_zero_mag[b]; }
+    M.nt = P.nt; M.ng = P.ng; M.node_stride = P.node_stride; M.niso = P.niso; M.npiso = p->niso;
+    M.nc = P.nc; M.np = P.np; M.npb = nb; M.nspec = P.nspec; M.dist_fit = P.dist_fit;
+    M.grid = c->d_grid; M.kgrid = c->d_kgrid; M.pix_lo = c->d_pix_lo; M.pix_t = P.pix_t; M.nwl = c->nwl; M.npix = P.npix;
+    M.median_flux = P.median_flux; M.use_av = P.use_av;
+    if ((rc = dev_alloc_copy(c, &tr, &M, (int64_t)1, &c->d_prod_member))) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->products_staged = true;
+    return MSX_OK;
+}
+
+// the codes against one context's tables; *need_piso: a MASS or LUM column is among them
+static bool products_cols_ok(const msx_ctx *c, const uint32_t *cols, int32_t ncols, int32_t *need_piso) {
+    const ProdMember &M = c->PM;
+    for (int32_t j = 0; j < ncols; ++j) {
+        if (!pcol_known(cols[j], 2 * M.nspec + 2, M.nspec, M.npb, M.nc, M.np)) return false;
+        const uint32_t kind = cols[j] >> 24;
+        if (kind == kPcolMass || kind == kPcolLum) *need_piso = 1;
+    }
+    return true;
+}
+
+static void products_launch(int nspec, const ProdLaunch &L, int64_t max_count, int k, hipStream_t st) {
+    const dim3 grid((unsigned)((max_count + kProdThreads - 1) / kProdThreads), (unsigned)k);
+    if (nspec == 2) hipLaunchKernelGGL(products_kernel<2>, grid, dim3(kProdThreads), 0, st, L);
+    else hipLaunchKernelGGL(products_kernel<3>, grid, dim3(kProdThreads), 0, st, L);
+}
+
+// (need_piso < 0: the codes live on the device and were not looked at -- the product isochrone's range is then enforced)
+static int products_batch_launch(msx_ctx *c, const double *d_theta, int64_t n, int32_t ndim, const uint32_t *d_cols, int32_t ncols,
+                                 double *d_out, int32_t *d_status, hipStream_t st, int32_t need_piso) {
+    ProdLaunch L;
+    memset(&L, 0, sizeof(L));
+    L.members = c->d_prod_member; L.off = nullptr; L.n_single = n;
+    L.in = d_theta; L.in_sw = ndim; L.in_sr = 0; L.in_sd = 1;
+    L.out = d_out; L.out_sw = ncols; L.out_sr = 0; L.out_sd = 1;
+    L.row0 = 0; L.nrows = 1; L.cols = d_cols; L.ncols = ncols; L.need_piso = need_piso != 0;
+    L.status = d_status; L.worst = nullptr;
+    products_launch(c->P.nspec, L, n, 1, st);
+    HIP_TRY(c, hipGetLastError());
+    return MSX_OK;
+}
+
+static int products_batch_check(msx_ctx *c, const char *who, const void *theta, int64_t n, int32_t ndim, const void *cols, int32_t ncols,
+                                const void *out, const void *status) {
+    const std::string w(who);
+    if (!theta || !cols || !out || !status || n < 0 || ncols < 1) return fail(c, MSX_ERR_INVALID, w + ": bad arguments");
+    if (!c->problem_staged || !c->products_staged) return fail(c, MSX_ERR_STATE, w + ": no products staged (msx_stage_products)");
+    if (ndim != 2 * c->P.nspec + 2) return fail(c, MSX_ERR_INVALID, w + ": ndim must be 2 * nspec + 2");
+    if (ncols > MSX_MAX_PCOLS) return fail(c, MSX_ERR_RANGE, w + ": more than MSX_MAX_PCOLS columns");
+    return MSX_OK;
+}
+
+int msx_products_batch_dev(msx_ctx *c, const double *d_theta, int64_t n, int32_t ndim, const uint32_t *d_cols, int32_t ncols,
+                           double *d_out, int32_t *d_status, void *hip_stream) {
+    if (!c) return MSX_ERR_INVALID;
+    if (int rc = products_batch_check(c, "msx_products_batch_dev", d_theta, n, ndim, d_cols, ncols, d_out, d_status)) return rc;
+    if (n == 0) return MSX_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    return products_batch_launch(c, d_theta, n, ndim, d_cols, ncols, d_out, d_status, (hipStream_t)hip_stream, -1);
+}
+
+int msx_products_batch(msx_ctx *c, const double *theta, int64_t n, int32_t ndim, const uint32_t *cols, int32_t ncols, double *out,
+                       int32_t *status) {
+    if (!c) return MSX_ERR_INVALID;
+    if (int rc = products_batch_check(c, "msx_products_batch", theta, n, ndim, cols, ncols, out, status)) return rc;
+    int32_t need_piso = 0;
+    if (!products_cols_ok(c, cols, ncols, &need_piso))
+        return fail(c, MSX_ERR_RANGE, "msx_products_batch: a column code the staged problem and products cannot answer");
+    if (n == 0) return MSX_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    // [theta | out | status | cols] in one device buffer that grows with the batch
+    const size_t b_theta = sizeof(double) * (size_t)(n * ndim), b_out = sizeof(double) * (size_t)(n * ncols);
+    const size_t b_status = sizeof(int32_t) * (size_t)n, b_cols = sizeof(uint32_t) * (size_t)ncols;
+    const size_t need = b_theta + b_out + b_status + b_cols;
+    if (need > c->prod_buf_bytes) {
+        if (c->d_prod_buf) (void)hipFree(c->d_prod_buf);
+        c->d_prod_buf = nullptr; c->prod_buf_bytes = 0;
+        HIP_TRY(c, hipMalloc((void **)&c->d_prod_buf, need));
+        c->prod_buf_bytes = need;
+    }
+    double *d_theta = reinterpret_cast<double *>(c->d_prod_buf);
+    double *d_out = reinterpret_cast<double *>(c->d_prod_buf + b_theta);
+    int32_t *d_status = reinterpret_cast<int32_t *>(c->d_prod_buf + b_theta + b_out);
+    uint32_t *d_cols = reinterpret_cast<uint32_t *>(c->d_prod_buf + b_theta + b_out + b_status);
+    HIP_TRY(c, hipMemcpyAsync(d_theta, theta, b_theta, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_cols, cols, b_cols, hipMemcpyHostToDevice, c->stream));
+    if (int rc = products_batch_launch(c, d_theta, n, ndim, d_cols, ncols, d_out, d_status, c->stream, need_piso)) return rc;
+    HIP_TRY(c, hipMemcpyAsync(out, d_out, b_out, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(status, d_status, b_status, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return MSX_OK;
+}
+
+int msx_products_spectra(msx_ctx *c, const double *theta, int64_t n, int32_t ndim, int32_t flags, double *out, double *scale_out,
+                         int32_t *status) {
+    if (!c) return MSX_ERR_INVALID;
+    if (!theta || !out || !scale_out || !status || n < 0 || (flags & ~MSX_SPEC_MEDIAN_SCALE))
+        return fail(c, MSX_ERR_INVALID, "msx_products_spectra: bad arguments");
+    if (!c->problem_staged || !c->products_staged) return fail(c, MSX_ERR_STATE, "msx_products_spectra: no products staged (msx_stage_products)");
+    if (ndim != 2 * c->P.nspec + 2) return fail(c, MSX_ERR_INVALID, "msx_products_spectra: ndim must be 2 * nspec + 2");
+    if (c->P.npix > INT32_MAX) return fail(c, MSX_ERR_RANGE, "msx_products_spectra: too many pixels");
+    if (n == 0) return MSX_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int ns = c->P.nspec;
+    const size_t b_out = sizeof(double) * (size_t)(n * (1 + ns) * c->P.npix), b_theta = sizeof(double) * (size_t)(n * ndim);
+    const size_t b_scale = sizeof(double) * (size_t)n, b_status = sizeof(int32_t) * (size_t)n;
+    const size_t need = b_out + b_theta + b_scale + b_status;
+    if (need > c->prod_buf_bytes) {
+        if (c->d_prod_buf) (void)hipFree(c->d_prod_buf);
+        c->d_prod_buf = nullptr; c->prod_buf_bytes = 0;
+        HIP_TRY(c, hipMalloc((void **)&c->d_prod_buf, need));
+        c->prod_buf_bytes = need;
+    }
+    SpecLaunch L;
+    memset(&L, 0, sizeof(L));
+    L.M = c->d_prod_member;
+    L.out = reinterpret_cast<double *>(c->d_prod_buf);
+    double *d_theta = reinterpret_cast<double *>(c->d_prod_buf + b_out);
+    L.theta = d_theta;
+    L.scale_out = reinterpret_cast<double *>(c->d_prod_buf + b_out + b_theta);
+    L.status = reinterpret_cast<int32_t *>(c->d_prod_buf + b_out + b_theta + b_scale);
+    L.ndim = ndim; L.flags = flags;
+    HIP_TRY(c, hipMemcpyAsync(d_theta, theta, b_theta, hipMemcpyHostToDevice, c->stream));
+    if (ns == 2) hipLaunchKernelGGL(products_spectra_kernel<2>, dim3((unsigned)n), dim3(kProdThreads), 0, c->stream, L);
+    else hipLaunchKernelGGL(products_spectra_kernel<3>, dim3((unsigned)n), dim3(kProdThreads), 0, c->stream, L);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(out, L.out, b_out, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(scale_out, L.scale_out, b_scale, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(status, L.status, b_status, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return MSX_OK;
+}
+
+int msx_composite_parts(msx_ctx *c, const double *teff, const double *logg, const double *rad, int32_t use_distance, double plx,
+                        int64_t j0, int64_t n, double *comp_out, int32_t *status) {
+    if (!c) return MSX_ERR_INVALID;
+    if (!c->problem_staged) return fail(c, MSX_ERR_STATE, "msx_composite_parts: no problem staged");
+    if (!teff || !logg || !rad || !comp_out || !status) return fail(c, MSX_ERR_INVALID, "msx_composite_parts: bad arguments");
+    if (j0 < 0 || n < 1 || j0 + n > c->nwl) return fail(c, MSX_ERR_RANGE, "msx_composite_parts: the window is outside the staged grid");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int ns = c->P.nspec;
+    double args[3 * MSX_MAX_SPEC + 1];
+    for (int i = 0; i < ns; ++i) { args[i] = teff[i]; args[ns + i] = logg[i]; args[2 * ns + i] = rad[i]; }
+    args[3 * ns] = plx;
+    double *d_out = nullptr;
+    HIP_TRY(c, hipMalloc((void **)&d_out, sizeof(double) * (size_t)(ns * n)));
+    double *d_args = c->d_misc;
+    WalkerDesc *d_desc = reinterpret_cast<WalkerDesc *>(c->d_misc + 64);
+    WalkerDesc h;
+    hipError_t e = hipMemcpyAsync(d_args, args, sizeof(double) * (3 * ns + 1), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(composite_setup_kernel, dim3(1), dim3(64), 0, c->stream, c->P, d_args, (int)use_distance, d_desc);
+        hipLaunchKernelGGL(composite_parts_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)ns), dim3(256), 0, c->stream, c->P, d_desc,
+                           j0, n, d_out);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&h, d_desc, sizeof(WalkerDesc), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess && h.status == MSX_W_OK) e = hipMemcpy(comp_out, d_out, sizeof(double) * (size_t)(ns * n), hipMemcpyDeviceToHost);
+    (void)hipFree(d_out);
+    if (e != hipSuccess) return fail(c, MSX_ERR_HIP, std::string("msx_composite_parts: ") + hipGetErrorString(e));
+    *status = h.status;
+    return MSX_OK;
+}
+
+int msx_series_derive(msx_series *src, msx_ctx **ctxs, const uint32_t *cols, int32_t ncols, int64_t row0, int64_t nrows, msx_series *dst,
+                      int32_t *worst_status) {
+    if (!src) return MSX_ERR_INVALID;
+    if (!dst || !ctxs || !cols || ncols < 1 || row0 < 0 || nrows < 1) return fail(src, MSX_ERR_INVALID, "msx_series_derive: bad arguments");
+    if (ncols > MSX_MAX_DIM) return fail(src, MSX_ERR_RANGE, "msx_series_derive: more columns than a series is wide (MSX_MAX_DIM)");
+    if (dst == src || dst->device != src->device || dst->nw != src->nw || dst->off != src->off || dst->ndim != ncols)
+        return fail(src, MSX_ERR_INVALID, "msx_series_derive: dst must be another series on the same device with src's members and ndim = ncols");
+    if (dst->run) return fail(src, MSX_ERR_STATE, "msx_series_derive: a run in flight appends to dst");
+    if (row0 + nrows > src->rows) return fail(src, MSX_ERR_RANGE, "msx_series_derive: rows past the ones src holds");
+    if (row0 > dst->rows) return fail(src, MSX_ERR_RANGE, "msx_series_derive: row0 past the rows dst holds (it would leave a gap)");
+    const int k = (int)src->off.size() - 1;
+    int32_t need_piso = 0;
+    int nspec = 0;
+    for (int m = 0; m < k; ++m) {
+        const msx_ctx *c = ctxs[m];
+        const std::string who = "msx_series_derive: member " + std::to_string(m);
+        if (!c) return fail(src, MSX_ERR_INVALID, who + " is null");
+        if (c->device != src->device) return fail(src, MSX_ERR_INVALID, who + " lives on another device");
+        if (!c->problem_staged || !c->products_staged) return fail(src, MSX_ERR_STATE, who + " has no staged products (msx_stage_products)");
+        if (m == 0) nspec = c->PM.nspec;
+        if (c->PM.nspec != nspec || src->ndim != 2 * nspec + 2)
+            return fail(src, MSX_ERR_INVALID, who + ": src's ndim must be 2 * nspec + 2 of every member");
+        if (!products_cols_ok(c, cols, ncols, &need_piso))
+            return fail(src, MSX_ERR_RANGE, who + " cannot answer a column code (band, star, filter or coordinate it does not have)");
+    }
+    HIP_TRY(src, hipSetDevice(src->device));
+    hipStream_t st = src->stream;
+    // dst grows the way append grows it: the copy and its event on the stream that then writes the rows
+    HIP_TRY(src, series_reserve(dst, row0 + nrows, dst->rows, st));
+    const size_t b_mem = sizeof(ProdMember) * (size_t)k, b_worst = sizeof(int32_t) * (size_t)k, b_cols = sizeof(uint32_t) * (size_t)ncols;
+    HIP_TRY(src, series_scratch(src, b_mem + b_worst + b_cols));
+    ProdMember *d_mem = reinterpret_cast<ProdMember *>(src->d_scratch);
+    int32_t *d_worst = reinterpret_cast<int32_t *>(src->d_scratch + b_mem);
+    uint32_t *d_cols = reinterpret_cast<uint32_t *>(src->d_scratch + b_mem + b_worst);
+    std::vector<ProdMember> mem((size_t)k);
+    int64_t max_count = 0;
+    for (int m = 0; m < k; ++m) {
+        mem[(size_t)m] = ctxs[m]->PM;
+        max_count = std::max(max_count, (src->off[(size_t)m + 1] - src->off[(size_t)m]) * nrows);
+    }
+    HIP_TRY(src, hipMemcpyAsync(d_mem, mem.data(), b_mem, hipMemcpyHostToDevice, st));
+    HIP_TRY(src, hipMemsetAsync(d_worst, 0, b_worst, st));
+    HIP_TRY(src, hipMemcpyAsync(d_cols, cols, b_cols, hipMemcpyHostToDevice, st));
+    HIP_TRY(src, series_wait_growth(src));
+    if (dst->grown_set) HIP_TRY(src, hipStreamWaitEvent(st, dst->grown, 0));
+    ProdLaunch L;
+    memset(&L, 0, sizeof(L));
+    L.members = d_mem; L.off = src->d_off;
+    L.in = src->d_rows; L.in_sw = src->cap; L.in_sr = 1; L.in_sd = src->nw * src->cap;
+    L.out = dst->d_rows; L.out_sw = dst->cap; L.out_sr = 1; L.out_sd = dst->nw * dst->cap;
+    L.row0 = row0; L.nrows = nrows; L.cols = d_cols; L.ncols = ncols; L.need_piso = need_piso;
+    L.status = nullptr; L.worst = d_worst;
+    products_launch(nspec, L, max_count, k, st);
+    HIP_TRY(src, hipGetLastError());
+    std::vector<int32_t> worst((size_t)k, 0);
+    HIP_TRY(src, hipMemcpyAsync(worst.data(), d_worst, b_worst, hipMemcpyDeviceToHost, st));
+    HIP_TRY(src, hipStreamSynchronize(st));
+    if (worst_status) memcpy(worst_status, worst.data(), b_worst);
+    dst->rows = std::max(dst->rows, row0 + nrows);
     return MSX_OK;
 }
 

@@ -56,6 +56,7 @@ class Engine:
         self.device = device
         self.grid = None
         self.tables = None
+        self.products = None
 
     # ---- A0 ---------------------------------------------------------------------------------------
     def stage_grid(self, wl, teff_nodes, logg_nodes, flux, present=None):
@@ -77,6 +78,7 @@ class Engine:
         self.grid = dict(wl=np.asarray(wl, dtype=float), teff=np.asarray(teff_nodes, dtype=float),
                          logg=np.asarray(logg_nodes, dtype=float))
         self.tables = None
+        self.products = None
 
     def broaden_grid_window(self, w_aa, resolution, placement='staging', vsini=0, limb=0):
         """Broaden every node over the data window ``[min(w), max(w)]`` [A] in place: the staging step
@@ -98,6 +100,7 @@ class Engine:
         idx = np.where((wl >= min(w_aa)) & (wl <= max(w_aa)))[0]
         self.ctx.broaden_grid(int(idx[0]), int(idx.size), resolution, 5.0)
         self.tables = None
+        self.products = None   # (the library drops the problem and its products with it)
         if pairs is None:
             if vsini != 0 and limb != 0:
                 self.ctx.rot_broaden_grid(int(idx[0]), int(idx.size), vsini, limb)
@@ -122,6 +125,8 @@ class Engine:
                                    use_av=use_av, dist_fit=dist_fit, rad_prior=rad_prior, spectrum=spectrum)
         self.ctx.stage_problem(st.prob)
         self.tables = st
+        self._tm = (ctm, ptm)   # (products.stage builds the plot=True window from the same curves)
+        self.products = None    # the library drops staged products with the problem
         self.nspec = int(nspec)
         self.ndim = 2 * self.nspec + 2
 
@@ -144,6 +149,16 @@ class Engine:
 
     def loglikelihood(self, theta, optimize=False):
         return self._eval(theta, _lib.MODE_CHISQ if optimize else _lib.MODE_LOGLIKE)
+
+    def stage_products(self, kepler, gaia=None, matrix=None, **kw):
+        """``products.stage`` on this engine: the Kepler / Gaia product bands and the mass-luminosity isochrone."""
+        from . import products
+        return products.stage(self, kepler, gaia, matrix, **kw)
+
+    def derived(self, theta, cols):
+        """``products.evaluate``: the derived columns (names or codes) of the samples ``theta``."""
+        from . import products
+        return products.evaluate(self, theta, cols)
 
     def make_composite(self, teff, logg, rad, distance):
         """Returns (wl, spec, contrast list, phot_cwl, phot) like mft6.py:831."""

@@ -396,6 +396,36 @@ class DeviceGroupSampler(GroupSampler):
             out = summary.summarize(chain, self.group.engines[0].ctx, self.nwalkers, q, cols, discard, thin)
         return out if k is None else {name: v[k] for name, v in out.items()}
 
+    def get_products(self, cols, q=(0.16, 0.5, 0.84), discard=0, thin=1, indices=None, k=None):
+        """``get_summary``'s dict over DERIVED columns (``mcmc_spec_amd.products``) of every target's stored chain, each
+        target's samples evaluated with its own engine's problem and products in one launch: with autocorr='device' on
+        the chains held there, otherwise the host chains are uploaded first.  ``indices``: positions in each target's flat
+        sample ``get_chain(k, discard=, thin=, flat=True)`` to use instead of all of it -- one index array for every
+        target or a sequence of K (mft6.py:2486: the caller draws them); those samples are taken from the host copies of the
+        chains and go through msx_products_batch target by target, whatever ``autocorr`` is.  ``k``: one target (the arrays lose their first
+        axis).  Every engine needs staged products (``products.stage``)."""
+        from . import products, summary
+        engines = self.group.engines
+        n_total = len(self.samplers[0]._chain)
+        if indices is not None:
+            per = [indices] * len(engines) if np.ndim(indices[0]) == 0 else list(indices)
+            if len(per) != len(engines):
+                raise ValueError('indices: one array for all targets or one per target')
+            outs = []
+            for m, e in enumerate(engines):
+                flat = self.samplers[m].get_chain(flat=True, thin=thin, discard=discard)
+                outs.append(products._summary_of_values(e.ctx, products.evaluate(e, flat[np.asarray(per[m], dtype=np.int64)], cols), q))
+            out = {name: np.stack([o[name] for o in outs]) for name in outs[0]}
+        elif self._series is not None:
+            out = products.summarize_chain(self._series, n_total, engines, cols, q, discard, thin)
+        else:
+            if n_total < 1:
+                raise ValueError('the selection rows[0:n][discard::thin] is empty')
+            chain = np.concatenate([np.array(s._chain) for s in self.samplers], axis=1)
+            with summary.uploaded(chain, engines[0].ctx, self.nwalkers) as (series, n):
+                out = products.summarize_chain(series, n, engines, cols, q, discard, thin)
+        return out if k is None else {name: v[k] for name, v in out.items()}
+
 
 def run_group_protocol(sampler, pos, nburn, nsteps, nthin=10, dirname=None, fnames=None):
     """``sampler.run_reference_protocol`` (run_emcee's driver, mft6.py:1494-1529) applied to every target of a group

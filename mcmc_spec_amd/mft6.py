@@ -30,6 +30,7 @@ import numpy as np
 from .engine import Engine
 
 _BANDS = None
+_PRODUCT_BANDS = None
 _AV_TABLE = None
 _AV_OPTIONAL = False
 _SPECTRUM = True
@@ -49,6 +50,16 @@ def set_band_library(bands):
     """``{name: bands.Band}`` for the names pyphot's library uses (mft6.py:766-769)."""
     global _BANDS
     _BANDS = bands
+    _invalidate_problems()
+
+
+def set_product_bands(kepler=None, gaia=None):
+    """Register what ``make_composite(..., plot=True)`` reads besides its arguments: ``kepler = (wl [A], transmission)`` as
+    ``get_transmission('kepler', res)`` returns it (mft6.py:788), and ``gaia``, a ``bands.Band`` for ``lib['Gaia_G']``
+    (:811) whose ``zero_flux`` is ``Vega_zero_flux`` and whose optional ``zero_mag`` attribute is ``Vega_zero_mag`` (default
+    ``-2.5 log10(zero_flux)``); a triple needs the Kepler curve only.  ``set_product_bands()`` forgets them."""
+    global _PRODUCT_BANDS
+    _PRODUCT_BANDS = None if kepler is None else ((np.asarray(kepler[0], float), np.asarray(kepler[1], float)), gaia)
     _invalidate_problems()
 
 
@@ -255,9 +266,14 @@ def logprior(p0, nspec, ndust, tmin, tmax, matrix, ra, dec, prior=0, ext=True, d
 
 def make_composite(teff, logg, rad, distance, contrast_filt, phot_filt, r, specs, ctm, ptm, tmi, tma, vs, nspec=2,
                    normalize=False, res=1000, npix=3, models='btsettl', plot=False):
-    """mft6.py:651-831 (``plot=False``): ``(wl, spec, contrast, phot_cwl, phot)``."""
+    """mft6.py:651-831: ``(wl, spec, contrast, phot_cwl, phot)``; with ``plot=True`` the reference's other tuples over the
+    window that joins the Kepler curve's extrema in -- a binary's nine entries ``(wl, spec, pri_spec, sec_spec, pri_kep,
+    sec_kep, gaia_pri, gaia_sec, gaia_mag)`` (:816), a triple's eight ``(wl, spec, pri, sec, ter, pri_kep, sec_kep, ter_kep)``
+    whose magnitudes are the six-element arrays the ``/ zp`` list makes them (:828).  The curves come from
+    ``set_product_bands``; the stars' spectra from the device (msx_composite_parts), the band integrals are the staged
+    weights' sums over them."""
     if plot:
-        raise NotImplementedError('make_composite(plot=True) is plotting support (out of scope, SURVEY.md §2)')
+        return _make_composite_plot(teff, logg, rad, distance, contrast_filt, phot_filt, r, specs, ctm, ptm, tmi, tma, nspec)
     eng = _engine_for(specs)
     wl4 = np.linspace(min(r), max(r), 4)
     key = ('composite', _ids(ctm, ptm), tuple(float(x) for x in r), float(tmi), float(tma), int(nspec),
@@ -270,6 +286,46 @@ def make_composite(teff, logg, rad, distance, contrast_filt, phot_filt, r, specs
         eng._problem_key = key
         eng._problem_refs = None
     return eng.make_composite(teff, logg, rad, distance)
+
+
+def _make_composite_plot(teff, logg, rad, distance, contrast_filt, phot_filt, r, specs, ctm, ptm, tmi, tma, nspec):
+    from . import products, staging
+    nspec = int(nspec)
+    if _PRODUCT_BANDS is None or (nspec == 2 and _PRODUCT_BANDS[1] is None):
+        raise RuntimeError('make_composite(plot=True) needs the Kepler transmission curve' + (' and the Gaia G band' if nspec == 2 else '')
+                           + ': call mcmc_spec_amd.mft6.set_product_bands(kepler=(wl, tm), gaia=Band) first (the reference '
+                           "reads get_transmission('kepler', res) and lib['Gaia_G'] here, mft6.py:788-811)")
+    kepler, gaia = _PRODUCT_BANDS
+    eng = _engine_for(specs)
+    key = ('composite', _ids(ctm, ptm), tuple(float(x) for x in r), float(tmi), float(tma), nspec, len(contrast_filt),
+           len(phot_filt))
+    if eng._problem_key != key:
+        nc, nph = len(contrast_filt), len(phot_filt)
+        wl4 = np.linspace(min(r), max(r), 4)
+        fr = [np.zeros(nc), np.ones(nc), list(contrast_filt), np.zeros(nph), np.ones(nph), list(phot_filt)]
+        eng.stage_problem([wl4, np.ones(4)], np.ones(4), fr, r, ctm, ptm, tmi, tma, _flat_matrix(), nspec=nspec, bands=_BANDS)
+        eng._problem_key = key
+        eng._problem_refs = None
+    pt = staging.build_products(eng.grid['wl'], r, tmi, tma, ctm, ptm, _flat_matrix(), kepler, gaia if nspec == 2 else None,
+                                kepler_kind='trapz' if nspec == 2 else 'sum')
+    j0, n = pt.window
+    use_d = not (type(distance) == bool)
+    parts, status = eng.ctx.composite_parts(teff, logg, rad, use_d, float(distance) if use_d else 0.0, j0, n)
+    from .engine import _raise_for_status
+    _raise_for_status(np.array([status]), np.array([list(teff) + list(logg)]))
+    wl = eng.grid['wl'][j0:j0 + n].copy()
+    spec1 = parts[0] + parts[1] if nspec == 2 else parts[0] + parts[1] + parts[2]  # mft6.py:744,751
+
+    def integral(b, s):
+        i0, w = pt.band_tables[b]
+        return np.sum(w * s[i0 - j0:i0 - j0 + len(w)])
+    if nspec == 2:
+        kep = [-2.5 * np.log10(integral(0, parts[s])) for s in range(2)]               # mft6.py:802
+        gm = -2.5 * np.log10(integral(1, spec1) / gaia.zero_flux)                      # mft6.py:812
+        gs = [-2.5 * np.log10(integral(1, parts[s])) - pt.zero_mag[1] for s in range(2)]  # mft6.py:813-814
+        return wl, spec1, parts[0].copy(), parts[1].copy(), kep[0], kep[1], gs[0], gs[1], gm
+    mags = [-2.5 * np.log10(integral(0, parts[s]) / np.array(products.TRIPLE_ZP)) for s in range(3)]  # mft6.py:820-825
+    return wl, spec1, parts[0].copy(), parts[1].copy(), parts[2].copy(), mags[0], mags[1], mags[2]
 
 
 def _flat_matrix():

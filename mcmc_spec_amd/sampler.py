@@ -512,6 +512,29 @@ class DeviceEnsembleSampler(EnsembleSampler):
             out = summary.summarize(np.array(self._chain), self.engine.ctx, None, q, cols, discard, thin)
         return {name: v[0] for name, v in out.items()}
 
+    def get_products(self, cols, q=(0.16, 0.5, 0.84), discard=0, thin=1, indices=None):
+        """``get_summary``'s dict over DERIVED columns of the stored chain (``mcmc_spec_amd.products``: names such as
+        'kep_contrast', 'pri_corr', 'sec_corr', or codes): every sample of ``get_chain(discard=, thin=, flat=True)`` goes
+        through the products kernel -- with autocorr='device' the chain held on the device, without a copy; otherwise the
+        host chain is uploaded first -- and the device selects the order statistics.  ``indices``: positions in that flat
+        sample to use instead of all of it (the reference draws 2,000 with ``np.random.choice(len(sample), 2000,
+        replace=False)``, mft6.py:2486; the caller draws them): those samples are taken from the host copy of the chain
+        and go through msx_products_batch, whatever ``autocorr`` is.  The engine needs staged products (``products.stage``)."""
+        from . import products, summary
+        n_total = len(self._chain)
+        if indices is not None:
+            flat = self.get_chain(flat=True, thin=thin, discard=discard)
+            vals = products.evaluate(self.engine, flat[np.asarray(indices, dtype=np.int64)], cols)
+            return products._summary_of_values(self.engine.ctx, vals, q)
+        if self._series is not None:
+            out = products.summarize_chain(self._series, n_total, [self.engine], cols, q, discard, thin)
+        else:
+            if n_total < 1:
+                raise ValueError('the selection rows[0:n][discard::thin] is empty')
+            with summary.uploaded(np.array(self._chain), self.engine.ctx) as (series, n):
+                out = products.summarize_chain(series, n, [self.engine], cols, q, discard, thin)
+        return {name: v[0] for name, v in out.items()}
+
 
 def _autocorr_1d(x):
     x = np.asarray(x, dtype=float)

@@ -294,3 +294,110 @@ def isochrone_radius(teff, matrix):
     lm = np.interp(teff, x, lum)
     sigma_sb, lsun, rsun = 5.670374e-5, 3.839e33, 6.957e10
     return np.sqrt(lm * lsun / (4 * np.pi * sigma_sb * np.asarray(teff, dtype=float) ** 4)) / rsun
+
+
+# ---- derived posteriors: the product bands of make_composite(plot=True) ---------------------------
+def product_window_um(r, tmi, tma, ctm, ptm, kepler_wl):
+    """The window make_composite passes to get_spec with ``plot=True``, in micron: the extrema of the contrast and
+    photometry curves (mft6.py:663-673) with the Kepler curve's joined in (:677-682), then :687."""
+    wlmin, wlmax = np.inf, 0
+    for w in list(ctm[0]) + list(ptm[0]):
+        if min(w) < wlmin:
+            wlmin = min(w)
+        if max(w) > wlmax:
+            wlmax = max(w)
+    if min(kepler_wl) < wlmin:
+        wlmin = min(kepler_wl)
+    if max(kepler_wl) > wlmax:
+        wlmax = max(kepler_wl)
+    return [min(min(r), tmi / 1e4, wlmin / 1e4) - 1e-4, max(max(r), tma / 1e4, wlmax / 1e4) + 1e-4]
+
+
+def curve_weights(wave, ran, tm, kind):
+    """(i0, w) on the window ``wave`` for one transmission curve: the samples of the reference's mask
+    ``(wave >= min(ran)) & (wave <= max(ran))`` -- clipped to the window as the boolean mask clips it -- and
+    ``kind='trapz'``: w with sum(w * S) = np.trapz(S[mask] * interp1d(ran, tm)(wave[mask]), wave[mask]) (mft6.py:792-799);
+    ``kind='sum'``: w = the interpolated transmission, for np.sum(S[mask] * data_tm) (mft6.py:820-822)."""
+    ran = np.asarray(ran, dtype=float)
+    inband = np.where((wave >= min(ran)) & (wave <= max(ran)))[0]
+    if inband.size < 2:
+        raise ValueError('a product band does not overlap the model window')
+    if inband[-1] - inband[0] + 1 != inband.size:
+        raise ValueError('model wavelength grid must be sorted')
+    w = wave[inband]
+    tran = interp1d(ran, tm)(w)
+    if kind == 'trapz':
+        return int(inband[0]), _trapz_weights(w) * tran
+    if kind == 'sum':
+        return int(inband[0]), np.array(tran, dtype=float)
+    raise ValueError("curve_weights: kind must be 'trapz' or 'sum'")
+
+
+def product_isochrone(matrix, log_columns=False):
+    """(teff, mass, lum) of the first 200 rows of age 9.0 (mft6.py:2604-2605, :2650, :2679), sorted by Teff the way interp1d
+    sorts its x.  ``log_columns``: Teff and luminosity are stored as log10, as in the file plot_results reads (:2618);
+    the default takes them as ``matrix`` holds them for get_logg / get_radius."""
+    m = np.asarray(matrix)
+    sel = np.where(m[:, 1] == 9.0)[0]
+    t, ma, lu = np.asarray(m[sel, 4], dtype=float), np.asarray(m[sel, 3], dtype=float), np.asarray(m[sel, 6], dtype=float)
+    if log_columns:
+        t, lu = 10.0 ** t, 10.0 ** lu
+    t, ma, lu = t[:200], ma[:200], lu[:200]
+    order = np.argsort(t, kind='mergesort')
+    return t[order], ma[order], lu[order]
+
+
+PRODUCT_KINDS = {'trapz': _lib.PB_TRAPZ, 'sum': _lib.PB_SUM, 'mean': _lib.PB_MEAN}
+
+
+def build_products(grid_wl, r, tmi, tma, ctm, ptm, matrix, kepler, gaia=None, kepler_kind='trapz', extra=(),
+                   log_columns=False):
+    """Assemble ``struct msx_products``.  ``kepler = (wl [A], transmission)`` as get_transmission('kepler', res) returns it:
+    band 0, of ``kepler_kind`` ('trapz': the binary's integral, 'sum': the triple's).  ``gaia``: a ``bands.Band`` whose
+    ``zero_mag`` attribute (default -2.5 log10(zero_flux)) is the magnitude subtracted -- band 1, of kind 'mean'.
+    ``extra``: further ``(kind, curve)`` pairs, a curve being (wl, tm) or a Band.  Returns the tables (``.prod``,
+    ``.window``, ``.band_names``)."""
+    st = StagedTables()
+    P = _lib.MsxProducts()
+    grid_wl = np.asarray(grid_wl, dtype=float)
+    kw, kt = np.asarray(kepler[0], dtype=float), np.asarray(kepler[1], dtype=float)
+    reg = product_window_um(r, tmi, tma, ctm, ptm, kw)
+    j0, nwin = window_slice(grid_wl, reg)
+    wave = grid_wl[j0:j0 + nwin]
+    todo = [('kepler', kepler_kind, (kw, kt))]
+    if gaia is not None:
+        todo.append(('gaia', 'mean', gaia))
+    todo += [('extra{}'.format(i), k, cv) for i, (k, cv) in enumerate(extra)]
+    if len(todo) > _lib.MAX_BANDS:
+        raise ValueError('at most {} product bands'.format(_lib.MAX_BANDS))
+    kinds, i0s, lens, ws, zms = [], [], [], [], []
+    for name, kind, cv in todo:
+        if kind == 'mean':
+            i0, w = cv.weights_on(wave)
+            zm = getattr(cv, 'zero_mag', None)
+            zms.append(float(-2.5 * np.log10(cv.zero_flux) if zm is None else zm))
+        else:
+            i0, w = curve_weights(wave, cv[0], cv[1], kind)
+            zms.append(0.0)
+        kinds.append(PRODUCT_KINDS[kind])
+        i0s.append(i0 + j0)
+        lens.append(len(w))
+        ws.append(w)
+    P.struct_size = C.sizeof(_lib.MsxProducts)
+    P.nbands = len(todo)
+    ka = np.ascontiguousarray(kinds, dtype=np.int32)
+    st.keep.append(ka)
+    P.band_kind = ka.ctypes.data_as(C.POINTER(C.c_int32))
+    P.band_i0, P.band_len = st.i64(i0s), st.i64(lens)
+    P.band_w = st.f64(np.concatenate(ws))
+    P.band_zero_mag = st.f64(zms)
+    it, im, il = product_isochrone(matrix, log_columns)
+    P.niso = len(it)
+    P.iso_teff, P.iso_mass, P.iso_lum = st.f64(it), st.f64(im), st.f64(il)
+    st.prod = P
+    st.window = (j0, nwin)
+    st.band_names = [t[0] for t in todo]
+    st.band_kinds = [t[1] for t in todo]
+    st.band_tables = list(zip(i0s, ws))
+    st.zero_mag = np.array(zms)
+    return st

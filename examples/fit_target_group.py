@@ -6,7 +6,11 @@ the ensembles stay on the GPU, DeviceGroupSampler: no host round trip between ha
 Every target gets its own data spectrum (a binary at its own truth, its own pixel count and noise) on one synthetic grid.
 Target k's chain is the chain a separate EnsembleSampler with target k's seed would walk.
 
-    python examples/fit_target_group.py --targets 4 --nwalkers 32 --nsteps 200 [--device [--rng device]]
+    python examples/fit_target_group.py --targets 4 --nwalkers 32 --nsteps 200 [--device [--rng device]] [--moves de]
+
+With --moves de every target's iterations take one of three moves -- the stretch move (weight 0.5), the
+differential-evolution move (0.4) and its mode-jumping variant gamma0 = 1 (0.1): emcee's remedy for posteriors with two
+peaks, whose relative weight the stretch move alone leaves where the initial ensemble put it (mcmc_spec_amd.moves).
 
 With --protocol DIR the targets are fitted the way the reference's driver fits one (run_group_protocol: burn-in, then
 production with every target's own convergence check every --nthin iterations; a converged target stops there) and
@@ -49,6 +53,8 @@ def main():
     ap.add_argument('--rng', choices=('host', 'device'), default='host',
                     help="with --device: who draws the stretch move's randomness -- the host's generators (default), or the GPU "
                          "itself, one launch per chunk and nothing uploaded (another stream: other chains, same posterior)")
+    ap.add_argument('--moves', choices=('stretch', 'de'), default='stretch',
+                    help="'de': a mixture of the stretch move with differential-evolution moves (for bimodal posteriors)")
     ap.add_argument('--protocol', default=None, metavar='DIR', help="run the reference's driver per target (run_group_protocol)")
     ap.add_argument('--nburn', type=int, default=100)
     ap.add_argument('--nthin', type=int, default=50)
@@ -60,6 +66,7 @@ def main():
     from mcmc_spec_amd import bands, synth
     from mcmc_spec_amd.engine import Engine
     from mcmc_spec_amd.group import DeviceGroupSampler, GroupSampler, TargetGroup, run_group_protocol
+    from mcmc_spec_amd.moves import DEMove, StretchMove
     from oracle import mft6_oracle as orc
 
     rng = np.random.default_rng(args.seed)
@@ -102,11 +109,12 @@ def main():
     print('one launch:', group.launch_info([args.nwalkers] * args.targets)['kernel'])
     p0s = [truths[k] + 1e-3 * np.abs(truths[k]) * rng.normal(size=(args.nwalkers, 6)) for k in range(args.targets)]
     seeds = [args.seed + k for k in range(args.targets)]
+    moves = [(StretchMove(), 0.5), (DEMove(), 0.4), (DEMove(gamma0=1.0), 0.1)] if args.moves == 'de' else None
     if args.device:
         sampler = DeviceGroupSampler([args.nwalkers] * args.targets, 6, group, seeds=seeds, rng=args.rng,
-                                     autocorr='device' if args.protocol else 'host')
+                                     autocorr='device' if args.protocol else 'host', moves=moves)
     else:
-        sampler = GroupSampler([args.nwalkers] * args.targets, 6, group.logposterior, seeds=seeds)
+        sampler = GroupSampler([args.nwalkers] * args.targets, 6, group.logposterior, seeds=seeds, moves=moves)
     t0 = time.time()
     if args.protocol:
         out = run_group_protocol(sampler, p0s, args.nburn, args.nsteps, nthin=args.nthin, dirname=args.protocol,

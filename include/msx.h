@@ -334,6 +334,55 @@ int msx_sampler_overlapped(msx_ctx *ctx, int32_t *out);
  * collected chunk stands).  Takes effect at the next msx_sampler_begin.                                                */
 int msx_sampler_policy(msx_ctx *ctx, int32_t overlap);
 
+/* ---- moves other than the stretch move, and mixtures of moves (emcee 3's `moves=`) ---------------
+ * An iteration is split into two halves as above; each ITERATION takes one move of a set, for both of its half-steps,
+ * chosen with the set's normalised weights.  For entry j of a half-step, s the moving walker and C its complementary half
+ * (nc walkers):
+ *   MSX_MOVE_STRETCH (a)            c = C[p1], z = ((a - 1) u + 1)^2 / a, q = c - (c - s) z, factor (ndim - 1) ln z
+ *   MSX_MOVE_DE (sigma, gamma0)     differential evolution (ter Braak 2006, as emcee 3's DEMove): an ordered pair of
+ *                                   DISTINCT walkers C[p1], C[p2], uniform over the nc (nc - 1) pairs; g = g0 (1 + sigma n),
+ *                                   n standard normal, g0 = gamma0, or 2.38 / sqrt(2 ndim) for gamma0 <= 0;
+ *                                   q = s + g (C[p1] - C[p2]), factor 0 (gamma0 = 1: the mode-jumping variant)
+ * and every move accepts when ln u < (factor + ln p(q)) - ln p(s) (a NaN difference compares false).
+ * These chunks run BESIDE the fused kernel, whose proposal is the stretch move's: per half-step the plain evaluation
+ * (msx_logprob_batch_dev / msx_group_logprob_batch_dev) scores proposals that a small kernel wrote, and the same small
+ * kernel -- one workgroup per member, one launch -- applies the accept rule to them and proposes the next half-step.
+ * Plain launches: the first msx_*_enqueue_moves* call of a run fixes overlap = 0 (a run whose stretch chunks already
+ * overlap, and a sharded run, are refused with MSX_ERR_STATE).  begin, collect, end and attach_series are the calls above,
+ * and chunks of either family may alternate within a run: both leave the same resident state.                        */
+#define MSX_MOVE_STRETCH 0
+#define MSX_MOVE_DE 1
+#define MSX_MAX_MOVES 4
+typedef struct {
+    int32_t n;               /* moves in the set, 1..MSX_MAX_MOVES                               */
+    int32_t kind[4];         /* MSX_MOVE_*                                                       */
+    double weight[4];        /* normalised: > 0, summing to 1 within 1e-12                       */
+    double a[4];             /* stretch scale (> 1) of a MSX_MOVE_STRETCH entry                  */
+    double gamma0[4];        /* DE: g0; <= 0: 2.38 / sqrt(2 ndim)                                */
+    double sigma[4];         /* DE: relative scatter of g (>= 0)                                 */
+} msx_move_set;
+/* host-drawn chunk in the GENERAL layout: sidx, cidx, p1, p2 (indices into the complementary half), g, fac, logu are
+ * [nsteps][2][nw/2]; kind [nsteps] (one move per iteration).  Stretch entries carry p1 = p2 = partner, g = z, fac =
+ * (ndim - 1) ln z; DE entries fac = 0.  Checked (MSX_ERR_INVALID, nothing queued): indices in range, kind a MSX_MOVE_*,
+ * p1 != p2 on DE entries.                                                                                             */
+int msx_sampler_enqueue_moves(msx_ctx *ctx, int32_t slot, int64_t nsteps, const int32_t *sidx, const int32_t *cidx,
+                              const int32_t *kind, const int32_t *p1, const int32_t *p2, const double *g, const double *fac,
+                              const double *logu);
+/* the same chunk DRAWN ON THE DEVICE by msx_sampler_enqueue_drawn's counter generator: the split (stream 0) and u_z, u_p,
+ * u_a (streams 1..6) are the ones the stretch-only generator gives the same seed; stream 7, index 0 chooses the
+ * iteration's move (the first i with u < weight[0] + .. + weight[i]); per half-step h, stream 8 + 3h index j is the DE
+ * pair (p = min(floor(u nc (nc - 1)), nc (nc - 1) - 1), j1 = p / (nc - 1), r = p % (nc - 1), j2 = r + (r >= j1)) and
+ * streams 9 + 3h, 10 + 3h the normal deviate n = sqrt(-2 ln(1 - u1)) cos(2 pi u2).  The set travels by value: one launch
+ * per chunk, nothing uploaded.  first_iter as for msx_sampler_enqueue_drawn.  A bad set (n, a kind, a weight, weights
+ * that do not sum to 1, a <= 1, sigma < 0), more than 4096 walkers, fewer than 4 with a DE move: MSX_ERR_INVALID.      */
+int msx_sampler_enqueue_moves_drawn(msx_ctx *ctx, int32_t slot, int64_t nsteps, uint64_t seed, const msx_move_set *set,
+                                    int64_t first_iter);
+/* that stream on the host, in the general layout (p1, p2 index the complementary half): the host loop fed with it walks
+ * the device-drawn chain bit for bit; mcmc_spec_amd/moves.py::counter_draws_moves restates it in NumPy                  */
+int msx_sampler_draw_moves(msx_ctx *ctx, uint64_t seed, const msx_move_set *set, int64_t first_iter, int64_t nsteps,
+                           int64_t nw, int32_t ndim, int32_t *sidx, int32_t *cidx, int32_t *kind, int32_t *p1, int32_t *p2,
+                           double *g, double *fac, double *logu);
+
 /* ---- A4-A6: make_composite (mft6.py:651-831, plot=False) -------------------------------------- */
 /* teff/logg/rad are [nspec]; use_distance = 0 mirrors `distance=False` (mft6.py:701-703).         */
 /* spec_out [win_n], contrast_out [n_contrast], phot_out [n_phot] (unreddened magnitudes).         */
@@ -466,6 +515,16 @@ int msx_group_sampler_enqueue(msx_group *group, int32_t slot, int64_t nsteps, co
  * MSX_ERR_INVALID, nothing queued.  Otherwise as msx_group_sampler_enqueue, with which it may alternate within a run.   */
 int msx_group_sampler_enqueue_drawn(msx_group *group, int32_t slot, int64_t nsteps, const uint64_t *seeds /* [k] */, double a,
                                     int64_t first_iter);
+/* the group's chunks with a set of moves (msx_sampler_enqueue_moves, _moves_drawn above): arrays as for
+ * msx_group_sampler_enqueue in the general layout, indices member-local, kind [nsteps][k] -- every member takes its own
+ * move per iteration (drawn: from its own seed) -- and the same checks per member.  Member m's chain is the chain
+ * msx_sampler_enqueue_moves* gives its context alone.  One step-kernel launch (a workgroup per member) and one plain group
+ * evaluation per half-step.                                                                                            */
+int msx_group_sampler_enqueue_moves(msx_group *group, int32_t slot, int64_t nsteps, const int32_t *sidx, const int32_t *cidx,
+                                    const int32_t *kind, const int32_t *p1, const int32_t *p2, const double *g,
+                                    const double *fac, const double *logu);
+int msx_group_sampler_enqueue_moves_drawn(msx_group *group, int32_t slot, int64_t nsteps, const uint64_t *seeds /* [k] */,
+                                          const msx_move_set *set, int64_t first_iter);
 /* waits for the chunk in `slot`: chain_out [nsteps][sum counts][ndim], logp_out [nsteps][sum counts], naccept [sum counts]
  * (cumulative over the run), worst_status [k] (the worst walker status of each member's walkers in the chunk)          */
 int msx_group_sampler_collect(msx_group *group, int32_t slot, double *chain_out, double *logp_out, int64_t *naccept,

@@ -31,6 +31,7 @@ MAX_GROUP = 64  # include/msx.h MSX_MAX_GROUP: members of a target group
 PB_TRAPZ, PB_SUM, PB_MEAN = 0, 1, 2  # include/msx.h MSX_PB_*: the kinds of a product band
 SPEC_MEDIAN_SCALE = 1  # include/msx.h MSX_SPEC_MEDIAN_SCALE
 MAX_PCOLS = 64  # include/msx.h MSX_MAX_PCOLS: derived columns of one products_batch call
+from .moves import MOVE_STRETCH, MOVE_DE, MAX_MOVES, MsxMoveSet  # noqa: E402  include/msx.h MSX_MOVE_*, MSX_MAX_MOVES, msx_move_set
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int64)
@@ -141,6 +142,13 @@ def load():
         'msx_sampler_draw': (C.c_int, [vp, C.c_uint64, C.c_double, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_int32),
                                        C.POINTER(C.c_int32), C.POINTER(C.c_int32), _dp, _dp, _dp]),
         'msx_sampler_end': (C.c_int, [vp, _dp, _dp]),
+        'msx_sampler_enqueue_moves': (C.c_int, [vp, C.c_int32, C.c_int64] + [C.POINTER(C.c_int32)] * 5 + [_dp, _dp, _dp]),
+        'msx_sampler_enqueue_moves_drawn': (C.c_int, [vp, C.c_int32, C.c_int64, C.c_uint64, C.POINTER(MsxMoveSet), C.c_int64]),
+        'msx_sampler_draw_moves': (C.c_int, [vp, C.c_uint64, C.POINTER(MsxMoveSet), C.c_int64, C.c_int64, C.c_int64, C.c_int32] +
+                                   [C.POINTER(C.c_int32)] * 5 + [_dp, _dp, _dp]),
+        'msx_group_sampler_enqueue_moves': (C.c_int, [vp, C.c_int32, C.c_int64] + [C.POINTER(C.c_int32)] * 5 + [_dp, _dp, _dp]),
+        'msx_group_sampler_enqueue_moves_drawn': (C.c_int, [vp, C.c_int32, C.c_int64, C.POINTER(C.c_uint64), C.POINTER(MsxMoveSet),
+                                                            C.c_int64]),
         'msx_make_composite': (C.c_int, [vp, _dp, _dp, _dp, C.c_int32, C.c_double, _dp, _dp, _dp,
                                          C.POINTER(C.c_int32)]),
         'msx_comm_unique_id': (C.c_int, [vp, C.POINTER(C.c_uint8)]),
@@ -214,7 +222,9 @@ EXPORTED = ['msx_create', 'msx_destroy', 'msx_last_error', 'msx_device_info', 'm
             'msx_group_sampler_attach_series', 'msx_series_append', 'msx_series_read', 'msx_series_acf',
             'msx_series_order_stats', 'msx_series_hist', 'msx_series_hist2d',
             'msx_stage_products', 'msx_products_batch', 'msx_products_batch_dev', 'msx_series_derive',
-            'msx_products_spectra', 'msx_composite_parts']
+            'msx_products_spectra', 'msx_composite_parts',
+            'msx_sampler_enqueue_moves', 'msx_sampler_enqueue_moves_drawn', 'msx_sampler_draw_moves',
+            'msx_group_sampler_enqueue_moves', 'msx_group_sampler_enqueue_moves_drawn']
 
 
 def as_f64(a):
@@ -637,6 +647,32 @@ class Context:
                                              dptr(dbl[0]), dptr(dbl[1]), dptr(dbl[2])))
         return tuple(ints) + tuple(dbl)
 
+    def sampler_enqueue_moves(self, slot, sidx, cidx, kind, p1, p2, g, fac, logu):
+        """Queue one chunk in the general layout (msx_sampler_enqueue_moves): kind (nsteps,), the others (nsteps, 2, nw/2)."""
+        return _sampler_enqueue_moves(self, self.lib.msx_sampler_enqueue_moves, 1, slot, (sidx, cidx, kind, p1, p2, g, fac, logu))
+
+    def sampler_enqueue_moves_drawn(self, slot, nsteps, seed, moves, first_iter):
+        """Queue one chunk of a set of moves whose randomness the device draws (msx_sampler_enqueue_moves_drawn): ``moves``
+        as the samplers' ``moves=``; the chunk's first step is the ABSOLUTE iteration ``first_iter`` of the seed's stream."""
+        st = _move_set(moves)
+        self.check(self.lib.msx_sampler_enqueue_moves_drawn(self.h, int(slot), int(nsteps), int(seed) & 0xffffffffffffffff, C.byref(st),
+                                                            int(first_iter)))
+        return int(nsteps)
+
+    def sampler_draw_moves(self, seed, moves, first_iter, nsteps, nw, ndim):
+        """The device generator's stream for a set of moves, iterations [first_iter, first_iter + nsteps): the general
+        layout (sidx, cidx, kind, p1, p2, g, fac, logu) -- what EnsembleSampler(moves=...)._draw_steps returns."""
+        i32p = C.POINTER(C.c_int32)
+        shp = (int(nsteps), 2, int(nw) // 2)
+        sidx, cidx, p1, p2 = (np.empty(shp, dtype=np.int32) for _ in range(4))
+        kind = np.empty(int(nsteps), dtype=np.int32)
+        g, fac, logu = (np.empty(shp) for _ in range(3))
+        st = _move_set(moves)
+        self.check(self.lib.msx_sampler_draw_moves(self.h, int(seed) & 0xffffffffffffffff, C.byref(st), int(first_iter), int(nsteps), int(nw),
+                                                   int(ndim), *[a.ctypes.data_as(i32p) for a in (sidx, cidx, kind, p1, p2)], dptr(g),
+                                                   dptr(fac), dptr(logu)))
+        return sidx, cidx, kind, p1, p2, g, fac, logu
+
     def sampler_collect(self, slot, nsteps):
         """Wait for the chunk in `slot`: (chain [nsteps][nw][ndim], logp [nsteps][nw], naccept [nw], worst)."""
         chain, lpc, nacc = _collect_out(self._smp_shape, nsteps)
@@ -822,6 +858,22 @@ class Group:
                                                             float(a), int(first_iter)))
         return int(nsteps)
 
+    def sampler_enqueue_moves(self, slot, sidx, cidx, kind, p1, p2, g, fac, logu):
+        """Queue one chunk in the general layout (msx_group_sampler_enqueue_moves): kind (nsteps, k), the others (nsteps, 2,
+        sum(counts)/2), the members' active halves side by side, indices member-local."""
+        return _sampler_enqueue_moves(self, self.lib.msx_group_sampler_enqueue_moves, self.k, slot, (sidx, cidx, kind, p1, p2, g, fac, logu))
+
+    def sampler_enqueue_moves_drawn(self, slot, nsteps, seeds, moves, first_iter):
+        """Queue one chunk of a set of moves whose randomness the device draws (msx_group_sampler_enqueue_moves_drawn): member m
+        from ``seeds[m]``, the chunk's first step the ABSOLUTE iteration ``first_iter`` of every member's stream."""
+        seeds = np.ascontiguousarray([int(s) & 0xffffffffffffffff for s in seeds], dtype=np.uint64)
+        if seeds.shape != (self.k,):
+            raise ValueError('one seed per member ({} given, {} members)'.format(seeds.size, self.k))
+        st = _move_set(moves)
+        self.check(self.lib.msx_group_sampler_enqueue_moves_drawn(self.h, int(slot), int(nsteps), seeds.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                                  C.byref(st), int(first_iter)))
+        return int(nsteps)
+
     def sampler_collect(self, slot, nsteps):
         """Wait for the chunk in `slot`: (chain [nsteps][n][ndim], logp [nsteps][n], naccept [n], worst [k])."""
         chain, lpc, nacc = _collect_out(self._smp_shape, nsteps)
@@ -973,6 +1025,31 @@ def _sampler_enqueue(owner, fn, half, slot, arrays):
             raise ValueError('sampler_enqueue: arrays must have shape (nsteps, 2, {})'.format(half))
     owner.check(fn(owner.h, int(slot), nsteps, arrs[0].ctypes.data_as(i32p), arrs[1].ctypes.data_as(i32p),
                    arrs[2].ctypes.data_as(i32p), dptr(dbl[0]), dptr(dbl[1]), dptr(dbl[2])))
+    return nsteps
+
+
+def _move_set(moves):
+    """``moves`` (a MsxMoveSet, or anything the samplers' ``moves=`` takes) as msx_move_set."""
+    if isinstance(moves, MsxMoveSet):
+        return moves
+    from .moves import parse_moves
+    return parse_moves(moves).as_struct()
+
+
+def _sampler_enqueue_moves(owner, fn, k, slot, arrays):
+    """fn(h, slot, nsteps, sidx, cidx, kind, p1, p2, g, fac, logu) for one chunk in the general layout: kind (nsteps,) for
+    one ensemble or (nsteps, k), the others (nsteps, 2, owner's walkers / 2)."""
+    i32p = C.POINTER(C.c_int32)
+    sidx, cidx, kind, p1, p2 = (np.ascontiguousarray(a, dtype=np.int32) for a in arrays[:5])
+    dbl = [as_f64(a) for a in arrays[5:]]
+    nsteps = dbl[0].shape[0]
+    for a in [sidx, cidx, p1, p2] + dbl:
+        if a.shape != (nsteps, 2, owner._smp_shape[0] // 2):
+            raise ValueError('sampler_enqueue_moves: arrays must have shape (nsteps, 2, walkers / 2)')
+    if kind.size != nsteps * k:
+        raise ValueError('sampler_enqueue_moves: kind must have one entry per iteration and member')
+    owner.check(fn(owner.h, int(slot), nsteps, *[a.ctypes.data_as(i32p) for a in (sidx, cidx, kind, p1, p2)], dptr(dbl[0]), dptr(dbl[1]),
+                   dptr(dbl[2])))
     return nsteps
 
 

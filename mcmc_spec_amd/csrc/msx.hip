@@ -61,6 +61,7 @@
 #include "recipe.h"
 #include "median.h"
 #include "logprob_kernel.h"
+#include "move_kernels.h"
 #include "group_kernel.h"
 #include "pair_kernel.h"
 #include "staging_kernels.h"
@@ -3372,6 +3373,280 @@ int msx_group_sampler_end(msx_group *g, double *coords, double *logp) {
     group_run_free(g);
     if (e != hipSuccess) return fail(g, MSX_ERR_HIP, std::string("msx_group_sampler_end: ") + hipGetErrorString(e));
     return MSX_OK;
+}
+
+// ---- moves other than the stretch move, and mixtures (include/msx.h, msx_*_enqueue_moves*; move_kernels.h) --------------
+// The path BESIDE the fused kernel: a chunk of nsteps iterations is  step(propose 0) ; { eval ; step(apply j, propose j + 1) }
+// ... eval ; step(apply 2 nsteps - 1)  -- the unchanged plain evaluation plus one launch per half-step (and one per chunk).
+// The context's run is the one-member case of the group's.
+
+// where the general layout's arrays live in a slot (move_kernels.h, MoveChunk); kind [lay][k]
+struct MoveChunkPtrs {
+    double *g, *fac, *logu;
+    int32_t *sidx, *cidx, *c1, *c2, *kind;
+};
+static MoveChunkPtrs move_chunk_ptrs(const SamplerRun *r, const ChunkPtrs &cp, int64_t nsteps) {
+    const int64_t L = r->lay(nsteps) * 2 * r->ns;
+    int32_t *c2 = (int32_t *)const_cast<SmpRec *>(cp.d_rec);
+    return {cp.d_zz, cp.d_zfac, cp.d_logu, cp.d_sidx, cp.d_cidx, cp.d_partner, c2, c2 + L};
+}
+
+// msx_move_set -> the kernel's form; nullptr, or what is wrong with it.  min_nw: the smallest member
+static const char *move_set_dev(const msx_move_set *set, int32_t ndim, int64_t min_nw, MoveSetDev *S) {
+    if (!set || set->n < 1 || set->n > MSX_MAX_MOVES) return "a set holds 1..MSX_MAX_MOVES moves";
+    memset(S, 0, sizeof(*S));
+    S->n = set->n;
+    double cum = 0.0;
+    for (int i = 0; i < set->n; ++i) {
+        const int kd = set->kind[i];
+        if (kd != MSX_MOVE_STRETCH && kd != MSX_MOVE_DE) return "unknown kind of move";
+        if (!std::isfinite(set->weight[i]) || !(set->weight[i] > 0.0)) return "weights must be finite and > 0";
+        if (kd == MSX_MOVE_STRETCH && !(std::isfinite(set->a[i]) && set->a[i] > 1.0)) return "a stretch move needs a scale a > 1";
+        if (kd == MSX_MOVE_DE && !(std::isfinite(set->sigma[i]) && set->sigma[i] >= 0.0 && std::isfinite(set->gamma0[i])))
+            return "a DE move needs a finite sigma >= 0 and a finite gamma0";
+        if (kd == MSX_MOVE_DE && min_nw < 4) return "the DE move needs two distinct walkers in each half: at least 4 walkers";
+        cum += set->weight[i];
+        S->kind[i] = kd; S->cum[i] = cum; S->a[i] = set->a[i]; S->sigma[i] = set->sigma[i];
+        S->g0[i] = set->gamma0[i] > 0.0 ? set->gamma0[i] : 2.38 / std::sqrt(2.0 * (double)ndim);
+    }
+    if (std::fabs(cum - 1.0) > 1e-12) return "the weights must be normalised (sum 1 within 1e-12)";
+    return nullptr;
+}
+
+static MoveMembers move_members(const SamplerRun *r, bool walkers) {
+    MoveMembers M;
+    memset(&M, 0, sizeof(M));
+    for (size_t m = 0; m < r->m_nw.size(); ++m) {
+        M.astart[m] = (int32_t)r->m_astart[m]; M.off[m] = (int32_t)r->m_off[m];
+        M.nh[m] = (int32_t)(walkers ? r->m_nw[m] : r->m_nw[m] / 2);
+    }
+    return M;
+}
+
+// The chunk's host randomness in the general layout -- [nsteps][2][ns] each, kind [nsteps][k], indices member-local -- into
+// the slot's pinned staging (run_pack's place and checks): every index is dereferenced on the device.  nullptr, or what is wrong.
+static const char *run_pack_moves(SamplerRun *r, SamplerRun::Slot &sl, int64_t nsteps, const int32_t *sidx, const int32_t *cidx,
+                                  const int32_t *kind, const int32_t *p1, const int32_t *p2, const double *g, const double *fac,
+                                  const double *logu) {
+    const int64_t ns = r->ns, nh = nsteps * 2 * ns, L = r->lay(nsteps) * 2 * ns;
+    const size_t km = r->m_nw.size();
+    for (int64_t i = 0; i < nsteps * (int64_t)km; ++i)
+        if (kind[i] != MSX_MOVE_STRETCH && kind[i] != MSX_MOVE_DE) return "kind out of range";
+    double *hz = (double *)sl.h_in;
+    int32_t *hi = (int32_t *)(hz + 3 * L);
+    int32_t *hc2 = hi + 3 * L, *hk = hc2 + L;
+    memcpy(hz, g, sizeof(double) * nh); memcpy(hz + L, fac, sizeof(double) * nh); memcpy(hz + 2 * L, logu, sizeof(double) * nh);
+    memcpy(hi, sidx, sizeof(int32_t) * nh); memcpy(hi + L, cidx, sizeof(int32_t) * nh);
+    memcpy(hk, kind, sizeof(int32_t) * nsteps * km);
+    for (int64_t row = 0; row < 2 * nsteps; ++row)
+        for (size_t m = 0; m < km; ++m) {
+            const int64_t b = row * ns + r->m_astart[m], off = r->m_off[m];
+            const uint32_t mw = (uint32_t)r->m_nw[m], mh = mw / 2;
+            const bool de = kind[(row / 2) * (int64_t)km + (int64_t)m] == MSX_MOVE_DE;
+            for (int64_t j = b; j < b + (int64_t)mh; ++j) {
+                if ((uint32_t)sidx[j] >= mw || (uint32_t)cidx[j] >= mw || (uint32_t)p1[j] >= mh || (uint32_t)p2[j] >= mh)
+                    return "walker / partner index out of range";
+                if (de && p1[j] == p2[j]) return "a DE entry needs two distinct walkers (p1 != p2)";
+            }
+            for (int64_t j = b; j < b + (int64_t)mh; ++j) {  // (the complementary half is checked: resolve)
+                hi[2 * L + j] = (int32_t)(off + cidx[b + p1[j]]);
+                hc2[j] = (int32_t)(off + cidx[b + p2[j]]);
+            }
+        }
+    return nullptr;
+}
+
+// What a chunk's launches need besides the run: the stream, and the plain evaluation of the ns proposals in r->d_q.
+struct MoveTarget {
+    hipStream_t stream;
+    msx_ctx *c;      // the context's run, or
+    msx_group *g;    // the group's
+    std::vector<int64_t> half;
+};
+static int move_eval(const MoveTarget &t, SamplerRun *r) {
+    if (t.c) return msx_logprob_batch_dev(t.c, r->mode, r->d_q, r->ns, r->ndim, r->d_newlp, r->d_wst, t.stream, 0);
+    return msx_group_logprob_batch_dev(t.g, r->mode, r->d_q, t.half.data(), r->ndim, r->d_newlp, r->d_wst, t.stream, 0);
+}
+
+// the chunk's 2 nsteps + 1 step launches and 2 nsteps evaluations; MSX_OK, or the failing call's code (*herr: a HIP error's)
+static int move_chunk_launches(const MoveTarget &t, SamplerRun *r, const ChunkPtrs &cp, const MoveChunkPtrs &mp, int64_t nsteps, hipError_t *herr) {
+    const int64_t ns = r->ns, nw = r->nw;
+    const int k = (int)r->m_nw.size();
+    const MoveMembers M = move_members(r, false);
+    MoveStepArgs A;
+    memset(&A, 0, sizeof(A));
+    A.coords = r->d_coords; A.logp = r->d_logp; A.q = r->d_q; A.newlp = r->d_newlp; A.nacc = r->d_nacc;
+    A.ndim = r->ndim; A.worst = cp.d_worst;
+    auto half_arrays = [&](int64_t j) {  // half-step j of the chunk
+        const int64_t o = j * ns;
+        return MoveChunk{mp.g + o, mp.fac + o, mp.logu + o, mp.sidx + o, mp.c1 + o, mp.c2 + o, mp.kind + (j / 2) * k};
+    };
+    for (int64_t j = 0; j <= 2 * nsteps; ++j) {
+        A.a_on = j > 0; A.p_on = j < 2 * nsteps;
+        if (A.a_on) {
+            A.a = half_arrays(j - 1);
+            A.chain_row = cp.d_chain + ((j - 1) / 2) * nw * r->ndim; A.lp_row = cp.d_lpchain + ((j - 1) / 2) * nw;
+        }
+        if (A.p_on) A.p = half_arrays(j);
+        hipLaunchKernelGGL(move_step_kernel, dim3((unsigned)k), dim3(256), 0, t.stream, A, M);
+        *herr = hipGetLastError();
+        if (*herr != hipSuccess) return MSX_ERR_HIP;
+        if (A.p_on)
+            if (int rc = move_eval(t, r)) return rc;
+    }
+    return MSX_OK;
+}
+
+struct MoveDraw { const uint64_t *seeds; const msx_move_set *set; int64_t first_iter; };
+
+// one chunk of either run: the checks the families share, the chunk's arrays (drawn or packed and uploaded), the launches
+static int moves_enqueue(std::string *err, const MoveTarget &t, SamplerRun *r, const std::string &w, int32_t slot, int64_t nsteps,
+                         const int32_t *sidx, const int32_t *cidx, const int32_t *kind, const int32_t *p1, const int32_t *p2,
+                         const double *g, const double *fac, const double *logu, const MoveDraw *draw) {
+    auto bad = [&](int code, const std::string &msg) { *err = w + ": " + msg; return code; };
+    if (r->sharded) return bad(MSX_ERR_STATE, "the sharded run is stretch only");
+    if (r->overlap == 1) return bad(MSX_ERR_STATE, "this run's stretch chunks overlap their half-steps; a run with moves takes plain launches from its first chunk (msx_sampler_policy(ctx, 0))");
+    MoveSetDev S;
+    if (draw) {
+        int64_t min_nw = r->m_nw[0], max_nw = r->m_nw[0];
+        for (int64_t n : r->m_nw) { min_nw = std::min(min_nw, n); max_nw = std::max(max_nw, n); }
+        if (max_nw > kDrawMaxWalkers || draw->first_iter < 0) return bad(MSX_ERR_INVALID, "the device generator takes up to 4096 walkers per ensemble and a first iteration >= 0");
+        if (const char *why = move_set_dev(draw->set, r->ndim, min_nw, &S)) return bad(MSX_ERR_INVALID, why);
+    }
+    SamplerRun::Slot &sl = r->slot[slot];
+    if (!draw)
+        if (const char *why = run_pack_moves(r, sl, nsteps, sidx, cidx, kind, p1, p2, g, fac, logu)) return bad(MSX_ERR_INVALID, why);
+    r->overlap = 0;
+    ChunkPtrs cp;
+    run_chunk_ptrs(r, sl, nsteps, &cp);
+    const MoveChunkPtrs mp = move_chunk_ptrs(r, cp, nsteps);
+    const int k = (int)r->m_nw.size();
+    hipError_t e = hipSuccess;
+    if (draw) {
+        MoveDrawTable T;
+        memset(&T, 0, sizeof(T));
+        T.M = move_members(r, true);
+        for (int m = 0; m < k; ++m) T.seed[m] = (unsigned long long)draw->seeds[m];
+        // (the slot was collected: no launch still reads its arrays, and the stream orders this one before the half-steps)
+        hipLaunchKernelGGL(moves_draw_kernel, dim3((unsigned)nsteps, (unsigned)k), dim3(kDrawThreads), 0, t.stream, T, S, draw->first_iter,
+                           (int32_t)r->ndim, 1, r->ns, mp.sidx, mp.cidx, mp.c1, mp.c2, mp.g, mp.fac, mp.logu, mp.kind);
+        e = hipGetLastError();
+    } else {
+        e = run_upload(r, sl, nsteps, t.stream);
+    }
+    if (e == hipSuccess) e = hipMemsetAsync(cp.d_worst, 0, sizeof(int32_t) * (size_t)r->nworst, t.stream);
+    int rc = MSX_OK;
+    if (e == hipSuccess) rc = move_chunk_launches(t, r, cp, mp, nsteps, &e);
+    if (e == hipSuccess && rc == MSX_OK) e = run_finish(r, slot, nsteps, cp, t.stream);
+    if (e != hipSuccess || rc != MSX_OK) {
+        r->failed = true;  // some of the chunk's half-steps may be queued: only the run's end from here on
+        if (e != hipSuccess) return bad(MSX_ERR_HIP, hipGetErrorString(e));
+        if (t.c ? !t.c->err.empty() : !t.g->err.empty()) *err = t.c ? t.c->err : t.g->err;
+        return rc;
+    }
+    r->steps_done += nsteps;
+    return MSX_OK;
+}
+
+static int sampler_enqueue_moves(msx_ctx *c, const char *who, int32_t slot, int64_t nsteps, const int32_t *sidx, const int32_t *cidx,
+                                 const int32_t *kind, const int32_t *p1, const int32_t *p2, const double *g, const double *fac,
+                                 const double *logu, const MoveDraw *draw) {
+    if (!c) return MSX_ERR_INVALID;
+    SamplerRun *r = c->smp;
+    if (int rc = run_enqueue_check(&c->err, r, who, "msx_sampler_begin", "msx_sampler_end", slot, nsteps,
+                                   draw ? draw->set != nullptr : (sidx && cidx && kind && p1 && p2 && g && fac && logu)))
+        return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->P.smp_on = 0;  // (the plain evaluation)
+    c->P.smp_defer = 0;
+    MoveTarget t{c->stream, c, nullptr, {}};
+    std::string err;
+    const int rc = moves_enqueue(&err, t, r, who, slot, nsteps, sidx, cidx, kind, p1, p2, g, fac, logu, draw);
+    if (rc != MSX_OK) c->err = err;
+    return rc;
+}
+
+int msx_sampler_enqueue_moves(msx_ctx *c, int32_t slot, int64_t nsteps, const int32_t *sidx, const int32_t *cidx, const int32_t *kind,
+                              const int32_t *p1, const int32_t *p2, const double *g, const double *fac, const double *logu) {
+    return sampler_enqueue_moves(c, "msx_sampler_enqueue_moves", slot, nsteps, sidx, cidx, kind, p1, p2, g, fac, logu, nullptr);
+}
+
+int msx_sampler_enqueue_moves_drawn(msx_ctx *c, int32_t slot, int64_t nsteps, uint64_t seed, const msx_move_set *set, int64_t first_iter) {
+    const MoveDraw dd = {&seed, set, first_iter};
+    return sampler_enqueue_moves(c, "msx_sampler_enqueue_moves_drawn", slot, nsteps, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                 nullptr, nullptr, &dd);
+}
+
+int msx_sampler_draw_moves(msx_ctx *c, uint64_t seed, const msx_move_set *set, int64_t first_iter, int64_t nsteps, int64_t nw, int32_t ndim,
+                           int32_t *sidx, int32_t *cidx, int32_t *kind, int32_t *p1, int32_t *p2, double *g, double *fac, double *logu) {
+    if (!c) return MSX_ERR_INVALID;
+    if (!sidx || !cidx || !kind || !p1 || !p2 || !g || !fac || !logu || nsteps < 1 || nw < 2 || (nw & 1) || nw > kDrawMaxWalkers ||
+        first_iter < 0 || ndim < 1)
+        return fail(c, MSX_ERR_INVALID, "msx_sampler_draw_moves: bad arguments (an even number of walkers, at most 4096)");
+    MoveSetDev S;
+    if (const char *why = move_set_dev(set, ndim, nw, &S)) return fail(c, MSX_ERR_INVALID, std::string("msx_sampler_draw_moves: ") + why);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int64_t nh = nsteps * nw;
+    char *d = nullptr;
+    HIP_TRY(c, hipMalloc((void **)&d, (size_t)nh * (3 * sizeof(double) + 4 * sizeof(int32_t)) + (size_t)nsteps * sizeof(int32_t)));
+    double *g_g = (double *)d, *g_fac = g_g + nh, *g_logu = g_fac + nh;
+    int32_t *g_sidx = (int32_t *)(g_logu + nh), *g_cidx = g_sidx + nh, *g_p1 = g_cidx + nh, *g_p2 = g_p1 + nh, *g_kind = g_p2 + nh;
+    MoveDrawTable T;
+    memset(&T, 0, sizeof(T));
+    T.seed[0] = (unsigned long long)seed;
+    T.M.nh[0] = (int32_t)nw;
+    hipLaunchKernelGGL(moves_draw_kernel, dim3((unsigned)nsteps, 1u), dim3(kDrawThreads), 0, c->stream, T, S, first_iter, ndim, 0, nw / 2, g_sidx,
+                       g_cidx, g_p1, g_p2, g_g, g_fac, g_logu, g_kind);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = hipMemcpy(g, g_g, sizeof(double) * nh, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(fac, g_fac, sizeof(double) * nh, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(logu, g_logu, sizeof(double) * nh, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(sidx, g_sidx, sizeof(int32_t) * nh, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(cidx, g_cidx, sizeof(int32_t) * nh, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(p1, g_p1, sizeof(int32_t) * nh, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(p2, g_p2, sizeof(int32_t) * nh, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(kind, g_kind, sizeof(int32_t) * nsteps, hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    if (e != hipSuccess) return fail(c, MSX_ERR_HIP, std::string("msx_sampler_draw_moves: ") + hipGetErrorString(e));
+    return MSX_OK;
+}
+
+static int group_sampler_enqueue_moves(msx_group *g, const char *who, int32_t slot, int64_t nsteps, const int32_t *sidx, const int32_t *cidx,
+                                       const int32_t *kind, const int32_t *p1, const int32_t *p2, const double *gg, const double *fac,
+                                       const double *logu, const MoveDraw *draw) {
+    if (!g) return MSX_ERR_INVALID;
+    GroupRun *gr = g->run;
+    if (int rc = run_enqueue_check(&g->err, gr ? gr->r : nullptr, who, "msx_group_sampler_begin", "msx_group_sampler_end", slot, nsteps,
+                                   draw ? (draw->seeds && draw->set) : (sidx && cidx && kind && p1 && p2 && gg && fac && logu)))
+        return rc;
+    SamplerRun *r = gr->r;
+    // a member restaged or destroyed since begin: the run is over (group_sampler_enqueue)
+    int64_t total = 0;
+    std::vector<int64_t> counts(r->m_nw);
+    if (int rc = group_check(g, who, r->mode, counts.data(), r->ndim, &total)) {
+        r->failed = true;
+        return rc;
+    }
+    HIP_TRY(g, hipSetDevice(g->device));
+    MoveTarget t{gr->stream, nullptr, g, {}};
+    for (int64_t n : r->m_nw) t.half.push_back(n / 2);
+    std::string err;
+    const int rc = moves_enqueue(&err, t, r, who, slot, nsteps, sidx, cidx, kind, p1, p2, gg, fac, logu, draw);
+    if (rc != MSX_OK) g->err = err;
+    return rc;
+}
+
+int msx_group_sampler_enqueue_moves(msx_group *g, int32_t slot, int64_t nsteps, const int32_t *sidx, const int32_t *cidx, const int32_t *kind,
+                                    const int32_t *p1, const int32_t *p2, const double *gg, const double *fac, const double *logu) {
+    return group_sampler_enqueue_moves(g, "msx_group_sampler_enqueue_moves", slot, nsteps, sidx, cidx, kind, p1, p2, gg, fac, logu, nullptr);
+}
+
+int msx_group_sampler_enqueue_moves_drawn(msx_group *g, int32_t slot, int64_t nsteps, const uint64_t *seeds, const msx_move_set *set,
+                                          int64_t first_iter) {
+    const MoveDraw dd = {seeds, set, first_iter};
+    return group_sampler_enqueue_moves(g, "msx_group_sampler_enqueue_moves_drawn", slot, nsteps, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                       nullptr, nullptr, nullptr, &dd);
 }
 
 // ---- device chain series ------------------------------------------------------------------------

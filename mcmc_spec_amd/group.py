@@ -95,7 +95,9 @@ class GroupSampler:
     ``draws(first_iteration, m)`` callable per target, handed to the target's ``EnsembleSampler(draws=...)`` in place of its
     generators -- with ``ctx.sampler_draw`` of target k's device seed, the host twin of ``DeviceGroupSampler(rng='device')``."""
 
-    def __init__(self, nwalkers, ndim, log_prob_fn, a=2.0, seeds=None, draws=None):
+    def __init__(self, nwalkers, ndim, log_prob_fn, a=None, seeds=None, draws=None, moves=None, _general=False):
+        """``moves``: ``EnsembleSampler``'s, one set for every target (each target chooses its own move per iteration from
+        its own stream)."""
         nwalkers = [int(n) for n in nwalkers]
         seeds = [None] * len(nwalkers) if seeds is None else list(seeds)
         if len(seeds) != len(nwalkers):
@@ -106,8 +108,9 @@ class GroupSampler:
         self.ndim = int(ndim)
         self.log_prob_fn = log_prob_fn
         # one EnsembleSampler per target holds its generators and its bookkeeping; its own log_prob_fn is never called
-        self.samplers = [EnsembleSampler(n, ndim, None, a=a, vectorize=True, seed=s, draws=d)
+        self.samplers = [EnsembleSampler(n, ndim, None, a=a, vectorize=True, seed=s, draws=d, moves=moves, _general=_general)
                          for n, s, d in zip(nwalkers, seeds, draws)]
+        self._moves = self.samplers[0]._moves if self.samplers else None
 
     @property
     def nwalkers(self):
@@ -137,7 +140,7 @@ class GroupSampler:
         return out
 
     def _stretch_step(self, coords, logp):
-        """One iteration of every target: the stretch move's half-steps (_propose, _accept), the K targets' evaluations batched."""
+        """One iteration of every target: the move's half-steps (_propose, _accept), the K targets' evaluations batched."""
         draws = [s._draw_steps(1) for s in self.samplers]
         accepted = [np.zeros(s.nwalkers, dtype=bool) for s in self.samplers]
         for h in (0, 1):
@@ -240,7 +243,8 @@ class DeviceGroupSampler(GroupSampler):
 
     DEVICE_RNG_MAX_WALKERS = 4096   # csrc/logprob_kernel.h, kDrawMaxWalkers: one ensemble's (key, index) sort in LDS
 
-    def __init__(self, nwalkers, ndim, group, mode='logposterior', a=2.0, seeds=None, chunk=64, autocorr='host', rng='host'):
+    def __init__(self, nwalkers, ndim, group, mode='logposterior', a=None, seeds=None, chunk=64, autocorr='host', rng='host',
+                 moves=None, _general=False):
         if mode not in ('logposterior', 'loglikelihood'):
             raise ValueError("mode must be 'logposterior' or 'loglikelihood'")
         if rng not in ('host', 'device'):
@@ -261,7 +265,7 @@ class DeviceGroupSampler(GroupSampler):
         fn = group.logposterior if mode == 'logposterior' else group.loglikelihood
         if autocorr not in ('host', 'device'):
             raise ValueError("autocorr must be 'host' or 'device'")
-        super().__init__(nwalkers, ndim, fn, a=a, seeds=seeds)
+        super().__init__(nwalkers, ndim, fn, a=a, seeds=seeds, moves=moves, _general=_general)
         self.chunk = int(chunk)
         self.rng_mode = rng
         seeds = [None] * len(nwalkers) if seeds is None else list(seeds)
@@ -278,15 +282,20 @@ class DeviceGroupSampler(GroupSampler):
 
     def _draw_moves_all(self, m):
         moves = [s._draw_moves(m) for s in self.samplers]
+        if self._moves is not None:   # the general layout: kind (m, K), the other arrays side by side
+            return [np.stack([mv[0] for mv in moves], axis=1)] + [np.concatenate(x, axis=2) for x in list(zip(*moves))[1:]]
         return [np.concatenate(x, axis=2) for x in zip(*moves)]
 
     def _enqueue(self, slot, m, arrays):
         grp = self.group.group
         if arrays is not None:
-            return grp.sampler_enqueue(slot, *arrays)
+            return (grp.sampler_enqueue_moves if self._moves is not None else grp.sampler_enqueue)(slot, *arrays)
         # the device draws: every target's stream at its absolute iteration (equal for all targets), which only a queued
         # chunk advances
-        grp.sampler_enqueue_drawn(slot, m, self.device_seeds, self.samplers[0].a, self.samplers[0]._drawn)
+        if self._moves is not None:
+            grp.sampler_enqueue_moves_drawn(slot, m, self.device_seeds, self._moves, self.samplers[0]._drawn)
+        else:
+            grp.sampler_enqueue_drawn(slot, m, self.device_seeds, self.samplers[0].a, self.samplers[0]._drawn)
         for s in self.samplers:
             s._drawn += m
         return m

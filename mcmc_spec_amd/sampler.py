@@ -41,6 +41,22 @@ def counter_draws(seed, a, ndim, first_iter, m, nwalkers):
     differences), which is why the device-drawn chain is checked against the host loop fed with ``msx_sampler_draw``'s
     arrays, and this restatement against those arrays (tests/test_gpu_overlap.py)."""
     nw, ns = int(nwalkers), int(nwalkers) // 2
+    sidx, cidx, uniform = counter_streams(seed, first_iter, m, nw)
+    uz, up, ua = (np.stack([uniform(k + 3 * h, ns) for h in (0, 1)], axis=1) for k in (1, 2, 3))
+    t1 = (float(a) - 1.0) * uz + 1.0
+    zz = (t1 * t1) / float(a)
+    partner = np.minimum((up * ns).astype(np.int32), ns - 1)
+    with np.errstate(divide='ignore'):
+        logu = np.log(ua)
+    zfac = (float(ndim) - 1.0) * np.log(zz)
+    return sidx, cidx, partner, zz, zfac, logu
+
+
+def counter_streams(seed, first_iter, m, nwalkers):
+    """The counter generator's pieces for iterations ``first_iter .. first_iter + m - 1`` of ``seed``: ``sidx, cidx`` (the
+    split: the walkers sorted by stream 0's keys) and ``uniform(stream, n)`` -> (m, n), the uniforms of indices 0..n-1 of
+    one stream.  Shared by ``counter_draws`` and ``moves.counter_draws_moves``."""
+    nw, ns = int(nwalkers), int(nwalkers) // 2
     u64 = np.uint64
     seed = u64(int(seed) & 0xffffffffffffffff)
 
@@ -53,24 +69,16 @@ def counter_draws(seed, a, ndim, first_iter, m, nwalkers):
             x ^= x >> u64(31)
         return x
 
-    def uniform(it, stream, index):
-        return (mix(it, stream, index) >> u64(11)).astype(np.float64) * (1.0 / 9007199254740992.0)
-
     it = (np.arange(m, dtype=np.int64) + int(first_iter))[:, None]
+
+    def uniform(stream, n):
+        k = mix(np.broadcast_to(it, (m, n)), stream, np.broadcast_to(np.arange(n)[None, :], (m, n)))
+        return (k >> u64(11)).astype(np.float64) * (1.0 / 9007199254740992.0)
+
     keys = mix(np.broadcast_to(it, (m, nw)), 0, np.broadcast_to(np.arange(nw)[None, :], (m, nw)))
     perm = np.argsort(keys, axis=1, kind='stable').astype(np.int32)      # sorted by (key, index)
     halves = perm.reshape(m, 2, ns)
-    sidx, cidx = halves, halves[:, ::-1]
-    j = np.broadcast_to(np.arange(ns)[None, :], (m, ns))
-    itb = np.broadcast_to(it, (m, ns))
-    uz, up, ua = (np.stack([uniform(itb, k + 3 * h, j) for h in (0, 1)], axis=1) for k in (1, 2, 3))
-    t1 = (float(a) - 1.0) * uz + 1.0
-    zz = (t1 * t1) / float(a)
-    partner = np.minimum((up * ns).astype(np.int32), ns - 1)
-    with np.errstate(divide='ignore'):
-        logu = np.log(ua)
-    zfac = (float(ndim) - 1.0) * np.log(zz)
-    return np.ascontiguousarray(sidx), np.ascontiguousarray(cidx), partner, zz, zfac, logu
+    return np.ascontiguousarray(halves), np.ascontiguousarray(halves[:, ::-1]), uniform
 
 
 def device_seed(seed):
@@ -85,22 +93,31 @@ def device_seed(seed):
 
 
 class EnsembleSampler:
-    def __init__(self, nwalkers, ndim, log_prob_fn, args=None, kwargs=None, a=2.0, vectorize=False, pool=None,
-                 threads=None, seed=None, draws=None):
-        """``draws(first_iteration, m)`` (optional) replaces the sampler's own generators: it returns the randomness of
+    def __init__(self, nwalkers, ndim, log_prob_fn, args=None, kwargs=None, a=None, vectorize=False, pool=None,
+                 threads=None, seed=None, draws=None, moves=None, _general=False):
+        """``moves`` (optional): a ``moves.StretchMove`` / ``moves.DEMove``, a list of them (equal weights) or a list of
+        ``(move, weight)`` -- emcee's ``moves=``; each iteration takes one move of the set, chosen with the normalised
+        weights.  None, or a ``StretchMove`` alone, is the stretch move through the code path it has always had (``a=`` and
+        ``moves=`` exclude each other); a set with another move goes through the general propose / accept
+        (``mcmc_spec_amd.moves``).
+
+        ``draws(first_iteration, m)`` (optional) replaces the sampler's own generators: it returns the randomness of
         ``m`` iterations in ``_draw_steps``' layout -- e.g. ``lambda i, m: ctx.sampler_draw(seed, a, i, m, nwalkers, ndim)``
         makes this host loop walk the chain the device-resident sampler draws for itself (``rng='device'``)."""
         self._draws = draws
         self._drawn = 0
+        a, self._moves = _resolve_moves(a, moves, _general)
         if nwalkers < 2 * ndim or nwalkers % 2:
             raise ValueError('the stretch move needs an even number of walkers >= 2*ndim')
+        if self._moves is not None and not self._moves.pure_stretch and nwalkers < 4:
+            raise ValueError('the DE move needs two distinct walkers in each half: at least 4 walkers')
         if threads is not None:
             warnings.warn('threads= is an emcee-2 argument and is ignored (as in emcee 3)', DeprecationWarning)
         self.nwalkers, self.ndim = int(nwalkers), int(ndim)
         self.log_prob_fn = log_prob_fn
         self.args = list(args or [])
         self.kwargs = dict(kwargs or {})
-        self.a = float(a)
+        self.a = a
         self.vectorize = bool(vectorize)
         self.pool = pool
         # two independent streams of one seed: uniforms (stretch factors, partners, accept draws) and the
@@ -163,7 +180,9 @@ class EnsembleSampler:
         half the stretch factors ``z = ((a-1)u+1)^2/a``, the partner index ``floor(u*n_half)`` and ``ln u`` of
         the accept draw.  Returns ``sidx, cidx, partner`` (int32) and ``zz, zfac, logu`` (float64), each of
         shape (m, 2, nwalkers/2); ``zfac = (ndim-1) ln z``.  Shared by the host loop and the device-resident
-        loop; everything is vectorised over the m iterations (the host must stay ahead of a 23 us kernel)."""
+        loop; everything is vectorised over the m iterations (the host must stay ahead of a 23 us kernel).
+        A sampler with a set of moves returns the general layout instead: ``sidx, cidx, kind[m], p1, p2, g, fac, logu``
+        (``mcmc_spec_amd.moves``)."""
         if self._draws is not None:
             out = self._draws(self._drawn, m)
             self._drawn += m
@@ -179,8 +198,23 @@ class EnsembleSampler:
         return halves, halves[:, ::-1]
 
     def _draw_moves(self, m):
-        """(partner, zz, zfac, logu) of m iterations (stream ``rng``)."""
+        """(partner, zz, zfac, logu) of m iterations (stream ``rng``); with a set of moves the general layout's (kind, p1,
+        p2, g, fac, logu) -- ``moves.general_draws``.  Per iteration the generator yields the stretch move's 3 x 2 x ns
+        uniforms and, for a set with a DE move, one more for the move's choice and 3 x 2 x ns for the pairs and the
+        normal deviates: row by row, so m iterations at once are m calls of one, and a pure-stretch set consumes the
+        stream exactly as the default move does."""
         ns = self.nwalkers // 2
+        if self._moves is not None:
+            from . import moves as mv
+            mset, n6 = self._moves, 6 * ns
+            u = self.rng.random((m, n6 if mset.pure_stretch else 2 * n6 + 1))
+            uz, up, ua = (np.ascontiguousarray(u[:, :n6].reshape(m, 3, 2, ns)[:, j]) for j in range(3))
+            if mset.pure_stretch:
+                which, ud, u1, u2 = np.zeros(m, dtype=np.int32), None, None, None
+            else:
+                which = mv.choose_kind(mset, u[:, n6])
+                ud, u1, u2 = (np.ascontiguousarray(u[:, n6 + 1:].reshape(m, 3, 2, ns)[:, j]) for j in range(3))
+            return mv.general_draws(mset, self.ndim, ns, which, uz, up, ua, ud, u1, u2)
         u = self.rng.random((m, 3, 2, ns))
         # contiguous operands: the elementwise loops (log in particular) then take the same code path for
         # every m, which the bit-identity of host and device chains relies on
@@ -300,25 +334,53 @@ def _device_integrated_time(series, n_total, c, discard, thin):
     return tau
 
 
-# One half-step of the stretch move, in two parts around the evaluation of the proposals (EnsembleSampler, and
-# GroupSampler for each of its targets).  draws: _draw_steps' six arrays for one iteration; h: the half.
+# One half-step of a move, in two parts around the evaluation of the proposals (EnsembleSampler, and GroupSampler for
+# each of its targets).  draws: _draw_steps' arrays for one iteration -- the stretch move's six (sidx, cidx, partner, zz,
+# zfac, logu) or the general layout's eight (sidx, cidx, kind, p1, p2, g, fac, logu: mcmc_spec_amd.moves); h: the half.
 def _propose(coords, draws, h):
-    """The proposals q of half h: each active walker s stretched towards its partner in the other half."""
-    sidx, cidx, part, zz = (d[0, h] for d in draws[:4])
+    """The proposals q of half h: each active walker s stretched towards its partner in the other half, or (a DE
+    iteration of the general layout) displaced by g times the difference of two walkers of the other half."""
+    if len(draws) == 6:
+        sidx, cidx, p1, g = (d[0, h] for d in draws[:4])
+        de = False
+    else:
+        sidx, cidx, p1, p2, g = (draws[i][0, h] for i in (0, 1, 3, 4, 5))
+        de = int(draws[2][0]) != 0
     s, c = coords[sidx], coords[cidx]
-    partner = c[part]
-    return partner - (partner - s) * zz[:, None]
+    if de:
+        diff = c[p1] - c[p2]
+        prod = g[:, None] * diff
+        return s + prod
+    partner = c[p1]
+    return partner - (partner - s) * g[:, None]
 
 
 def _accept(coords, logp, accepted, draws, h, q, new_lp):
-    """The accept rule of half h, in place: walkers whose ln u < (ndim-1) ln z + ln p(q) - ln p(s) move to q."""
-    s_idx, zfac, logu = draws[0][0, h], draws[4][0, h], draws[5][0, h]
+    """The accept rule of half h, in place: walkers whose ln u < factor + ln p(q) - ln p(s) move to q (factor: the stretch
+    move's (ndim-1) ln z, 0 for a DE iteration)."""
+    s_idx, zfac, logu = draws[0][0, h], draws[-2][0, h], draws[-1][0, h]
     with np.errstate(invalid='ignore'):  # -inf - -inf = nan -> compares False -> rejected
         lnpdiff = zfac + new_lp - logp[s_idx]
     acc = logu < lnpdiff
     coords[s_idx[acc]] = q[acc]
     logp[s_idx[acc]] = new_lp[acc]
     accepted[s_idx[acc]] = True
+
+
+def _resolve_moves(a, moves, general=False):
+    """(a, MoveSet or None) of a sampler's ``a=`` and ``moves=``: None for the stretch move through its own path -- no
+    ``moves=``, or a ``StretchMove`` alone (whose ``a`` is then the sampler's) unless ``general`` forces it through the
+    general one (the tests' comparison of the two paths)."""
+    if moves is None:
+        return (2.0 if a is None else float(a)), None
+    if a is not None:
+        raise ValueError('a= and moves= exclude each other: give the stretch scale as moves.StretchMove(a)')
+    from .moves import parse_moves
+    mset = parse_moves(moves)
+    a0 = next((m.a for m in mset.moves if m.kind == 0), 2.0)
+    if len(mset) == 1 and mset.pure_stretch and not general:
+        return a0, None
+    return a0, mset
 
 
 def _pump(iterations, chunk, draws, enqueue, collect, end):
@@ -383,8 +445,8 @@ class DeviceEnsembleSampler(EnsembleSampler):
     stepped.  Both remain valid chains; a later run on the same sampler then matches a twin whose ``_drawn`` is set to
     this sampler's."""
 
-    def __init__(self, nwalkers, ndim, engine, mode='logposterior', a=2.0, seed=None, chunk=64, shard=None, rng='host', overlap=None,
-                 autocorr='host'):
+    def __init__(self, nwalkers, ndim, engine, mode='logposterior', a=None, seed=None, chunk=64, shard=None, rng='host', overlap=None,
+                 autocorr='host', moves=None, _general=False):
         """``shard = (rank, world)`` runs the SHARDED form: every rank holds the whole ensemble on
         its GPU, evaluates block ``rank`` of each half-step's proposals, one RCCL all-gather of the new
         log-probabilities crosses xGMI and every rank applies the accept rule for all walkers on the device.
@@ -402,6 +464,9 @@ class DeviceEnsembleSampler(EnsembleSampler):
         # half-steps fit the chip together: include/msx.h, msx_sampler_policy); False: plain launches -- the choice for a
         # GPU shared with other work, where a waiting workgroup's producer may not get a CU (the chunk then fails with
         # MSX_W_HANDOVER after a bounded wait, a RuntimeError here, and the run has to be started again).
+        # moves: EnsembleSampler's.  A set with a move other than the stretch move runs beside the fused kernel: a small kernel
+        # proposes, the plain evaluation scores, a small kernel accepts (msx_sampler_enqueue_moves*) --
+        # plain launches (overlapped is False: the overlapped hand-over is part of the fused proposal), one GPU.
         # autocorr = 'host' (default): get_autocorr_time is EnsembleSampler's (the chain on the host, one FFT per walker and
         # dimension).  'device': the sampler keeps its stored chain on the device as well (a _lib.Series that every
         # sample(store=True) run appends to, from row len(self._chain) on) and get_autocorr_time computes the
@@ -423,7 +488,11 @@ class DeviceEnsembleSampler(EnsembleSampler):
         self.engine = engine
         self._mode = {'logposterior': _lib.MODE_LOGPOST, 'loglikelihood': _lib.MODE_LOGLIKE}[mode]
         fn = engine.logposterior if mode == 'logposterior' else engine.loglikelihood
-        super().__init__(nwalkers, ndim, fn, a=a, vectorize=True, seed=seed)
+        super().__init__(nwalkers, ndim, fn, a=a, vectorize=True, seed=seed, moves=moves, _general=_general)
+        if self._moves is not None:
+            if self.shard is not None and self.shard[1] > 1:
+                raise ValueError('moves=: the sharded run (shard=(rank, world > 1)) is stretch only')
+            self.overlap_policy = 0
         self.chunk = int(chunk)
         if autocorr == 'device':
             self._series = _lib.Series(engine.ctx, self.nwalkers, self.ndim)
@@ -448,15 +517,20 @@ class DeviceEnsembleSampler(EnsembleSampler):
         def enqueue(slot, m, arrays):
             if arrays is None:
                 # the device draws: the stream at its absolute iteration, which only a queued chunk advances
-                ctx.sampler_enqueue_drawn(slot, m, self.device_seed, self.a, self._drawn)
+                if self._moves is not None:
+                    ctx.sampler_enqueue_moves_drawn(slot, m, self.device_seed, self._moves, self._drawn)
+                else:
+                    ctx.sampler_enqueue_drawn(slot, m, self.device_seed, self.a, self._drawn)
                 self._drawn += m
+            elif self._moves is not None:
+                ctx.sampler_enqueue_moves(slot, *arrays)
             else:
                 ctx.sampler_enqueue(slot, *arrays)
             self.overlapped = ctx.sampler_overlapped() == 1   # (half-steps on two streams: include/msx.h)
 
         ctx.sampler_policy(self.overlap_policy)
         ctx.sampler_begin(self._mode, coords, logp, self.chunk)
-        if self.shard is not None:
+        if self.shard is not None and self._moves is None:   # (a set of moves runs on one GPU: world is 1, nothing to shard)
             ctx.sampler_shard(*self.shard)
         if store and self._series is not None:
             try:

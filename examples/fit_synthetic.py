@@ -9,6 +9,9 @@
     samples.txt
 
     python examples/fit_synthetic.py --out /tmp/fit --nwalk 48 --nstep 40 --nburn 50 --nsteps 300
+
+With ``--tempered T [--beta-min B]`` the sampler is a ladder of T ensembles (mcmc_spec_amd.tempered):
+burn-in, reset, production; the swap fractions and the cold rung's summary are printed.
 """
 import argparse
 import os
@@ -32,6 +35,9 @@ def main():
                     help="where the protocol's convergence checks compute tau ('device': from the chain kept on the GPU)")
     ap.add_argument('--resident-optimiser', action='store_true',
                     help="the optimiser's chains live on the GPU (optimizer.fit_spec_device): same chains, no host round trip per proposal")
+    ap.add_argument('--tempered', type=int, default=0, metavar='T',
+                    help='parallel tempering: a ladder of T ensembles, geometric from beta = 1 down to --beta-min (0: off)')
+    ap.add_argument('--beta-min', type=float, default=0.02, help='the hottest rung of --tempered')
     args = ap.parse_args()
 
     import mcmc_spec_amd.mft6 as gpu
@@ -90,6 +96,8 @@ def main():
     prior = [*np.zeros(10), plx, plx_err]  # mft6.py:3689
     eng = gpu._staged(specs, fr, 2, data, err, [wl_um.min(), wl_um.max()], ctm, ptm, tmi, tma, matrix, 3000.0, 4200.0, prior,
                       True, True, False, need_prior=True)
+    if args.tempered:
+        return tempered_run(args, eng, p0, truth, t2)
     sampler = DeviceEnsembleSampler(len(p0), 6, eng, seed=args.seed, chunk=50, autocorr=args.autocorr)
     samples = run_reference_protocol(sampler, p0, args.nburn, args.nsteps, nthin=50, dirname=args.out, fname='synthetic')
     print('sampler: {} walkers, {} + {} iterations in {:.2f} s; acceptance {:.2f}'.format(
@@ -108,6 +116,32 @@ def main():
     prod = sampler.get_products(['kep_contrast', 'pri_corr', 'sec_corr'])
     for nm, (lo, mid, hi) in zip(['dKep', 'f_pri', 'f_sec'], prod['quantiles']):
         print('  {:5s} {:.6g} / {:.6g} / {:.6g}'.format(nm, lo, mid, hi))
+    print('wrote', os.path.join(args.out, 'samples.txt'), samples.shape)
+    return truth, med, samples
+
+
+def tempered_run(args, eng, p0, truth, t2):
+    """The sampler block with a temperature ladder: every rung starts from the optimiser's walkers; rung 0 is the posterior."""
+    from mcmc_spec_amd import summary
+    from mcmc_spec_amd.tempered import DeviceTemperedSampler
+    sampler = DeviceTemperedSampler(len(p0), 6, eng, ntemps=args.tempered, beta_min=args.beta_min, seed=args.seed, chunk=50, rng='device')
+    state = sampler.run_mcmc(p0, args.nburn)
+    sampler.reset()
+    sampler.run_mcmc(state, args.nsteps)
+    print('tempered sampler: {} rungs x {} walkers, betas {}, {} + {} iterations in {:.2f} s'.format(
+        sampler.ntemps, len(p0), np.round(sampler.betas, 4), args.nburn, sampler.iteration, time.time() - t2))
+    print('acceptance per rung :', np.round(sampler.acceptance_fraction.mean(axis=1), 3))
+    print('swap fractions      :', np.round(sampler.swap_fraction, 3))
+    cold = np.ascontiguousarray(sampler.get_chain(t=0))
+    samples = cold.reshape(-1, 6)
+    med = np.median(samples, axis=0)
+    print('truth   :', truth)
+    print('median  :', np.round(med, 5))
+    summ = {k: v[0] for k, v in summary.summarize(cold, eng.ctx, None, (0.16, 0.5, 0.84), None, 0, 1).items()}
+    print('posterior 16 / 50 / 84 of the cold rung ({} samples):'.format(int(summ['count'])))
+    for nm, (lo, mid, hi) in zip(['T1', 'T2', 'Av', 'R1', 'R2', 'plx'], summ['quantiles']):
+        print('  {:4s} {:.6g} / {:.6g} / {:.6g}'.format(nm, lo, mid, hi))
+    np.savetxt(os.path.join(args.out, 'samples.txt'), samples)
     print('wrote', os.path.join(args.out, 'samples.txt'), samples.shape)
     return truth, med, samples
 

@@ -383,6 +383,51 @@ int msx_sampler_draw_moves(msx_ctx *ctx, uint64_t seed, const msx_move_set *set,
                            int64_t nw, int32_t ndim, int32_t *sidx, int32_t *cidx, int32_t *kind, int32_t *p1, int32_t *p2,
                            double *g, double *fac, double *logu);
 
+/* ---- parallel tempering: a temperature ladder on the device-resident sampler -------------------
+ * ntemps ensembles ("rungs") of nw walkers on this context's staged problem; rung t samples
+ *   P_t(x) = lpr(x) + beta_t * ll(x),   lpr = MSX_MODE_LOGPRIOR, ll = MSX_MODE_LOGLIKE,   1 = beta_0 > beta_1 > ... > 0
+ * (any strictly descending positive ladder is taken), evaluated in two roundings: prod = beta_t * ll; P = lpr + prod.
+ * Iteration i, for every rung independently, is one iteration of the general layout above for a member of nw walkers (the
+ * split, the iteration's move, proposals, fac, ln u unchanged) with the accept rule ln u < (fac + P_t(q)) - P_t(s), P_t(s)
+ * from the stored lpr and ll.  A proposal whose prior status is MSX_W_REJECT is rejected and its likelihood status ignored;
+ * an error status of the prior, or of the likelihood on a proposal the prior admits, counts toward the rung's worst status.
+ * After the second half-step THE SWAP SWEEP runs, for t = ntemps-1 down to 1 and every walker index w independently:
+ * walker w of rung t and walker w of rung t-1 exchange coordinates, ll and lpr when
+ *   ln u < (beta[t-1] - beta[t]) * (ll[t][w] - ll[t-1][w])      (the difference of the betas formed once, in float64;
+ * a NaN compares false).  Serial in t: a walker can travel several rungs in one iteration.  The chain rows of iteration i
+ * are the state after the sweep.  Beside the fused kernel, as the moves above: per half-step one small launch (one
+ * workgroup per rung) and TWO plain evaluations of the ntemps * nw / 2 proposals, per iteration one launch for the sweep.
+ * One GPU, plain launches: begin is refused (MSX_ERR_STATE) without a staged problem, with a run (msx_sampler_* or
+ * msx_tempered_*) in flight, on a context that holds a communicator, and unless msx_sampler_policy(ctx, 0) was set.
+ * MSX_ERR_INVALID: ntemps outside 1..MSX_MAX_GROUP, betas not finite, not > 0 or not strictly descending, nw odd or < 2, an
+ * initial walker whose lpr is not finite or whose ll is NaN.  While a tempered run is in flight msx_sampler_begin is refused
+ * (MSX_ERR_STATE; so is everything that needs its run, msx_sampler_attach_series included: no device series here).
+ * coords [ntemps][nw][ndim], ll, lpr [ntemps][nw].  Memory: the state and two slots sized for max_chunk_steps.          */
+int msx_tempered_begin(msx_ctx *ctx, int32_t ntemps, const double *betas, int64_t nw, int32_t ndim, int64_t max_chunk_steps,
+                       const double *coords, const double *ll, const double *lpr);
+/* host-drawn chunk: the ntemps members' general layouts -- sidx, cidx, p1, p2, g, fac, logu [nsteps][ntemps][2][nw/2], kind
+ * [nsteps][ntemps], indices rung-local -- and swap_logu [nsteps][ntemps-1][nw], row p of an iteration for the pair of rungs
+ * (p + 1, p) (NULL for one rung).  Checked as msx_sampler_enqueue_moves checks (MSX_ERR_INVALID, nothing queued).        */
+int msx_tempered_enqueue(msx_ctx *ctx, int32_t slot, int64_t nsteps, const int32_t *sidx, const int32_t *cidx,
+                         const int32_t *kind, const int32_t *p1, const int32_t *p2, const double *g, const double *fac,
+                         const double *logu, const double *swap_logu);
+/* the same chunk DRAWN ON THE DEVICE: rung t is msx_sampler_enqueue_moves_drawn's stream of seeds[t] (streams 0..13), and
+ * the swap draws are u = uniform(seeds[0], iteration, stream 14, index (t - 1) * 4096 + w) for the pair (t, t - 1).  A bad
+ * set, more than 4096 walkers per rung, fewer than 4 with a DE move, first_iter < 0: MSX_ERR_INVALID, nothing queued.
+ * Chunks of either family may alternate within a run.                                                                   */
+int msx_tempered_enqueue_drawn(msx_ctx *ctx, int32_t slot, int64_t nsteps, const uint64_t *seeds, const msx_move_set *set,
+                               int64_t first_iter);
+/* that stream on the host, in msx_tempered_enqueue's layout (p1, p2 index the complementary half); needs no run           */
+int msx_tempered_draw(msx_ctx *ctx, int32_t ntemps, const uint64_t *seeds, const msx_move_set *set, int64_t first_iter,
+                      int64_t nsteps, int64_t nw, int32_t ndim, int32_t *sidx, int32_t *cidx, int32_t *kind, int32_t *p1,
+                      int32_t *p2, double *g, double *fac, double *logu, double *swap_logu);
+/* waits for the slot: chain [nsteps][ntemps][nw][ndim], ll_chain, lpr_chain [nsteps][ntemps][nw]; naccept [ntemps][nw] and
+ * nswap [ntemps-1] (swaps accepted per pair) count since begin -- integers, exact whatever the launch; worst [ntemps]   */
+int msx_tempered_collect(msx_ctx *ctx, int32_t slot, double *chain, double *ll_chain, double *lpr_chain, int64_t *naccept,
+                         int64_t *nswap, int32_t *worst);
+/* ends the run (no run: MSX_OK); its final state where the pointers are not NULL                                        */
+int msx_tempered_end(msx_ctx *ctx, double *coords, double *ll, double *lpr);
+
 /* ---- A4-A6: make_composite (mft6.py:651-831, plot=False) -------------------------------------- */
 /* teff/logg/rad are [nspec]; use_distance = 0 mirrors `distance=False` (mft6.py:701-703).         */
 /* spec_out [win_n], contrast_out [n_contrast], phot_out [n_phot] (unreddened magnitudes).         */

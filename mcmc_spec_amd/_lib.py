@@ -149,6 +149,13 @@ def load():
         'msx_group_sampler_enqueue_moves': (C.c_int, [vp, C.c_int32, C.c_int64] + [C.POINTER(C.c_int32)] * 5 + [_dp, _dp, _dp]),
         'msx_group_sampler_enqueue_moves_drawn': (C.c_int, [vp, C.c_int32, C.c_int64, C.POINTER(C.c_uint64), C.POINTER(MsxMoveSet),
                                                             C.c_int64]),
+        'msx_tempered_begin': (C.c_int, [vp, C.c_int32, _dp, C.c_int64, C.c_int32, C.c_int64, _dp, _dp, _dp]),
+        'msx_tempered_enqueue': (C.c_int, [vp, C.c_int32, C.c_int64] + [C.POINTER(C.c_int32)] * 5 + [_dp, _dp, _dp, _dp]),
+        'msx_tempered_enqueue_drawn': (C.c_int, [vp, C.c_int32, C.c_int64, C.POINTER(C.c_uint64), C.POINTER(MsxMoveSet), C.c_int64]),
+        'msx_tempered_draw': (C.c_int, [vp, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(MsxMoveSet), C.c_int64, C.c_int64, C.c_int64,
+                                        C.c_int32] + [C.POINTER(C.c_int32)] * 5 + [_dp, _dp, _dp, _dp]),
+        'msx_tempered_collect': (C.c_int, [vp, C.c_int32, _dp, _dp, _dp, _ip, _ip, C.POINTER(C.c_int32)]),
+        'msx_tempered_end': (C.c_int, [vp, _dp, _dp, _dp]),
         'msx_make_composite': (C.c_int, [vp, _dp, _dp, _dp, C.c_int32, C.c_double, _dp, _dp, _dp,
                                          C.POINTER(C.c_int32)]),
         'msx_comm_unique_id': (C.c_int, [vp, C.POINTER(C.c_uint8)]),
@@ -224,7 +231,9 @@ EXPORTED = ['msx_create', 'msx_destroy', 'msx_last_error', 'msx_device_info', 'm
             'msx_stage_products', 'msx_products_batch', 'msx_products_batch_dev', 'msx_series_derive',
             'msx_products_spectra', 'msx_composite_parts',
             'msx_sampler_enqueue_moves', 'msx_sampler_enqueue_moves_drawn', 'msx_sampler_draw_moves',
-            'msx_group_sampler_enqueue_moves', 'msx_group_sampler_enqueue_moves_drawn']
+            'msx_group_sampler_enqueue_moves', 'msx_group_sampler_enqueue_moves_drawn',
+            'msx_tempered_begin', 'msx_tempered_enqueue', 'msx_tempered_enqueue_drawn', 'msx_tempered_draw', 'msx_tempered_collect',
+            'msx_tempered_end']
 
 
 def as_f64(a):
@@ -686,6 +695,83 @@ class Context:
     def sampler_attach_series(self, series, at_row):
         """Append every chunk of the run begun by sampler_begin to ``series`` from row ``at_row`` on (msx_sampler_attach_series)."""
         self.check(self.lib.msx_sampler_attach_series(self.h, series.h, int(at_row)))
+
+    # ---- parallel tempering (msx_tempered_*; mcmc_spec_amd.tempered) -------------------------------------------------
+    def tempered_begin(self, betas, coords, ll, lpr, max_chunk_steps):
+        """Start a tempered run (msx_tempered_begin): coords (T, nw, ndim), ll, lpr (T, nw).  Plain launches:
+        ``sampler_policy(0)`` must have been set."""
+        betas, coords, ll, lpr = as_f64(betas), as_f64(coords), as_f64(ll), as_f64(lpr)
+        T, nw, ndim = coords.shape
+        if betas.shape != (T,) or ll.shape != (T, nw) or lpr.shape != (T, nw):
+            raise ValueError('tempered_begin: betas (T,), coords (T, nw, ndim), ll and lpr (T, nw)')
+        self.check(self.lib.msx_tempered_begin(self.h, T, dptr(betas), nw, ndim, int(max_chunk_steps), dptr(coords), dptr(ll), dptr(lpr)))
+        self._tmp_shape = (T, nw, ndim)
+
+    def tempered_enqueue(self, slot, sidx, cidx, kind, p1, p2, g, fac, logu, swap_logu):
+        """Queue one host-drawn chunk (msx_tempered_enqueue): kind (nsteps, T), swap_logu (nsteps, T - 1, nw), the others
+        (nsteps, T, 2, nw / 2)."""
+        i32p = C.POINTER(C.c_int32)
+        T, nw, _ = self._tmp_shape
+        ints = [np.ascontiguousarray(a, dtype=np.int32) for a in (sidx, cidx, kind, p1, p2)]
+        dbl = [as_f64(a) for a in (g, fac, logu, swap_logu)]
+        nsteps = dbl[0].shape[0]
+        for a in [ints[0], ints[1], ints[3], ints[4]] + dbl[:3]:
+            if a.shape != (nsteps, T, 2, nw // 2):
+                raise ValueError('tempered_enqueue: arrays must have shape (nsteps, T, 2, walkers / 2)')
+        if ints[2].shape != (nsteps, T) or dbl[3].shape != (nsteps, T - 1, nw):
+            raise ValueError('tempered_enqueue: kind (nsteps, T), swap_logu (nsteps, T - 1, walkers)')
+        self.check(self.lib.msx_tempered_enqueue(self.h, int(slot), nsteps, *[a.ctypes.data_as(i32p) for a in ints], *[dptr(a) for a in dbl]))
+        return nsteps
+
+    def tempered_enqueue_drawn(self, slot, nsteps, seeds, moves, first_iter):
+        """Queue one chunk whose randomness the device draws (msx_tempered_enqueue_drawn): rung t from ``seeds[t]``, the swap
+        draws from ``seeds[0]``; the chunk's first step is the ABSOLUTE iteration ``first_iter``."""
+        seeds = np.array([int(s) & 0xffffffffffffffff for s in seeds], dtype=np.uint64)
+        if seeds.shape != (self._tmp_shape[0],):
+            raise ValueError('tempered_enqueue_drawn: one seed per rung')
+        st = _move_set(moves)
+        self.check(self.lib.msx_tempered_enqueue_drawn(self.h, int(slot), int(nsteps), seeds.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                       C.byref(st), int(first_iter)))
+        return int(nsteps)
+
+    def tempered_draw(self, seeds, moves, first_iter, nsteps, nw, ndim):
+        """The device's stream for a ladder of ``len(seeds)`` rungs, iterations [first_iter, first_iter + nsteps): ``(members,
+        swap_logu)`` -- members[t] the general layout of rung t (what ``sampler_draw_moves(seeds[t], ...)`` returns) and
+        swap_logu (nsteps, T - 1, nw): what ``TemperedSampler(draws=...)`` takes."""
+        i32p = C.POINTER(C.c_int32)
+        seeds = np.array([int(s) & 0xffffffffffffffff for s in seeds], dtype=np.uint64)
+        T, m = len(seeds), int(nsteps)
+        shp = (m, T, 2, int(nw) // 2)
+        sidx, cidx, p1, p2 = (np.empty(shp, dtype=np.int32) for _ in range(4))
+        kind = np.empty((m, T), dtype=np.int32)
+        g, fac, logu = (np.empty(shp) for _ in range(3))
+        swap = np.empty((m, T - 1, int(nw)))
+        st = _move_set(moves)
+        self.check(self.lib.msx_tempered_draw(self.h, T, seeds.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(st), int(first_iter), m, int(nw),
+                                              int(ndim), *[a.ctypes.data_as(i32p) for a in (sidx, cidx, kind, p1, p2)], dptr(g), dptr(fac),
+                                              dptr(logu), dptr(swap)))
+        members = [tuple(np.ascontiguousarray(a[:, t]) for a in (sidx, cidx, kind, p1, p2, g, fac, logu)) for t in range(T)]
+        return members, swap
+
+    def tempered_collect(self, slot, nsteps):
+        """Wait for the chunk in `slot`: (chain [nsteps][T][nw][ndim], ll, lpr [nsteps][T][nw], naccept [T][nw], nswap [T-1],
+        worst [T]); the counts run since begin."""
+        T, nw, ndim = self._tmp_shape
+        chain, llc, lprc = np.empty((nsteps, T, nw, ndim)), np.empty((nsteps, T, nw)), np.empty((nsteps, T, nw))
+        nacc, nswap, worst = np.zeros((T, nw), dtype=np.int64), np.zeros(T - 1, dtype=np.int64), np.zeros(T, dtype=np.int32)
+        self.check(self.lib.msx_tempered_collect(self.h, int(slot), dptr(chain), dptr(llc), dptr(lprc), iptr(nacc), iptr(nswap),
+                                                 worst.ctypes.data_as(C.POINTER(C.c_int32))))
+        return chain, llc, lprc, nacc, nswap, worst
+
+    def tempered_end(self, want_state=False):
+        """End the run (msx_tempered_end); its final (coords, ll, lpr) if want_state."""
+        if not want_state:
+            self.check(self.lib.msx_tempered_end(self.h, None, None, None))
+            return None
+        T, nw, ndim = self._tmp_shape
+        coords, ll, lpr = np.empty((T, nw, ndim)), np.empty((T, nw)), np.empty((T, nw))
+        self.check(self.lib.msx_tempered_end(self.h, dptr(coords), dptr(ll), dptr(lpr)))
+        return coords, ll, lpr
 
     def make_composite(self, teff, logg, rad, use_distance, plx, win_n, nc, nph):
         teff, logg, rad = as_f64(teff), as_f64(logg), as_f64(rad)

@@ -62,6 +62,7 @@
 #include "median.h"
 #include "logprob_kernel.h"
 #include "move_kernels.h"
+#include "tempered_kernels.h"
 #include "group_kernel.h"
 #include "pair_kernel.h"
 #include "staging_kernels.h"
@@ -155,6 +156,7 @@ struct msx_ctx {
     unsigned char *d_recipe_block = nullptr;  // ... and its tables in one block (dev_types.h), freed with the problem
     struct SamplerRun *smp = nullptr;  // device-resident sampler in flight (msx_sampler_begin .. _end)
     struct OptRun *opt_run = nullptr;  // device-resident pre-optimiser in flight (msx_opt_run_begin .. _end)
+    struct TemperedRun *tmp = nullptr; // tempered ladder in flight (msx_tempered_begin .. _end); excludes smp
     bool smp_overlap_launch = false;   // the launch being queued is a half-step of an overlapped run: fused form, bit 20
     bool probe_launch = false;         // ... is msx_probe_launch's: the kernel leaves clock stamps (bit 21)
     int32_t last_form = 0;             // MSX_FORM_* of the last launch queued (msx_last_form)
@@ -178,6 +180,7 @@ struct msx_ctx {
 };
 static void sampler_free(msx_ctx *c);
 static void opt_run_free(msx_ctx *c);
+static void tempered_free(msx_ctx *c);
 
 // A TARGET GROUP (include/msx.h): 1..MSX_MAX_GROUP staged contexts on one device whose walkers one launch of
 // logprob_group_kernel evaluates, each against its own member's problem.  The group owns snapshots of the members'
@@ -300,6 +303,7 @@ int dev_alloc_copy(msx_ctx *c, std::vector<void *> *track, const T *host, int64_
 void free_problem(msx_ctx *c) {
     sampler_free(c);  // a sampler in flight holds pointers into the problem's tables
     opt_run_free(c);  // ... and a pre-optimiser run into the chains' data vectors
+    tempered_free(c); // ... and a tempered ladder
     for (msx_group *g : c->groups) group_run_drain(g);  // ... and so does a group's (its next enqueue is refused)
     ++c->prob_gen;    // (target groups holding a snapshot of the problem refuse this member from now on)
     for (void *p : c->prob_allocs) (void)hipFree(p);
@@ -2301,6 +2305,7 @@ int msx_sampler_begin(msx_ctx *c, int32_t mode, int64_t nw, int32_t ndim, int64_
         return fail(c, MSX_ERR_INVALID, "msx_sampler_begin: bad arguments (need an even number of walkers)");
     if (ndim != 2 * c->P.nspec + 2) return fail(c, MSX_ERR_INVALID, "P0 doesn't match what I was expecting");
     if (mode != MSX_MODE_LOGPOST && mode != MSX_MODE_LOGLIKE) return fail(c, MSX_ERR_INVALID, "msx_sampler_begin: bad mode");
+    if (c->tmp) return fail(c, MSX_ERR_STATE, "msx_sampler_begin: a tempered run is in flight on this context (msx_tempered_end)");
     HIP_TRY(c, hipSetDevice(c->device));
     sampler_free(c);
     SamplerRun *r = new SamplerRun;
@@ -3647,6 +3652,387 @@ int msx_group_sampler_enqueue_moves_drawn(msx_group *g, int32_t slot, int64_t ns
     const MoveDraw dd = {seeds, set, first_iter};
     return group_sampler_enqueue_moves(g, "msx_group_sampler_enqueue_moves_drawn", slot, nsteps, nullptr, nullptr, nullptr, nullptr, nullptr,
                                        nullptr, nullptr, nullptr, &dd);
+}
+
+// ---- parallel tempering (include/msx.h, msx_tempered_*; tempered_kernels.h) ------------------------
+// The path beside the fused kernel once more: T rungs of nw walkers, all of this context's problem, as the T members of one
+// ensemble in the general layout.  An iteration is
+//   step(propose 0) ; prior ; like ; step(apply 0, propose 1) ; prior ; like ; step(apply 1) ; swap
+// with `prior` / `like` the UNCHANGED plain evaluation of the T ns proposals in MSX_MODE_LOGPRIOR / _LOGLIKE, each into
+// buffers of its own.  Plain launches on the context's stream; nothing allocates or synchronises after begin.
+struct TemperedRun {
+    int32_t T = 0, ndim = 0;
+    int64_t nw = 0, ns = 0, cap_steps = 0;   // nw, ns: per rung
+    bool failed = false;                     // an enqueue returned an error after queuing part of its launches
+    double beta[MSX_MAX_GROUP], db[MSX_MAX_GROUP];
+    char *d_state = nullptr;
+    double *d_coords = nullptr, *d_ll = nullptr, *d_lpr = nullptr, *d_q = nullptr, *d_new_lpr = nullptr, *d_new_ll = nullptr;
+    int64_t *d_nacc = nullptr;
+    unsigned long long *d_nswap = nullptr;
+    int32_t *d_st_lpr = nullptr, *d_st_ll = nullptr;
+    hipStream_t copy = nullptr, up = nullptr;
+    struct Slot {
+        char *d_in = nullptr, *d_out = nullptr, *h_in = nullptr, *h_out = nullptr;
+        hipEvent_t in_ready = nullptr, kernels_done = nullptr, out_ready = nullptr;
+        int64_t nsteps = 0;
+        bool busy = false;
+    } slot[2];
+    // a chunk of st iterations in its slot, laid out for its own length:
+    //   in  [g | fac | logu  (st 2 T ns doubles each) | swap_logu (st (T-1) nw doubles) | sidx | cidx | c1 | c2 (int32) | kind (st T)]
+    //   out [chain st T nw ndim | ll st T nw | lpr st T nw | naccept T nw (int64) | nswap MSX_MAX_GROUP (int64) | worst MSX_MAX_GROUP (int32)]
+    int64_t entries(int64_t st) const { return st * 2 * T * ns; }
+    size_t in_bytes(int64_t st) const {
+        return sizeof(double) * (size_t)(3 * entries(st) + st * (T - 1) * nw) + sizeof(int32_t) * (size_t)(4 * entries(st) + st * T);
+    }
+    size_t out_bytes(int64_t st) const {
+        return sizeof(double) * (size_t)(st * T * nw * (ndim + 2)) + sizeof(int64_t) * (size_t)(T * nw + MSX_MAX_GROUP) + sizeof(int32_t) * MSX_MAX_GROUP;
+    }
+};
+
+struct TemperedIn {
+    double *g, *fac, *logu, *swap_logu;
+    int32_t *sidx, *cidx, *c1, *c2, *kind;
+};
+static TemperedIn tempered_in(const TemperedRun *r, char *base, int64_t st) {
+    const int64_t L = r->entries(st);
+    TemperedIn p;
+    p.g = (double *)base; p.fac = p.g + L; p.logu = p.fac + L; p.swap_logu = p.logu + L;
+    p.sidx = (int32_t *)(p.swap_logu + st * (r->T - 1) * r->nw); p.cidx = p.sidx + L; p.c1 = p.cidx + L; p.c2 = p.c1 + L; p.kind = p.c2 + L;
+    return p;
+}
+struct TemperedOut {
+    double *chain, *ll, *lpr;
+    int64_t *nacc, *nswap;
+    int32_t *worst;
+};
+static TemperedOut tempered_out(const TemperedRun *r, char *base, int64_t st) {
+    const int64_t rows = st * r->T * r->nw;
+    TemperedOut p;
+    p.chain = (double *)base; p.ll = p.chain + rows * r->ndim; p.lpr = p.ll + rows;
+    p.nacc = (int64_t *)(p.lpr + rows); p.nswap = p.nacc + r->T * r->nw; p.worst = (int32_t *)(p.nswap + MSX_MAX_GROUP);
+    return p;
+}
+
+static void tempered_free(msx_ctx *c) {
+    TemperedRun *r = c->tmp;
+    if (!r) return;
+    (void)hipSetDevice(c->device);
+    (void)hipStreamSynchronize(c->stream);
+    if (r->copy) (void)hipStreamSynchronize(r->copy);
+    if (r->up) (void)hipStreamSynchronize(r->up);
+    for (auto &sl : r->slot) {
+        if (sl.d_in) (void)hipFree(sl.d_in);
+        if (sl.d_out) (void)hipFree(sl.d_out);
+        if (sl.h_in) (void)hipHostFree(sl.h_in);
+        if (sl.h_out) (void)hipHostFree(sl.h_out);
+        if (sl.in_ready) (void)hipEventDestroy(sl.in_ready);
+        if (sl.kernels_done) (void)hipEventDestroy(sl.kernels_done);
+        if (sl.out_ready) (void)hipEventDestroy(sl.out_ready);
+    }
+    if (r->d_state) (void)hipFree(r->d_state);
+    if (r->copy) (void)hipStreamDestroy(r->copy);
+    if (r->up) (void)hipStreamDestroy(r->up);
+    delete r;
+    c->tmp = nullptr;
+}
+
+int msx_tempered_begin(msx_ctx *c, int32_t ntemps, const double *betas, int64_t nw, int32_t ndim, int64_t max_chunk_steps,
+                       const double *coords, const double *ll, const double *lpr) {
+    if (!c) return MSX_ERR_INVALID;
+    if (!c->problem_staged) return fail(c, MSX_ERR_STATE, "msx_tempered_begin: no problem staged");
+    if (c->smp || c->tmp) return fail(c, MSX_ERR_STATE, "msx_tempered_begin: a run is already in flight on this context (msx_sampler_end / msx_tempered_end)");
+    if (c->rccl_comm || !c->loop_peers.empty()) return fail(c, MSX_ERR_STATE, "msx_tempered_begin: a tempered run is one GPU; this context holds a communicator");
+    if (c->smp_overlap_policy != 0)
+        return fail(c, MSX_ERR_STATE, "msx_tempered_begin: the run takes plain launches; set msx_sampler_policy(ctx, 0) first");
+    if (!betas || !coords || !ll || !lpr || max_chunk_steps < 1) return fail(c, MSX_ERR_INVALID, "msx_tempered_begin: bad arguments");
+    if (ntemps < 1 || ntemps > MSX_MAX_GROUP) return fail(c, MSX_ERR_INVALID, "msx_tempered_begin: a ladder has 1..MSX_MAX_GROUP rungs");
+    for (int t = 0; t < ntemps; ++t)
+        if (!std::isfinite(betas[t]) || !(betas[t] > 0.0) || (t > 0 && !(betas[t] < betas[t - 1])))
+            return fail(c, MSX_ERR_INVALID, "msx_tempered_begin: betas must be finite, > 0 and strictly descending");
+    if (nw < 2 || (nw & 1)) return fail(c, MSX_ERR_INVALID, "msx_tempered_begin: a rung needs an even number of walkers");
+    if (ndim != 2 * c->P.nspec + 2) return fail(c, MSX_ERR_INVALID, "P0 doesn't match what I was expecting");
+    if ((int64_t)ntemps * nw * (int64_t)ndim * max_chunk_steps > ((int64_t)1 << 31))
+        return fail(c, MSX_ERR_INVALID, "msx_tempered_begin: the chunk is too long for this ladder (ntemps x nw x ndim x steps <= 2^31)");
+    for (int64_t i = 0; i < (int64_t)ntemps * nw; ++i)
+        if (!std::isfinite(lpr[i]) || std::isnan(ll[i]))
+            return fail(c, MSX_ERR_INVALID, "msx_tempered_begin: an initial walker lies outside the prior (lpr not finite) or its ll is NaN");
+    HIP_TRY(c, hipSetDevice(c->device));
+    TemperedRun *r = new TemperedRun;
+    c->tmp = r;
+    r->T = ntemps; r->ndim = ndim; r->nw = nw; r->ns = nw / 2; r->cap_steps = max_chunk_steps;
+    memset(r->beta, 0, sizeof(r->beta)); memset(r->db, 0, sizeof(r->db));
+    for (int t = 0; t < ntemps; ++t) r->beta[t] = betas[t];
+    for (int t = 0; t + 1 < ntemps; ++t) r->db[t] = betas[t] - betas[t + 1];
+    const int64_t W = (int64_t)ntemps * nw, H = (int64_t)ntemps * r->ns;
+    const size_t state_bytes = sizeof(double) * (size_t)(W * ndim + 2 * W + H * ndim + 2 * H) + sizeof(int64_t) * (size_t)(W + MSX_MAX_GROUP) +
+                               sizeof(int32_t) * (size_t)(2 * H);
+    hipError_t e = hipMalloc((void **)&r->d_state, state_bytes);
+    if (e == hipSuccess) e = hipMemsetAsync(r->d_state, 0, state_bytes, c->stream);
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&r->copy, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&r->up, hipStreamNonBlocking);
+    for (auto &sl : r->slot) {
+        if (e == hipSuccess) e = hipMalloc((void **)&sl.d_in, r->in_bytes(r->cap_steps));
+        if (e == hipSuccess) e = hipMalloc((void **)&sl.d_out, r->out_bytes(r->cap_steps));
+        if (e == hipSuccess) e = hipHostMalloc((void **)&sl.h_in, r->in_bytes(r->cap_steps), hipHostMallocDefault);
+        if (e == hipSuccess) e = hipHostMalloc((void **)&sl.h_out, r->out_bytes(r->cap_steps), hipHostMallocDefault);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.in_ready, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.kernels_done, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.out_ready, hipEventDisableTiming);
+    }
+    if (e == hipSuccess) {
+        r->d_coords = (double *)r->d_state; r->d_ll = r->d_coords + W * ndim; r->d_lpr = r->d_ll + W; r->d_q = r->d_lpr + W;
+        r->d_new_lpr = r->d_q + H * ndim; r->d_new_ll = r->d_new_lpr + H;
+        r->d_nacc = (int64_t *)(r->d_new_ll + H); r->d_nswap = (unsigned long long *)(r->d_nacc + W);
+        r->d_st_lpr = (int32_t *)(r->d_nswap + MSX_MAX_GROUP); r->d_st_ll = r->d_st_lpr + H;
+        e = hipMemcpyAsync(r->d_coords, coords, sizeof(double) * (size_t)(W * ndim), hipMemcpyHostToDevice, c->stream);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(r->d_ll, ll, sizeof(double) * (size_t)W, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(r->d_lpr, lpr, sizeof(double) * (size_t)W, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        tempered_free(c);
+        return fail(c, MSX_ERR_HIP, std::string("msx_tempered_begin: ") + hipGetErrorString(e));
+    }
+    return MSX_OK;
+}
+
+// The chunk's host randomness -- the T members' general layouts [nsteps][T][2][ns], kind [nsteps][T], indices rung-local,
+// swap_logu [nsteps][T - 1][nw] -- checked (run_pack_moves' checks: every index is dereferenced on the device) and packed
+// into the slot's pinned staging in the device's order [nsteps][2][T][ns].  nullptr, or what is wrong.
+static const char *tempered_pack(const TemperedRun *r, char *h_in, int64_t nsteps, const int32_t *sidx, const int32_t *cidx, const int32_t *kind,
+                                 const int32_t *p1, const int32_t *p2, const double *g, const double *fac, const double *logu,
+                                 const double *swap_logu) {
+    const int64_t ns = r->ns, T = r->T;
+    const uint32_t mw = (uint32_t)r->nw, mh = (uint32_t)ns;
+    for (int64_t i = 0; i < nsteps * T; ++i)
+        if (kind[i] != MSX_MOVE_STRETCH && kind[i] != MSX_MOVE_DE) return "kind out of range";
+    for (int64_t i = 0; i < nsteps * T; ++i)
+        if (kind[i] == MSX_MOVE_DE && r->nw < 4) return "the DE move needs two distinct walkers in each half: at least 4 walkers";
+    const int64_t n = nsteps * T * 2 * ns;
+    for (int64_t i = 0; i < n; ++i) {
+        if ((uint32_t)sidx[i] >= mw || (uint32_t)cidx[i] >= mw || (uint32_t)p1[i] >= mh || (uint32_t)p2[i] >= mh)
+            return "walker / partner index out of range";
+        if (kind[i / (2 * ns)] == MSX_MOVE_DE && p1[i] == p2[i]) return "a DE entry needs two distinct walkers (p1 != p2)";
+    }
+    const TemperedIn P = tempered_in(r, h_in, nsteps);
+    for (int64_t st = 0; st < nsteps; ++st)
+        for (int64_t t = 0; t < T; ++t)
+            for (int h = 0; h < 2; ++h) {
+                const int64_t src = ((st * T + t) * 2 + h) * ns, dst = ((st * 2 + h) * T + t) * ns;
+                memcpy(P.g + dst, g + src, sizeof(double) * ns); memcpy(P.fac + dst, fac + src, sizeof(double) * ns);
+                memcpy(P.logu + dst, logu + src, sizeof(double) * ns);
+                memcpy(P.sidx + dst, sidx + src, sizeof(int32_t) * ns); memcpy(P.cidx + dst, cidx + src, sizeof(int32_t) * ns);
+                for (int64_t j = 0; j < ns; ++j) {  // resolved to ensemble indices, as run_pack_moves does
+                    P.c1[dst + j] = (int32_t)(t * r->nw + cidx[src + p1[src + j]]);
+                    P.c2[dst + j] = (int32_t)(t * r->nw + cidx[src + p2[src + j]]);
+                }
+            }
+    memcpy(P.kind, kind, sizeof(int32_t) * nsteps * T);
+    if (T > 1) memcpy(P.swap_logu, swap_logu, sizeof(double) * nsteps * (T - 1) * r->nw);
+    return nullptr;
+}
+
+static MoveDrawTable tempered_members(int32_t T, int64_t nw, const uint64_t *seeds) {
+    MoveDrawTable Tb;
+    memset(&Tb, 0, sizeof(Tb));
+    for (int t = 0; t < T; ++t) {
+        Tb.seed[t] = (unsigned long long)seeds[t];
+        Tb.M.astart[t] = (int32_t)(t * (nw / 2)); Tb.M.nh[t] = (int32_t)nw; Tb.M.off[t] = (int32_t)(t * nw);
+    }
+    return Tb;
+}
+
+struct TemperedDraw { const uint64_t *seeds; const msx_move_set *set; int64_t first_iter; };
+
+static int tempered_enqueue(msx_ctx *c, const char *who, int32_t slot, int64_t nsteps, const int32_t *sidx, const int32_t *cidx,
+                            const int32_t *kind, const int32_t *p1, const int32_t *p2, const double *g, const double *fac,
+                            const double *logu, const double *swap_logu, const TemperedDraw *draw) {
+    if (!c) return MSX_ERR_INVALID;
+    const std::string w(who);
+    TemperedRun *r = c->tmp;
+    if (!r) return fail(c, MSX_ERR_STATE, w + ": call msx_tempered_begin first");
+    const bool args_ok = draw ? (draw->seeds && draw->set) : (sidx && cidx && kind && p1 && p2 && g && fac && logu && (swap_logu || r->T == 1));
+    if (slot < 0 || slot > 1 || nsteps < 1 || nsteps > r->cap_steps || !args_ok) return fail(c, MSX_ERR_INVALID, w + ": bad arguments");
+    if (r->failed) return fail(c, MSX_ERR_STATE, w + ": an earlier enqueue failed part-way; end this run (msx_tempered_end) and begin again");
+    TemperedRun::Slot &sl = r->slot[slot];
+    if (sl.busy) return fail(c, MSX_ERR_STATE, w + ": slot not collected yet");
+    if (!c->problem_staged) return fail(c, MSX_ERR_STATE, w + ": no problem staged");
+    MoveSetDev S;
+    if (draw) {
+        if (r->nw > kDrawMaxWalkers || draw->first_iter < 0)
+            return fail(c, MSX_ERR_INVALID, w + ": the device generator takes up to 4096 walkers per rung and a first iteration >= 0");
+        if (const char *why = move_set_dev(draw->set, r->ndim, r->nw, &S)) return fail(c, MSX_ERR_INVALID, w + ": " + why);
+    } else if (const char *why = tempered_pack(r, sl.h_in, nsteps, sidx, cidx, kind, p1, p2, g, fac, logu, swap_logu)) {
+        return fail(c, MSX_ERR_INVALID, w + ": " + why);
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->P.smp_on = 0;  // (the plain evaluation)
+    c->P.smp_defer = 0;
+    const int T = r->T, ndim = r->ndim;
+    const int64_t ns = r->ns, nw = r->nw, H = T * ns;
+    const TemperedIn in = tempered_in(r, sl.d_in, nsteps);
+    const TemperedOut out = tempered_out(r, sl.d_out, nsteps);
+    hipStream_t s = c->stream;
+    hipError_t e = hipSuccess;
+    int rc = MSX_OK;
+    if (draw) {
+        // (the slot was collected: no launch still reads its arrays, and the stream orders these before the half-steps)
+        const MoveDrawTable Tb = tempered_members(T, nw, draw->seeds);
+        hipLaunchKernelGGL(moves_draw_kernel, dim3((unsigned)nsteps, (unsigned)T), dim3(kDrawThreads), 0, s, Tb, S, draw->first_iter, (int32_t)ndim, 1,
+                           H, in.sidx, in.cidx, in.c1, in.c2, in.g, in.fac, in.logu, in.kind);
+        e = hipGetLastError();
+        if (e == hipSuccess && T > 1) {
+            hipLaunchKernelGGL(tempered_swap_draw_kernel, dim3((unsigned)nsteps, (unsigned)(T - 1), (unsigned)((nw + 255) / 256)), dim3(256), 0, s,
+                               (unsigned long long)draw->seeds[0], draw->first_iter, (int32_t)nw, in.swap_logu);
+            e = hipGetLastError();
+        }
+    } else {
+        e = hipMemcpyAsync(sl.d_in, sl.h_in, r->in_bytes(nsteps), hipMemcpyHostToDevice, r->up);
+        if (e == hipSuccess) e = hipEventRecord(sl.in_ready, r->up);
+        if (e == hipSuccess) e = hipStreamWaitEvent(s, sl.in_ready, 0);
+    }
+    if (e == hipSuccess) e = hipMemsetAsync(out.worst, 0, sizeof(int32_t) * MSX_MAX_GROUP, s);
+    TemperedStepArgs A;
+    memset(&A, 0, sizeof(A));
+    A.coords = r->d_coords; A.ll = r->d_ll; A.lpr = r->d_lpr; A.q = r->d_q; A.new_lpr = r->d_new_lpr; A.new_ll = r->d_new_ll;
+    A.st_lpr = r->d_st_lpr; A.st_ll = r->d_st_ll; A.nacc = r->d_nacc; A.ndim = ndim; A.nw = (int32_t)nw; A.ns = (int32_t)ns; A.worst = out.worst;
+    memcpy(A.beta, r->beta, sizeof(A.beta));
+    TemperedSwapArgs W;
+    memset(&W, 0, sizeof(W));
+    W.coords = r->d_coords; W.ll = r->d_ll; W.lpr = r->d_lpr; W.nswap = r->d_nswap; W.ntemps = T; W.nw = (int32_t)nw; W.ndim = ndim;
+    memcpy(W.db, r->db, sizeof(W.db));
+    auto half_arrays = [&](int64_t j) {  // half-step j of the chunk
+        const int64_t o = j * H;
+        return MoveChunk{in.g + o, in.fac + o, in.logu + o, in.sidx + o, in.c1 + o, in.c2 + o, in.kind + (j / 2) * T};
+    };
+    for (int64_t st = 0; st < nsteps && e == hipSuccess && rc == MSX_OK; ++st) {
+        for (int k = 0; k < 3 && e == hipSuccess && rc == MSX_OK; ++k) {  // propose 0 | apply 0, propose 1 | apply 1
+            A.a_on = k > 0; A.p_on = k < 2;
+            if (A.a_on) A.a = half_arrays(2 * st + k - 1);
+            if (A.p_on) A.p = half_arrays(2 * st + k);
+            hipLaunchKernelGGL(tempered_step_kernel, dim3((unsigned)T), dim3(256), 0, s, A);
+            e = hipGetLastError();
+            if (e != hipSuccess || !A.p_on) continue;
+            rc = msx_logprob_batch_dev(c, MSX_MODE_LOGPRIOR, r->d_q, H, ndim, r->d_new_lpr, r->d_st_lpr, s, 0);
+            if (rc == MSX_OK) rc = msx_logprob_batch_dev(c, MSX_MODE_LOGLIKE, r->d_q, H, ndim, r->d_new_ll, r->d_st_ll, s, 0);
+        }
+        if (e != hipSuccess || rc != MSX_OK) break;
+        W.logu = in.swap_logu + st * (T - 1) * nw;
+        W.chain_row = out.chain + st * T * nw * ndim; W.ll_row = out.ll + st * T * nw; W.lpr_row = out.lpr + st * T * nw;
+        hipLaunchKernelGGL(tempered_swap_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s, W);
+        e = hipGetLastError();
+    }
+    // the counters keep running while this chunk's results travel: snapshot them in stream order, then bring the slot back
+    if (e == hipSuccess && rc == MSX_OK) e = hipMemcpyAsync(out.nacc, r->d_nacc, sizeof(int64_t) * (size_t)(T * nw), hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess && rc == MSX_OK) e = hipMemcpyAsync(out.nswap, r->d_nswap, sizeof(int64_t) * MSX_MAX_GROUP, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess && rc == MSX_OK) e = hipEventRecord(sl.kernels_done, s);
+    if (e == hipSuccess && rc == MSX_OK) e = hipStreamWaitEvent(r->copy, sl.kernels_done, 0);
+    if (e == hipSuccess && rc == MSX_OK) e = hipMemcpyAsync(sl.h_out, sl.d_out, r->out_bytes(nsteps), hipMemcpyDeviceToHost, r->copy);
+    if (e == hipSuccess && rc == MSX_OK) e = hipEventRecord(sl.out_ready, r->copy);
+    if (e != hipSuccess || rc != MSX_OK) {
+        r->failed = true;  // some of the chunk's half-steps may be queued: only the run's end from here on
+        if (e != hipSuccess) return fail(c, MSX_ERR_HIP, w + ": " + hipGetErrorString(e));
+        return rc;
+    }
+    sl.nsteps = nsteps;
+    sl.busy = true;
+    return MSX_OK;
+}
+
+int msx_tempered_enqueue(msx_ctx *c, int32_t slot, int64_t nsteps, const int32_t *sidx, const int32_t *cidx, const int32_t *kind,
+                         const int32_t *p1, const int32_t *p2, const double *g, const double *fac, const double *logu,
+                         const double *swap_logu) {
+    return tempered_enqueue(c, "msx_tempered_enqueue", slot, nsteps, sidx, cidx, kind, p1, p2, g, fac, logu, swap_logu, nullptr);
+}
+
+int msx_tempered_enqueue_drawn(msx_ctx *c, int32_t slot, int64_t nsteps, const uint64_t *seeds, const msx_move_set *set, int64_t first_iter) {
+    const TemperedDraw dd = {seeds, set, first_iter};
+    return tempered_enqueue(c, "msx_tempered_enqueue_drawn", slot, nsteps, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                            nullptr, &dd);
+}
+
+int msx_tempered_draw(msx_ctx *c, int32_t ntemps, const uint64_t *seeds, const msx_move_set *set, int64_t first_iter, int64_t nsteps,
+                      int64_t nw, int32_t ndim, int32_t *sidx, int32_t *cidx, int32_t *kind, int32_t *p1, int32_t *p2, double *g,
+                      double *fac, double *logu, double *swap_logu) {
+    if (!c) return MSX_ERR_INVALID;
+    if (!seeds || !sidx || !cidx || !kind || !p1 || !p2 || !g || !fac || !logu || (!swap_logu && ntemps > 1) || ntemps < 1 ||
+        ntemps > MSX_MAX_GROUP || nsteps < 1 || nw < 2 || (nw & 1) || nw > kDrawMaxWalkers || first_iter < 0 || ndim < 1)
+        return fail(c, MSX_ERR_INVALID, "msx_tempered_draw: bad arguments (1..MSX_MAX_GROUP rungs of an even number of walkers, at most 4096)");
+    MoveSetDev S;
+    if (const char *why = move_set_dev(set, ndim, nw, &S)) return fail(c, MSX_ERR_INVALID, std::string("msx_tempered_draw: ") + why);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int64_t T = ntemps, ns = nw / 2, H = T * ns, L = nsteps * 2 * H, nsw = nsteps * (T - 1) * nw;
+    char *d = nullptr;
+    const size_t bytes = sizeof(double) * (size_t)(3 * L + nsw) + sizeof(int32_t) * (size_t)(4 * L + nsteps * T);
+    HIP_TRY(c, hipMalloc((void **)&d, bytes));
+    double *d_g = (double *)d, *d_fac = d_g + L, *d_logu = d_fac + L, *d_sw = d_logu + L;
+    int32_t *d_sidx = (int32_t *)(d_sw + nsw), *d_cidx = d_sidx + L, *d_p1 = d_cidx + L, *d_p2 = d_p1 + L, *d_kind = d_p2 + L;
+    const MoveDrawTable Tb = tempered_members(ntemps, nw, seeds);
+    hipLaunchKernelGGL(moves_draw_kernel, dim3((unsigned)nsteps, (unsigned)T), dim3(kDrawThreads), 0, c->stream, Tb, S, first_iter, ndim, 0, H, d_sidx,
+                       d_cidx, d_p1, d_p2, d_g, d_fac, d_logu, d_kind);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess && T > 1) {
+        hipLaunchKernelGGL(tempered_swap_draw_kernel, dim3((unsigned)nsteps, (unsigned)(T - 1), (unsigned)((nw + 255) / 256)), dim3(256), 0, c->stream,
+                           (unsigned long long)seeds[0], first_iter, (int32_t)nw, d_sw);
+        e = hipGetLastError();
+    }
+    std::vector<char> h(bytes);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = hipMemcpy(h.data(), d, bytes, hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    if (e != hipSuccess) return fail(c, MSX_ERR_HIP, std::string("msx_tempered_draw: ") + hipGetErrorString(e));
+    const double *h_g = (const double *)h.data(), *h_fac = h_g + L, *h_logu = h_fac + L, *h_sw = h_logu + L;
+    const int32_t *h_sidx = (const int32_t *)(h_sw + nsw), *h_cidx = h_sidx + L, *h_p1 = h_cidx + L, *h_p2 = h_p1 + L, *h_kind = h_p2 + L;
+    for (int64_t st = 0; st < nsteps; ++st)   // the device's [nsteps][2][T][ns] -> the members' [nsteps][T][2][ns]
+        for (int64_t t = 0; t < T; ++t)
+            for (int hh = 0; hh < 2; ++hh) {
+                const int64_t dst = ((st * T + t) * 2 + hh) * ns, src = ((st * 2 + hh) * T + t) * ns;
+                memcpy(g + dst, h_g + src, sizeof(double) * ns); memcpy(fac + dst, h_fac + src, sizeof(double) * ns);
+                memcpy(logu + dst, h_logu + src, sizeof(double) * ns);
+                memcpy(sidx + dst, h_sidx + src, sizeof(int32_t) * ns); memcpy(cidx + dst, h_cidx + src, sizeof(int32_t) * ns);
+                memcpy(p1 + dst, h_p1 + src, sizeof(int32_t) * ns); memcpy(p2 + dst, h_p2 + src, sizeof(int32_t) * ns);
+            }
+    memcpy(kind, h_kind, sizeof(int32_t) * nsteps * T);
+    if (T > 1) memcpy(swap_logu, h_sw, sizeof(double) * nsw);
+    return MSX_OK;
+}
+
+int msx_tempered_collect(msx_ctx *c, int32_t slot, double *chain, double *ll_chain, double *lpr_chain, int64_t *naccept, int64_t *nswap,
+                         int32_t *worst) {
+    if (!c) return MSX_ERR_INVALID;
+    TemperedRun *r = c->tmp;
+    if (!r) return fail(c, MSX_ERR_STATE, "msx_tempered_collect: call msx_tempered_begin first");
+    if (slot < 0 || slot > 1 || !chain || !ll_chain || !lpr_chain || !naccept || !worst || (!nswap && r->T > 1))
+        return fail(c, MSX_ERR_INVALID, "msx_tempered_collect: bad arguments");
+    TemperedRun::Slot &sl = r->slot[slot];
+    if (!sl.busy) return fail(c, MSX_ERR_STATE, "msx_tempered_collect: nothing enqueued in this slot");
+    const hipError_t e = hipEventSynchronize(sl.out_ready);
+    if (e != hipSuccess) return fail(c, MSX_ERR_HIP, std::string("msx_tempered_collect: ") + hipGetErrorString(e));
+    const TemperedOut o = tempered_out(r, sl.h_out, sl.nsteps);
+    const int64_t rows = sl.nsteps * r->T * r->nw;
+    memcpy(chain, o.chain, sizeof(double) * rows * r->ndim);
+    memcpy(ll_chain, o.ll, sizeof(double) * rows);
+    memcpy(lpr_chain, o.lpr, sizeof(double) * rows);
+    memcpy(naccept, o.nacc, sizeof(int64_t) * r->T * r->nw);
+    if (r->T > 1) memcpy(nswap, o.nswap, sizeof(int64_t) * (r->T - 1));
+    memcpy(worst, o.worst, sizeof(int32_t) * r->T);
+    sl.busy = false;
+    return MSX_OK;
+}
+
+int msx_tempered_end(msx_ctx *c, double *coords, double *ll, double *lpr) {
+    if (!c) return MSX_ERR_INVALID;
+    TemperedRun *r = c->tmp;
+    if (!r) return MSX_OK;
+    const int64_t W = (int64_t)r->T * r->nw;
+    hipError_t e = hipSetDevice(c->device);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess && coords) e = hipMemcpy(coords, r->d_coords, sizeof(double) * (size_t)(W * r->ndim), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && ll) e = hipMemcpy(ll, r->d_ll, sizeof(double) * (size_t)W, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && lpr) e = hipMemcpy(lpr, r->d_lpr, sizeof(double) * (size_t)W, hipMemcpyDeviceToHost);
+    tempered_free(c);
+    if (e != hipSuccess) return fail(c, MSX_ERR_HIP, std::string("msx_tempered_end: ") + hipGetErrorString(e));
+    return MSX_OK;
 }
 
 // ---- device chain series ------------------------------------------------------------------------

@@ -195,7 +195,7 @@ def logposterior(p0, fr, nspec, ndust, data, err, broadening, r, specs, ctm, ptm
     return eng.logposterior(p)
 
 
-def device_sampler(nwalkers, ndim, args, kwargs=None, a=None, seed=None, chunk=64, moves=None, rng='host'):
+def device_sampler(nwalkers, ndim, args, kwargs=None, a=None, seed=None, chunk=64, moves=None, rng='host', betas=None):
     """The sampler line of ``run_emcee`` -- ``emcee.EnsembleSampler(nwalkers, ndim, logposterior, args=[...],
     kwargs={...})``, mft6.py:1490-1492 -- with the walker state RESIDENT on the GPU: ``args`` / ``kwargs`` are exactly
     what that line passes for ``logposterior`` (everything after ``p0``); the problem they describe is staged once and
@@ -203,7 +203,10 @@ def device_sampler(nwalkers, ndim, args, kwargs=None, a=None, seed=None, chunk=6
     ``get_chain``, ``get_log_prob``, ``acceptance_fraction``, ``reset`` -- and, for the same seed, the same chain bit
     for bit as ``EnsembleSampler(nwalkers, ndim, logposterior, args=args, kwargs=kwargs, vectorize=True)``).  ``moves``:
     emcee's ``moves=`` (``mcmc_spec_amd.moves``: e.g. ``[(StretchMove(), 0.5), (DEMove(), 0.4), (DEMove(gamma0=1.0), 0.1)]``
-    for a bimodal posterior); ``rng='device'`` draws the randomness on the GPU (``DeviceEnsembleSampler``)."""
+    for a bimodal posterior); ``rng='device'`` draws the randomness on the GPU (``DeviceEnsembleSampler``).  ``betas``: a
+    temperature ladder (``mcmc_spec_amd.tempered``: e.g. ``default_betas(8, 0.02)``) -- the sampler is then a
+    ``DeviceTemperedSampler`` of ``len(betas)`` rungs of ``nwalkers`` on the same engine, whose rung 0 is the posterior
+    (``a=`` goes as ``moves=StretchMove(a)``)."""
     from .sampler import DeviceEnsembleSampler
     names = ('fr', 'nspec', 'ndust', 'data', 'err', 'broadening', 'r', 'specs', 'ctm', 'ptm', 'tmi', 'tma', 'vs', 'tmin',
              'tmax', 'matrix', 'ra', 'dec', 'wu', 'dust', 'norm', 'prior', 'a', 'models', 'dist_fit', 'rad_prior')
@@ -228,6 +231,13 @@ def device_sampler(nwalkers, ndim, args, kwargs=None, a=None, seed=None, chunk=6
     eng = _staged(g('specs'), g('fr'), g('nspec'), g('data'), g('err'), g('r'), g('ctm'), g('ptm'), g('tmi'), g('tma'),
                   g('matrix'), g('tmin'), g('tmax'), g('prior', 0), g('a', True), g('dist_fit', True),
                   g('rad_prior', False), need_prior=True)
+    if betas is not None:
+        from .moves import StretchMove
+        from .tempered import DeviceTemperedSampler
+        if a is not None and moves is not None:
+            raise ValueError('a= and moves= exclude each other: give the stretch scale as moves.StretchMove(a)')
+        return DeviceTemperedSampler(nwalkers, ndim, eng, betas=betas, seed=seed, chunk=chunk, rng=rng,
+                                     moves=StretchMove(a) if a is not None else moves)
     return DeviceEnsembleSampler(nwalkers, ndim, eng, mode='logposterior', a=a, seed=seed, chunk=chunk, moves=moves, rng=rng)
 
 

@@ -1,0 +1,389 @@
+"""Parallel tempering: a ladder of ensembles, each sampling ``ln prior(x) + beta_t ln L(x)``.
+
+``1 = beta_0 > beta_1 > ... > beta_{T-1} > 0``; rung 0 is the posterior, the hot rungs cross between modes that differ in
+width or orientation and hand their walkers down.  Per ABSOLUTE iteration i every rung t takes one iteration of the general
+layout (``mcmc_spec_amd.moves``: the split, the iteration's move, the proposals, ``fac`` and ``ln u`` of a member of ``nw``
+walkers keyed by ``seeds[t]``) with the accept rule
+
+    ln u < (fac + P_t(q)) - P_t(s),     P_t(x) = lpr(x) + beta_t * ll(x)     (two roundings; P_t(s) from the stored lpr, ll)
+
+and then the swap sweep runs, for t = T-1 down to 1 and every walker index w independently: walker w of rung t and walker
+w of rung t-1 exchange coordinates, ``ll`` and ``lpr`` when ``ln u < (beta[t-1] - beta[t]) * (ll[t][w] - ll[t-1][w])`` (a
+NaN compares false).  The sweep is serial in t, so a walker can travel several rungs in one iteration.  The chain row of
+iteration i is the state AFTER the sweep.  ``TemperedSampler`` is this text as a host loop -- the definition;
+``DeviceTemperedSampler`` keeps the ladder resident on the GPU (``msx_tempered_*``) and walks the same chain bit for bit.
+
+The swap draws: device-drawn, ``u = counter_uniform(seeds[0], i, 14, (t-1) * 4096 + w)`` (stream 14 of the counter
+generator; ``counter_swap_logu`` restates it); host-drawn, ``swap_generator(seeds[0])``, one float64 ``ln u`` per
+(iteration, pair, walker), consumed row by row.
+"""
+from __future__ import annotations
+
+from contextlib import closing
+
+import numpy as np
+
+from .sampler import EnsembleSampler, State, _propose, _pump, device_seed
+
+MAX_TEMPS = 64        # include/msx.h MSX_MAX_GROUP: rungs of a ladder
+SWAP_STREAM = 14      # the counter generator's stream of the swap draws (0..13: moves.counter_draws_moves)
+SWAP_STRIDE = 4096    # index = (t - 1) * SWAP_STRIDE + w: at most 64 rungs of at most 4,096 walkers, below 2^24
+W_REJECT = 1          # include/msx.h MSX_W_REJECT
+
+
+def default_betas(ntemps, beta_min):
+    """A geometric ladder from 1 down to ``beta_min``."""
+    return np.geomspace(1.0, float(beta_min), int(ntemps))
+
+
+def resolve_betas(ntemps, betas, beta_min=0.02):
+    """The ladder of ``ntemps`` rungs (``default_betas(ntemps, beta_min)``) or the given ``betas``, checked: 1..64 rungs,
+    finite, > 0, strictly descending; both given must agree in length.  ValueError otherwise."""
+    if betas is None:
+        if ntemps is None:
+            raise ValueError('give ntemps or betas')
+        if not 1 <= int(ntemps) <= MAX_TEMPS:
+            raise ValueError('a ladder has 1..{} rungs ({} asked for)'.format(MAX_TEMPS, ntemps))
+        betas = default_betas(ntemps, beta_min) if int(ntemps) > 1 else np.array([1.0])
+    b = np.array(betas, dtype=np.float64).reshape(-1)
+    if ntemps is not None and int(ntemps) != len(b):
+        raise ValueError('ntemps = {} but {} betas given'.format(ntemps, len(b)))
+    if not 1 <= len(b) <= MAX_TEMPS:
+        raise ValueError('a ladder has 1..{} rungs ({} given)'.format(MAX_TEMPS, len(b)))
+    if not np.all(np.isfinite(b)) or np.any(b <= 0.0):
+        raise ValueError('betas must be finite and > 0')
+    if np.any(np.diff(b) >= 0.0):
+        raise ValueError('betas must be strictly descending')
+    return b
+
+
+def resolve_seeds(ntemps, seed, seeds):
+    """One 64-bit key per rung: ``seeds``, or ``(device_seed(seed) + t) mod 2^64``."""
+    if seeds is not None:
+        out = [device_seed(s) for s in seeds]
+        if len(out) != ntemps:
+            raise ValueError('seeds: one per rung ({} given for {} rungs)'.format(len(out), ntemps))
+        return out
+    s0 = device_seed(seed)
+    return [(s0 + t) & 0xffffffffffffffff for t in range(ntemps)]
+
+
+def swap_generator(seed0):
+    """The host-drawn swap stream of a ladder whose rung 0 is keyed by ``seed0``: one uniform per (iteration, pair, walker),
+    row by row -- m iterations at once are m calls of one.  Defined here once, for both samplers."""
+    return np.random.Generator(np.random.PCG64(np.random.SeedSequence(int(seed0), spawn_key=(SWAP_STREAM,))))
+
+
+def draw_swap_logu(rng, m, ntemps, nwalkers):
+    """``ln u`` (m, ntemps - 1, nwalkers) of m iterations from the swap stream; row p belongs to the pair (p + 1, p)."""
+    u = rng.random((int(m), int(ntemps) - 1, int(nwalkers)))
+    with np.errstate(divide='ignore'):
+        return np.log(u)
+
+
+def counter_swap_logu(seed0, first_iter, m, ntemps, nwalkers):
+    """NumPy restatement of the DEVICE's swap draws (csrc/tempered_kernels.h, tempered_swap_draw_kernel): ``ln u`` (m,
+    ntemps - 1, nwalkers) of iterations ``first_iter ..`` -- stream 14, index ``(t - 1) * 4096 + w`` for the pair (t, t - 1).
+    The uniforms equal the device's bit for bit; the logarithm goes through NumPy's (last-place differences)."""
+    from .sampler import counter_streams
+    T, nw = int(ntemps), int(nwalkers)
+    if T < 2:
+        return np.empty((int(m), 0, nw))
+    _, _, uniform = counter_streams(seed0, first_iter, m, 2)
+    u = uniform(SWAP_STREAM, (T - 2) * SWAP_STRIDE + nw)
+    cols = (np.arange(T - 1)[:, None] * SWAP_STRIDE + np.arange(nw)[None, :]).ravel()
+    with np.errstate(divide='ignore'):
+        return np.log(np.ascontiguousarray(u[:, cols])).reshape(int(m), T - 1, nw)
+
+
+def counter_draws_tempered(seeds, mset, ndim, first_iter, m, nwalkers):
+    """NumPy restatement of ``ctx.tempered_draw``: ``(members, swap_logu)`` of iterations ``first_iter .. first_iter + m - 1``
+    -- rung t is ``moves.counter_draws_moves(seeds[t], ...)`` unchanged (streams 0..13), the swap draws are stream 14 of
+    ``seeds[0]``."""
+    from .moves import counter_draws_moves
+    members = [counter_draws_moves(s, mset, ndim, first_iter, m, nwalkers) for s in seeds]
+    return members, counter_swap_logu(seeds[0], first_iter, m, len(seeds), nwalkers)
+
+
+def _values(out):
+    """(values, statuses or None) of what a density function returned: an array, or ``(values, statuses)``."""
+    if isinstance(out, tuple):
+        return np.asarray(out[0], dtype=float), np.asarray(out[1])
+    return np.asarray(out, dtype=float), None
+
+
+def _accept_rung(beta, coords, ll, lpr, accepted, draws, h, q, lpr_q, ll_q):
+    """The accept rule of half h of one rung, in place."""
+    s_idx, fac, logu = draws[0][0, h], draws[-2][0, h], draws[-1][0, h]
+    with np.errstate(invalid='ignore'):   # -inf - -inf = nan -> compares False -> rejected
+        prod_q = beta * ll_q
+        p_q = lpr_q + prod_q
+        prod_s = beta * ll[s_idx]
+        p_s = lpr[s_idx] + prod_s
+        lnpdiff = (fac + p_q) - p_s
+    acc = logu < lnpdiff
+    coords[s_idx[acc]] = q[acc]
+    ll[s_idx[acc]] = ll_q[acc]
+    lpr[s_idx[acc]] = lpr_q[acc]
+    accepted[s_idx[acc]] = True
+
+
+def swap_sweep(db, coords, ll, lpr, swap_logu, nswap):
+    """The sweep of one iteration, in place on coords (T, nw, ndim), ll, lpr (T, nw); swap_logu (T-1, nw); nswap (T-1,)
+    counts the swaps accepted per pair.  db[p] = beta[p] - beta[p + 1]."""
+    for t in range(len(ll) - 1, 0, -1):
+        with np.errstate(invalid='ignore'):
+            d = ll[t] - ll[t - 1]
+            lnr = db[t - 1] * d
+        sw = swap_logu[t - 1] < lnr
+        for arr in (coords, ll, lpr):
+            tmp = arr[t, sw].copy()
+            arr[t, sw] = arr[t - 1, sw]
+            arr[t - 1, sw] = tmp
+        nswap[t - 1] += int(np.count_nonzero(sw))
+
+
+class _Ladder:
+    """What both samplers keep and return."""
+
+    def _init_ladder(self, nwalkers, ndim, ntemps, betas, beta_min, seed, seeds, moves):
+        self.betas = resolve_betas(ntemps, betas, beta_min)
+        self.ntemps = len(self.betas)
+        self._db = self.betas[:-1] - self.betas[1:]           # formed once, in float64
+        self.nwalkers, self.ndim = int(nwalkers), int(ndim)
+        if self.nwalkers % 2 or self.nwalkers < 2:
+            raise ValueError('a rung needs an even number of walkers')
+        self.seeds = resolve_seeds(self.ntemps, seed, seeds)
+        from .moves import StretchMove
+        # every rung is a member in the general layout; its generators are EnsembleSampler's for seeds[t]
+        self._rungs = [EnsembleSampler(self.nwalkers, self.ndim, None, seed=s, moves=StretchMove() if moves is None else moves,
+                                       _general=True) for s in self.seeds]
+        self._moves = self._rungs[0]._moves
+        self._swap_rng = swap_generator(self.seeds[0])
+        self._drawn = 0
+        self.reset()
+
+    def reset(self):
+        """Forget the stored chain and counts.  The streams' positions (and ``_drawn``) are left alone."""
+        self._chain, self._ll, self._lpr = [], [], []
+        self._accepted = np.zeros((self.ntemps, self.nwalkers))
+        self._nswap = np.zeros(max(self.ntemps - 1, 0), dtype=np.int64)
+        self.iteration = 0
+        self._last = None
+
+    def _rows(self, rows, t, flat, thin, discard, tail):
+        a = np.array(rows)[discard::thin] if rows else np.empty((0, self.ntemps, self.nwalkers) + tail)
+        if t is not None:
+            a = a[:, int(t)]
+            return a.reshape((-1,) + tail) if flat else a
+        return np.moveaxis(a, 1, 0).reshape((self.ntemps, -1) + tail) if flat else a
+
+    def get_chain(self, t=0, flat=False, thin=1, discard=0):
+        """Rung t's chain (steps, nw, ndim) -- rung 0 is the posterior; ``t=None``: all rungs, (steps, T, nw, ndim).  flat:
+        the steps and walkers merged."""
+        return self._rows(self._chain, t, flat, thin, discard, (self.ndim,))
+
+    def get_log_like(self, t=0, flat=False, thin=1, discard=0):
+        return self._rows(self._ll, t, flat, thin, discard, ())
+
+    def get_log_prior(self, t=0, flat=False, thin=1, discard=0):
+        return self._rows(self._lpr, t, flat, thin, discard, ())
+
+    def get_log_prob(self, t=0, flat=False, thin=1, discard=0):
+        """``lpr + ll``: the untempered posterior of rung t's samples."""
+        return self.get_log_prior(t, flat, thin, discard) + self.get_log_like(t, flat, thin, discard)
+
+    @property
+    def acceptance_fraction(self):
+        """(T, nw): moves accepted per iteration (swaps are not counted)."""
+        return self._accepted / max(self.iteration, 1)
+
+    @property
+    def swap_fraction(self):
+        """(T-1,): swaps accepted between rungs p + 1 and p / (iterations x nw)."""
+        return self._nswap / float(max(self.iteration, 1) * self.nwalkers)
+
+    def get_last_sample(self):
+        return self._last
+
+    def run_mcmc(self, initial_state, nsteps, **kw):
+        st = None
+        for st in self.sample(initial_state, iterations=nsteps, **kw):
+            pass
+        return st
+
+    def _start(self, initial_state):
+        """(coords (T, nw, ndim), ll, lpr (T, nw)) of an initial state: a TemperedState, or coordinates -- (nw, ndim) for
+        every rung alike or (T, nw, ndim).  ValueError for a walker outside the prior or with a NaN likelihood."""
+        if isinstance(initial_state, TemperedState):
+            coords, ll, lpr = (np.array(a, dtype=float) for a in (initial_state.coords, initial_state.log_like, initial_state.log_prior))
+        else:
+            coords = np.array(initial_state, dtype=float)
+            if coords.ndim == 2:
+                coords = np.repeat(coords[None], self.ntemps, axis=0)
+            ll = lpr = None
+        if coords.shape != (self.ntemps, self.nwalkers, self.ndim):
+            raise ValueError('incompatible input dimensions')
+        if np.any(~np.isfinite(coords)):
+            raise ValueError('At least one parameter value was infinite or NaN')
+        if ll is None:
+            flat = coords.reshape(-1, self.ndim)
+            lpr, ll = self._evaluate(flat)
+            lpr, ll = lpr.reshape(self.ntemps, -1).copy(), ll.reshape(self.ntemps, -1).copy()
+        if not np.all(np.isfinite(lpr)):
+            raise ValueError('an initial walker lies outside the prior (its log-prior is not finite)')
+        if np.any(np.isnan(ll)):
+            raise ValueError('Probability function returned NaN')
+        return np.ascontiguousarray(coords), np.ascontiguousarray(ll), np.ascontiguousarray(lpr)
+
+
+class TemperedState(State):
+    """``coords`` (T, nw, ndim), ``log_like``, ``log_prior`` (T, nw); ``log_prob = log_prior + log_like``."""
+
+    def __init__(self, coords, log_like, log_prior):
+        self.coords = np.array(coords, dtype=float)
+        self.log_like = np.array(log_like, dtype=float)
+        self.log_prior = np.array(log_prior, dtype=float)
+        self.log_prob = self.log_prior + self.log_like
+        self.random_state = None
+
+
+class TemperedSampler(_Ladder):
+    """The host loop, and the definition (the module docstring).  ``loglike_fn`` / ``logprior_fn`` take (n, ndim) and return
+    n values, or ``(values, statuses)`` (``ctx.logprob_batch``): a proposal whose prior status is ``MSX_W_REJECT`` is
+    rejected whatever its likelihood reports; an error status of the prior, or of the likelihood on a proposal the prior
+    admits, raises what ``engine._raise_for_status`` raises.  An ``Engine`` in ``loglike_fn``'s place (``logprior_fn=None``)
+    stands for its two status-carrying evaluations.
+
+    ``draws(first_iteration, m)`` (optional) replaces the generators: ``(members, swap_logu)``, members a list of T
+    general layouts (m iterations each) and swap_logu (m, T-1, nw) -- ``ctx.tempered_draw`` makes this loop walk the chain
+    ``DeviceTemperedSampler(rng='device')`` draws for itself."""
+
+    def __init__(self, nwalkers, ndim, loglike_fn, logprior_fn=None, ntemps=None, betas=None, beta_min=0.02, seed=None, seeds=None,
+                 moves=None, draws=None):
+        if logprior_fn is None and hasattr(loglike_fn, 'ctx'):
+            from . import _lib
+            ctx = loglike_fn.ctx
+            loglike_fn, logprior_fn = (lambda q: ctx.logprob_batch(q, _lib.MODE_LOGLIKE)), (lambda q: ctx.logprob_batch(q, _lib.MODE_LOGPRIOR))
+        self.loglike_fn, self.logprior_fn = loglike_fn, logprior_fn
+        self._draws = draws
+        self._init_ladder(nwalkers, ndim, ntemps, betas, beta_min, seed, seeds, moves)
+
+    def _evaluate(self, q):
+        """(lpr, ll) of the proposals q with the status rule."""
+        from .engine import _raise_for_status
+        lpr, st_p = _values(self.logprior_fn(q))
+        ll, st_l = _values(self.loglike_fn(q))
+        if lpr.shape != (len(q),) or ll.shape != (len(q),):
+            raise ValueError('a density function returned the wrong shape')
+        if st_p is not None:
+            _raise_for_status(st_p, q)
+        if st_l is not None:
+            admitted = np.isfinite(lpr) if st_p is None else st_p != W_REJECT
+            _raise_for_status(np.where(admitted, st_l, 0), q)
+        elif np.any(np.isnan(ll) & np.isfinite(lpr)):
+            raise ValueError('Probability function returned NaN')
+        return lpr, ll
+
+    def _draw_steps(self, m):
+        if self._draws is not None:
+            out = self._draws(self._drawn, m)
+            self._drawn += m
+            return out
+        return [r._draw_steps(m) for r in self._rungs], draw_swap_logu(self._swap_rng, m, self.ntemps, self.nwalkers)
+
+    def sample(self, initial_state, iterations=1, store=True):
+        coords, ll, lpr = self._start(initial_state)
+        T, ns = self.ntemps, self.nwalkers // 2
+        for _ in range(int(iterations)):
+            members, swap_logu = self._draw_steps(1)
+            accepted = np.zeros((T, self.nwalkers), dtype=bool)
+            for h in (0, 1):
+                q = np.concatenate([_propose(coords[t], members[t], h) for t in range(T)])
+                lpr_q, ll_q = self._evaluate(q)
+                for t in range(T):
+                    sl = slice(t * ns, (t + 1) * ns)
+                    _accept_rung(self.betas[t], coords[t], ll[t], lpr[t], accepted[t], members[t], h, q[sl], lpr_q[sl], ll_q[sl])
+            swap_sweep(self._db, coords, ll, lpr, np.asarray(swap_logu)[0], self._nswap)
+            self._accepted += accepted
+            self.iteration += 1
+            if store:
+                self._chain.append(coords.copy())
+                self._ll.append(ll.copy())
+                self._lpr.append(lpr.copy())
+            self._last = TemperedState(coords, ll, lpr)
+            yield self._last
+
+
+class DeviceTemperedSampler(_Ladder):
+    """The ladder resident on the GPU (``msx_tempered_*``; csrc/tempered_kernels.h): per half-step ONE launch proposes for
+    all T rungs, the plain evaluation scores the ``T * nw / 2`` proposals twice (prior, likelihood), and after the second
+    half-step one launch sweeps the swaps; only the chains come back.  ``engine`` is a staged ``Engine`` on one GPU.
+
+    ``rng='host'``: the randomness is this object's NumPy generators, exactly ``TemperedSampler``'s calls -- same seed, same
+    chain.  ``rng='device'``: the library draws every chunk from ``seeds`` and the ABSOLUTE iteration ``_drawn``, which
+    every chunk queued advances and ``reset()`` leaves alone (as ``DeviceEnsembleSampler`` documents: consecutive runs
+    continue one stream; a loop left early leaves ``_drawn`` past the last iteration yielded by the chunks already
+    queued).  The chain is the one ``TemperedSampler(draws=lambda i, m: ctx.tempered_draw(seeds, moves, i, m, nw, ndim))``
+    walks."""
+
+    def __init__(self, nwalkers, ndim, engine, ntemps=None, betas=None, beta_min=0.02, seed=None, seeds=None, chunk=64, rng='host',
+                 moves=None):
+        if rng not in ('host', 'device'):
+            raise ValueError("rng must be 'host' or 'device'")
+        self.rng_mode = rng
+        self.engine = engine
+        self.chunk = int(chunk)
+        self._init_ladder(nwalkers, ndim, ntemps, betas, beta_min, seed, seeds, moves)
+
+    def _evaluate(self, q):
+        from . import _lib
+        from .engine import _raise_for_status
+        ctx = self.engine.ctx
+        lpr, st_p = ctx.logprob_batch(q, _lib.MODE_LOGPRIOR)
+        ll, st_l = ctx.logprob_batch(q, _lib.MODE_LOGLIKE)
+        _raise_for_status(st_p, q)
+        _raise_for_status(np.where(st_p != W_REJECT, st_l, 0), q)
+        return lpr, ll
+
+    def _draw_members(self, m):
+        """The T members' general layouts of m iterations, stacked rung by rung: eight arrays (m, T, ...)."""
+        per = [r._draw_steps(m) for r in self._rungs]
+        return [np.stack([p[i] for p in per], axis=1) for i in range(8)]
+
+    def _draw_swaps(self, m):
+        return [draw_swap_logu(self._swap_rng, m, self.ntemps, self.nwalkers)]
+
+    def sample(self, initial_state, iterations=1, store=True):
+        from .engine import _raise_for_status
+        coords, ll, lpr = self._start(initial_state)
+        if int(iterations) <= 0:
+            return
+        ctx = self.engine.ctx
+        base_acc, base_swap = self._accepted.copy(), self._nswap.copy()
+
+        def enqueue(slot, m, arrays):
+            if arrays is None:
+                ctx.tempered_enqueue_drawn(slot, m, self.seeds, self._moves, self._drawn)
+                self._drawn += m
+            else:
+                ctx.tempered_enqueue(slot, *arrays)
+
+        ctx.sampler_policy(0)   # plain launches: the overlapped hand-over is part of the fused proposal
+        ctx.tempered_begin(self.betas, coords, ll, lpr, self.chunk)
+        draws = None if self.rng_mode == 'device' else (self._draw_members, self._draw_swaps)
+        with closing(_pump(iterations, self.chunk, draws, enqueue, ctx.tempered_collect, ctx.tempered_end)) as chunks:
+            for mm, (chain, llc, lprc, nacc, nswap, worst) in chunks:
+                bad = np.nonzero(np.asarray(worst) > W_REJECT)[0]
+                if bad.size:
+                    _raise_for_status(np.array([worst[bad[0]]]), chain[-1][int(bad[0])][:1])
+                self._accepted = base_acc + nacc
+                self._nswap = base_swap + nswap
+                for i in range(mm):
+                    self.iteration += 1
+                    if store:
+                        self._chain.append(chain[i])
+                        self._ll.append(llc[i])
+                        self._lpr.append(lprc[i])
+                    self._last = TemperedState(chain[i], llc[i], lprc[i])
+                    yield self._last

@@ -11,7 +11,9 @@
     python examples/fit_synthetic.py --out /tmp/fit --nwalk 48 --nstep 40 --nburn 50 --nsteps 300
 
 With ``--tempered T [--beta-min B]`` the sampler is a ladder of T ensembles (mcmc_spec_amd.tempered):
-burn-in, reset, production; the swap fractions and the cold rung's summary are printed.
+burn-in, reset, production; the swap fractions and the cold rung's summary are printed.  ``--evidence`` adds the cold
+rung's autocorrelation time and ln Z by thermodynamic integration and the stepping stone (section 18), from the rows the
+run kept on the GPU with ``--autocorr device``; an evidence run wants a much smaller ``--beta-min`` than the default.
 """
 import argparse
 import os
@@ -38,6 +40,8 @@ def main():
     ap.add_argument('--tempered', type=int, default=0, metavar='T',
                     help='parallel tempering: a ladder of T ensembles, geometric from beta = 1 down to --beta-min (0: off)')
     ap.add_argument('--beta-min', type=float, default=0.02, help='the hottest rung of --tempered')
+    ap.add_argument('--evidence', action='store_true',
+                    help="with --tempered: print the cold rung's tau and ln Z +- mc_error (ladder ladder_error)")
     args = ap.parse_args()
 
     import mcmc_spec_amd.mft6 as gpu
@@ -124,7 +128,8 @@ def tempered_run(args, eng, p0, truth, t2):
     """The sampler block with a temperature ladder: every rung starts from the optimiser's walkers; rung 0 is the posterior."""
     from mcmc_spec_amd import summary
     from mcmc_spec_amd.tempered import DeviceTemperedSampler
-    sampler = DeviceTemperedSampler(len(p0), 6, eng, ntemps=args.tempered, beta_min=args.beta_min, seed=args.seed, chunk=50, rng='device')
+    sampler = DeviceTemperedSampler(len(p0), 6, eng, ntemps=args.tempered, beta_min=args.beta_min, seed=args.seed, chunk=50, rng='device',
+                                    autocorr=args.autocorr, cap_hint=max(args.nburn, args.nsteps))
     state = sampler.run_mcmc(p0, args.nburn)
     sampler.reset()
     sampler.run_mcmc(state, args.nsteps)
@@ -141,6 +146,12 @@ def tempered_run(args, eng, p0, truth, t2):
     print('posterior 16 / 50 / 84 of the cold rung ({} samples):'.format(int(summ['count'])))
     for nm, (lo, mid, hi) in zip(['T1', 'T2', 'Av', 'R1', 'R2', 'plx'], summ['quantiles']):
         print('  {:4s} {:.6g} / {:.6g} / {:.6g}'.format(nm, lo, mid, hi))
+    if args.evidence:
+        print('tau of the cold rung :', np.round(sampler.get_autocorr_time(t=0, quiet=True), 2))
+        for method in ('ti', 'ss'):
+            ev = sampler.log_evidence(blocks=min(8, sampler.iteration), method=method)
+            print('ln Z ({}) = {:.4f} +- {:.4f} (ladder {:.4f})'.format(method, ev.log_z, ev.mc_error, ev.ladder_error))
+        print('<ln L> per rung      :', np.round(ev.mean_log_like, 3))
     np.savetxt(os.path.join(args.out, 'samples.txt'), samples)
     print('wrote', os.path.join(args.out, 'samples.txt'), samples.shape)
     return truth, med, samples

@@ -427,6 +427,7 @@ int msx_tempered_collect(msx_ctx *ctx, int32_t slot, double *chain, double *ll_c
                          int64_t *nswap, int32_t *worst);
 /* ends the run (no run: MSX_OK); its final state where the pointers are not NULL                                        */
 int msx_tempered_end(msx_ctx *ctx, double *coords, double *ll, double *lpr);
+/* (the ladder's device series: msx_series_attach_tempered, with the series below)                                       */
 
 /* ---- A4-A6: make_composite (mft6.py:651-831, plot=False) -------------------------------------- */
 /* teff/logg/rad are [nspec]; use_distance = 0 mirrors `distance=False` (mft6.py:701-703).         */
@@ -598,6 +599,15 @@ int msx_series_rows(msx_series *s, int64_t *out);
  * copy).  The run detaches at its end (msx_sampler_end / msx_group_sampler_end, or destruction).                        */
 int msx_sampler_attach_series(msx_ctx *ctx, msx_series *s, int64_t at_row);
 int msx_group_sampler_attach_series(msx_group *group, msx_series *s, int64_t at_row);
+/* A tempered run's series: called once, between msx_tempered_begin and the first enqueue, with the
+ * rules above for at_row.  Either series may be NULL, not both.  Both have k = ntemps members of nw walkers each, member
+ * t = rung t (member 0 is the posterior); chain has the run's ndim, dens has ndim = 2: column 0 is ll, column 1 is lpr.
+ * Every chunk, host-drawn or device-drawn, appends its iterations' rows -- the state after the swap sweep, what
+ * msx_tempered_collect returns -- at at_row, at_row + 1, ... on the compute stream before the chunk's results travel: a
+ * collected chunk's rows are in place.  The series grow as above and are detached by msx_tempered_end.  MSX_ERR_STATE: no
+ * tempered run, after the first enqueue, a series with a run attached.  MSX_ERR_INVALID: a series on another device, or
+ * whose nw, ndim, k or counts do not match; at_row outside 0 .. the rows each series holds.                              */
+int msx_series_attach_tempered(msx_ctx *ctx, msx_series *chain, msx_series *dens, int64_t at_row);
 /* host rows [nrows][nw][ndim] appended (synchronous; refused while a run is attached)                                    */
 int msx_series_append(msx_series *s, const double *rows, int64_t nrows);
 /* rows row0 .. row0 + nrows - 1 back as [nrows][nw][ndim] (synchronous)                                                */
@@ -644,6 +654,21 @@ int msx_series_hist(msx_series *s, int64_t n, int64_t discard, int64_t thin, con
 int msx_series_hist2d(msx_series *s, int64_t n, int64_t discard, int64_t thin, const uint32_t *pairs, int32_t npairs,
                       const double *xedges, int32_t nx, const double *yedges, int32_t ny, int32_t closed_last,
                       int64_t *counts_out);
+
+/* ---- block means and log-mean-exponentials of a series column ----------------------------------
+ * What thermodynamic integration and the stepping stone make of a ladder's ln L (ptemcee's log_evidence_estimate); for any
+ * series.  The selection x = rows[0:n][discard::thin] (n' rows) is msx_series_acf's; member m contributes column col of its
+ * W_m walkers.  The n' rows are cut into nblocks consecutive blocks, block b = rows floor(b n' / B) .. floor((b + 1) n' / B)
+ * - 1.  mean_out[m * (B + 1)] = the mean of all n' W_m values, mean_out[m * (B + 1) + 1 + b] = block b's mean.  lme_out, in
+ * the same layout, = ln((1 / N) sum exp(db[m] x)), computed as db[m] M + ln((1 / N) sum exp(db[m] (x - M))) with M the
+ * maximum of the values summed (a block's own; the total combines the blocks by rescaling to their maximum); written for
+ * db >= 0.  db [k]; db == NULL skips lme_out.  -inf values give a -inf mean and weigh zero in lme; all -inf gives -inf,
+ * never NaN; a NaN gives NaN.  The order of every sum is fixed by (n', W_m, nblocks) alone -- not by the launch, the
+ * buffer's capacity, thin or how the rows arrived -- so the same input gives the same bits.  Synchronous, on the series'
+ * own stream, waits for nothing but the latest growth copy.  MSX_ERR_RANGE: n past the rows held, an empty selection, col
+ * outside the series, nblocks outside 1 .. min(n', 64).                                                                   */
+int msx_series_evidence(msx_series *s, int64_t n, int64_t discard, int64_t thin, int32_t col, const double *db, int32_t nblocks,
+                        double *mean_out, double *lme_out);
 
 /* ---- derived posteriors: product bands and derived columns of samples -------------------------
  * What the reference makes of chain samples after the run: make_composite(..., plot=True) (mft6.py:786-828) gives each

@@ -204,6 +204,8 @@ def load():
         'msx_products_spectra': (C.c_int, [vp, _dp, C.c_int64, C.c_int32, C.c_int32, _dp, _dp, C.POINTER(C.c_int32)]),
         'msx_composite_parts': (C.c_int, [vp, _dp, _dp, _dp, C.c_int32, C.c_double, C.c_int64, C.c_int64, _dp, C.POINTER(C.c_int32)]),
         'msx_series_derive': (C.c_int, [vp, C.POINTER(vp), _up, C.c_int32, C.c_int64, C.c_int64, vp, C.POINTER(C.c_int32)]),
+        'msx_series_attach_tempered': (C.c_int, [vp, vp, vp, C.c_int64]),
+        'msx_series_evidence': (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _dp, C.c_int32, _dp, _dp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = header/library skew, fail loudly
@@ -233,7 +235,7 @@ EXPORTED = ['msx_create', 'msx_destroy', 'msx_last_error', 'msx_device_info', 'm
             'msx_sampler_enqueue_moves', 'msx_sampler_enqueue_moves_drawn', 'msx_sampler_draw_moves',
             'msx_group_sampler_enqueue_moves', 'msx_group_sampler_enqueue_moves_drawn',
             'msx_tempered_begin', 'msx_tempered_enqueue', 'msx_tempered_enqueue_drawn', 'msx_tempered_draw', 'msx_tempered_collect',
-            'msx_tempered_end']
+            'msx_tempered_end', 'msx_series_attach_tempered', 'msx_series_evidence']
 
 
 def as_f64(a):
@@ -773,6 +775,12 @@ class Context:
         self.check(self.lib.msx_tempered_end(self.h, dptr(coords), dptr(ll), dptr(lpr)))
         return coords, ll, lpr
 
+    def tempered_attach_series(self, chain, dens, at_row):
+        """Append every chunk of the run begun by tempered_begin to the series ``chain`` (T members of nw walkers, ndim) and
+        ``dens`` (the same members, ndim 2: ll, lpr) from row ``at_row`` on (msx_series_attach_tempered); either may be None."""
+        self.check(self.lib.msx_series_attach_tempered(self.h, None if chain is None else chain.h, None if dens is None else dens.h,
+                                                       int(at_row)))
+
     def make_composite(self, teff, logg, rad, use_distance, plx, win_n, nc, nph):
         teff, logg, rad = as_f64(teff), as_f64(logg), as_f64(rad)
         spec = np.empty(win_n)
@@ -1039,6 +1047,22 @@ class Series:
         f = np.full((self.k, self.ndim, nlag), np.nan)
         self.check(self.lib.msx_series_acf(self.h, int(n), int(discard), int(thin), int(lag0), nlag, mask, dptr(f)))
         return f
+
+    def evidence(self, n, discard=0, thin=1, col=0, db=None, nblocks=1):
+        """(mean, lme), each (k, nblocks + 1): per member the mean of column ``col`` over rows[0:n][discard::thin] and all the
+        member's walkers ([:, 0]) and over each of ``nblocks`` consecutive blocks of those rows ([:, 1:]), and
+        ``ln mean exp(db[m] x)`` likewise -- None without ``db`` (k,).  msx_series_evidence: fixed summation order."""
+        nblocks = int(nblocks)
+        mean = np.empty((self.k, max(nblocks, 0) + 1))
+        lme = None
+        if db is not None:
+            db = as_f64(db)
+            if db.shape != (self.k,):
+                raise ValueError('evidence: db needs one entry per member')
+            lme = np.empty_like(mean)
+        self.check(self.lib.msx_series_evidence(self.h, int(n), int(discard), int(thin), int(col), None if db is None else dptr(db), nblocks,
+                                                dptr(mean), None if lme is None else dptr(lme)))
+        return mean, lme
 
     def derive(self, contexts, cols, dst, row0=0, nrows=None):
         """Rows row0 .. row0 + nrows - 1 of this series mapped to the derived columns ``cols`` (codes) and written to the

@@ -26,6 +26,7 @@
 //   opt_run_kernels.h  the device-resident pre-optimiser: fit_spec's per-chain state machine, one thread per chain
 //   staging_kernels.h  CCM89, pair gather, band integrals, broadening, resample, composite, stream copy
 //   summary_kernels.h  order statistics and binned marginals of a device chain series
+//   evidence_kernels.h block means and log-mean-exponentials of a series column (thermodynamic integration, stepping stone)
 //   msx.hip            host context + the C ABI of include/msx.h
 //
 // Design notes (details in DESIGN.md):
@@ -69,6 +70,7 @@
 #include "inpath_kernels.h"
 #include "autocorr_kernels.h"
 #include "summary_kernels.h"
+#include "evidence_kernels.h"
 #include "product_kernels.h"
 #include "opt_run_kernels.h"
 
@@ -226,6 +228,7 @@ struct msx_series {
     char *d_scratch = nullptr;           // acf's partial sums and results, append's / read's staging
     size_t scratch_bytes = 0;
     struct SamplerRun *run = nullptr;    // the run appending to it (msx_*sampler_attach_series .. the run's end)
+    struct TemperedRun *trun = nullptr;  // ... or the tempered run (msx_series_attach_tempered .. msx_tempered_end)
 };
 
 namespace {
@@ -3664,6 +3667,11 @@ struct TemperedRun {
     int32_t T = 0, ndim = 0;
     int64_t nw = 0, ns = 0, cap_steps = 0;   // nw, ns: per rung
     bool failed = false;                     // an enqueue returned an error after queuing part of its launches
+    bool enqueued = false;                   // an enqueue has queued something (msx_series_attach_tempered comes before)
+    // the device series the run appends its chunks to (msx_series_attach_tempered): the coordinates [T nw][ndim] and
+    // (ll, lpr) [T nw][2], rung t member t; either may be absent.  series_row: the row the next chunk starts at
+    struct msx_series *s_chain = nullptr, *s_dens = nullptr;
+    int64_t series_row = 0;
     double beta[MSX_MAX_GROUP], db[MSX_MAX_GROUP];
     char *d_state = nullptr;
     double *d_coords = nullptr, *d_ll = nullptr, *d_lpr = nullptr, *d_q = nullptr, *d_new_lpr = nullptr, *d_new_ll = nullptr;
@@ -3730,6 +3738,8 @@ static void tempered_free(msx_ctx *c) {
         if (sl.out_ready) (void)hipEventDestroy(sl.out_ready);
     }
     if (r->d_state) (void)hipFree(r->d_state);
+    if (r->s_chain) r->s_chain->trun = nullptr;  // (the series outlive the run)
+    if (r->s_dens) r->s_dens->trun = nullptr;
     if (r->copy) (void)hipStreamDestroy(r->copy);
     if (r->up) (void)hipStreamDestroy(r->up);
     delete r;
@@ -3832,6 +3842,38 @@ static const char *tempered_pack(const TemperedRun *r, char *h_in, int64_t nstep
     return nullptr;
 }
 
+// The chunk's rows appended to the run's series on the compute stream (series_put_chunk's rules: growth at enqueue time, in
+// stream order).  The slot's chain [st][T][nw][ndim] is [st][T nw][ndim]: series_put_kernel as it is; ll and lpr [st][T nw]
+// are one-column chunks going to columns 0 and 1 of the density series.
+static hipError_t tempered_put_chunk(TemperedRun *r, const TemperedOut &out, int64_t nsteps, hipStream_t compute) {
+    const int64_t W = (int64_t)r->T * r->nw, row0 = r->series_row;
+    if (msx_series *sr = r->s_chain) {
+        hipError_t e = series_reserve(sr, row0 + nsteps, row0, compute);
+        if (e != hipSuccess) return e;
+        const int64_t total = nsteps * W * r->ndim;
+        hipLaunchKernelGGL(series_put_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, compute, (const double *)out.chain, nsteps, W,
+                           (int32_t)r->ndim, sr->d_rows, sr->cap, row0);
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        sr->rows = row0 + nsteps;
+    }
+    if (msx_series *sr = r->s_dens) {
+        hipError_t e = series_reserve(sr, row0 + nsteps, row0, compute);
+        if (e != hipSuccess) return e;
+        const int64_t total = nsteps * W;
+        const double *src[2] = {out.ll, out.lpr};
+        for (int col = 0; col < 2; ++col) {
+            hipLaunchKernelGGL(series_put_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, compute, src[col], nsteps, W, (int32_t)1,
+                               sr->d_rows + (int64_t)col * W * sr->cap, sr->cap, row0);
+            e = hipGetLastError();
+            if (e != hipSuccess) return e;
+        }
+        sr->rows = row0 + nsteps;
+    }
+    r->series_row = row0 + nsteps;
+    return hipSuccess;
+}
+
 static MoveDrawTable tempered_members(int32_t T, int64_t nw, const uint64_t *seeds) {
     MoveDrawTable Tb;
     memset(&Tb, 0, sizeof(Tb));
@@ -3866,6 +3908,7 @@ static int tempered_enqueue(msx_ctx *c, const char *who, int32_t slot, int64_t n
         return fail(c, MSX_ERR_INVALID, w + ": " + why);
     }
     HIP_TRY(c, hipSetDevice(c->device));
+    r->enqueued = true;
     c->P.smp_on = 0;  // (the plain evaluation)
     c->P.smp_defer = 0;
     const int T = r->T, ndim = r->ndim;
@@ -3922,6 +3965,8 @@ static int tempered_enqueue(msx_ctx *c, const char *who, int32_t slot, int64_t n
         hipLaunchKernelGGL(tempered_swap_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s, W);
         e = hipGetLastError();
     }
+    // the chunk's rows into the attached series, before kernels_done: a collected chunk's rows are in place
+    if (e == hipSuccess && rc == MSX_OK) e = tempered_put_chunk(r, out, nsteps, s);
     // the counters keep running while this chunk's results travel: snapshot them in stream order, then bring the slot back
     if (e == hipSuccess && rc == MSX_OK) e = hipMemcpyAsync(out.nacc, r->d_nacc, sizeof(int64_t) * (size_t)(T * nw), hipMemcpyDeviceToDevice, s);
     if (e == hipSuccess && rc == MSX_OK) e = hipMemcpyAsync(out.nswap, r->d_nswap, sizeof(int64_t) * MSX_MAX_GROUP, hipMemcpyDeviceToDevice, s);
@@ -4043,7 +4088,7 @@ static constexpr size_t kAcfPartBudget = (size_t)256 << 20;     // acf's partial
 static hipError_t series_scratch(msx_series *sr, size_t bytes) {
     if (bytes <= sr->scratch_bytes) return hipSuccess;
     if (sr->d_scratch) {
-        if (sr->run) sr->retired.push_back(sr->d_scratch);
+        if (sr->run || sr->trun) sr->retired.push_back(sr->d_scratch);
         else {
             (void)hipStreamSynchronize(sr->stream);
             (void)hipFree(sr->d_scratch);
@@ -4111,6 +4156,12 @@ void msx_series_destroy(msx_series *sr) {
         if (r->series == sr) r->series = nullptr;
         (void)hipDeviceSynchronize();
     }
+    if (sr->trun) {  // ... or a tempered run
+        TemperedRun *r = sr->trun;
+        if (r->s_chain == sr) r->s_chain = nullptr;
+        if (r->s_dens == sr) r->s_dens = nullptr;
+        (void)hipDeviceSynchronize();
+    }
     if (sr->stream) (void)hipStreamSynchronize(sr->stream);
     if (sr->grown_set) (void)hipEventSynchronize(sr->grown);
     for (void *p : sr->retired) (void)hipFree(p);
@@ -4139,7 +4190,7 @@ static int series_attach(std::string *err, msx_series *sr, SamplerRun *r, int de
         *err = w + ": attach once, between " + begin + " and the run's first enqueue";
         return MSX_ERR_STATE;
     }
-    if (sr->run) { *err = w + ": the series is attached to another run in flight"; return MSX_ERR_STATE; }
+    if (sr->run || sr->trun) { *err = w + ": the series is attached to another run in flight"; return MSX_ERR_STATE; }
     if (sr->device != device) { *err = w + ": the series lives on another device"; return MSX_ERR_INVALID; }
     bool same = sr->nw == r->nw && sr->ndim == r->ndim && sr->off.size() == r->m_nw.size() + 1;
     for (size_t m = 0; same && m < r->m_nw.size(); ++m) same = sr->off[m + 1] - sr->off[m] == r->m_nw[m];
@@ -4166,10 +4217,46 @@ int msx_group_sampler_attach_series(msx_group *g, msx_series *sr, int64_t at_row
                          "msx_group_sampler_begin");
 }
 
+// A tempered run's two series: the T rungs are the T members, rung 0 first.  series_attach's rules.
+int msx_series_attach_tempered(msx_ctx *c, msx_series *chain, msx_series *dens, int64_t at_row) {
+    if (!c) return MSX_ERR_INVALID;
+    const std::string w("msx_series_attach_tempered");
+    if (!chain && !dens) return fail(c, MSX_ERR_INVALID, w + ": bad arguments (give the chain's series, the densities' or both)");
+    TemperedRun *r = c->tmp;
+    if (!r) return fail(c, MSX_ERR_STATE, w + ": call msx_tempered_begin first");
+    if (r->enqueued || r->failed || r->slot[0].busy || r->slot[1].busy || r->s_chain || r->s_dens)
+        return fail(c, MSX_ERR_STATE, w + ": attach once, between msx_tempered_begin and the run's first enqueue");
+    HIP_TRY(c, hipSetDevice(c->device));
+    msx_series *both[2] = {chain, dens};
+    const int32_t want_dim[2] = {r->ndim, 2};
+    if (chain == dens) return fail(c, MSX_ERR_INVALID, w + ": the chain and the densities need a series each");
+    for (int i = 0; i < 2; ++i) {
+        msx_series *sr = both[i];
+        if (!sr) continue;
+        if (sr->run || sr->trun) return fail(c, MSX_ERR_STATE, w + ": the series is attached to another run in flight");
+        if (sr->device != c->device) return fail(c, MSX_ERR_INVALID, w + ": the series lives on another device");
+        bool same = sr->nw == (int64_t)r->T * r->nw && sr->ndim == want_dim[i] && (int64_t)sr->off.size() == (int64_t)r->T + 1;
+        for (int t = 0; same && t < r->T; ++t) same = sr->off[t + 1] - sr->off[t] == r->nw;
+        if (!same)
+            return fail(c, MSX_ERR_INVALID, w + ": a series needs ntemps members of nw walkers each and the run's ndim (the densities: ndim = 2)");
+        if (at_row < 0 || at_row > sr->rows) return fail(c, MSX_ERR_INVALID, w + ": at_row must lie in 0 .. the rows each series holds");
+    }
+    for (msx_series *sr : both) {
+        if (!sr) continue;
+        series_release(sr);
+        sr->rows = at_row;   // (rows at or after at_row are dropped: the run overwrites them)
+        sr->trun = r;
+    }
+    r->s_chain = chain;
+    r->s_dens = dens;
+    r->series_row = at_row;
+    return MSX_OK;
+}
+
 int msx_series_append(msx_series *sr, const double *rows, int64_t nrows) {
     if (!sr) return MSX_ERR_INVALID;
     if (!rows || nrows < 1) return fail(sr, MSX_ERR_INVALID, "msx_series_append: bad arguments");
-    if (sr->run) return fail(sr, MSX_ERR_STATE, "msx_series_append: a run in flight appends to this series");
+    if (sr->run || sr->trun) return fail(sr, MSX_ERR_STATE, "msx_series_append: a run in flight appends to this series");
     HIP_TRY(sr, hipSetDevice(sr->device));
     const int64_t per = sr->nw * sr->ndim;
     const int64_t piece = std::max<int64_t>(1, (int64_t)(kSeriesStageBytes / (sizeof(double) * (size_t)per)));
@@ -4254,6 +4341,52 @@ int msx_series_acf(msx_series *sr, int64_t n, int64_t discard, int64_t thin, int
                 memcpy(f_out + ((int64_t)m * sr->ndim + dims.d[q]) * nlag + (lb - lag0), h.data() + ((int64_t)m * nd + q) * cnt,
                        sizeof(double) * (size_t)cnt);
     }
+    return MSX_OK;
+}
+
+// ---- block means and log-mean-exponentials of a series column (evidence_kernels.h) ------------------
+int msx_series_evidence(msx_series *sr, int64_t n, int64_t discard, int64_t thin, int32_t col, const double *db, int32_t nblocks,
+                        double *mean_out, double *lme_out) {
+    if (!sr) return MSX_ERR_INVALID;
+    if (!mean_out || discard < 0 || thin < 1 || (db && !lme_out))
+        return fail(sr, MSX_ERR_INVALID, "msx_series_evidence: bad arguments (discard >= 0, thin >= 1, lme_out with db)");
+    if (n < 1 || n > sr->rows) return fail(sr, MSX_ERR_RANGE, "msx_series_evidence: n must lie in 1 .. the rows the series holds");
+    const int64_t np = n > discard ? (n - discard + thin - 1) / thin : 0;
+    if (np < 1) return fail(sr, MSX_ERR_RANGE, "msx_series_evidence: the selection rows[0:n][discard::thin] is empty");
+    if (col < 0 || col >= sr->ndim) return fail(sr, MSX_ERR_RANGE, "msx_series_evidence: col outside the series");
+    if (nblocks < 1 || nblocks > kEvdMaxBlocks || nblocks > np)
+        return fail(sr, MSX_ERR_RANGE, "msx_series_evidence: nblocks must lie in 1 .. min(n', 64)");
+    HIP_TRY(sr, hipSetDevice(sr->device));
+    const int k = (int)sr->off.size() - 1;
+    const int64_t B = nblocks, parts = sr->nw * B;
+    // scratch: [psum nw B | pmax nw B | pexp nw B | mmax k B | mean k (B + 1) | lme k (B + 1)]
+    const int64_t nout = (int64_t)k * (B + 1);
+    HIP_TRY(sr, series_scratch(sr, sizeof(double) * (size_t)(3 * parts + k * B + 2 * nout)));
+    double *d_psum = (double *)sr->d_scratch, *d_pmax = d_psum + parts, *d_pexp = d_pmax + parts, *d_mmax = d_pexp + parts;
+    double *d_mean = d_mmax + k * B, *d_lme = d_mean + nout;
+    HIP_TRY(sr, series_wait_growth(sr));
+    hipStream_t st = sr->stream;
+    const dim3 grid((unsigned)sr->nw, (unsigned)B);
+    hipLaunchKernelGGL(evd_part_kernel, grid, dim3(kEvdThreads), 0, st, (const double *)sr->d_rows, sr->cap, sr->nw, col, np, discard, thin,
+                       nblocks, d_psum, d_pmax);
+    HIP_TRY(sr, hipGetLastError());
+    hipLaunchKernelGGL(evd_mean_kernel, dim3((unsigned)k), dim3(kEvdMaxBlocks), 0, st, (const double *)d_psum, (const double *)d_pmax,
+                       (const int64_t *)sr->d_off, np, nblocks, d_mean, d_mmax);
+    HIP_TRY(sr, hipGetLastError());
+    if (db) {
+        EvdDb D;
+        memset(&D, 0, sizeof(D));
+        for (int m = 0; m < k; ++m) D.v[m] = db[m];
+        hipLaunchKernelGGL(evd_exp_kernel, grid, dim3(kEvdThreads), 0, st, (const double *)sr->d_rows, sr->cap, sr->nw, col, np, discard, thin,
+                           nblocks, (const int64_t *)sr->d_off, (int32_t)k, D, (const double *)d_mmax, d_pexp);
+        HIP_TRY(sr, hipGetLastError());
+        hipLaunchKernelGGL(evd_lme_kernel, dim3((unsigned)k), dim3(kEvdMaxBlocks), 0, st, (const double *)d_pexp, (const double *)d_mmax,
+                           (const int64_t *)sr->d_off, np, nblocks, D, d_lme);
+        HIP_TRY(sr, hipGetLastError());
+        HIP_TRY(sr, hipMemcpyAsync(lme_out, d_lme, sizeof(double) * (size_t)nout, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(sr, hipMemcpyAsync(mean_out, d_mean, sizeof(double) * (size_t)nout, hipMemcpyDeviceToHost, st));
+    HIP_TRY(sr, hipStreamSynchronize(st));
     return MSX_OK;
 }
 
@@ -4688,7 +4821,7 @@ int msx_series_derive(msx_series *src, msx_ctx **ctxs, const uint32_t *cols, int
     if (ncols > MSX_MAX_DIM) return fail(src, MSX_ERR_RANGE, "msx_series_derive: more columns than a series is wide (MSX_MAX_DIM)");
     if (dst == src || dst->device != src->device || dst->nw != src->nw || dst->off != src->off || dst->ndim != ncols)
         return fail(src, MSX_ERR_INVALID, "msx_series_derive: dst must be another series on the same device with src's members and ndim = ncols");
-    if (dst->run) return fail(src, MSX_ERR_STATE, "msx_series_derive: a run in flight appends to dst");
+    if (dst->run || dst->trun) return fail(src, MSX_ERR_STATE, "msx_series_derive: a run in flight appends to dst");
     if (row0 + nrows > src->rows) return fail(src, MSX_ERR_RANGE, "msx_series_derive: rows past the ones src holds");
     if (row0 > dst->rows) return fail(src, MSX_ERR_RANGE, "msx_series_derive: row0 past the rows dst holds (it would leave a gap)");
     const int k = (int)src->off.size() - 1;

@@ -16,9 +16,31 @@ iteration i is the state AFTER the sweep.  ``TemperedSampler`` is this text as a
 The swap draws: device-drawn, ``u = counter_uniform(seeds[0], i, 14, (t-1) * 4096 + w)`` (stream 14 of the counter
 generator; ``counter_swap_logu`` restates it); host-drawn, ``swap_generator(seeds[0])``, one float64 ``ln u`` per
 (iteration, pair, walker), consumed row by row.
+
+What a finished ladder gives.  Rungs are members: ``get_autocorr_time(t)``, ``get_summary(t)`` and
+``get_products(cols, t)`` are the other samplers' (sections 12, 14, 15) for rung t -- ``t=None`` for every rung -- and
+``DeviceTemperedSampler(autocorr='device')`` keeps the rows in two device series while the run goes
+(``msx_series_attach_tempered``), so none of them downloads or uploads a chain.  And the evidence: with ``m_t`` the mean
+of ``ln L`` over rung t's stored samples (``mean_log_like``), ``log_evidence`` estimates ``ln Z = int_0^1 <ln L>_beta dbeta``
+
+  * ``method='ti'`` (thermodynamic integration; Lartillot & Philippe 2006): the trapezoid over the ladder,
+    ``ln Z = sum_p (beta_p - beta_{p+1}) (m_p + m_{p+1}) / 2  +  beta_{T-1} m_{T-1}``;
+  * ``method='ss'`` (the stepping stone; Xie et al. 2011): ``ln Z = sum_{t >= 1} lme_t  +  beta_{T-1} m_{T-1}`` with
+    ``lme_t = ln mean exp((beta_{t-1} - beta_t) ln L)`` over rung t's samples, computed around their maximum.
+
+The last term of both is ptemcee's convention for a ladder that stops above beta = 0: the hottest rung's mean continued
+to 0, a rectangle.  BOTH ESTIMATES OMIT [0, beta_min] EXCEPT FOR THAT RECTANGLE: ``<ln L>_beta`` usually falls steeply
+there (for a d-dimensional Gaussian likelihood as ``-d / (2 beta)``), so an evidence run wants a much smaller ``beta_min``
+than a mode-hopping run -- small enough that the hottest rung samples the prior.  ``mc_error`` is the standard error of
+the estimates of ``blocks`` consecutive blocks of the stored rows, ``sqrt(var(ddof=1) / blocks)`` (NaN for one block; it
+knows nothing of a burn-in left in, and underestimates when a block is shorter than the autocorrelation time);
+``ladder_error`` is ``|ln Z - ln Z(rungs [::2], the last rung kept)|``, the estimate's change when every other rung is
+dropped.  ``TemperedSampler``'s NumPy (``host_evidence``) is the definition; the device computes the same sums in a fixed
+order of its own (``msx_series_evidence``; tests/evidence_numpy.py restates that order).
 """
 from __future__ import annotations
 
+from collections import namedtuple
 from contextlib import closing
 
 import numpy as np
@@ -143,8 +165,185 @@ def swap_sweep(db, coords, ll, lpr, swap_logu, nswap):
         nswap[t - 1] += int(np.count_nonzero(sw))
 
 
+LogEvidence = namedtuple('LogEvidence', ['log_z', 'mc_error', 'ladder_error', 'mean_log_like'])
+MAX_BLOCKS = 64       # csrc/evidence_kernels.h kEvdMaxBlocks
+
+
+def block_bounds(n, blocks):
+    """The ``blocks`` consecutive blocks of n rows: block b is rows ``lo[b] .. lo[b + 1] - 1``, ``lo[b] = floor(b n / blocks)``."""
+    n, blocks = int(n), int(blocks)
+    if not 1 <= blocks <= min(n, MAX_BLOCKS):
+        raise ValueError("blocks must lie in 1 .. min(n', {})".format(MAX_BLOCKS))
+    return [b * n // blocks for b in range(blocks + 1)]
+
+
+def _lme(x, db):
+    """``ln mean exp(db x)`` of a flat sample around its maximum; -inf values weigh zero, all -inf gives -inf."""
+    M = np.max(x)
+    if np.isnan(M):
+        return np.nan
+    if M == -np.inf:
+        return -np.inf
+    with np.errstate(invalid='ignore'):
+        e = np.where(x == -np.inf, 0.0, np.exp(db * (x - M)))
+    return db * M + np.log(np.sum(e) / x.size)
+
+
+def host_evidence(x, db=None, blocks=1):
+    """(mean, lme), each (T, blocks + 1), of x (n', T, nw): [:, 0] over all rows and walkers of a member, [:, 1 + b] over
+    block b's rows (``block_bounds``); lme = ``ln mean exp(db[t] x)`` (None without db).  What msx_series_evidence computes,
+    in NumPy's summation order."""
+    x = np.asarray(x, dtype=float)
+    lo = block_bounds(x.shape[0], blocks)
+    T = x.shape[1]
+    parts = [x] + [x[lo[b]:lo[b + 1]] for b in range(int(blocks))]
+    with np.errstate(invalid='ignore'):
+        mean = np.array([[np.mean(p[:, t]) for p in parts] for t in range(T)])
+    if db is None:
+        return mean, None
+    return mean, np.array([[_lme(p[:, t].ravel(), db[t]) for p in parts] for t in range(T)])
+
+
+def ti_log_z(betas, m):
+    """The trapezoid of the rung means m over the ladder, plus ``beta_{T-1} m_{T-1}`` (the module docstring)."""
+    betas, m = np.asarray(betas, dtype=float), np.asarray(m, dtype=float)
+    return float(np.sum((betas[:-1] - betas[1:]) * (m[:-1] + m[1:]) / 2.0) + betas[-1] * m[-1])
+
+
+def ss_log_z(betas, lme, m_last):
+    """The stepping stone: ``sum_{t >= 1} lme[t] + beta_{T-1} m_last`` (lme[0] is not used)."""
+    return float(np.sum(np.asarray(lme, dtype=float)[1:]) + np.asarray(betas, dtype=float)[-1] * m_last)
+
+
+def halved(ntemps):
+    """The rungs [::2] with the last one kept."""
+    idx = list(range(0, int(ntemps), 2))
+    return idx if idx[-1] == int(ntemps) - 1 else idx + [int(ntemps) - 1]
+
+
+def _ss_db(betas, idx):
+    """db (T,) of the stepping stone over the rungs idx: member idx[j] gets ``beta[idx[j-1]] - beta[idx[j]]``, the others 0."""
+    db = np.zeros(len(betas))
+    for a, b in zip(idx[:-1], idx[1:]):
+        db[b] = betas[a] - betas[b]
+    return db
+
+
+def _host_tau(x, c):
+    """EnsembleSampler.get_autocorr_time's tau (before ``* thin`` and the tol rule) of a chain x (n, nw, ndim)."""
+    from .sampler import _autocorr_1d, _integrated_time
+    n, nw, ndim = x.shape
+    f = np.empty((ndim, n))
+    for d in range(ndim):
+        f[d] = 0.0
+        for k in range(nw):
+            f[d] += _autocorr_1d(x[:, k, d])
+        f[d] /= nw
+    return _integrated_time(f, c)
+
+
 class _Ladder:
     """What both samplers keep and return."""
+
+    _series = _dens = None   # DeviceTemperedSampler(autocorr='device'): the chain's and the densities' device series
+    engine = None            # the staged Engine, where the sampler was built on one (get_summary, get_products)
+
+    def _pick(self, out, t):
+        return out if t is None else {name: v[int(t)] for name, v in out.items()}
+
+    def _ctx(self):
+        if self.engine is None:
+            raise ValueError('this needs the GPU: build the sampler on a staged Engine')
+        return self.engine.ctx
+
+    def _flat_members(self):
+        """The stored chain as (n, T nw, ndim): the rungs as members, side by side."""
+        if not self._chain:
+            raise ValueError('the selection rows[0:n][discard::thin] is empty')
+        return np.array(self._chain).reshape(len(self._chain), self.ntemps * self.nwalkers, self.ndim)
+
+    def get_autocorr_time(self, t=0, quiet=False, c=5.0, tol=50.0, discard=0, thin=1):
+        """Rung t's integrated autocorrelation time (ndim,) -- rung 0 is the posterior -- or every rung's (T, ndim) for
+        ``t=None``: ``EnsembleSampler.get_autocorr_time``'s rules and keywords.  With autocorr='device' from the chain on
+        the device, one msx_series_acf call per lag tile over all rungs."""
+        from .sampler import _check_tau, _device_integrated_time
+        n_total = len(self._chain)
+        n = len(range(discard, n_total, thin))
+        rungs = range(self.ntemps) if t is None else [int(t)]
+        if n < 4:
+            if quiet:
+                return np.full((self.ntemps, self.ndim) if t is None else (self.ndim,), np.nan)
+            raise ValueError('chain too short')
+        if self._series is not None:
+            tau = _device_integrated_time(self._series, n_total, c, discard, thin)[list(rungs)]
+        else:
+            tau = np.array([_host_tau(self.get_chain(t=r, discard=discard, thin=thin), c) for r in rungs])
+        return _check_tau((tau if t is None else tau[0]) * thin, n, thin, tol, quiet)
+
+    def get_summary(self, t=0, q=(0.16, 0.5, 0.84), discard=0, thin=1, cols=None):
+        """Rung t's posterior summary over its stored chain, flattened over its walkers (``DeviceEnsembleSampler.get_summary``'s
+        dict and numbers: DESIGN.md section 14); ``t=None``: every rung's, the arrays with a leading axis T.  With
+        autocorr='device' from the chain held there; otherwise the host chain is uploaded first (the sampler must have
+        been built on an Engine)."""
+        from . import summary
+        if self._series is not None:
+            return self._pick(summary.summary_of(self._series, len(self._chain), q, cols, discard, thin), t)
+        return self._pick(summary.summarize(self._flat_members(), self._ctx(), [self.nwalkers] * self.ntemps, q, cols, discard, thin), t)
+
+    def get_products(self, cols, t=0, q=(0.16, 0.5, 0.84), discard=0, thin=1, indices=None):
+        """``get_summary``'s dict over DERIVED columns (``mcmc_spec_amd.products``) of rung t's stored chain (``t=None``: every
+        rung's), as ``DeviceEnsembleSampler.get_products``; the one engine serves every rung.
+        ``indices``: positions in the rung's flat sample ``get_chain(t, discard=, thin=, flat=True)`` to use instead of all
+        of it; those go through msx_products_batch from the host copy."""
+        from . import products, summary
+        engines = [self.engine] * self.ntemps
+        self._ctx()
+        if indices is not None:
+            idx = np.asarray(indices, dtype=np.int64)
+            outs = []
+            for r in (range(self.ntemps) if t is None else [int(t)]):
+                flat = self.get_chain(t=r, flat=True, thin=thin, discard=discard)
+                outs.append(products._summary_of_values(self.engine.ctx, products.evaluate(self.engine, flat[idx], cols), q))
+            return {name: np.stack([o[name] for o in outs]) if t is None else outs[0][name] for name in outs[0]}
+        if self._series is not None:
+            return self._pick(products.summarize_chain(self._series, len(self._chain), engines, cols, q, discard, thin), t)
+        with summary.uploaded(self._flat_members(), self.engine.ctx, [self.nwalkers] * self.ntemps) as (series, n):
+            return self._pick(products.summarize_chain(series, n, engines, cols, q, discard, thin), t)
+
+    def _evidence(self, discard, thin, db, blocks):
+        """(mean, lme) (T, blocks + 1) of the stored ln L: ``host_evidence``, or msx_series_evidence on the device series."""
+        n_total = len(self._ll)
+        if len(range(int(discard), n_total, int(thin))) < 1:
+            raise ValueError('the selection rows[0:n][discard::thin] is empty')
+        if self._dens is not None:
+            return self._dens.evidence(n_total, discard, thin, 0, db, blocks)
+        return host_evidence(np.array(self._ll)[int(discard)::int(thin)], db, blocks)
+
+    def mean_log_like(self, discard=0, thin=1):
+        """(T,): the mean of ``ln L`` over each rung's stored samples, ``<ln L>_beta`` at the ladder's betas."""
+        return self._evidence(discard, thin, None, 1)[0][:, 0].copy()
+
+    def log_evidence(self, discard=0, thin=1, blocks=8, method='ti'):
+        """``LogEvidence(log_z, mc_error, ladder_error, mean_log_like)`` of the stored run (the module docstring):
+        ``method='ti'`` thermodynamic integration, ``'ss'`` the stepping stone; ``blocks`` consecutive blocks of the rows for
+        ``mc_error`` (1 .. min(rows, 64))."""
+        if method not in ('ti', 'ss'):
+            raise ValueError("method must be 'ti' or 'ss'")
+        T, betas, blocks = self.ntemps, self.betas, int(blocks)
+        half = halved(T)
+        if method == 'ti':
+            mean, _ = self._evidence(discard, thin, None, blocks)
+            est = np.array([ti_log_z(betas, mean[:, j]) for j in range(blocks + 1)])
+            coarse = ti_log_z(betas[half], mean[half, 0])
+        else:
+            mean, lme = self._evidence(discard, thin, _ss_db(betas, list(range(T))), blocks)
+            est = np.array([ss_log_z(betas, lme[:, j], mean[-1, j]) for j in range(blocks + 1)])
+            lme2 = self._evidence(discard, thin, _ss_db(betas, half), 1)[1]
+            coarse = ss_log_z(betas[half], lme2[half, 0], mean[-1, 0])
+        with np.errstate(invalid='ignore'):
+            mc = float(np.sqrt(np.var(est[1:], ddof=1) / blocks)) if blocks > 1 else float('nan')
+            ladder = float(abs(est[0] - coarse))
+        return LogEvidence(float(est[0]), mc, ladder, mean[:, 0].copy())
 
     def _init_ladder(self, nwalkers, ndim, ntemps, betas, beta_min, seed, seeds, moves):
         self.betas = resolve_betas(ntemps, betas, beta_min)
@@ -263,6 +462,7 @@ class TemperedSampler(_Ladder):
                  moves=None, draws=None):
         if logprior_fn is None and hasattr(loglike_fn, 'ctx'):
             from . import _lib
+            self.engine = loglike_fn   # (get_summary / get_products upload the host chain to its device)
             ctx = loglike_fn.ctx
             loglike_fn, logprior_fn = (lambda q: ctx.logprob_batch(q, _lib.MODE_LOGLIKE)), (lambda q: ctx.logprob_batch(q, _lib.MODE_LOGPRIOR))
         self.loglike_fn, self.logprior_fn = loglike_fn, logprior_fn
@@ -325,16 +525,31 @@ class DeviceTemperedSampler(_Ladder):
     every chunk queued advances and ``reset()`` leaves alone (as ``DeviceEnsembleSampler`` documents: consecutive runs
     continue one stream; a loop left early leaves ``_drawn`` past the last iteration yielded by the chunks already
     queued).  The chain is the one ``TemperedSampler(draws=lambda i, m: ctx.tempered_draw(seeds, moves, i, m, nw, ndim))``
-    walks."""
+    walks.
+
+    ``autocorr='device'`` (the other device samplers' option): the stored rows are kept on the device as well, in two
+    ``_lib.Series`` of T members -- the coordinates, and (ll, lpr) -- that every ``sample(store=True)`` run appends to from
+    row ``len(self._chain)`` on (``msx_series_attach_tempered``); ``get_autocorr_time``, ``get_summary``, ``get_products``,
+    ``mean_log_like`` and ``log_evidence`` then work there.  ``cap_hint``: the rows to reserve at once (the iterations
+    planned, when known); the series grow by doubling otherwise.  ``reset()`` drops the rows.  The chain is the same, bit
+    for bit, whatever ``autocorr`` is."""
 
     def __init__(self, nwalkers, ndim, engine, ntemps=None, betas=None, beta_min=0.02, seed=None, seeds=None, chunk=64, rng='host',
-                 moves=None):
+                 moves=None, autocorr='host', cap_hint=0):
         if rng not in ('host', 'device'):
             raise ValueError("rng must be 'host' or 'device'")
+        if autocorr not in ('host', 'device'):
+            raise ValueError("autocorr must be 'host' or 'device'")
         self.rng_mode = rng
+        self.autocorr = autocorr
         self.engine = engine
         self.chunk = int(chunk)
         self._init_ladder(nwalkers, ndim, ntemps, betas, beta_min, seed, seeds, moves)
+        if autocorr == 'device':
+            from . import _lib
+            counts = [self.nwalkers] * self.ntemps
+            self._series = _lib.Series(engine.ctx, self.ntemps * self.nwalkers, self.ndim, counts, cap_hint=int(cap_hint))
+            self._dens = _lib.Series(engine.ctx, self.ntemps * self.nwalkers, 2, counts, cap_hint=int(cap_hint))
 
     def _evaluate(self, q):
         from . import _lib
@@ -371,6 +586,12 @@ class DeviceTemperedSampler(_Ladder):
 
         ctx.sampler_policy(0)   # plain launches: the overlapped hand-over is part of the fused proposal
         ctx.tempered_begin(self.betas, coords, ll, lpr, self.chunk)
+        if store and self._series is not None:
+            try:
+                ctx.tempered_attach_series(self._series, self._dens, len(self._chain))   # (rows a consumer never saw are overwritten)
+            except Exception:
+                ctx.tempered_end()
+                raise
         draws = None if self.rng_mode == 'device' else (self._draw_members, self._draw_swaps)
         with closing(_pump(iterations, self.chunk, draws, enqueue, ctx.tempered_collect, ctx.tempered_end)) as chunks:
             for mm, (chain, llc, lprc, nacc, nswap, worst) in chunks:

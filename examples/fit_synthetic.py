@@ -14,6 +14,8 @@ With ``--tempered T [--beta-min B]`` the sampler is a ladder of T ensembles (mcm
 burn-in, reset, production; the swap fractions and the cold rung's summary are printed.  ``--evidence`` adds the cold
 rung's autocorrelation time and ln Z by thermodynamic integration and the stepping stone (section 18), from the rows the
 run kept on the GPU with ``--autocorr device``; an evidence run wants a much smaller ``--beta-min`` than the default.
+``--adaptive N`` first moves the rungs for N iterations until adjacent pairs swap at equal rates (section 19), prints the
+ladder before and after with the swap fractions, freezes it and goes on as above.
 """
 import argparse
 import os
@@ -40,6 +42,8 @@ def main():
     ap.add_argument('--tempered', type=int, default=0, metavar='T',
                     help='parallel tempering: a ladder of T ensembles, geometric from beta = 1 down to --beta-min (0: off)')
     ap.add_argument('--beta-min', type=float, default=0.02, help='the hottest rung of --tempered')
+    ap.add_argument('--adaptive', type=int, default=0, metavar='N',
+                    help='with --tempered: N adaptive iterations first (the rungs move towards equal swap rates), then the ladder is frozen')
     ap.add_argument('--evidence', action='store_true',
                     help="with --tempered: print the cold rung's tau and ln Z +- mc_error (ladder ladder_error)")
     args = ap.parse_args()
@@ -129,10 +133,17 @@ def tempered_run(args, eng, p0, truth, t2):
     from mcmc_spec_amd import summary
     from mcmc_spec_amd.tempered import DeviceTemperedSampler
     sampler = DeviceTemperedSampler(len(p0), 6, eng, ntemps=args.tempered, beta_min=args.beta_min, seed=args.seed, chunk=50, rng='device',
-                                    autocorr=args.autocorr, cap_hint=max(args.nburn, args.nsteps))
-    state = sampler.run_mcmc(p0, args.nburn)
+                                    autocorr=args.autocorr, cap_hint=max(args.nburn, args.nsteps), adaptive=args.adaptive > 0,
+                                    adaptation_lag=max(args.adaptive / 2.0, 1.0), adaptation_time=10.0)
+    if args.adaptive > 0:
+        print('ladder before        :', np.round(sampler.betas, 4))
+        p0 = sampler.run_mcmc(p0, args.adaptive, store=False)
+        print('swap fractions while the ladder moved ({} iterations):'.format(args.adaptive), np.round(sampler.swap_fraction, 3))
+        print('ladder after, frozen :', np.round(sampler.betas, 4), '({} steps skipped)'.format(sampler.ladder_skipped))
+        sampler.reset()
+    state = sampler.run_mcmc(p0, args.nburn, adapt=False)
     sampler.reset()
-    sampler.run_mcmc(state, args.nsteps)
+    sampler.run_mcmc(state, args.nsteps, adapt=False)
     print('tempered sampler: {} rungs x {} walkers, betas {}, {} + {} iterations in {:.2f} s'.format(
         sampler.ntemps, len(p0), np.round(sampler.betas, 4), args.nburn, sampler.iteration, time.time() - t2))
     print('acceptance per rung :', np.round(sampler.acceptance_fraction.mean(axis=1), 3))

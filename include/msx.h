@@ -429,6 +429,33 @@ int msx_tempered_collect(msx_ctx *ctx, int32_t slot, double *chain, double *ll_c
 int msx_tempered_end(msx_ctx *ctx, double *coords, double *ll, double *lpr);
 /* (the ladder's device series: msx_series_attach_tempered, with the series below)                                       */
 
+/* ---- adaptive ladders (mcmc_spec_amd.tempered.ladder_step is the definition) --------------------
+ * msx_ladder_adapt, once between msx_tempered_begin and the run's first enqueue, makes the run adaptive from k0, the
+ * adaptive iterations done before it: the ladder lives in device memory, every iteration's moves and sweep read it there
+ * (db = beta[t-1] - beta[t] formed from it), and after each sweep a one-workgroup launch applies one ladder step with the
+ * swaps that iteration accepted:  r = counts / nw;  kappa = (lag / (k + lag)) / time;  Ti = 1 / beta;  the gap
+ * g[p] = Ti[p] - Ti[p-1] of each free rung p = 1..T-2 is scaled by ladder_exp(kappa * (r[p-1] - r[p])), the hottest gap kept;
+ * c = the running sum of g in index order;  beta'[p] = 1 / (Ti[0] + (Ti[T-1] - Ti[0]) * (c[p] / c[T-1])).  Both ends stay;
+ * ntemps <= 2 moves nothing; a result that is not finite or not strictly descending is dropped and counted as skipped.
+ * float64 + - * / without contraction; ladder_exp is the degree-12 Taylor polynomial in x / 8 squared three times, never a
+ * library's exp: the host definition, msx_ladder_step and the kernel give the same bits.  Everything else about the run is
+ * msx_tempered_*'s above, unchanged.  MSX_ERR_STATE: no run, after the first enqueue, twice.  MSX_ERR_INVALID: lag not
+ * finite or <= 0, time not finite or < 1 (the bound keeps |kappa (r - r')| <= 1), k0 < 0.                                */
+int msx_ladder_adapt(msx_ctx *ctx, double lag, double time, int64_t k0);
+/* the ladders [nsteps][ntemps] that the iterations of the chunk LAST COLLECTED from `slot` ran with, until the slot is
+ * enqueued again (MSX_ERR_STATE before a collect and while a chunk is in the slot).  A fixed run: the begin ladder in every
+ * row.                                                                                                                   */
+int msx_ladder_betas(msx_ctx *ctx, int32_t slot, double *out);
+/* the run's current ladder [ntemps], behind everything queued: waits for the compute stream.  k: adaptive iterations done
+ * (k0 + those queued); skipped: ladder steps skipped in this run; either may be NULL.  A fixed run: the begin ladder, 0, 0. */
+int msx_ladder_current(msx_ctx *ctx, double *betas, int64_t *k, int64_t *skipped);
+/* one ladder step ON THE HOST, through the inline functions the kernel calls: needs no context and no GPU.  counts
+ * [ntemps-1]: the iteration's swaps, pair p = rungs (p + 1, p); betas_out [ntemps]; *skipped 0 or 1 (may be NULL).
+ * MSX_ERR_INVALID: ntemps outside 1..MSX_MAX_GROUP, nw < 1, k < 0, lag / time as above.  betas is taken as strictly
+ * descending and > 0.                                                                                                    */
+int msx_ladder_step(int32_t ntemps, const double *betas, const int64_t *counts, int64_t nw, int64_t k, double lag, double time,
+                    double *betas_out, int32_t *skipped);
+
 /* ---- A4-A6: make_composite (mft6.py:651-831, plot=False) -------------------------------------- */
 /* teff/logg/rad are [nspec]; use_distance = 0 mirrors `distance=False` (mft6.py:701-703).         */
 /* spec_out [win_n], contrast_out [n_contrast], phot_out [n_phot] (unreddened magnitudes).         */

@@ -156,6 +156,10 @@ def load():
                                         C.c_int32] + [C.POINTER(C.c_int32)] * 5 + [_dp, _dp, _dp, _dp]),
         'msx_tempered_collect': (C.c_int, [vp, C.c_int32, _dp, _dp, _dp, _ip, _ip, C.POINTER(C.c_int32)]),
         'msx_tempered_end': (C.c_int, [vp, _dp, _dp, _dp]),
+        'msx_ladder_adapt': (C.c_int, [vp, C.c_double, C.c_double, C.c_int64]),
+        'msx_ladder_betas': (C.c_int, [vp, C.c_int32, _dp]),
+        'msx_ladder_current': (C.c_int, [vp, _dp, _ip, _ip]),
+        'msx_ladder_step': (C.c_int, [C.c_int32, _dp, _ip, C.c_int64, C.c_int64, C.c_double, C.c_double, _dp, C.POINTER(C.c_int32)]),
         'msx_make_composite': (C.c_int, [vp, _dp, _dp, _dp, C.c_int32, C.c_double, _dp, _dp, _dp,
                                          C.POINTER(C.c_int32)]),
         'msx_comm_unique_id': (C.c_int, [vp, C.POINTER(C.c_uint8)]),
@@ -235,7 +239,8 @@ EXPORTED = ['msx_create', 'msx_destroy', 'msx_last_error', 'msx_device_info', 'm
             'msx_sampler_enqueue_moves', 'msx_sampler_enqueue_moves_drawn', 'msx_sampler_draw_moves',
             'msx_group_sampler_enqueue_moves', 'msx_group_sampler_enqueue_moves_drawn',
             'msx_tempered_begin', 'msx_tempered_enqueue', 'msx_tempered_enqueue_drawn', 'msx_tempered_draw', 'msx_tempered_collect',
-            'msx_tempered_end', 'msx_series_attach_tempered', 'msx_series_evidence']
+            'msx_tempered_end', 'msx_series_attach_tempered', 'msx_series_evidence', 'msx_ladder_adapt', 'msx_ladder_betas',
+            'msx_ladder_current', 'msx_ladder_step']
 
 
 def as_f64(a):
@@ -775,6 +780,23 @@ class Context:
         self.check(self.lib.msx_tempered_end(self.h, dptr(coords), dptr(ll), dptr(lpr)))
         return coords, ll, lpr
 
+    def tempered_adapt(self, lag, time, k0):
+        """Make the run begun by tempered_begin adaptive from ``k0`` adaptive iterations done (msx_ladder_adapt; DESIGN.md
+        section 19): once, before the first enqueue."""
+        self.check(self.lib.msx_ladder_adapt(self.h, float(lag), float(time), int(k0)))
+
+    def tempered_betas(self, slot, nsteps):
+        """(nsteps, T): the ladders the iterations of the chunk last collected from ``slot`` ran with (msx_ladder_betas)."""
+        out = np.empty((int(nsteps), self._tmp_shape[0]))
+        self.check(self.lib.msx_ladder_betas(self.h, int(slot), dptr(out)))
+        return out
+
+    def tempered_ladder(self):
+        """(betas (T,), k, skipped): the run's ladder behind everything queued (msx_ladder_current; it waits for the GPU)."""
+        betas, k, skipped = np.empty(self._tmp_shape[0]), np.zeros(1, dtype=np.int64), np.zeros(1, dtype=np.int64)
+        self.check(self.lib.msx_ladder_current(self.h, dptr(betas), iptr(k), iptr(skipped)))
+        return betas, int(k[0]), int(skipped[0])
+
     def tempered_attach_series(self, chain, dens, at_row):
         """Append every chunk of the run begun by tempered_begin to the series ``chain`` (T members of nw walkers, ndim) and
         ``dens`` (the same members, ndim 2: ll, lpr) from row ``at_row`` on (msx_series_attach_tempered); either may be None."""
@@ -1178,3 +1200,17 @@ def _sampler_end(owner, fn, want_state):
     coords, logp = np.empty((n, ndim)), np.empty(n)
     owner.check(fn(owner.h, dptr(coords), dptr(logp)))
     return coords, logp
+
+
+def ladder_step(betas, counts, nw, k, lag, time):
+    """``(betas', skipped)`` of one ladder step through the library's host entry (msx_ladder_step): the C text the adapt kernel
+    runs, with no context and no GPU.  ``mcmc_spec_amd.tempered.ladder_step`` is the definition it must equal bit for bit."""
+    betas = as_f64(betas).reshape(-1)
+    counts = np.ascontiguousarray(counts, dtype=np.int64).reshape(-1)
+    if len(counts) != max(len(betas) - 1, 0):
+        raise ValueError('ladder_step: one count per adjacent pair')
+    out, skipped = np.empty(len(betas)), C.c_int32(0)
+    rc = load().msx_ladder_step(len(betas), dptr(betas), iptr(counts), int(nw), int(k), float(lag), float(time), dptr(out), C.byref(skipped))
+    if rc != MSX_OK:
+        raise ValueError('msx_ladder_step refused its arguments (code {})'.format(rc))
+    return out, int(skipped.value)

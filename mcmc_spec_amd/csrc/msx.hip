@@ -3673,6 +3673,14 @@ struct TemperedRun {
     struct msx_series *s_chain = nullptr, *s_dens = nullptr;
     int64_t series_row = 0;
     double beta[MSX_MAX_GROUP], db[MSX_MAX_GROUP];
+    // an adaptive run (msx_ladder_adapt): the ladder, the sweep's counters at the previous iteration's
+    // end and (k, skipped) live in device memory, and every chunk carries beta_chain [st][T], the ladder each iteration ran with
+    bool adaptive = false;
+    double lag = 0.0, time = 0.0;
+    char *d_adapt = nullptr;
+    double *d_beta = nullptr;
+    unsigned long long *d_prev = nullptr;
+    long long *d_kstate = nullptr;
     char *d_state = nullptr;
     double *d_coords = nullptr, *d_ll = nullptr, *d_lpr = nullptr, *d_q = nullptr, *d_new_lpr = nullptr, *d_new_ll = nullptr;
     int64_t *d_nacc = nullptr;
@@ -3683,18 +3691,23 @@ struct TemperedRun {
         char *d_in = nullptr, *d_out = nullptr, *h_in = nullptr, *h_out = nullptr;
         hipEvent_t in_ready = nullptr, kernels_done = nullptr, out_ready = nullptr;
         int64_t nsteps = 0;
-        bool busy = false;
+        bool busy = false, collected = false;   // collected: h_out holds the last collected chunk (msx_ladder_betas)
     } slot[2];
     // a chunk of st iterations in its slot, laid out for its own length:
     //   in  [g | fac | logu  (st 2 T ns doubles each) | swap_logu (st (T-1) nw doubles) | sidx | cidx | c1 | c2 (int32) | kind (st T)]
-    //   out [chain st T nw ndim | ll st T nw | lpr st T nw | naccept T nw (int64) | nswap MSX_MAX_GROUP (int64) | worst MSX_MAX_GROUP (int32)]
+    //   out [chain st T nw ndim | ll st T nw | lpr st T nw | naccept T nw (int64) | nswap MSX_MAX_GROUP (int64) | worst MSX_MAX_GROUP (int32)
+    //        | beta_chain st T (doubles): an adaptive run's only, though the slots always have room for it]
     int64_t entries(int64_t st) const { return st * 2 * T * ns; }
     size_t in_bytes(int64_t st) const {
         return sizeof(double) * (size_t)(3 * entries(st) + st * (T - 1) * nw) + sizeof(int32_t) * (size_t)(4 * entries(st) + st * T);
     }
     size_t out_bytes(int64_t st) const {
+        return fixed_out_bytes(st) + (adaptive ? sizeof(double) * (size_t)(st * T) : 0);
+    }
+    size_t fixed_out_bytes(int64_t st) const {
         return sizeof(double) * (size_t)(st * T * nw * (ndim + 2)) + sizeof(int64_t) * (size_t)(T * nw + MSX_MAX_GROUP) + sizeof(int32_t) * MSX_MAX_GROUP;
     }
+    size_t cap_out_bytes() const { return fixed_out_bytes(cap_steps) + sizeof(double) * (size_t)(cap_steps * T); }
 };
 
 struct TemperedIn {
@@ -3712,12 +3725,14 @@ struct TemperedOut {
     double *chain, *ll, *lpr;
     int64_t *nacc, *nswap;
     int32_t *worst;
+    double *betas;   // beta_chain [st][T]
 };
 static TemperedOut tempered_out(const TemperedRun *r, char *base, int64_t st) {
     const int64_t rows = st * r->T * r->nw;
     TemperedOut p;
     p.chain = (double *)base; p.ll = p.chain + rows * r->ndim; p.lpr = p.ll + rows;
     p.nacc = (int64_t *)(p.lpr + rows); p.nswap = p.nacc + r->T * r->nw; p.worst = (int32_t *)(p.nswap + MSX_MAX_GROUP);
+    p.betas = (double *)(p.worst + MSX_MAX_GROUP);
     return p;
 }
 
@@ -3738,6 +3753,7 @@ static void tempered_free(msx_ctx *c) {
         if (sl.out_ready) (void)hipEventDestroy(sl.out_ready);
     }
     if (r->d_state) (void)hipFree(r->d_state);
+    if (r->d_adapt) (void)hipFree(r->d_adapt);
     if (r->s_chain) r->s_chain->trun = nullptr;  // (the series outlive the run)
     if (r->s_dens) r->s_dens->trun = nullptr;
     if (r->copy) (void)hipStreamDestroy(r->copy);
@@ -3782,9 +3798,9 @@ int msx_tempered_begin(msx_ctx *c, int32_t ntemps, const double *betas, int64_t 
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&r->up, hipStreamNonBlocking);
     for (auto &sl : r->slot) {
         if (e == hipSuccess) e = hipMalloc((void **)&sl.d_in, r->in_bytes(r->cap_steps));
-        if (e == hipSuccess) e = hipMalloc((void **)&sl.d_out, r->out_bytes(r->cap_steps));
+        if (e == hipSuccess) e = hipMalloc((void **)&sl.d_out, r->cap_out_bytes());
         if (e == hipSuccess) e = hipHostMalloc((void **)&sl.h_in, r->in_bytes(r->cap_steps), hipHostMallocDefault);
-        if (e == hipSuccess) e = hipHostMalloc((void **)&sl.h_out, r->out_bytes(r->cap_steps), hipHostMallocDefault);
+        if (e == hipSuccess) e = hipHostMalloc((void **)&sl.h_out, r->cap_out_bytes(), hipHostMallocDefault);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.in_ready, hipEventDisableTiming);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.kernels_done, hipEventDisableTiming);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.out_ready, hipEventDisableTiming);
@@ -3803,6 +3819,102 @@ int msx_tempered_begin(msx_ctx *c, int32_t ntemps, const double *betas, int64_t 
         tempered_free(c);
         return fail(c, MSX_ERR_HIP, std::string("msx_tempered_begin: ") + hipGetErrorString(e));
     }
+    return MSX_OK;
+}
+
+// Makes the run begun by msx_tempered_begin adaptive from k0: the ladder goes to device memory, where
+// the step and sweep instantiations read it and tempered_adapt_kernel moves it after every iteration's sweep.
+int msx_ladder_adapt(msx_ctx *c, double lag, double time, int64_t k0) {
+    if (!c) return MSX_ERR_INVALID;
+    TemperedRun *r = c->tmp;
+    if (!r) return fail(c, MSX_ERR_STATE, "msx_ladder_adapt: call msx_tempered_begin first");
+    if (r->enqueued || r->adaptive)
+        return fail(c, MSX_ERR_STATE, "msx_ladder_adapt: call once, between msx_tempered_begin and the run's first enqueue");
+    if (!std::isfinite(lag) || !(lag > 0.0) || !std::isfinite(time) || !(time >= 1.0) || k0 < 0)
+        return fail(c, MSX_ERR_INVALID, "msx_ladder_adapt: lag must be finite and > 0, time finite and >= 1, k0 >= 0");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t bytes = sizeof(double) * MSX_MAX_GROUP + sizeof(unsigned long long) * MSX_MAX_GROUP + sizeof(long long) * 2;
+    hipError_t e = hipMalloc((void **)&r->d_adapt, bytes);
+    if (e == hipSuccess) e = hipMemsetAsync(r->d_adapt, 0, bytes, c->stream);
+    if (e == hipSuccess) {
+        r->d_beta = (double *)r->d_adapt; r->d_prev = (unsigned long long *)(r->d_beta + MSX_MAX_GROUP);
+        r->d_kstate = (long long *)(r->d_prev + MSX_MAX_GROUP);
+        e = hipMemcpyAsync(r->d_beta, r->beta, sizeof(double) * (size_t)r->T, hipMemcpyHostToDevice, c->stream);
+    }
+    const long long k = (long long)k0;
+    if (e == hipSuccess) e = hipMemcpyAsync(r->d_kstate, &k, sizeof(k), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        if (r->d_adapt) (void)hipFree(r->d_adapt);
+        r->d_adapt = nullptr;
+        return fail(c, MSX_ERR_HIP, std::string("msx_ladder_adapt: ") + hipGetErrorString(e));
+    }
+    r->adaptive = true; r->lag = lag; r->time = time;
+    return MSX_OK;
+}
+
+// The current ladder of the run, behind everything queued (it waits for the compute stream); k: the adaptive iterations done,
+// skipped: the ladder steps skipped in this run.  A fixed run: the begin ladder, 0, 0.
+int msx_ladder_current(msx_ctx *c, double *betas, int64_t *k, int64_t *skipped) {
+    if (!c) return MSX_ERR_INVALID;
+    TemperedRun *r = c->tmp;
+    if (!r) return fail(c, MSX_ERR_STATE, "msx_ladder_current: call msx_tempered_begin first");
+    if (!betas) return fail(c, MSX_ERR_INVALID, "msx_ladder_current: bad arguments");
+    long long st[2] = {0, 0};
+    if (r->adaptive) {
+        hipError_t e = hipSetDevice(c->device);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e == hipSuccess) e = hipMemcpy(betas, r->d_beta, sizeof(double) * (size_t)r->T, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(st, r->d_kstate, sizeof(st), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return fail(c, MSX_ERR_HIP, std::string("msx_ladder_current: ") + hipGetErrorString(e));
+    } else {
+        memcpy(betas, r->beta, sizeof(double) * (size_t)r->T);
+    }
+    if (k) *k = (int64_t)st[0];
+    if (skipped) *skipped = (int64_t)st[1];
+    return MSX_OK;
+}
+
+// The ladders the last collected chunk of `slot` ran with, [nsteps][T], until the slot is enqueued again.  A fixed run: the
+// begin ladder in every row.
+int msx_ladder_betas(msx_ctx *c, int32_t slot, double *out) {
+    if (!c) return MSX_ERR_INVALID;
+    TemperedRun *r = c->tmp;
+    if (!r) return fail(c, MSX_ERR_STATE, "msx_ladder_betas: call msx_tempered_begin first");
+    if (slot < 0 || slot > 1 || !out) return fail(c, MSX_ERR_INVALID, "msx_ladder_betas: bad arguments");
+    const TemperedRun::Slot &sl = r->slot[slot];
+    if (sl.busy || !sl.collected) return fail(c, MSX_ERR_STATE, "msx_ladder_betas: no collected chunk in this slot");
+    if (r->adaptive) {
+        memcpy(out, tempered_out(r, sl.h_out, sl.nsteps).betas, sizeof(double) * (size_t)(sl.nsteps * r->T));
+    } else {
+        for (int64_t st = 0; st < sl.nsteps; ++st) memcpy(out + st * r->T, r->beta, sizeof(double) * (size_t)r->T);
+    }
+    return MSX_OK;
+}
+
+// One ladder step on the host: the inline pieces tempered_adapt_kernel calls (tempered_kernels.h), in its order.  No
+// context, no GPU.  betas (T) strictly descending, counts (T - 1) the iteration's swaps; betas_out (T); *skipped 0 or 1.
+int msx_ladder_step(int32_t ntemps, const double *betas, const int64_t *counts, int64_t nw, int64_t k, double lag, double time,
+                    double *betas_out, int32_t *skipped) {
+    if (ntemps < 1 || ntemps > MSX_MAX_GROUP || !betas || !betas_out || (!counts && ntemps > 1) || nw < 1 || k < 0) return MSX_ERR_INVALID;
+    if (!std::isfinite(lag) || !(lag > 0.0) || !std::isfinite(time) || !(time >= 1.0)) return MSX_ERR_INVALID;
+    const int T = ntemps;
+    double Ti[MSX_MAX_GROUP], rr[MSX_MAX_GROUP], g[MSX_MAX_GROUP], cs[MSX_MAX_GROUP], nb[MSX_MAX_GROUP];
+    for (int t = 0; t < T; ++t) betas_out[t] = nb[t] = betas[t];
+    if (skipped) *skipped = 0;
+    if (T <= 2) return MSX_OK;
+    for (int t = 0; t < T; ++t) Ti[t] = 1.0 / betas[t];
+    for (int t = 0; t < T - 1; ++t) rr[t] = (double)counts[t] / (double)nw;
+    const double kappa = ladder_kappa((double)k, lag, time);
+    for (int p = 1; p < T; ++p) g[p] = ladder_gap(p, T, Ti, rr, kappa);
+    ladder_sums(T, g, cs);
+    const double span = Ti[T - 1] - Ti[0];
+    for (int p = 1; p < T - 1; ++p) nb[p] = ladder_place(Ti[0], span, cs[p], cs[T - 1]);
+    if (!ladder_valid(T, nb)) {
+        if (skipped) *skipped = 1;
+        return MSX_OK;
+    }
+    for (int t = 0; t < T; ++t) betas_out[t] = nb[t];
     return MSX_OK;
 }
 
@@ -3940,6 +4052,10 @@ static int tempered_enqueue(msx_ctx *c, const char *who, int32_t slot, int64_t n
     A.coords = r->d_coords; A.ll = r->d_ll; A.lpr = r->d_lpr; A.q = r->d_q; A.new_lpr = r->d_new_lpr; A.new_ll = r->d_new_ll;
     A.st_lpr = r->d_st_lpr; A.st_ll = r->d_st_ll; A.nacc = r->d_nacc; A.ndim = ndim; A.nw = (int32_t)nw; A.ns = (int32_t)ns; A.worst = out.worst;
     memcpy(A.beta, r->beta, sizeof(A.beta));
+    TemperedAdaptArgs D;
+    memset(&D, 0, sizeof(D));
+    D.beta = r->d_beta; D.nswap = r->d_nswap; D.prev = r->d_prev; D.state = r->d_kstate; D.nw = (double)nw; D.lag = r->lag; D.time = r->time;
+    D.ntemps = T;
     TemperedSwapArgs W;
     memset(&W, 0, sizeof(W));
     W.coords = r->d_coords; W.ll = r->d_ll; W.lpr = r->d_lpr; W.nswap = r->d_nswap; W.ntemps = T; W.nw = (int32_t)nw; W.ndim = ndim;
@@ -3953,7 +4069,8 @@ static int tempered_enqueue(msx_ctx *c, const char *who, int32_t slot, int64_t n
             A.a_on = k > 0; A.p_on = k < 2;
             if (A.a_on) A.a = half_arrays(2 * st + k - 1);
             if (A.p_on) A.p = half_arrays(2 * st + k);
-            hipLaunchKernelGGL(tempered_step_kernel, dim3((unsigned)T), dim3(256), 0, s, A);
+            if (r->adaptive) hipLaunchKernelGGL(tempered_step_adaptive_kernel, dim3((unsigned)T), dim3(256), 0, s, A, (const double *)r->d_beta);
+            else hipLaunchKernelGGL(tempered_step_kernel, dim3((unsigned)T), dim3(256), 0, s, A);
             e = hipGetLastError();
             if (e != hipSuccess || !A.p_on) continue;
             rc = msx_logprob_batch_dev(c, MSX_MODE_LOGPRIOR, r->d_q, H, ndim, r->d_new_lpr, r->d_st_lpr, s, 0);
@@ -3962,7 +4079,17 @@ static int tempered_enqueue(msx_ctx *c, const char *who, int32_t slot, int64_t n
         if (e != hipSuccess || rc != MSX_OK) break;
         W.logu = in.swap_logu + st * (T - 1) * nw;
         W.chain_row = out.chain + st * T * nw * ndim; W.ll_row = out.ll + st * T * nw; W.lpr_row = out.lpr + st * T * nw;
-        hipLaunchKernelGGL(tempered_swap_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s, W);
+        if (!r->adaptive) {
+            hipLaunchKernelGGL(tempered_swap_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s, W);
+            e = hipGetLastError();
+            continue;
+        }
+        hipLaunchKernelGGL(tempered_swap_adaptive_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s, W, (const double *)r->d_beta);
+        e = hipGetLastError();
+        if (e != hipSuccess) break;
+        // the iteration's counts are complete once the sweep's launch has finished: a launch of its own, in stream order
+        D.beta_row = out.betas + st * T;
+        hipLaunchKernelGGL(tempered_adapt_kernel, dim3(1), dim3(64), 0, s, D);
         e = hipGetLastError();
     }
     // the chunk's rows into the attached series, before kernels_done: a collected chunk's rows are in place
@@ -3981,6 +4108,7 @@ static int tempered_enqueue(msx_ctx *c, const char *who, int32_t slot, int64_t n
     }
     sl.nsteps = nsteps;
     sl.busy = true;
+    sl.collected = false;
     return MSX_OK;
 }
 
@@ -4062,6 +4190,7 @@ int msx_tempered_collect(msx_ctx *c, int32_t slot, double *chain, double *ll_cha
     if (r->T > 1) memcpy(nswap, o.nswap, sizeof(int64_t) * (r->T - 1));
     memcpy(worst, o.worst, sizeof(int32_t) * r->T);
     sl.busy = false;
+    sl.collected = true;
     return MSX_OK;
 }
 

@@ -196,7 +196,7 @@ def logposterior(p0, fr, nspec, ndust, data, err, broadening, r, specs, ctm, ptm
 
 
 def device_sampler(nwalkers, ndim, args, kwargs=None, a=None, seed=None, chunk=64, moves=None, rng='host', betas=None,
-                   autocorr='host'):
+                   autocorr='host', adaptive=False, adaptation_lag=10000.0, adaptation_time=100.0):
     """The sampler line of ``run_emcee`` -- ``emcee.EnsembleSampler(nwalkers, ndim, logposterior, args=[...],
     kwargs={...})``, mft6.py:1490-1492 -- with the walker state RESIDENT on the GPU: ``args`` / ``kwargs`` are exactly
     what that line passes for ``logposterior`` (everything after ``p0``); the problem they describe is staged once and
@@ -207,7 +207,9 @@ def device_sampler(nwalkers, ndim, args, kwargs=None, a=None, seed=None, chunk=6
     for a bimodal posterior); ``rng='device'`` draws the randomness on the GPU (``DeviceEnsembleSampler``).  ``betas``: a
     temperature ladder (``mcmc_spec_amd.tempered``: e.g. ``default_betas(8, 0.02)``) -- the sampler is then a
     ``DeviceTemperedSampler`` of ``len(betas)`` rungs of ``nwalkers`` on the same engine, whose rung 0 is the posterior
-    (``a=`` goes as ``moves=StretchMove(a)``).  ``autocorr='device'`` is passed to either sampler: the stored chain is
+    (``a=`` goes as ``moves=StretchMove(a)``); ``adaptive``, ``adaptation_lag`` and ``adaptation_time`` are passed to it
+    (the rungs move during a burn-in until adjacent pairs swap at equal rates; ``adapt=False`` on a
+    later run freezes them); without ``betas`` an adaptive sampler is refused.  ``autocorr='device'`` is passed to either sampler: the stored chain is
     kept on the GPU as well, and ``get_autocorr_time`` / ``get_summary`` / ``get_products`` (a ladder's ``log_evidence``
     too) work there."""
     from .sampler import DeviceEnsembleSampler
@@ -240,7 +242,10 @@ def device_sampler(nwalkers, ndim, args, kwargs=None, a=None, seed=None, chunk=6
         if a is not None and moves is not None:
             raise ValueError('a= and moves= exclude each other: give the stretch scale as moves.StretchMove(a)')
         return DeviceTemperedSampler(nwalkers, ndim, eng, betas=betas, seed=seed, chunk=chunk, rng=rng,
-                                     moves=StretchMove(a) if a is not None else moves, autocorr=autocorr)
+                                     moves=StretchMove(a) if a is not None else moves, autocorr=autocorr, adaptive=adaptive,
+                                     adaptation_lag=adaptation_lag, adaptation_time=adaptation_time)
+    if adaptive:
+        raise ValueError('adaptive=True needs a temperature ladder: give betas=')
     return DeviceEnsembleSampler(nwalkers, ndim, eng, mode='logposterior', a=a, seed=seed, chunk=chunk, moves=moves, rng=rng,
                                  autocorr=autocorr)
 

@@ -37,6 +37,16 @@ knows nothing of a burn-in left in, and underestimates when a block is shorter t
 ``ladder_error`` is ``|ln Z - ln Z(rungs [::2], the last rung kept)|``, the estimate's change when every other rung is
 dropped.  ``TemperedSampler``'s NumPy (``host_evidence``) is the definition; the device computes the same sums in a fixed
 order of its own (``msx_series_evidence``; tests/evidence_numpy.py restates that order).
+
+Adaptive ladders.  ``adaptive=True`` on either sampler: iteration i is the iteration above on the
+CURRENT ladder (``db`` formed from it), and after its sweep ``ladder_step`` moves the rungs between the two pinned ends with
+the swaps this iteration accepted -- the temperature dynamics of Vousden, Farr & Mandel (2016), renormalised onto the
+ladder's span -- until adjacent pairs swap at equal rates.  ``adaptation_lag`` and ``adaptation_time`` are ptemcee's; the
+step decays as ``lag / (k + lag)`` with k = ``_adapted``, the adaptive iterations done, which ``reset()`` leaves alone.
+``run_mcmc(state, n, adapt=False)`` is the freeze call for the production run.  ``betas`` is the ladder after the last
+iteration, ``get_betas()`` the ladder each stored iteration ran WITH, ``ladder_skipped`` the steps dropped because two rungs
+would have met.  ``log_evidence`` refuses rows of a moving ladder.  ``ladder_step`` and ``ladder_exp`` are float64
+``+ - * /`` only: the host loop, msx_ladder_step and the device's tempered_adapt_kernel give the same bits.
 """
 from __future__ import annotations
 
@@ -77,6 +87,76 @@ def resolve_betas(ntemps, betas, beta_min=0.02):
     if np.any(np.diff(b) >= 0.0):
         raise ValueError('betas must be strictly descending')
     return b
+
+
+_EXP_COEF = [1.0]
+for _k in range(1, 13):
+    _EXP_COEF.append(_EXP_COEF[-1] * _k)        # k! (exact in float64)
+_EXP_COEF = [1.0 / f for f in _EXP_COEF]        # c[k] = 1.0 / k!
+
+
+def ladder_exp(x):
+    """The adaptive ladder's exponential for |x| <= 1, in float64 ``+ * /`` only, so NumPy, host C and
+    the device give the same bits: ``y = x * 0.125``, the degree-12 Taylor polynomial in y by Horner from the top, squared
+    three times.  Within 7 ulp of ``np.exp`` on [-1, 1]; exactly 1.0 at 0.  A scalar or an array."""
+    y = np.asarray(x, dtype=np.float64) * 0.125
+    p = np.full(y.shape, _EXP_COEF[12])
+    for k in range(11, -1, -1):
+        p = p * y
+        p = p + _EXP_COEF[k]
+    for _ in range(3):
+        p = p * p
+    return p if p.ndim else float(p)
+
+
+def check_adaptation(lag, time):
+    """(lag, time) as floats; ValueError unless lag is finite and > 0 and time is finite and >= 1 (which keeps |dS| <= 1)."""
+    lag, time = float(lag), float(time)
+    if not np.isfinite(lag) or lag <= 0.0:
+        raise ValueError('adaptation_lag must be finite and > 0')
+    if not np.isfinite(time) or time < 1.0:
+        raise ValueError('adaptation_time must be finite and >= 1')
+    return lag, time
+
+
+def ladder_step(betas, counts, nw, k, lag, time):
+    """One step of the temperature dynamics (Vousden, Farr & Mandel 2016): ``(betas', skipped)``.
+
+    ``betas`` (T,) strictly descending; ``counts`` (T-1,) the swaps accepted in THIS iteration, pair p = rungs (p + 1, p);
+    ``k`` the adaptive iterations done before this one.  With ``r = counts / nw``, ``kappa = (lag / (k + lag)) / time`` and
+    ``Ti = 1 / betas``, the gap ``g[p] = Ti[p] - Ti[p-1]`` of every free rung p = 1..T-2 is scaled by
+    ``ladder_exp(kappa * (r[p-1] - r[p]))`` -- the hottest gap is kept -- and the running sum c of the gaps is renormalised
+    onto the ladder's span: ``betas'[p] = 1 / (Ti[0] + (Ti[T-1] - Ti[0]) * (c[p] / c[T-1]))``.  Both ends are the input's.
+    T <= 2: unchanged.  A result that is not finite or not strictly descending: the input, and skipped = 1.  float64
+    ``+ - * /`` in this order; msx_ladder_step and tempered_adapt_kernel reproduce the bits."""
+    lag, time = check_adaptation(lag, time)
+    b = np.array(betas, dtype=np.float64).reshape(-1)
+    T = len(b)
+    if T <= 2:
+        return b, 0
+    r = np.asarray(counts, dtype=np.float64).reshape(-1) / float(nw)
+    if r.shape != (T - 1,):
+        raise ValueError('counts: one per adjacent pair')
+    decay = lag / (float(k) + lag)
+    kappa = decay / time
+    Ti = 1.0 / b
+    g = np.empty(T)
+    g[0] = 0.0
+    g[1:] = Ti[1:] - Ti[:-1]
+    dS = kappa * (r[:-1] - r[1:])                 # dS[p - 1] for p = 1..T-2
+    g[1:T - 1] = g[1:T - 1] * ladder_exp(dS)
+    c = np.empty(T)
+    c[0] = 0.0
+    c[1] = g[1]
+    for p in range(2, T):                         # in index order
+        c[p] = c[p - 1] + g[p]
+    span = Ti[T - 1] - Ti[0]
+    out = b.copy()
+    with np.errstate(all='ignore'):
+        out[1:T - 1] = 1.0 / (Ti[0] + span * (c[1:T - 1] / c[T - 1]))
+    if not np.all(np.isfinite(out)) or np.any(out[1:] >= out[:-1]):
+        return b, 1
+    return out, 0
 
 
 def resolve_seeds(ntemps, seed, seeds):
@@ -330,6 +410,9 @@ class _Ladder:
         if method not in ('ti', 'ss'):
             raise ValueError("method must be 'ti' or 'ss'")
         T, betas, blocks = self.ntemps, self.betas, int(blocks)
+        if np.any(self.get_betas(discard=discard, thin=thin) != betas):
+            raise ValueError('log_evidence: the selected rows were not all run with the ladder self.betas (an adaptive run moved it): '
+                             'freeze the ladder (adapt=False) and discard= the adaptive rows')
         half = halved(T)
         if method == 'ti':
             mean, _ = self._evidence(discard, thin, None, blocks)
@@ -345,10 +428,14 @@ class _Ladder:
             ladder = float(abs(est[0] - coarse))
         return LogEvidence(float(est[0]), mc, ladder, mean[:, 0].copy())
 
-    def _init_ladder(self, nwalkers, ndim, ntemps, betas, beta_min, seed, seeds, moves):
-        self.betas = resolve_betas(ntemps, betas, beta_min)
+    def _init_ladder(self, nwalkers, ndim, ntemps, betas, beta_min, seed, seeds, moves, adaptive=False, adaptation_lag=10000.0,
+                     adaptation_time=100.0):
+        self.betas = resolve_betas(ntemps, betas, beta_min)   # the ladder after the last iteration (never changed in place)
         self.ntemps = len(self.betas)
-        self._db = self.betas[:-1] - self.betas[1:]           # formed once, in float64
+        self.adaptive = bool(adaptive)
+        self.adaptation_lag, self.adaptation_time = check_adaptation(adaptation_lag, adaptation_time)
+        self._adapted = 0          # k: adaptive iterations done (on the device: queued); reset() leaves it alone, as _drawn
+        self.ladder_skipped = 0    # ladder steps that would have collapsed the ladder and were skipped
         self.nwalkers, self.ndim = int(nwalkers), int(ndim)
         if self.nwalkers % 2 or self.nwalkers < 2:
             raise ValueError('a rung needs an even number of walkers')
@@ -364,7 +451,7 @@ class _Ladder:
 
     def reset(self):
         """Forget the stored chain and counts.  The streams' positions (and ``_drawn``) are left alone."""
-        self._chain, self._ll, self._lpr = [], [], []
+        self._chain, self._ll, self._lpr, self._betas_rows = [], [], [], []
         self._accepted = np.zeros((self.ntemps, self.nwalkers))
         self._nswap = np.zeros(max(self.ntemps - 1, 0), dtype=np.int64)
         self.iteration = 0
@@ -381,6 +468,13 @@ class _Ladder:
         """Rung t's chain (steps, nw, ndim) -- rung 0 is the posterior; ``t=None``: all rungs, (steps, T, nw, ndim).  flat:
         the steps and walkers merged."""
         return self._rows(self._chain, t, flat, thin, discard, (self.ndim,))
+
+    def get_betas(self, discard=0, thin=1):
+        """(steps, T): the ladder each stored iteration was run WITH (constant rows unless the run was adaptive)."""
+        return np.array(self._betas_rows, dtype=np.float64).reshape(-1, self.ntemps)[discard::thin]
+
+    def _adapting(self, adapt):
+        return self.adaptive if adapt is None else bool(adapt)
 
     def get_log_like(self, t=0, flat=False, thin=1, discard=0):
         return self._rows(self._ll, t, flat, thin, discard, ())
@@ -459,7 +553,7 @@ class TemperedSampler(_Ladder):
     ``DeviceTemperedSampler(rng='device')`` draws for itself."""
 
     def __init__(self, nwalkers, ndim, loglike_fn, logprior_fn=None, ntemps=None, betas=None, beta_min=0.02, seed=None, seeds=None,
-                 moves=None, draws=None):
+                 moves=None, draws=None, adaptive=False, adaptation_lag=10000.0, adaptation_time=100.0):
         if logprior_fn is None and hasattr(loglike_fn, 'ctx'):
             from . import _lib
             self.engine = loglike_fn   # (get_summary / get_products upload the host chain to its device)
@@ -467,7 +561,7 @@ class TemperedSampler(_Ladder):
             loglike_fn, logprior_fn = (lambda q: ctx.logprob_batch(q, _lib.MODE_LOGLIKE)), (lambda q: ctx.logprob_batch(q, _lib.MODE_LOGPRIOR))
         self.loglike_fn, self.logprior_fn = loglike_fn, logprior_fn
         self._draws = draws
-        self._init_ladder(nwalkers, ndim, ntemps, betas, beta_min, seed, seeds, moves)
+        self._init_ladder(nwalkers, ndim, ntemps, betas, beta_min, seed, seeds, moves, adaptive, adaptation_lag, adaptation_time)
 
     def _evaluate(self, q):
         """(lpr, ll) of the proposals q with the status rule."""
@@ -492,22 +586,32 @@ class TemperedSampler(_Ladder):
             return out
         return [r._draw_steps(m) for r in self._rungs], draw_swap_logu(self._swap_rng, m, self.ntemps, self.nwalkers)
 
-    def sample(self, initial_state, iterations=1, store=True):
+    def sample(self, initial_state, iterations=1, store=True, adapt=None):
         coords, ll, lpr = self._start(initial_state)
         T, ns = self.ntemps, self.nwalkers // 2
+        adapt = self._adapting(adapt)
         for _ in range(int(iterations)):
             members, swap_logu = self._draw_steps(1)
+            betas = self.betas
+            db = betas[:-1] - betas[1:]                       # in float64, from the ladder of this iteration
+            before = self._nswap.copy()
             accepted = np.zeros((T, self.nwalkers), dtype=bool)
             for h in (0, 1):
                 q = np.concatenate([_propose(coords[t], members[t], h) for t in range(T)])
                 lpr_q, ll_q = self._evaluate(q)
                 for t in range(T):
                     sl = slice(t * ns, (t + 1) * ns)
-                    _accept_rung(self.betas[t], coords[t], ll[t], lpr[t], accepted[t], members[t], h, q[sl], lpr_q[sl], ll_q[sl])
-            swap_sweep(self._db, coords, ll, lpr, np.asarray(swap_logu)[0], self._nswap)
+                    _accept_rung(betas[t], coords[t], ll[t], lpr[t], accepted[t], members[t], h, q[sl], lpr_q[sl], ll_q[sl])
+            swap_sweep(db, coords, ll, lpr, np.asarray(swap_logu)[0], self._nswap)
+            if adapt:
+                self.betas, skipped = ladder_step(betas, self._nswap - before, self.nwalkers, self._adapted, self.adaptation_lag,
+                                                  self.adaptation_time)
+                self._adapted += 1
+                self.ladder_skipped += skipped
             self._accepted += accepted
             self.iteration += 1
             if store:
+                self._betas_rows.append(betas)
                 self._chain.append(coords.copy())
                 self._ll.append(ll.copy())
                 self._lpr.append(lpr.copy())
@@ -527,6 +631,13 @@ class DeviceTemperedSampler(_Ladder):
     queued).  The chain is the one ``TemperedSampler(draws=lambda i, m: ctx.tempered_draw(seeds, moves, i, m, nw, ndim))``
     walks.
 
+    ``adaptive=True`` (the module docstring): the ladder lives on the device (``msx_ladder_adapt``) and a small kernel moves
+    it after every sweep.  ``_adapted`` follows ``_drawn``'s rule: it counts the adaptive iterations QUEUED, ``reset()``
+    leaves it alone, and after a run ends -- finished or left early -- ``betas`` is the device's ladder behind everything
+    queued (``msx_ladder_current``), so the next run, adaptive or frozen, starts from it; while a run goes ``betas`` is still
+    the ladder it began with.  A run that does not adapt calls none of the context's ``tempered_adapt`` / ``tempered_betas``
+    / ``tempered_ladder``.
+
     ``autocorr='device'`` (the other device samplers' option): the stored rows are kept on the device as well, in two
     ``_lib.Series`` of T members -- the coordinates, and (ll, lpr) -- that every ``sample(store=True)`` run appends to from
     row ``len(self._chain)`` on (``msx_series_attach_tempered``); ``get_autocorr_time``, ``get_summary``, ``get_products``,
@@ -535,7 +646,7 @@ class DeviceTemperedSampler(_Ladder):
     for bit, whatever ``autocorr`` is."""
 
     def __init__(self, nwalkers, ndim, engine, ntemps=None, betas=None, beta_min=0.02, seed=None, seeds=None, chunk=64, rng='host',
-                 moves=None, autocorr='host', cap_hint=0):
+                 moves=None, autocorr='host', cap_hint=0, adaptive=False, adaptation_lag=10000.0, adaptation_time=100.0):
         if rng not in ('host', 'device'):
             raise ValueError("rng must be 'host' or 'device'")
         if autocorr not in ('host', 'device'):
@@ -544,7 +655,7 @@ class DeviceTemperedSampler(_Ladder):
         self.autocorr = autocorr
         self.engine = engine
         self.chunk = int(chunk)
-        self._init_ladder(nwalkers, ndim, ntemps, betas, beta_min, seed, seeds, moves)
+        self._init_ladder(nwalkers, ndim, ntemps, betas, beta_min, seed, seeds, moves, adaptive, adaptation_lag, adaptation_time)
         if autocorr == 'device':
             from . import _lib
             counts = [self.nwalkers] * self.ntemps
@@ -569,15 +680,19 @@ class DeviceTemperedSampler(_Ladder):
     def _draw_swaps(self, m):
         return [draw_swap_logu(self._swap_rng, m, self.ntemps, self.nwalkers)]
 
-    def sample(self, initial_state, iterations=1, store=True):
+    def sample(self, initial_state, iterations=1, store=True, adapt=None):
         from .engine import _raise_for_status
         coords, ll, lpr = self._start(initial_state)
         if int(iterations) <= 0:
             return
         ctx = self.engine.ctx
-        base_acc, base_swap = self._accepted.copy(), self._nswap.copy()
+        adapt = self._adapting(adapt)
+        base_acc, base_swap, base_skipped = self._accepted.copy(), self._nswap.copy(), self.ladder_skipped
+        fixed = self.betas
 
         def enqueue(slot, m, arrays):
+            if adapt:
+                self._adapted += m
             if arrays is None:
                 ctx.tempered_enqueue_drawn(slot, m, self.seeds, self._moves, self._drawn)
                 self._drawn += m
@@ -592,9 +707,26 @@ class DeviceTemperedSampler(_Ladder):
             except Exception:
                 ctx.tempered_end()
                 raise
+        collect, end = ctx.tempered_collect, ctx.tempered_end
+        if adapt:   # (a fixed run calls none of the three)
+            try:
+                ctx.tempered_adapt(self.adaptation_lag, self.adaptation_time, self._adapted)
+            except Exception:
+                ctx.tempered_end()
+                raise
+
+            def collect(slot, m):
+                return ctx.tempered_collect(slot, m) + (ctx.tempered_betas(slot, m),)
+
+            def end():   # the device's ladder behind everything queued, whether the loop finished or was left
+                try:
+                    self.betas, _, skipped = ctx.tempered_ladder()
+                    self.ladder_skipped = base_skipped + skipped
+                finally:
+                    ctx.tempered_end()
         draws = None if self.rng_mode == 'device' else (self._draw_members, self._draw_swaps)
-        with closing(_pump(iterations, self.chunk, draws, enqueue, ctx.tempered_collect, ctx.tempered_end)) as chunks:
-            for mm, (chain, llc, lprc, nacc, nswap, worst) in chunks:
+        with closing(_pump(iterations, self.chunk, draws, enqueue, collect, end)) as chunks:
+            for mm, (chain, llc, lprc, nacc, nswap, worst, *rows) in chunks:
                 bad = np.nonzero(np.asarray(worst) > W_REJECT)[0]
                 if bad.size:
                     _raise_for_status(np.array([worst[bad[0]]]), chain[-1][int(bad[0])][:1])
@@ -603,6 +735,7 @@ class DeviceTemperedSampler(_Ladder):
                 for i in range(mm):
                     self.iteration += 1
                     if store:
+                        self._betas_rows.append(rows[0][i].copy() if rows else fixed)
                         self._chain.append(chain[i])
                         self._ll.append(llc[i])
                         self._lpr.append(lprc[i])

@@ -15,6 +15,15 @@ peaks, whose relative weight the stretch move alone leaves where the initial ens
 With --protocol DIR the targets are fitted the way the reference's driver fits one (run_group_protocol: burn-in, then
 production with every target's own convergence check every --nthin iterations; a converged target stops there) and
 each target's dumps and samples.txt go to DIR/target<k>/; with --device the checks run on the GPU (autocorr='device').
+
+With --tempered T every target gets a ladder of T rungs and ALL the ladders share every launch
+(tempered.DeviceGroupTemperedSampler with --device -- eight launches per iteration for all targets, the rows kept in one
+pair of device series -- or its host definition GroupTemperedSampler): the remedy for a posterior whose two modes (primary and
+secondary exchanged) differ in width.  --adaptive N first moves every target's ladder for N iterations until adjacent rungs
+swap at equal rates, then freezes it for the production run; --evidence prints each target's ln Z (thermodynamic
+integration) with its Monte-Carlo and ladder errors.
+
+    python examples/fit_target_group.py --targets 4 --nwalkers 32 --nsteps 200 --device --rng device --tempered 4 --adaptive 100 --evidence
 """
 import argparse
 import os
@@ -43,6 +52,44 @@ def print_products(prod, targets):
                                                    for j, nm in enumerate(['dKep', 'f_pri', 'f_sec'])))
 
 
+def run_tempered(args, group, p0s, seeds, moves, truths):
+    """Every target's ladder in one run: adapt (if asked), freeze, sample; rung 0 of target k is its posterior."""
+    from mcmc_spec_amd.tempered import DeviceGroupTemperedSampler, GroupTemperedSampler
+    K, T = args.targets, args.tempered
+    kw = dict(ntemps=T, beta_min=args.beta_min, seeds=seeds, moves=moves, adaptive=args.adaptive > 0, adaptation_lag=max(10.0, args.adaptive / 10.0),
+              adaptation_time=10.0)
+    if args.device:
+        sampler = DeviceGroupTemperedSampler(group, [args.nwalkers] * K, 6, rng=args.rng, autocorr='device', **kw)
+    else:
+        sampler = GroupTemperedSampler([args.nwalkers] * K, 6, group, **kw)
+    t0 = time.time()
+    state = p0s
+    if args.adaptive:
+        state = sampler.run_mcmc(state, args.adaptive)
+        sampler.reset()
+        for k in range(K):
+            print('target {}: ladder after {} adaptive iterations: {}'.format(k, args.adaptive, np.array2string(sampler.target(k).betas, precision=4)))
+    sampler.run_mcmc(state, args.nsteps, adapt=False)
+    dt = time.time() - t0
+    n = args.adaptive + args.nsteps
+    print('{} targets x {} rungs x {} walkers x {} iterations in {:.2f} s ({:.0f} evaluations/s)'.format(
+        K, T, args.nwalkers, n, dt, 2.0 * K * T * args.nwalkers * n / dt))
+    for k in range(K):
+        v = sampler.target(k)
+        flat = v.get_chain(0, discard=args.nsteps // 2, flat=True)
+        print('target {}: Teff {:.0f} / {:.0f} (truth {:.0f} / {:.0f}), acceptance per rung {}, swaps per pair {}'.format(
+            k, *np.median(flat[:, :2], axis=0), *truths[k][:2], np.array2string(v.acceptance_fraction.mean(axis=1), precision=2),
+            np.array2string(v.swap_fraction, precision=2)))
+        if args.device:
+            q = v.get_summary(0, discard=args.nsteps // 2)['quantiles']
+            print('          T1 {:.5g} / {:.5g} / {:.5g}   T2 {:.5g} / {:.5g} / {:.5g}   (16 / 50 / 84, selected on the GPU)'.format(*q[0], *q[1]))
+        if args.evidence:
+            ev = v.log_evidence(discard=args.nsteps // 2, blocks=min(8, max(1, args.nsteps // 2)))
+            print('          ln Z = {:.3f} +- {:.3f} (Monte Carlo) +- {:.3f} (ladder; beta_min = {})'.format(
+                ev.log_z, ev.mc_error, ev.ladder_error, args.beta_min))
+    return sampler
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--targets', type=int, default=4)
@@ -58,7 +105,15 @@ def main():
     ap.add_argument('--protocol', default=None, metavar='DIR', help="run the reference's driver per target (run_group_protocol)")
     ap.add_argument('--nburn', type=int, default=100)
     ap.add_argument('--nthin', type=int, default=50)
+    ap.add_argument('--tempered', type=int, default=0, metavar='T', help='a ladder of T rungs per target, all ladders in one run')
+    ap.add_argument('--beta-min', type=float, default=0.02, help='--tempered: the hottest rung (an evidence run wants it much smaller)')
+    ap.add_argument('--adaptive', type=int, default=0, metavar='N', help='--tempered: adapt every ladder for N iterations first, then freeze')
+    ap.add_argument('--evidence', action='store_true', help="--tempered: print every target's ln Z")
     args = ap.parse_args()
+    if (args.adaptive or args.evidence) and not args.tempered:
+        ap.error('--adaptive and --evidence need --tempered T')
+    if args.tempered and args.protocol:
+        ap.error('--tempered runs a fixed number of iterations (no --protocol)')
     if args.rng == 'device' and not args.device:
         ap.error('--rng device needs --device (the device draws for the resident sampler)')
 
@@ -110,6 +165,10 @@ def main():
     p0s = [truths[k] + 1e-3 * np.abs(truths[k]) * rng.normal(size=(args.nwalkers, 6)) for k in range(args.targets)]
     seeds = [args.seed + k for k in range(args.targets)]
     moves = [(StretchMove(), 0.5), (DEMove(), 0.4), (DEMove(gamma0=1.0), 0.1)] if args.moves == 'de' else None
+    if args.tempered:
+        sampler = run_tempered(args, group, p0s, seeds, moves, truths)
+        group.close()
+        return sampler
     if args.device:
         sampler = DeviceGroupSampler([args.nwalkers] * args.targets, 6, group, seeds=seeds, rng=args.rng,
                                      autocorr='device' if args.protocol else 'host', moves=moves)

@@ -697,6 +697,55 @@ int msx_series_hist2d(msx_series *s, int64_t n, int64_t discard, int64_t thin, c
 int msx_series_evidence(msx_series *s, int64_t n, int64_t discard, int64_t thin, int32_t col, const double *db, int32_t nblocks,
                         double *mean_out, double *lme_out);
 
+/* ---- parallel tempering for a target group: every target's ladder in one run -------------------
+ * msx_tempered_*'s run with a target axis.  The group's K targets each get a ladder of ntemps rungs (one ntemps for the
+ * group, K * ntemps <= MSX_MAX_GROUP) and counts[k] walkers per rung; the K * ntemps (target, rung) pairs are the members of
+ * one ensemble in the general layout, target-major and rung-minor: member m = k * ntemps + t owns counts[k] walkers, the
+ * coordinates are [sum_k ntemps * counts[k]][ndim], ll and lpr alike.  For member (k, t) an iteration is msx_tempered_*'s
+ * iteration for rung t of target k alone -- the split, the moves, P = lpr + beta * ll in two roundings, the accept rule, the
+ * prior-reject rule, the sweep from the hottest rung down with db = beta[t-1] - beta[t], the chain rows after the sweep -- so
+ * target k's chain is bit for bit the chain of msx_tempered_* on its context alone.  Per iteration EIGHT launches for all
+ * targets (step; prior; like; step; prior; like; step; swap -- the evaluations are msx_group_logprob_batch_dev over
+ * ntemps * counts[k] / 2 proposals of target k), nine when adaptive; every run keeps its ladders in device memory.
+ *
+ * begin: betas [K][ntemps], each target's finite, > 0 and strictly descending; counts [K], each even and >= 2; coords, ll,
+ * lpr in the layout above.  MSX_ERR_INVALID: K * ntemps outside 1..MSX_MAX_GROUP, bad betas or counts, ndim != 2 nspec + 2, a
+ * chunk too long (walkers * ndim * steps > 2^31), an lpr that is not finite or a NaN ll.  MSX_ERR_STATE: a run of either
+ * family (msx_group_sampler_*, msx_group_tempered_*) in flight on the group -- msx_group_sampler_begin likewise refuses while
+ * a tempered run is in flight --, a member restaged or destroyed since msx_group_create, a member whose context has a run of
+ * its own in flight or holds a communicator.                                                                              */
+int msx_group_tempered_begin(msx_group *group, int32_t ntemps, const double *betas, const int64_t *counts, int32_t ndim,
+                             int64_t max_chunk_steps, const double *coords, const double *ll, const double *lpr);
+/* one host-drawn chunk: the general layout's arrays [nsteps][2][H], H = sum_k ntemps * counts[k] / 2, the members' halves side
+ * by side in member order and every index member-local (p1, p2 index the complementary half); kind [nsteps][K * ntemps];
+ * swap_logu [nsteps][sum_k (ntemps - 1) * counts[k]], target k's [ntemps - 1][counts[k]] block after target k - 1's (row p:
+ * the pair (p + 1, p)).  msx_tempered_enqueue's checks per member.  A refused call queues nothing; after a member was restaged
+ * or destroyed the call is refused with MSX_ERR_STATE and only msx_group_tempered_end is taken from then on.            */
+int msx_group_tempered_enqueue(msx_group *group, int32_t slot, int64_t nsteps, const int32_t *sidx, const int32_t *cidx,
+                               const int32_t *kind, const int32_t *p1, const int32_t *p2, const double *g, const double *fac,
+                               const double *logu, const double *swap_logu);
+/* one chunk drawn on the device: member (k, t) from seeds[k * ntemps + t] (streams 0..13), target k's swap draws stream 14 of
+ * seeds[k * ntemps] at index (t - 1) * 4096 + w -- the numbers msx_tempered_enqueue_drawn(seeds[k]) draws for that target
+ * alone.  first_iter: the chunk's first ABSOLUTE iteration, one for the whole group.  MSX_ERR_INVALID: more than 4,096 walkers
+ * per rung, first_iter < 0, a bad set (the DE move needs 4 walkers in every rung).                                        */
+int msx_group_tempered_enqueue_drawn(msx_group *group, int32_t slot, int64_t nsteps, const uint64_t *seeds, const msx_move_set *set,
+                                     int64_t first_iter);
+/* waits for the chunk: chain [nsteps][sum ntemps * counts][ndim], ll_chain, lpr_chain [nsteps][sum ntemps * counts], naccept
+ * [sum ntemps * counts] and nswap [K][ntemps - 1] running since begin, worst [K][ntemps] of this chunk                     */
+int msx_group_tempered_collect(msx_group *group, int32_t slot, double *chain, double *ll_chain, double *lpr_chain, int64_t *naccept,
+                               int64_t *nswap, int32_t *worst);
+/* ends the run (no run: MSX_OK); the final state where asked for (any may be NULL)                                       */
+int msx_group_tempered_end(msx_group *group, double *coords, double *ll, double *lpr);
+/* the run's two series, once between begin and the first enqueue: K * ntemps members, member k * ntemps + t of counts[k]
+ * walkers; `chain` with the run's ndim, `dens` with ndim 2 (ll, lpr); either may be NULL.  msx_series_attach_tempered's rules;
+ * msx_series_acf, _order_stats, _hist, _hist2d and _evidence then work per member (db [K * ntemps]).                       */
+int msx_group_tempered_attach_series(msx_group *group, msx_series *chain, msx_series *dens, int64_t at_row);
+/* msx_ladder_adapt / _betas / _current with a target axis: lag, time, k0 [K] (target k's own; msx_ladder_adapt's bounds and
+ * state rules); out [nsteps][K][ntemps]; betas [K][ntemps], k and skipped [K] (either may be NULL).                        */
+int msx_group_ladder_adapt(msx_group *group, const double *lag, const double *time, const int64_t *k0);
+int msx_group_ladder_betas(msx_group *group, int32_t slot, double *out);
+int msx_group_ladder_current(msx_group *group, double *betas, int64_t *k, int64_t *skipped);
+
 /* ---- derived posteriors: product bands and derived columns of samples -------------------------
  * What the reference makes of chain samples after the run: make_composite(..., plot=True) (mft6.py:786-828) gives each
  * star's Kepler-band and Gaia G magnitude, from which plot_results derives the Kepler contrast and the planet-radius

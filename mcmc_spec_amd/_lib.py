@@ -210,6 +210,15 @@ def load():
         'msx_series_derive': (C.c_int, [vp, C.POINTER(vp), _up, C.c_int32, C.c_int64, C.c_int64, vp, C.POINTER(C.c_int32)]),
         'msx_series_attach_tempered': (C.c_int, [vp, vp, vp, C.c_int64]),
         'msx_series_evidence': (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _dp, C.c_int32, _dp, _dp]),
+        'msx_group_tempered_begin': (C.c_int, [vp, C.c_int32, _dp, _ip, C.c_int32, C.c_int64, _dp, _dp, _dp]),
+        'msx_group_tempered_enqueue': (C.c_int, [vp, C.c_int32, C.c_int64] + [C.POINTER(C.c_int32)] * 5 + [_dp, _dp, _dp, _dp]),
+        'msx_group_tempered_enqueue_drawn': (C.c_int, [vp, C.c_int32, C.c_int64, C.POINTER(C.c_uint64), C.POINTER(MsxMoveSet), C.c_int64]),
+        'msx_group_tempered_collect': (C.c_int, [vp, C.c_int32, _dp, _dp, _dp, _ip, _ip, C.POINTER(C.c_int32)]),
+        'msx_group_tempered_end': (C.c_int, [vp, _dp, _dp, _dp]),
+        'msx_group_tempered_attach_series': (C.c_int, [vp, vp, vp, C.c_int64]),
+        'msx_group_ladder_adapt': (C.c_int, [vp, _dp, _dp, _ip]),
+        'msx_group_ladder_betas': (C.c_int, [vp, C.c_int32, _dp]),
+        'msx_group_ladder_current': (C.c_int, [vp, _dp, _ip, _ip]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = header/library skew, fail loudly
@@ -240,7 +249,10 @@ EXPORTED = ['msx_create', 'msx_destroy', 'msx_last_error', 'msx_device_info', 'm
             'msx_group_sampler_enqueue_moves', 'msx_group_sampler_enqueue_moves_drawn',
             'msx_tempered_begin', 'msx_tempered_enqueue', 'msx_tempered_enqueue_drawn', 'msx_tempered_draw', 'msx_tempered_collect',
             'msx_tempered_end', 'msx_series_attach_tempered', 'msx_series_evidence', 'msx_ladder_adapt', 'msx_ladder_betas',
-            'msx_ladder_current', 'msx_ladder_step']
+            'msx_ladder_current', 'msx_ladder_step',
+            'msx_group_tempered_begin', 'msx_group_tempered_enqueue', 'msx_group_tempered_enqueue_drawn', 'msx_group_tempered_collect',
+            'msx_group_tempered_end', 'msx_group_tempered_attach_series', 'msx_group_ladder_adapt', 'msx_group_ladder_betas',
+            'msx_group_ladder_current']
 
 
 def as_f64(a):
@@ -1004,6 +1016,98 @@ class Group:
     def sampler_attach_series(self, series, at_row):
         """Append every chunk of the group's run to ``series`` from row ``at_row`` on (msx_group_sampler_attach_series)."""
         self.check(self.lib.msx_group_sampler_attach_series(self.h, series.h, int(at_row)))
+
+    # ---- every target's ladder in one run (msx_group_tempered_*; mcmc_spec_amd.tempered.DeviceGroupTemperedSampler) ----
+    # The layout is target-major, rung-minor: member m = k T + t owns counts[k] walkers; walkers W = sum T counts[k], proposals
+    # per half-step H = W / 2, swap draws per iteration SW = sum (T - 1) counts[k].
+    def tempered_begin(self, betas, counts, coords, ll, lpr, max_chunk_steps):
+        """Start a tempered run over the group (msx_group_tempered_begin): betas (K, T), counts (K,) walkers per rung, coords
+        (W, ndim), ll and lpr (W,)."""
+        betas, coords, ll, lpr = as_f64(betas), as_f64(coords), as_f64(ll), as_f64(lpr)
+        counts = self._counts(counts)
+        if betas.ndim != 2 or betas.shape[0] != self.k or coords.ndim != 2:
+            raise ValueError('tempered_begin: betas (K, T), coords (W, ndim)')
+        T = betas.shape[1]
+        W, ndim = coords.shape
+        if W != T * int(counts.sum()) or ll.shape != (W,) or lpr.shape != (W,):
+            raise ValueError('tempered_begin: coords (W, ndim), ll and lpr (W,) with W = T * sum(counts)')
+        self.check(self.lib.msx_group_tempered_begin(self.h, T, dptr(betas), iptr(counts), ndim, int(max_chunk_steps), dptr(coords), dptr(ll),
+                                                     dptr(lpr)))
+        self._tmp_shape = (T, [int(n) for n in counts], ndim)
+
+    def tempered_enqueue(self, slot, sidx, cidx, kind, p1, p2, g, fac, logu, swap_logu):
+        """Queue one host-drawn chunk (msx_group_tempered_enqueue): kind (nsteps, K T), swap_logu (nsteps, SW), the others
+        (nsteps, 2, H), the members' halves side by side, indices member-local."""
+        i32p = C.POINTER(C.c_int32)
+        T, counts, _ = self._tmp_shape
+        ints = [np.ascontiguousarray(a, dtype=np.int32) for a in (sidx, cidx, kind, p1, p2)]
+        dbl = [as_f64(a) for a in (g, fac, logu, swap_logu)]
+        nsteps = dbl[0].shape[0]
+        for a in [ints[0], ints[1], ints[3], ints[4]] + dbl[:3]:
+            if a.shape != (nsteps, 2, T * sum(counts) // 2):
+                raise ValueError('tempered_enqueue: arrays must have shape (nsteps, 2, T * sum(counts) / 2)')
+        if ints[2].shape != (nsteps, self.k * T) or dbl[3].shape != (nsteps, (T - 1) * sum(counts)):
+            raise ValueError('tempered_enqueue: kind (nsteps, K T), swap_logu (nsteps, (T - 1) * sum(counts))')
+        self.check(self.lib.msx_group_tempered_enqueue(self.h, int(slot), nsteps, *[a.ctypes.data_as(i32p) for a in ints], *[dptr(a) for a in dbl]))
+        return nsteps
+
+    def tempered_enqueue_drawn(self, slot, nsteps, seeds, moves, first_iter):
+        """Queue one chunk whose randomness the device draws (msx_group_tempered_enqueue_drawn): seeds (K, T), member (k, t) from
+        ``seeds[k][t]``, target k's swap draws from ``seeds[k][0]``; ``first_iter`` the chunk's first ABSOLUTE iteration."""
+        seeds = np.array([[int(s) & 0xffffffffffffffff for s in row] for row in seeds], dtype=np.uint64)
+        if seeds.shape != (self.k, self._tmp_shape[0]):
+            raise ValueError('tempered_enqueue_drawn: one seed per target and rung')
+        st = _move_set(moves)
+        self.check(self.lib.msx_group_tempered_enqueue_drawn(self.h, int(slot), int(nsteps), seeds.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                             C.byref(st), int(first_iter)))
+        return int(nsteps)
+
+    def tempered_collect(self, slot, nsteps):
+        """Wait for the chunk in `slot`: (chain [nsteps][W][ndim], ll, lpr [nsteps][W], naccept [W], nswap [K][T-1], worst
+        [K][T]); the counts run since begin."""
+        T, counts, ndim = self._tmp_shape
+        W = T * sum(counts)
+        chain, llc, lprc = np.empty((nsteps, W, ndim)), np.empty((nsteps, W)), np.empty((nsteps, W))
+        nacc, nswap, worst = np.zeros(W, dtype=np.int64), np.zeros((self.k, T - 1), dtype=np.int64), np.zeros((self.k, T), dtype=np.int32)
+        self.check(self.lib.msx_group_tempered_collect(self.h, int(slot), dptr(chain), dptr(llc), dptr(lprc), iptr(nacc), iptr(nswap),
+                                                       worst.ctypes.data_as(C.POINTER(C.c_int32))))
+        return chain, llc, lprc, nacc, nswap, worst
+
+    def tempered_end(self, want_state=False):
+        """End the run (msx_group_tempered_end); its final (coords, ll, lpr) if want_state."""
+        if not want_state:
+            self.check(self.lib.msx_group_tempered_end(self.h, None, None, None))
+            return None
+        T, counts, ndim = self._tmp_shape
+        W = T * sum(counts)
+        coords, ll, lpr = np.empty((W, ndim)), np.empty(W), np.empty(W)
+        self.check(self.lib.msx_group_tempered_end(self.h, dptr(coords), dptr(ll), dptr(lpr)))
+        return coords, ll, lpr
+
+    def tempered_attach_series(self, chain, dens, at_row):
+        """Append every chunk of the run to the series ``chain`` (K T members, member k T + t of counts[k] walkers, ndim) and
+        ``dens`` (the same members, ndim 2: ll, lpr) from row ``at_row`` on (msx_group_tempered_attach_series)."""
+        self.check(self.lib.msx_group_tempered_attach_series(self.h, None if chain is None else chain.h, None if dens is None else dens.h,
+                                                             int(at_row)))
+
+    def tempered_adapt(self, lag, time, k0):
+        """Make the run adaptive (msx_group_ladder_adapt): lag, time, k0 one per target; once, before the first enqueue."""
+        lag, time, k0 = as_f64(lag), as_f64(time), np.ascontiguousarray(k0, dtype=np.int64)
+        if lag.shape != (self.k,) or time.shape != (self.k,) or k0.shape != (self.k,):
+            raise ValueError('tempered_adapt: lag, time and k0 one per target')
+        self.check(self.lib.msx_group_ladder_adapt(self.h, dptr(lag), dptr(time), iptr(k0)))
+
+    def tempered_betas(self, slot, nsteps):
+        """(nsteps, K, T): the ladders the iterations of the chunk last collected from ``slot`` ran with (msx_group_ladder_betas)."""
+        out = np.empty((int(nsteps), self.k, self._tmp_shape[0]))
+        self.check(self.lib.msx_group_ladder_betas(self.h, int(slot), dptr(out)))
+        return out
+
+    def tempered_ladder(self):
+        """(betas (K, T), k (K,), skipped (K,)): the ladders behind everything queued (msx_group_ladder_current; it waits)."""
+        betas, k, skipped = np.empty((self.k, self._tmp_shape[0])), np.zeros(self.k, dtype=np.int64), np.zeros(self.k, dtype=np.int64)
+        self.check(self.lib.msx_group_ladder_current(self.h, dptr(betas), iptr(k), iptr(skipped)))
+        return betas, k, skipped
 
 
 class Series:

@@ -64,6 +64,7 @@
 #include "logprob_kernel.h"
 #include "move_kernels.h"
 #include "tempered_kernels.h"
+#include "group_tempered_kernels.h"
 #include "group_kernel.h"
 #include "pair_kernel.h"
 #include "staging_kernels.h"
@@ -201,9 +202,12 @@ struct msx_group {
     void *h_pin = nullptr;                // pinned host staging of msx_group_logprob_batch
     int64_t cap_walkers = 0;
     struct GroupRun *run = nullptr;       // the device-resident sampler in flight (msx_group_sampler_begin .. _end)
+    struct GroupTemperedRun *trun = nullptr;  // ... or the tempered ladders (msx_group_tempered_begin .. _end); excludes run
 };
 static void group_run_drain(msx_group *g);
 static void group_run_free(msx_group *g);
+static void group_tempered_drain(msx_group *g);
+static void group_tempered_free(msx_group *g);
 
 // A DEVICE CHAIN SERIES (include/msx.h, msx_series_*): a chain kept on the device as
 // [ndim][nw][cap] doubles, filled by the runs it is attached to (run_finish) or from the host, read by the
@@ -229,7 +233,9 @@ struct msx_series {
     size_t scratch_bytes = 0;
     struct SamplerRun *run = nullptr;    // the run appending to it (msx_*sampler_attach_series .. the run's end)
     struct TemperedRun *trun = nullptr;  // ... or the tempered run (msx_series_attach_tempered .. msx_tempered_end)
+    struct GroupTemperedRun *gtrun = nullptr;  // ... or a group's (msx_group_tempered_attach_series .. msx_group_tempered_end)
 };
+static void group_tempered_detach(msx_series *sr);
 
 namespace {
 
@@ -3052,6 +3058,7 @@ int msx_group_create(msx_ctx **ctxs, int32_t k, msx_group **out) {
 void msx_group_destroy(msx_group *g) {
     if (!g) return;
     group_run_free(g);  // a run still open ends here
+    group_tempered_free(g);
     for (msx_ctx *c : g->members)
         if (c) c->groups.erase(std::remove(c->groups.begin(), c->groups.end(), g), c->groups.end());
     (void)hipSetDevice(g->device);
@@ -3176,6 +3183,7 @@ struct GroupRun {
 
 // a member's problem is about to go (free_problem): let the launches that read its tables finish
 static void group_run_drain(msx_group *g) {
+    group_tempered_drain(g);
     if (g->run && g->run->stream) (void)hipStreamSynchronize(g->run->stream);
 }
 
@@ -3193,6 +3201,7 @@ static void group_run_free(msx_group *g) {
 int msx_group_sampler_begin(msx_group *g, int32_t mode, const int64_t *counts, int32_t ndim, int64_t max_chunk_steps,
                             const double *coords, const double *logp, const int64_t *naccept) {
     if (!g) return MSX_ERR_INVALID;
+    if (g->trun) return fail(g, MSX_ERR_STATE, "msx_group_sampler_begin: a tempered run is in flight on this group (msx_group_tempered_end)");
     int64_t total = 0;
     if (int rc = group_check(g, "msx_group_sampler_begin", mode, counts, ndim, &total)) return rc;
     if (mode != MSX_MODE_LOGPOST && mode != MSX_MODE_LOGLIKE)
@@ -4217,7 +4226,7 @@ static constexpr size_t kAcfPartBudget = (size_t)256 << 20;     // acf's partial
 static hipError_t series_scratch(msx_series *sr, size_t bytes) {
     if (bytes <= sr->scratch_bytes) return hipSuccess;
     if (sr->d_scratch) {
-        if (sr->run || sr->trun) sr->retired.push_back(sr->d_scratch);
+        if (sr->run || sr->trun || sr->gtrun) sr->retired.push_back(sr->d_scratch);
         else {
             (void)hipStreamSynchronize(sr->stream);
             (void)hipFree(sr->d_scratch);
@@ -4291,6 +4300,10 @@ void msx_series_destroy(msx_series *sr) {
         if (r->s_dens == sr) r->s_dens = nullptr;
         (void)hipDeviceSynchronize();
     }
+    if (sr->gtrun) {  // ... or a group's
+        group_tempered_detach(sr);
+        (void)hipDeviceSynchronize();
+    }
     if (sr->stream) (void)hipStreamSynchronize(sr->stream);
     if (sr->grown_set) (void)hipEventSynchronize(sr->grown);
     for (void *p : sr->retired) (void)hipFree(p);
@@ -4319,7 +4332,7 @@ static int series_attach(std::string *err, msx_series *sr, SamplerRun *r, int de
         *err = w + ": attach once, between " + begin + " and the run's first enqueue";
         return MSX_ERR_STATE;
     }
-    if (sr->run || sr->trun) { *err = w + ": the series is attached to another run in flight"; return MSX_ERR_STATE; }
+    if (sr->run || sr->trun || sr->gtrun) { *err = w + ": the series is attached to another run in flight"; return MSX_ERR_STATE; }
     if (sr->device != device) { *err = w + ": the series lives on another device"; return MSX_ERR_INVALID; }
     bool same = sr->nw == r->nw && sr->ndim == r->ndim && sr->off.size() == r->m_nw.size() + 1;
     for (size_t m = 0; same && m < r->m_nw.size(); ++m) same = sr->off[m + 1] - sr->off[m] == r->m_nw[m];
@@ -4362,7 +4375,7 @@ int msx_series_attach_tempered(msx_ctx *c, msx_series *chain, msx_series *dens, 
     for (int i = 0; i < 2; ++i) {
         msx_series *sr = both[i];
         if (!sr) continue;
-        if (sr->run || sr->trun) return fail(c, MSX_ERR_STATE, w + ": the series is attached to another run in flight");
+        if (sr->run || sr->trun || sr->gtrun) return fail(c, MSX_ERR_STATE, w + ": the series is attached to another run in flight");
         if (sr->device != c->device) return fail(c, MSX_ERR_INVALID, w + ": the series lives on another device");
         bool same = sr->nw == (int64_t)r->T * r->nw && sr->ndim == want_dim[i] && (int64_t)sr->off.size() == (int64_t)r->T + 1;
         for (int t = 0; same && t < r->T; ++t) same = sr->off[t + 1] - sr->off[t] == r->nw;
@@ -4385,7 +4398,7 @@ int msx_series_attach_tempered(msx_ctx *c, msx_series *chain, msx_series *dens, 
 int msx_series_append(msx_series *sr, const double *rows, int64_t nrows) {
     if (!sr) return MSX_ERR_INVALID;
     if (!rows || nrows < 1) return fail(sr, MSX_ERR_INVALID, "msx_series_append: bad arguments");
-    if (sr->run || sr->trun) return fail(sr, MSX_ERR_STATE, "msx_series_append: a run in flight appends to this series");
+    if (sr->run || sr->trun || sr->gtrun) return fail(sr, MSX_ERR_STATE, "msx_series_append: a run in flight appends to this series");
     HIP_TRY(sr, hipSetDevice(sr->device));
     const int64_t per = sr->nw * sr->ndim;
     const int64_t piece = std::max<int64_t>(1, (int64_t)(kSeriesStageBytes / (sizeof(double) * (size_t)per)));
@@ -4950,7 +4963,7 @@ int msx_series_derive(msx_series *src, msx_ctx **ctxs, const uint32_t *cols, int
     if (ncols > MSX_MAX_DIM) return fail(src, MSX_ERR_RANGE, "msx_series_derive: more columns than a series is wide (MSX_MAX_DIM)");
     if (dst == src || dst->device != src->device || dst->nw != src->nw || dst->off != src->off || dst->ndim != ncols)
         return fail(src, MSX_ERR_INVALID, "msx_series_derive: dst must be another series on the same device with src's members and ndim = ncols");
-    if (dst->run || dst->trun) return fail(src, MSX_ERR_STATE, "msx_series_derive: a run in flight appends to dst");
+    if (dst->run || dst->trun || dst->gtrun) return fail(src, MSX_ERR_STATE, "msx_series_derive: a run in flight appends to dst");
     if (row0 + nrows > src->rows) return fail(src, MSX_ERR_RANGE, "msx_series_derive: rows past the ones src holds");
     if (row0 > dst->rows) return fail(src, MSX_ERR_RANGE, "msx_series_derive: row0 past the rows dst holds (it would leave a gap)");
     const int k = (int)src->off.size() - 1;
@@ -5022,5 +5035,7 @@ int msx_test_hook(msx_ctx *c, int32_t what, int32_t value) {
     }
     return fail(c, MSX_ERR_INVALID, "msx_test_hook: unknown hook");
 }
+
+#include "group_tempered_run.h"
 
 }  // extern "C"

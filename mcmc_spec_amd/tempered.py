@@ -47,6 +47,12 @@ step decays as ``lag / (k + lag)`` with k = ``_adapted``, the adaptive iteration
 iteration, ``get_betas()`` the ladder each stored iteration ran WITH, ``ladder_skipped`` the steps dropped because two rungs
 would have met.  ``log_evidence`` refuses rows of a moving ladder.  ``ladder_step`` and ``ladder_exp`` are float64
 ``+ - * /`` only: the host loop, msx_ladder_step and the device's tempered_adapt_kernel give the same bits.
+
+Every target's ladder in one run.  ``GroupTemperedSampler`` steps K ``TemperedSampler``s in lock-step,
+two batched evaluations per half-step for all targets -- the definition; ``DeviceGroupTemperedSampler`` keeps the K x T rungs
+of a ``TargetGroup`` resident as the members of ONE ensemble (``msx_group_tempered_*``: eight launches per iteration for all
+targets) and target k walks, bit for bit, the chain of its own ladder run alone.  ``sampler.target(k)`` is target k's ladder
+with everything above.
 """
 from __future__ import annotations
 
@@ -327,6 +333,19 @@ class _Ladder:
 
     _series = _dens = None   # DeviceTemperedSampler(autocorr='device'): the chain's and the densities' device series
     engine = None            # the staged Engine, where the sampler was built on one (get_summary, get_products)
+    _own = slice(None)       # this ladder's rungs among the device series' members (a target of a group run: its T of K T)
+
+    def _owned(self, out):
+        """The rows of this ladder's rungs in a per-member result of the device series (an array, or a dict of arrays)."""
+        return {name: v[self._own] for name, v in out.items()} if isinstance(out, dict) else out[self._own]
+
+    def _series_engines(self):
+        """One engine per member of the device series."""
+        return [self.engine] * self.ntemps
+
+    def _series_db(self, db):
+        """db (T,) of this ladder's rungs as the device series' per-member db."""
+        return db
 
     def _pick(self, out, t):
         return out if t is None else {name: v[int(t)] for name, v in out.items()}
@@ -355,7 +374,7 @@ class _Ladder:
                 return np.full((self.ntemps, self.ndim) if t is None else (self.ndim,), np.nan)
             raise ValueError('chain too short')
         if self._series is not None:
-            tau = _device_integrated_time(self._series, n_total, c, discard, thin)[list(rungs)]
+            tau = self._owned(_device_integrated_time(self._series, n_total, c, discard, thin))[list(rungs)]
         else:
             tau = np.array([_host_tau(self.get_chain(t=r, discard=discard, thin=thin), c) for r in rungs])
         return _check_tau((tau if t is None else tau[0]) * thin, n, thin, tol, quiet)
@@ -367,7 +386,7 @@ class _Ladder:
         been built on an Engine)."""
         from . import summary
         if self._series is not None:
-            return self._pick(summary.summary_of(self._series, len(self._chain), q, cols, discard, thin), t)
+            return self._pick(self._owned(summary.summary_of(self._series, len(self._chain), q, cols, discard, thin)), t)
         return self._pick(summary.summarize(self._flat_members(), self._ctx(), [self.nwalkers] * self.ntemps, q, cols, discard, thin), t)
 
     def get_products(self, cols, t=0, q=(0.16, 0.5, 0.84), discard=0, thin=1, indices=None):
@@ -386,7 +405,8 @@ class _Ladder:
                 outs.append(products._summary_of_values(self.engine.ctx, products.evaluate(self.engine, flat[idx], cols), q))
             return {name: np.stack([o[name] for o in outs]) if t is None else outs[0][name] for name in outs[0]}
         if self._series is not None:
-            return self._pick(products.summarize_chain(self._series, len(self._chain), engines, cols, q, discard, thin), t)
+            return self._pick(self._owned(products.summarize_chain(self._series, len(self._chain), self._series_engines(), cols, q, discard,
+                                                                   thin)), t)
         with summary.uploaded(self._flat_members(), self.engine.ctx, [self.nwalkers] * self.ntemps) as (series, n):
             return self._pick(products.summarize_chain(series, n, engines, cols, q, discard, thin), t)
 
@@ -396,7 +416,8 @@ class _Ladder:
         if len(range(int(discard), n_total, int(thin))) < 1:
             raise ValueError('the selection rows[0:n][discard::thin] is empty')
         if self._dens is not None:
-            return self._dens.evidence(n_total, discard, thin, 0, db, blocks)
+            mean, lme = self._dens.evidence(n_total, discard, thin, 0, None if db is None else self._series_db(db), blocks)
+            return self._owned(mean), None if lme is None else self._owned(lme)
         return host_evidence(np.array(self._ll)[int(discard)::int(thin)], db, blocks)
 
     def mean_log_like(self, discard=0, thin=1):
@@ -741,3 +762,350 @@ class DeviceTemperedSampler(_Ladder):
                         self._lpr.append(lprc[i])
                     self._last = TemperedState(chain[i], llc[i], lprc[i])
                     yield self._last
+
+
+# ---- every target's ladder in one run ------------------------------------------------------------------
+def _per_target(value, K, name):
+    """``value`` once per target: a scalar for all, or a sequence of K."""
+    if not isinstance(value, (list, tuple, np.ndarray)):
+        return [value] * K
+    if len(value) != K:
+        raise ValueError('{}: one per target ({} given, {} targets)'.format(name, len(value), K))
+    return list(value)
+
+
+def _target_betas(K, ntemps, betas, beta_min):
+    """K ladders of one length: ``betas`` is one ladder for all targets (1-D), one per target (K rows) or None (geometric)."""
+    if betas is None or np.ndim(betas[0]) == 0:
+        per = [resolve_betas(ntemps, betas, beta_min)] * K
+    else:
+        if len(betas) != K:
+            raise ValueError('betas: one ladder for all targets or one per target')
+        per = [resolve_betas(ntemps, b, beta_min) for b in betas]
+    if len({len(b) for b in per}) != 1:
+        raise ValueError('the targets of a group share ntemps')
+    if K * len(per[0]) > MAX_TEMPS:
+        raise ValueError('targets x rungs must not exceed {} ({} x {} asked for)'.format(MAX_TEMPS, K, len(per[0])))
+    return per
+
+
+def _seed_args(s):
+    """``seeds[k]`` as a ladder's (seed, seeds): one key (rung t gets key + t) or one per rung."""
+    return (s, None) if s is None or np.ndim(s) == 0 else (None, list(s))
+
+
+def _named(k, fn, *a):
+    """fn(*a) with a walker error prefixed ``target k:`` (as TargetGroup and DeviceGroupSampler name theirs)."""
+    try:
+        return fn(*a)
+    except (KeyError, IndexError, ValueError, RuntimeError) as e:
+        raise type(e)('target {}: {}'.format(k, e.args[0] if e.args else e)) from None
+
+
+class GroupTemperedSampler:
+    """K host ``TemperedSampler``s stepped in lock-step -- the definition of a group's tempered run.  Target k keeps its own
+    ``nwalkers[k]``, ``betas[k]``, ``seeds[k]`` (one key, or one per rung), moves and adaptation parameters; per half-step the
+    K x T rungs' proposals are evaluated in TWO batched calls, ``logprior_fn(list_of_K_arrays)`` and ``loglike_fn(...)``, each
+    returning K arrays of values or K ``(values, statuses)``.  A ``TargetGroup`` in ``loglike_fn``'s place (``logprior_fn=None``)
+    stands for its two status-carrying launches.  Everything else -- the status rule, the accept rule, the sweep, the ladder
+    step -- is ``TemperedSampler``'s own code on target k's own state, so target k's chain is ``TemperedSampler``'s on target k
+    alone.  ``draws``: one ``draws(first_iteration, m)`` per target (``TemperedSampler(draws=...)``).  ``target(k)``: target k's
+    ``TemperedSampler``, with the whole ladder interface."""
+
+    def __init__(self, nwalkers, ndim, loglike_fn, logprior_fn=None, ntemps=None, betas=None, beta_min=0.02, seeds=None, moves=None,
+                 draws=None, adaptive=False, adaptation_lag=10000.0, adaptation_time=100.0):
+        nwalkers = [int(n) for n in nwalkers]
+        K = len(nwalkers)
+        engines = [None] * K
+        if logprior_fn is None and hasattr(loglike_fn, 'engines'):
+            from . import _lib
+            grp = loglike_fn
+            engines = grp.engines
+            loglike_fn, logprior_fn = (lambda qs: _group_eval(grp, qs, _lib.MODE_LOGLIKE)), (lambda qs: _group_eval(grp, qs, _lib.MODE_LOGPRIOR))
+        if len(engines) != K:
+            raise ValueError('one walker count per target ({} given, {} targets)'.format(K, len(engines)))
+        self.loglike_fn, self.logprior_fn = loglike_fn, logprior_fn
+        self.ndim = int(ndim)
+        per_betas = _target_betas(K, ntemps, betas, beta_min)
+        seeds, draws = _per_target(seeds, K, 'seeds') if seeds is not None else [None] * K, _per_target(draws, K, 'draws')
+        lags, times = _per_target(adaptation_lag, K, 'adaptation_lag'), _per_target(adaptation_time, K, 'adaptation_time')
+        self._now = [None] * K   # the batched evaluation's results, handed to target k's own status rule
+        self.targets = []
+        for k in range(K):
+            seed, sds = _seed_args(seeds[k])
+            s = TemperedSampler(nwalkers[k], ndim, (lambda q, k=k: self._now[k][1]), (lambda q, k=k: self._now[k][0]), betas=per_betas[k],
+                                seed=seed, seeds=sds, moves=moves, draws=draws[k], adaptive=adaptive, adaptation_lag=lags[k],
+                                adaptation_time=times[k])
+            s.engine = engines[k]
+            self.targets.append(s)
+        self.ntemps = self.targets[0].ntemps
+
+    @property
+    def nwalkers(self):
+        return [s.nwalkers for s in self.targets]
+
+    def target(self, k):
+        return self.targets[int(k)]
+
+    def reset(self):
+        for s in self.targets:
+            s.reset()
+
+    def _evaluate(self, qs):
+        """(lpr, ll) per target of K arrays of proposals (an empty array: a target with nothing to evaluate): two batched
+        calls, then each target's own status rule."""
+        lprs, lls = self.logprior_fn(qs), self.loglike_fn(qs)
+        if len(lprs) != len(qs) or len(lls) != len(qs):
+            raise ValueError('a density function returned the wrong number of targets')
+        out = []
+        for k, s in enumerate(self.targets):
+            if len(qs[k]) == 0:
+                out.append(None)
+                continue
+            self._now[k] = (lprs[k], lls[k])
+            out.append(_named(k, s._evaluate, qs[k]))
+        return out
+
+    def _start(self, initial_states):
+        if len(initial_states) != len(self.targets):
+            raise ValueError('one initial state per target')
+        qs = []
+        for s, st in zip(self.targets, initial_states):   # the targets that come as coordinates are evaluated in one batch
+            flat = np.empty((0, self.ndim))
+            if not isinstance(st, TemperedState):
+                c = np.array(st, dtype=float)
+                c = np.repeat(c[None], s.ntemps, axis=0) if c.ndim == 2 else c
+                if c.shape == (s.ntemps, s.nwalkers, self.ndim) and np.all(np.isfinite(c)):
+                    flat = c.reshape(-1, self.ndim)
+            qs.append(flat)
+        if any(len(q) for q in qs):
+            lprs, lls = self.logprior_fn(qs), self.loglike_fn(qs)
+            for k in range(len(qs)):
+                self._now[k] = (lprs[k], lls[k])
+        return [_named(k, s._start, st) for k, (s, st) in enumerate(zip(self.targets, initial_states))]
+
+    def sample(self, initial_states, iterations=1, store=True, adapt=None):
+        """``initial_states``: one per target, what ``TemperedSampler.sample`` takes.  Yields a list of K TemperedStates."""
+        state = self._start(initial_states)
+        for _ in range(int(iterations)):
+            drawn = [s._draw_steps(1) for s in self.targets]
+            accepted = [np.zeros((s.ntemps, s.nwalkers), dtype=bool) for s in self.targets]
+            before = [s._nswap.copy() for s in self.targets]
+            for h in (0, 1):
+                qs = [np.concatenate([_propose(coords[t], members[t], h) for t in range(s.ntemps)])
+                      for s, (coords, _, _), (members, _) in zip(self.targets, state, drawn)]
+                for k, (s, (lpr_q, ll_q)) in enumerate(zip(self.targets, self._evaluate(qs))):
+                    coords, ll, lpr = state[k]
+                    members, ns = drawn[k][0], s.nwalkers // 2
+                    for t in range(s.ntemps):
+                        sl = slice(t * ns, (t + 1) * ns)
+                        _accept_rung(s.betas[t], coords[t], ll[t], lpr[t], accepted[k][t], members[t], h, qs[k][sl], lpr_q[sl], ll_q[sl])
+            out = []
+            for k, s in enumerate(self.targets):
+                coords, ll, lpr = state[k]
+                betas = s.betas
+                swap_sweep(betas[:-1] - betas[1:], coords, ll, lpr, np.asarray(drawn[k][1])[0], s._nswap)
+                if s._adapting(adapt):
+                    s.betas, skipped = ladder_step(betas, s._nswap - before[k], s.nwalkers, s._adapted, s.adaptation_lag, s.adaptation_time)
+                    s._adapted += 1
+                    s.ladder_skipped += skipped
+                s._accepted += accepted[k]
+                s.iteration += 1
+                if store:
+                    s._betas_rows.append(betas)
+                    s._chain.append(coords.copy())
+                    s._ll.append(ll.copy())
+                    s._lpr.append(lpr.copy())
+                s._last = TemperedState(coords, ll, lpr)
+                out.append(s._last)
+            yield out
+
+    def run_mcmc(self, initial_states, nsteps, **kw):
+        st = None
+        for st in self.sample(initial_states, iterations=nsteps, **kw):
+            pass
+        return st
+
+
+def _group_eval(group, qs, mode):
+    """K ``(values, statuses)`` of one launch of a ``TargetGroup`` over K arrays of walkers, statuses not raised."""
+    arrs, counts, theta = group._stack(qs)
+    if theta.shape[0] == 0:
+        return [(np.empty(0), np.empty(0, dtype=np.int32)) for _ in arrs]
+    logp, status = group.group.logprob_batch(theta, counts, mode)
+    off = np.concatenate([[0], np.cumsum(counts)]).astype(int)
+    return [(logp[off[k]:off[k + 1]].copy(), status[off[k]:off[k + 1]].copy()) for k in range(len(arrs))]
+
+
+class _TargetLadder(_Ladder):
+    """``DeviceGroupTemperedSampler.target(k)``: target k's ladder -- its stored rows, counts, generators and the whole
+    ``_Ladder`` interface.  With the run's series on the device (K T members) its T rungs are the members ``_own``."""
+
+    def __init__(self, parent, k, nwalkers, betas, seed, seeds, moves, adaptive, lag, time):
+        self.parent, self.k = parent, int(k)
+        self.engine = parent.group.engines[k]
+        self._init_ladder(nwalkers, parent.ndim, None, betas, None, seed, seeds, moves, adaptive, lag, time)
+        self._own = slice(self.k * self.ntemps, (self.k + 1) * self.ntemps)
+
+    _series = property(lambda self: self.parent._series)
+    _dens = property(lambda self: self.parent._dens)
+    _evaluate = DeviceTemperedSampler._evaluate
+
+    def _series_engines(self):
+        return [e for e in self.parent.group.engines for _ in range(self.ntemps)]
+
+    def _series_db(self, db):
+        full = np.zeros(len(self.parent.targets) * self.ntemps)
+        full[self._own] = db
+        return full
+
+
+class DeviceGroupTemperedSampler:
+    """Every target's ladder resident on the GPU in ONE run (``msx_group_tempered_*``; csrc/group_tempered_kernels.h; DESIGN.md
+    section 20): K targets x T rungs are the members of one ensemble, and an iteration takes eight launches for ALL targets
+    (nine when adaptive) where K ``DeviceTemperedSampler``s take eight each.  ``group`` is a ``TargetGroup``; ``nwalkers``
+    walkers per rung, one count per target; ``betas`` one ladder for all targets or one per target (one ``ntemps`` for the group,
+    K x ntemps <= 64); ``seeds[k]`` target k's key (rung t gets key + t) or its T keys; ``adaptation_lag`` / ``adaptation_time``
+    one for all or one per target.  Target k's chain is bit for bit ``DeviceTemperedSampler``'s on ``group.engines[k]`` alone
+    with ``seeds[k]`` -- whatever ``rng``, ``autocorr`` and ``adaptive`` are -- and so ``TemperedSampler``'s and
+    ``GroupTemperedSampler``'s.
+
+    ``target(k)`` is target k's ladder with ``_Ladder``'s interface (``get_chain(t)``, ``get_log_like``, ``get_betas``,
+    ``acceptance_fraction``, ``swap_fraction``, ``get_autocorr_time``, ``get_summary``, ``get_products``, ``mean_log_like``,
+    ``log_evidence``, ...).  ``autocorr='device'``: the rows are kept in ONE pair of device series of K T members and those
+    calls work there.  ``_drawn`` and ``_adapted`` (each target's) follow ``DeviceTemperedSampler``'s rules: they count the
+    iterations QUEUED, ``reset()`` leaves them alone, and after a run ends each target's ``betas`` is the device's ladder behind
+    everything queued.  A walker error raises what ``DeviceTemperedSampler`` raises, prefixed ``target k:``."""
+
+    def __init__(self, group, nwalkers, ndim, ntemps=None, betas=None, beta_min=0.02, seeds=None, chunk=64, rng='host', moves=None,
+                 autocorr='host', cap_hint=0, adaptive=False, adaptation_lag=10000.0, adaptation_time=100.0):
+        if rng not in ('host', 'device'):
+            raise ValueError("rng must be 'host' or 'device'")
+        if autocorr not in ('host', 'device'):
+            raise ValueError("autocorr must be 'host' or 'device'")
+        nwalkers = [int(n) for n in nwalkers]
+        K = len(nwalkers)
+        if K != len(group):
+            raise ValueError('one walker count per target ({} given, {} targets)'.format(K, len(group)))
+        if int(chunk) < 1:
+            raise ValueError('chunk must be at least 1')
+        self.group, self.ndim, self.chunk, self.rng_mode, self.autocorr = group, int(ndim), int(chunk), rng, autocorr
+        self.adaptive = bool(adaptive)
+        per_betas = _target_betas(K, ntemps, betas, beta_min)
+        seeds = _per_target(seeds, K, 'seeds') if seeds is not None else [None] * K
+        lags, times = _per_target(adaptation_lag, K, 'adaptation_lag'), _per_target(adaptation_time, K, 'adaptation_time')
+        self._series = self._dens = None
+        self.targets = []
+        for k in range(K):
+            seed, sds = _seed_args(seeds[k])
+            self.targets.append(_TargetLadder(self, k, nwalkers[k], per_betas[k], seed, sds, moves, adaptive, lags[k], times[k]))
+        self.ntemps = self.targets[0].ntemps
+        self._moves = self.targets[0]._moves
+        if autocorr == 'device':
+            from . import _lib
+            counts = [n for n in nwalkers for _ in range(self.ntemps)]
+            ctx = group.engines[0].ctx
+            self._series = _lib.Series(ctx, sum(counts), self.ndim, counts, cap_hint=int(cap_hint))
+            self._dens = _lib.Series(ctx, sum(counts), 2, counts, cap_hint=int(cap_hint))
+
+    @property
+    def nwalkers(self):
+        return [v.nwalkers for v in self.targets]
+
+    def target(self, k):
+        return self.targets[int(k)]
+
+    def reset(self):
+        """Forget every target's stored chain and counts; the streams' positions, ``_drawn`` and ``_adapted`` are left alone."""
+        for v in self.targets:
+            v.reset()
+
+    def _draw_members(self, m):
+        """The K T members' general layouts of m iterations, side by side in member order: kind (m, K T), the others (m, 2, H)."""
+        per = [r._draw_steps(m) for v in self.targets for r in v._rungs]
+        return [np.stack([p[i] for p in per], axis=1) if i == 2 else np.concatenate([p[i] for p in per], axis=2) for i in range(8)]
+
+    def _draw_swaps(self, m):
+        return [np.concatenate([draw_swap_logu(v._swap_rng, m, v.ntemps, v.nwalkers).reshape(int(m), -1) for v in self.targets], axis=1)]
+
+    def sample(self, initial_states, iterations=1, store=True, adapt=None):
+        """``initial_states``: one per target -- a TemperedState, or coordinates (nw_k, ndim) / (T, nw_k, ndim).  Yields a list
+        of K TemperedStates per iteration."""
+        from .engine import _raise_for_status
+        if len(initial_states) != len(self.targets):
+            raise ValueError('one initial state per target')
+        start = [_named(k, v._start, st) for k, (v, st) in enumerate(zip(self.targets, initial_states))]
+        if int(iterations) <= 0:
+            return
+        grp, T, ndim = self.group.group, self.ntemps, self.ndim
+        adapt = self.adaptive if adapt is None else bool(adapt)
+        counts = self.nwalkers
+        off = np.concatenate([[0], np.cumsum([T * n for n in counts])]).astype(int)
+        base = [(v._accepted.copy(), v._nswap.copy(), v.ladder_skipped, v.betas) for v in self.targets]
+
+        def enqueue(slot, m, arrays):
+            if adapt:
+                for v in self.targets:
+                    v._adapted += m
+            if arrays is None:
+                grp.tempered_enqueue_drawn(slot, m, [v.seeds for v in self.targets], self._moves, self.targets[0]._drawn)
+                for v in self.targets:
+                    v._drawn += m
+            else:
+                grp.tempered_enqueue(slot, *arrays)
+
+        grp.tempered_begin(np.array([v.betas for v in self.targets]), counts, np.concatenate([c.reshape(-1, ndim) for c, _, _ in start]),
+                           np.concatenate([ll.ravel() for _, ll, _ in start]), np.concatenate([lpr.ravel() for _, _, lpr in start]), self.chunk)
+        collect, end = grp.tempered_collect, grp.tempered_end
+        try:
+            if store and self._series is not None:
+                grp.tempered_attach_series(self._series, self._dens, len(self.targets[0]._chain))   # (rows a consumer never saw are overwritten)
+            if adapt:   # (a fixed run calls none of the three)
+                grp.tempered_adapt([v.adaptation_lag for v in self.targets], [v.adaptation_time for v in self.targets],
+                                   [v._adapted for v in self.targets])
+
+                def collect(slot, m):
+                    return grp.tempered_collect(slot, m) + (grp.tempered_betas(slot, m),)
+
+                def end():   # the device's ladders behind everything queued, whether the loop finished or was left
+                    try:
+                        betas, _, skipped = grp.tempered_ladder()
+                        for k, v in enumerate(self.targets):
+                            v.betas, v.ladder_skipped = betas[k].copy(), base[k][2] + int(skipped[k])
+                    finally:
+                        grp.tempered_end()
+        except Exception:
+            grp.tempered_end()
+            raise
+        draws = None if self.rng_mode == 'device' else (self._draw_members, self._draw_swaps)
+        with closing(_pump(iterations, self.chunk, draws, enqueue, collect, end)) as chunks:
+            for mm, (chain, llc, lprc, nacc, nswap, worst, *rows) in chunks:
+                per = []
+                for k, v in enumerate(self.targets):
+                    sl, shp = slice(off[k], off[k + 1]), (mm, T, v.nwalkers)
+                    per.append((chain[:, sl].reshape(shp + (ndim,)), llc[:, sl].reshape(shp), lprc[:, sl].reshape(shp)))
+                    bad = np.nonzero(worst[k] > W_REJECT)[0]
+                    if bad.size:
+                        _named(k, _raise_for_status, np.array([worst[k][bad[0]]]), per[k][0][-1][int(bad[0])][:1])
+                for k, v in enumerate(self.targets):
+                    v._accepted = base[k][0] + nacc[off[k]:off[k + 1]].reshape(T, v.nwalkers)
+                    v._nswap = base[k][1] + nswap[k]
+                for i in range(mm):
+                    out = []
+                    for k, v in enumerate(self.targets):
+                        c, ll, lpr = per[k]
+                        v.iteration += 1
+                        if store:
+                            v._betas_rows.append(rows[0][i, k].copy() if rows else base[k][3])
+                            v._chain.append(c[i])
+                            v._ll.append(ll[i])
+                            v._lpr.append(lpr[i])
+                        v._last = TemperedState(c[i], ll[i], lpr[i])
+                        out.append(v._last)
+                    yield out
+
+    def run_mcmc(self, initial_states, nsteps, **kw):
+        st = None
+        for st in self.sample(initial_states, iterations=nsteps, **kw):
+            pass
+        return st

@@ -5,9 +5,11 @@ typed twice).
     python tools/design_tables.py            # prints the block
     python tools/design_tables.py --write    # rewrites the blocks between the markers in DESIGN.md
     python tools/design_tables.py --group-rng  # ... and prints section 11.2's block too
+    python tools/design_tables.py --group-tempered  # ... and section 20's
 
 tests/test_design_tables.py checks that DESIGN.md holds exactly the first block (what this prints without flags);
-tests/test_group_rng_abi.py checks section 11.2's block (--group-rng) and that its no-regression condition holds.
+tests/test_group_rng_abi.py checks section 11.2's block (--group-rng) and that its no-regression condition holds;
+tests/test_group_tempered_abi.py checks section 20's block (--group-tempered) and that its acceptance bar holds.
 """
 import csv
 import glob
@@ -21,6 +23,8 @@ TAG = 'r4'
 BEGIN, END = '<!-- BEGIN GENERATED TABLES (tools/design_tables.py) -->', '<!-- END GENERATED TABLES -->'
 # section 11.2's tables (build_group_rng), a block of their own
 GROUP_RNG_BEGIN, GROUP_RNG_END = '<!-- BEGIN GENERATED GROUP RNG TABLES (tools/design_tables.py) -->', '<!-- END GENERATED GROUP RNG TABLES -->'
+# section 20's table (build_group_tempered)
+GROUP_TEMPERED_BEGIN, GROUP_TEMPERED_END = '<!-- BEGIN GENERATED GROUP TEMPERED TABLE (tools/design_tables.py) -->', '<!-- END GENERATED GROUP TEMPERED TABLE -->'
 
 
 def jload(name):
@@ -205,8 +209,32 @@ def build_group_rng():
     return '\n'.join(o).rstrip() + '\n'
 
 
+def build_group_tempered():
+    """Section 20: every target's ladder in one run against the targets' own ladders run one after another
+    (profiles/group_tempered_bench.jsonl, written by tools/group_tempered_bench.py)."""
+    rows = [r for r in jlines('group_tempered_bench.jsonl') if r.get('what') == 'group_tempered_us_per_iter']
+    if not rows:
+        return ''
+    o = []
+
+    def span(r, d):
+        v = r[d + '_rounds']
+        return '%s (%s … %s)' % (f(float(sorted(v)[len(v) // 2]), 1), f(min(v), 1), f(max(v), 1))
+    o.append('| targets × rungs × walkers | proposals per launch | one group run, µs/iter: median of %d (min … max) | the targets\' own ladders, '
+             'summed µs/iter | group / summed | bar | target 0\'s swap fractions | target 0 = its own run |' % len(rows[0]['group_rounds']))
+    o.append('|---|---|---|---|---|---|---|---|')
+    for r in rows:
+        sw = r['swap_fraction_target0']
+        o.append('| %d × %d × %d | %s | %s | %s | **%s** | %s | %s – %s | %s |' % (
+            r['targets'], r['ntemps'], r['walkers_per_rung'], f(r['proposals_per_launch'], 0), span(r, 'group'), span(r, 'solo'),
+            f(r['ratio'], 3), ('≤ %s: %s' % (r['bar'], 'holds' if r['meets_bar'] else '**fails**')) if 'bar' in r else 'recorded',
+            f(min(sw), 2), f(max(sw), 2), 'bit for bit' if r['target0_equals_its_solo_run'] else '**differs**'))
+    return '\n'.join(o).rstrip() + '\n'
+
+
 def main():
-    blocks = [(BEGIN, END, build()), (GROUP_RNG_BEGIN, GROUP_RNG_END, build_group_rng())]
+    blocks = [(BEGIN, END, build()), (GROUP_RNG_BEGIN, GROUP_RNG_END, build_group_rng()),
+              (GROUP_TEMPERED_BEGIN, GROUP_TEMPERED_END, build_group_tempered())]
     if '--write' in sys.argv:
         p = os.path.join(ROOT, 'DESIGN.md')
         s = open(p).read()
@@ -218,6 +246,8 @@ def main():
         sys.stdout.write(blocks[0][2])
         if '--group-rng' in sys.argv:
             sys.stdout.write(blocks[1][2])
+        if '--group-tempered' in sys.argv:
+            sys.stdout.write(blocks[2][2])
 
 
 if __name__ == '__main__':

@@ -8,7 +8,10 @@ table's storage), never on its values, so the problems are staged from ``mcmc_sp
 The group matrix asks ``msx_group_launch_info`` the same of target groups: members that mix pixel counts (whole trips of
 a variant or not, LDS-staged statics that fit or not), walker layouts around one and two walkers per CU with empty
 members, and every workgroup size.  ``tests/test_gpu_launch_plans.py`` runs both matrices against the library under test
-and compares them with the committed ``launch_plans.json`` and ``group_launch_plans.json``."""
+and compares them with the committed ``launch_plans.json`` and ``group_launch_plans.json``.
+
+These files pin WHICH instance a launch takes, not what it computes: the values of every instance are pinned in
+``tests/test_gpu_variant_matrix.py`` (one recipe per table entry in ``tests/variant_cases.py``)."""
 import json
 import os
 import sys

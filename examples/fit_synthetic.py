@@ -159,6 +159,7 @@ def tempered_run(args, eng, p0, truth, t2):
         print('  {:4s} {:.6g} / {:.6g} / {:.6g}'.format(nm, lo, mid, hi))
     if args.evidence:
         print('tau of the cold rung :', np.round(sampler.get_autocorr_time(t=0, quiet=True), 2))
+        print('R-hat of the cold rung:', np.round(sampler.get_rhat(t=0), 3), '(split, over the walkers)')
         for method in ('ti', 'ss'):
             ev = sampler.log_evidence(blocks=min(8, sampler.iteration), method=method)
             print('ln Z ({}) = {:.4f} +- {:.4f} (ladder {:.4f})'.format(method, ev.log_z, ev.mc_error, ev.ladder_error))

@@ -182,6 +182,10 @@ def main():
             args.targets, [len(x) // args.nwalkers for x in out], time.time() - t0, args.protocol))
         for k in range(args.targets):
             print('target {}: Teff {:.0f} / {:.0f} (truth {:.0f} / {:.0f})'.format(k, *np.median(out[k][:, :2], axis=0), *truths[k][:2]))
+        if sampler.samplers[0].iteration >= 4:   # (one computation for all targets; on the GPU with --device)
+            rhat = sampler.get_rhat()
+            for k in range(args.targets):
+                print('target {}: split R-hat max {:.3f} (over the walkers; < 1.05 wanted)'.format(k, np.max(rhat[k])))
         if args.device:
             print_summary(sampler.get_summary(), args.targets)
             print_products(sampler.get_products(['kep_contrast', 'pri_corr', 'sec_corr']), args.targets)
@@ -195,6 +199,10 @@ def main():
         flat = sampler.get_chain(k, discard=args.nsteps // 2, flat=True)
         print('target {}: Teff {:.0f} / {:.0f} (truth {:.0f} / {:.0f}), acceptance {:.2f}'.format(
             k, *np.median(flat[:, :2], axis=0), *truths[k][:2], sampler.acceptance_fraction[k].mean()))
+    if args.nsteps - args.nsteps // 2 >= 4:
+        rhat = sampler.get_rhat(discard=args.nsteps // 2)
+        for k in range(args.targets):
+            print('target {}: split R-hat max {:.3f} (second half, over the walkers)'.format(k, np.max(rhat[k])))
     if args.device:
         print_summary(sampler.get_summary(discard=args.nsteps // 2), args.targets)
         print_products(sampler.get_products(['kep_contrast', 'pri_corr', 'sec_corr'], discard=args.nsteps // 2), args.targets)

@@ -697,6 +697,25 @@ int msx_series_hist2d(msx_series *s, int64_t n, int64_t discard, int64_t thin, c
 int msx_series_evidence(msx_series *s, int64_t n, int64_t discard, int64_t thin, int32_t col, const double *db, int32_t nblocks,
                         double *mean_out, double *lme_out);
 
+/* ---- between-walker convergence and plain moments of a series -----------------------------------
+ * What split R-hat is made of, and the pooled mean and covariance, per member and column; for any series.  The selection x =
+ * rows[0:n][discard::thin] (n' >= 4 rows) is msx_series_acf's.  With h = n' / 2 each walker gives two half-chains, rows
+ * [0, h) and [n' - h, n') (an odd n' leaves the middle row to neither); half-chain j = 2 w + half of J = 2 W_m.  Per column
+ * m_j = S_j / h, s2_j = sum (x - m_j)^2 / (h - 1), and over the half-chains in order j:
+ *   within = (sum s2_j) / J,  between = sum (m_j - mbar)^2 / (J - 1) with mbar = (sum m_j) / J,
+ *   var_plus = ((h - 1) / h) within + between;   split R-hat = sqrt(var_plus / within), the caller's.
+ * mean = the walkers' sums over all n' rows, added in walker order, over N = n' W_m; cov[d][e] = sum (x_d - mean_d)(x_e -
+ * mean_e) / (N - 1), the walkers' sums added in walker order, computed for d <= e and mirrored.  within, var_plus, between,
+ * mean [k][ncols]; cov [k][ncols][ncols], or NULL: the cross products are then not computed.  cols [ncols]: coordinates <
+ * ndim, at most MSX_MAX_DIM; NULL: all of them (ncols = ndim).  Everything is float64 + - * / in an order fixed by n' and
+ * W_m alone -- not by thin, discard, the buffer's capacity or how the rows arrived -- so the same input gives the same bits.
+ * Special values are IEEE's: a constant column has within = 0; a NaN or an infinity stays in its member's column.
+ * Synchronous, on the series' own stream, waits for nothing but the latest growth copy.  MSX_ERR_INVALID: a null series or
+ * output (cov apart), discard < 0, thin < 1, ncols < 1.  MSX_ERR_RANGE: n past the rows held, fewer than 4 rows selected, a
+ * column >= ndim, ncols over MSX_MAX_DIM (or not ndim with cols NULL).  A refused call leaves the series as it was.         */
+int msx_series_moments(msx_series *s, int64_t n, int64_t discard, int64_t thin, const uint32_t *cols, int32_t ncols,
+                       double *within, double *var_plus, double *between, double *mean, double *cov);
+
 /* ---- parallel tempering for a target group: every target's ladder in one run -------------------
  * msx_tempered_*'s run with a target axis.  The group's K targets each get a ladder of ntemps rungs (one ntemps for the
  * group, K * ntemps <= MSX_MAX_GROUP) and counts[k] walkers per rung; the K * ntemps (target, rung) pairs are the members of

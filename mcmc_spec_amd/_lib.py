@@ -210,6 +210,7 @@ def load():
         'msx_series_derive': (C.c_int, [vp, C.POINTER(vp), _up, C.c_int32, C.c_int64, C.c_int64, vp, C.POINTER(C.c_int32)]),
         'msx_series_attach_tempered': (C.c_int, [vp, vp, vp, C.c_int64]),
         'msx_series_evidence': (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _dp, C.c_int32, _dp, _dp]),
+        'msx_series_moments': (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, _up, C.c_int32, _dp, _dp, _dp, _dp, _dp]),
         'msx_group_tempered_begin': (C.c_int, [vp, C.c_int32, _dp, _ip, C.c_int32, C.c_int64, _dp, _dp, _dp]),
         'msx_group_tempered_enqueue': (C.c_int, [vp, C.c_int32, C.c_int64] + [C.POINTER(C.c_int32)] * 5 + [_dp, _dp, _dp, _dp]),
         'msx_group_tempered_enqueue_drawn': (C.c_int, [vp, C.c_int32, C.c_int64, C.POINTER(C.c_uint64), C.POINTER(MsxMoveSet), C.c_int64]),
@@ -252,7 +253,7 @@ EXPORTED = ['msx_create', 'msx_destroy', 'msx_last_error', 'msx_device_info', 'm
             'msx_ladder_current', 'msx_ladder_step',
             'msx_group_tempered_begin', 'msx_group_tempered_enqueue', 'msx_group_tempered_enqueue_drawn', 'msx_group_tempered_collect',
             'msx_group_tempered_end', 'msx_group_tempered_attach_series', 'msx_group_ladder_adapt', 'msx_group_ladder_betas',
-            'msx_group_ladder_current']
+            'msx_group_ladder_current', 'msx_series_moments']
 
 
 def as_f64(a):
@@ -1189,6 +1190,23 @@ class Series:
         self.check(self.lib.msx_series_evidence(self.h, int(n), int(discard), int(thin), int(col), None if db is None else dptr(db), nblocks,
                                                 dptr(mean), None if lme is None else dptr(lme)))
         return mean, lme
+
+    def moments(self, n, discard=0, thin=1, cols=None, cov=True):
+        """Split R-hat and the pooled moments of rows[0:n][discard::thin] (n' >= 4 rows), per member and column
+        (msx_series_moments): {'within', 'var_plus', 'between', 'rhat', 'mean' (k, ncols), 'cov'
+        (k, ncols, ncols) -- None without ``cov`` --, 'count' (k,) = n' W_m}.  ``rhat = sqrt(var_plus / within)`` is taken
+        here; the rest are the device's numbers, in a summation order n' and the walker counts fix.  ``cols``: coordinates
+        (None: all)."""
+        cols = _col_codes(range(self.ndim) if cols is None else cols)
+        nc = int(cols.size)
+        within, var_plus, between, mean = (np.empty((self.k, nc)) for _ in range(4))
+        cv = np.empty((self.k, nc, nc)) if cov else None
+        self.check(self.lib.msx_series_moments(self.h, int(n), int(discard), int(thin), uptr(cols), nc, dptr(within), dptr(var_plus),
+                                               dptr(between), dptr(mean), None if cv is None else dptr(cv)))
+        with np.errstate(invalid='ignore', divide='ignore'):
+            rhat = np.sqrt(var_plus / within)
+        count = len(range(int(discard), int(n), int(thin))) * self.counts
+        return {'within': within, 'var_plus': var_plus, 'between': between, 'rhat': rhat, 'mean': mean, 'cov': cv, 'count': count}
 
     def derive(self, contexts, cols, dst, row0=0, nrows=None):
         """Rows row0 .. row0 + nrows - 1 of this series mapped to the derived columns ``cols`` (codes) and written to the

@@ -27,6 +27,7 @@
 //   staging_kernels.h  CCM89, pair gather, band integrals, broadening, resample, composite, stream copy
 //   summary_kernels.h  order statistics and binned marginals of a device chain series
 //   evidence_kernels.h block means and log-mean-exponentials of a series column (thermodynamic integration, stepping stone)
+//   diag_kernels.h     split R-hat's within / between variances and the pooled mean and covariance of a series' members
 //   msx.hip            host context + the C ABI of include/msx.h
 //
 // Design notes (details in DESIGN.md):
@@ -72,6 +73,7 @@
 #include "autocorr_kernels.h"
 #include "summary_kernels.h"
 #include "evidence_kernels.h"
+#include "diag_kernels.h"
 #include "product_kernels.h"
 #include "opt_run_kernels.h"
 
@@ -4529,6 +4531,66 @@ int msx_series_evidence(msx_series *sr, int64_t n, int64_t discard, int64_t thin
     }
     HIP_TRY(sr, hipMemcpyAsync(mean_out, d_mean, sizeof(double) * (size_t)nout, hipMemcpyDeviceToHost, st));
     HIP_TRY(sr, hipStreamSynchronize(st));
+    return MSX_OK;
+}
+
+// ---- split R-hat's parts and the pooled moments of a series' members (diag_kernels.h) ---------------
+int msx_series_moments(msx_series *sr, int64_t n, int64_t discard, int64_t thin, const uint32_t *cols, int32_t ncols, double *within,
+                       double *var_plus, double *between, double *mean, double *cov) {
+    if (!sr) return MSX_ERR_INVALID;
+    if (!within || !var_plus || !between || !mean || discard < 0 || thin < 1 || ncols < 1)
+        return fail(sr, MSX_ERR_INVALID, "msx_series_moments: bad arguments (discard >= 0, thin >= 1, ncols >= 1, every output but cov)");
+    if (n < 1 || n > sr->rows) return fail(sr, MSX_ERR_RANGE, "msx_series_moments: n must lie in 1 .. the rows the series holds");
+    const int64_t np = n > discard ? (n - discard + thin - 1) / thin : 0;
+    if (np < 4) return fail(sr, MSX_ERR_RANGE, "msx_series_moments: the selection rows[0:n][discard::thin] needs at least 4 rows");
+    if (ncols > MSX_MAX_DIM) return fail(sr, MSX_ERR_RANGE, "msx_series_moments: more columns than a series is wide (MSX_MAX_DIM)");
+    DiagCols C;
+    memset(&C, 0, sizeof(C));
+    C.n = ncols;
+    if (!cols && ncols != sr->ndim) return fail(sr, MSX_ERR_RANGE, "msx_series_moments: cols == NULL means all columns (ncols = ndim)");
+    for (int32_t q = 0; q < ncols; ++q) {
+        const uint32_t c = cols ? cols[q] : (uint32_t)q;
+        if (c >= (uint32_t)sr->ndim) return fail(sr, MSX_ERR_RANGE, "msx_series_moments: a column outside the series");
+        C.c[q] = (int32_t)c;
+    }
+    HIP_TRY(sr, hipSetDevice(sr->device));
+    const int k = (int)sr->off.size() - 1;
+    const int64_t nc = ncols, npairs = cov ? nc * (nc + 1) / 2 : 0, nw = sr->nw;
+    // scratch: [psum 3 nc nw | pss 2 nc nw | pcross npairs nw | mean k nc | within k nc | var_plus k nc | between k nc | cov k nc nc]
+    const int64_t kc = (int64_t)k * nc, ncov = cov ? kc * nc : 0;
+    HIP_TRY(sr, series_scratch(sr, sizeof(double) * (size_t)((5 * nc + npairs) * nw + 4 * kc + ncov)));
+    double *d_psum = (double *)sr->d_scratch, *d_pss = d_psum + 3 * nc * nw, *d_pcross = d_pss + 2 * nc * nw;
+    double *d_mean = d_pcross + npairs * nw, *d_within = d_mean + kc, *d_vplus = d_within + kc, *d_between = d_vplus + kc;
+    double *d_cov = d_between + kc;
+    HIP_TRY(sr, series_wait_growth(sr));
+    hipStream_t st = sr->stream;
+    hipLaunchKernelGGL(diag_sum_kernel, dim3((unsigned)nw, (unsigned)nc, 3u), dim3(kDiagThreads), 0, st, (const double *)sr->d_rows, sr->cap,
+                       nw, C, np, discard, thin, d_psum);
+    HIP_TRY(sr, hipGetLastError());
+    hipLaunchKernelGGL(diag_mean_kernel, dim3((unsigned)k), dim3(MSX_MAX_DIM), 0, st, (const double *)d_psum, (const int64_t *)sr->d_off, nw,
+                       (int32_t)nc, np, d_mean);
+    HIP_TRY(sr, hipGetLastError());
+    hipLaunchKernelGGL(diag_dev_kernel, dim3((unsigned)nw, (unsigned)nc, 2u), dim3(kDiagThreads), 0, st, (const double *)sr->d_rows, sr->cap,
+                       nw, C, np, discard, thin, (const double *)d_psum, d_pss);
+    HIP_TRY(sr, hipGetLastError());
+    if (cov) {
+        hipLaunchKernelGGL(diag_cross_kernel, dim3((unsigned)nw, (unsigned)npairs), dim3(kDiagThreads), 0, st, (const double *)sr->d_rows,
+                           sr->cap, nw, C, np, discard, thin, (const int64_t *)sr->d_off, (int32_t)k, (const double *)d_mean, d_pcross);
+        HIP_TRY(sr, hipGetLastError());
+    }
+    hipLaunchKernelGGL(diag_combine_kernel, dim3((unsigned)k), dim3(kDiagMaxPairs), 0, st, (const double *)d_psum, (const double *)d_pss,
+                       (const double *)(cov ? d_pcross : nullptr), (const int64_t *)sr->d_off, nw, (int32_t)nc, np, d_within, d_vplus,
+                       d_between, cov ? d_cov : nullptr);
+    HIP_TRY(sr, hipGetLastError());
+    // (mean .. between lie side by side: one copy, then the host splits them)
+    std::vector<double> hbuf((size_t)(4 * kc));
+    HIP_TRY(sr, hipMemcpyAsync(hbuf.data(), d_mean, sizeof(double) * (size_t)(4 * kc), hipMemcpyDeviceToHost, st));
+    if (cov) HIP_TRY(sr, hipMemcpyAsync(cov, d_cov, sizeof(double) * (size_t)ncov, hipMemcpyDeviceToHost, st));
+    HIP_TRY(sr, hipStreamSynchronize(st));
+    memcpy(mean, hbuf.data(), sizeof(double) * (size_t)kc);
+    memcpy(within, hbuf.data() + kc, sizeof(double) * (size_t)kc);
+    memcpy(var_plus, hbuf.data() + 2 * kc, sizeof(double) * (size_t)kc);
+    memcpy(between, hbuf.data() + 3 * kc, sizeof(double) * (size_t)kc);
     return MSX_OK;
 }
 

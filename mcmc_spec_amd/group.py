@@ -20,7 +20,8 @@ import numpy as np
 
 from . import _lib
 from .engine import _raise_for_status
-from .sampler import EnsembleSampler, State, _accept, _check_tau, _device_integrated_time, _propose, _pump, device_seed
+from .sampler import (_MOMENTS, EnsembleSampler, State, _accept, _check_tau, _device_integrated_time, _device_moments, _max_rhat,
+                      _propose, _pump, device_seed)
 
 
 class TargetGroup:
@@ -214,6 +215,23 @@ class GroupSampler:
             return self.samplers[k].get_autocorr_time(**kw)
         return np.array([s.get_autocorr_time(**kw) for s in self.samplers])
 
+    def get_rhat(self, k=None, discard=0, thin=1, cols=None):
+        """Target k's split R-hat (ncols,), or every target's (K, ncols) for k None: each over the target's own walkers
+        (EnsembleSampler.get_rhat's keywords and rules)."""
+        kw = dict(discard=discard, thin=thin, cols=cols)
+        if k is not None:
+            return self.samplers[k].get_rhat(**kw)
+        return np.array([s.get_rhat(**kw) for s in self.samplers])
+
+    def get_moments(self, k=None, discard=0, thin=1, cols=None):
+        """Target k's {'mean', 'cov', 'count'} (EnsembleSampler.get_moments), or every target's for k None: the arrays
+        with a leading axis K."""
+        kw = dict(discard=discard, thin=thin, cols=cols)
+        if k is not None:
+            return self.samplers[k].get_moments(**kw)
+        outs = [s.get_moments(**kw) for s in self.samplers]
+        return {name: np.array([o[name] for o in outs]) for name in _MOMENTS}
+
 
 class DeviceGroupSampler(GroupSampler):
     """``GroupSampler`` with the K ensembles resident in HBM (``msx_group_sampler_*``, include/msx.h): ``chunk`` iterations
@@ -387,6 +405,21 @@ class DeviceGroupSampler(GroupSampler):
         tau = _device_integrated_time(self._series, n_total, c, discard, thin) * thin
         return _check_tau(tau if k is None else tau[k], n, thin, tol, quiet)
 
+    def get_rhat(self, k=None, discard=0, thin=1, cols=None):
+        """GroupSampler.get_rhat; with autocorr='device' every target's from the chains on the device, ONE
+        msx_series_moments call over all targets (rows queued past the stored chains are not part of it)."""
+        if self._series is None:
+            return super().get_rhat(k, discard=discard, thin=thin, cols=cols)
+        r = _device_moments(self._series, len(self.samplers[0]._chain), discard, thin, cols, False)['rhat']
+        return r if k is None else r[k]
+
+    def get_moments(self, k=None, discard=0, thin=1, cols=None):
+        """GroupSampler.get_moments; with autocorr='device' from the chains on the device (get_rhat's rules)."""
+        if self._series is None:
+            return super().get_moments(k, discard=discard, thin=thin, cols=cols)
+        out = _device_moments(self._series, len(self.samplers[0]._chain), discard, thin, cols, True)
+        return {name: out[name] if k is None else out[name][k] for name in _MOMENTS}
+
     def get_summary(self, k=None, q=(0.16, 0.5, 0.84), discard=0, thin=1, cols=None):
         """Every target's posterior summary from its stored chain, flattened over its walkers: {'count' (K,), 'min', 'max'
         (K, ncols), 'quantiles' (K, ncols, len(q))}, ``np.quantile``'s numbers exactly; for one target with ``k`` (the
@@ -436,7 +469,7 @@ class DeviceGroupSampler(GroupSampler):
         return out if k is None else {name: v[k] for name, v in out.items()}
 
 
-def run_group_protocol(sampler, pos, nburn, nsteps, nthin=10, dirname=None, fnames=None):
+def run_group_protocol(sampler, pos, nburn, nsteps, nthin=10, dirname=None, fnames=None, rhat=None):
     """``sampler.run_reference_protocol`` (run_emcee's driver, mft6.py:1494-1529) applied to every target of a group
     sampler (GroupSampler or DeviceGroupSampler) stepped in lock-step: burn-in, reset, then production with one tau
     computation for all targets every ``nthin`` iterations.  Each target keeps its own ``old_acl``; a target that meets
@@ -447,7 +480,11 @@ def run_group_protocol(sampler, pos, nburn, nsteps, nthin=10, dirname=None, fnam
     which target k writes into ``dirname/fnames[k]/``; ``fnames``: the targets' file prefixes (default ``run0``, ``run1``,
     ...).  Target k's files are those ``run_reference_protocol(dirname=<its directory>, fname=fnames[k])`` writes.
     Returns the K targets' flattened samples; target k's are exactly ``run_reference_protocol``'s on target k alone with
-    k's seed (its chain in the group is its own chain, bit for bit)."""
+    k's seed (its chain in the group is its own chain, bit for bit).
+
+    ``rhat`` (a float; None: nothing changes): ``run_reference_protocol``'s -- a target finishes at a check only when the
+    maximum of its split R-hat lies below ``rhat`` as well, and with ``dirname`` every check appends that maximum to the
+    target's ``{fname}_rhat.txt``."""
     import os
     K, ndim = len(sampler.samplers), sampler.ndim
     fnames = ['run{}'.format(k) for k in range(K)] if fnames is None else [str(f) for f in fnames]
@@ -489,15 +526,28 @@ def run_group_protocol(sampler, pos, nburn, nsteps, nthin=10, dirname=None, fnam
             acls = sampler.get_autocorr_time(quiet=True)
         else:
             acls = {k: sampler.get_autocorr_time(k, quiet=True) for k in active}
+        if rhat is not None:
+            if at_once:   # (one device computation for all targets; NaN while the chains are shorter than 4 rows)
+                try:
+                    mrhats = np.max(sampler.get_rhat(), axis=1)
+                except ValueError:
+                    mrhats = np.full(K, np.nan)
+            else:
+                mrhats = {k: _max_rhat(lambda: sampler.get_rhat(k)) for k in active}
         for k in active:
             acl = acls[k]
             macl = np.mean(acl)
             if dirs:
                 with open('{}/{}_autocorr.txt'.format(dirs[k], fnames[k]), 'a') as f:
                     f.write(str(macl) + '\n')
+                if rhat is not None:
+                    with open('{}/{}_rhat.txt'.format(dirs[k], fnames[k]), 'a') as f:
+                        f.write(str(float(mrhats[k])) + '\n')
             if not np.isnan(macl):
                 converged = np.all(acl * 50 < n)
                 converged &= np.all((np.abs(old_acl[k] - acl) / acl) < 0.1)
+                if rhat is not None:
+                    converged &= mrhats[k] < rhat
                 if converged:
                     stop[k] = n
                     continue

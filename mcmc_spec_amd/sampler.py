@@ -276,6 +276,36 @@ class EnsembleSampler:
             f[d] /= self.nwalkers
         return _check_tau(_integrated_time(f, c) * thin, n, thin, tol, quiet)
 
+    def get_rhat(self, discard=0, thin=1, cols=None):
+        """Split R-hat per column over the walkers of the stored chain, rows ``[discard::thin]`` (at least 4):
+        ``diagnostics.split_rhat``.  ``cols``: coordinates; None for all."""
+        from . import diagnostics
+        return diagnostics.split_rhat(_selection(self._chain, discard, thin, cols))
+
+    def get_moments(self, discard=0, thin=1, cols=None):
+        """{'mean' (ncols,), 'cov' (ncols, ncols), 'count'}: the mean and covariance of
+        ``get_chain(discard=, thin=, flat=True)`` (``diagnostics.moments``)."""
+        from . import diagnostics
+        return diagnostics.moments(_selection(self._chain, discard, thin, cols))
+
+
+def _selection(rows, discard, thin, cols):
+    """Stored rows (a list of (nw, ndim) arrays, or an array) as the selection (n', nw, ncols) of get_rhat / get_moments."""
+    x = np.asarray(rows)[discard::thin]
+    if x.ndim != 3 or x.shape[0] < 4:
+        raise ValueError('chain too short')
+    return x if cols is None else x[:, :, np.asarray(cols, dtype=np.int64).ravel()]
+
+
+def _device_moments(series, n_total, discard, thin, cols, cov):
+    """``Series.moments`` of the first n_total rows (the rows consumed; those queued past them are not part of it)."""
+    if len(range(discard, n_total, thin)) < 4:
+        raise ValueError('chain too short')
+    return series.moments(n_total, discard, thin, cols, cov)
+
+
+_MOMENTS = ('mean', 'cov', 'count')
+
 
 def _window(f, c):
     """The Sokal window over the lags f[:L] of one dimension: (the first index idx with idx >= c * taus[idx], or None if
@@ -570,6 +600,20 @@ class DeviceEnsembleSampler(EnsembleSampler):
         tau = _device_integrated_time(self._series, n_total, c, discard, thin)[0]
         return _check_tau(tau * thin, n, thin, tol, quiet)
 
+    def get_rhat(self, discard=0, thin=1, cols=None):
+        """EnsembleSampler.get_rhat; with autocorr='device' from the chain on the device (msx_series_moments), without a
+        download.  Rows the device holds past len(self._chain) -- queued chunks not consumed yet -- are not part of it."""
+        if self._series is None:
+            return super().get_rhat(discard=discard, thin=thin, cols=cols)
+        return _device_moments(self._series, len(self._chain), discard, thin, cols, False)['rhat'][0]
+
+    def get_moments(self, discard=0, thin=1, cols=None):
+        """EnsembleSampler.get_moments; with autocorr='device' from the chain on the device (get_rhat's rules)."""
+        if self._series is None:
+            return super().get_moments(discard=discard, thin=thin, cols=cols)
+        out = _device_moments(self._series, len(self._chain), discard, thin, cols, True)
+        return {name: out[name][0] for name in _MOMENTS}
+
     def get_summary(self, q=(0.16, 0.5, 0.84), discard=0, thin=1, cols=None):
         """The posterior summary of the stored chain, flattened over the walkers: {'count': N, 'min', 'max' (ncols,),
         'quantiles' (ncols, len(q))} -- ``np.quantile(get_chain(discard=, thin=, flat=True), q, axis=0).T`` exactly, from
@@ -628,10 +672,22 @@ class _Call:
         return self.f(x, *self.args, **self.kwargs)
 
 
-def run_reference_protocol(sampler, pos, nburn, nsteps, nthin=10, dirname=None, fname='run'):
+def _max_rhat(get_rhat):
+    """max over the columns of a check's split R-hat; NaN while the chain is shorter than 4 rows."""
+    try:
+        return float(np.max(get_rhat()))   # (np.max: a NaN column makes the maximum NaN, and NaN < rhat is False)
+    except ValueError:
+        return float('nan')
+
+
+def run_reference_protocol(sampler, pos, nburn, nsteps, nthin=10, dirname=None, fname='run', rhat=None):
     """The driver loop of ``run_emcee`` (mft6.py:1494-1529): burn-in, reset, production with the
     ``acl*50 < n`` / 10 % stability convergence test, thinned coordinate dumps and ``samples.txt``.
-    Returns the flattened samples ``(nwalkers*nsteps_run, ndim)``."""
+    Returns the flattened samples ``(nwalkers*nsteps_run, ndim)``.
+
+    ``rhat`` (a float; None: the reference's rule alone, nothing else changes): a check stops only when
+    ``max(sampler.get_rhat()) < rhat`` as well -- the second opinion that looks ACROSS the walkers, which tau cannot give
+     -- and with ``dirname`` every check appends that maximum to ``{fname}_rhat.txt``."""
     import os
     for n, s in enumerate(sampler.sample(pos, iterations=nburn)):
         if dirname and n % nthin == 0:
@@ -652,9 +708,16 @@ def run_reference_protocol(sampler, pos, nburn, nsteps, nthin=10, dirname=None, 
             if dirname:
                 with open('{}/{}_autocorr.txt'.format(dirname, fname), 'a') as f:
                     f.write(str(macl) + '\n')
+            if rhat is not None:
+                mrhat = _max_rhat(sampler.get_rhat)
+                if dirname:
+                    with open('{}/{}_rhat.txt'.format(dirname, fname), 'a') as f:
+                        f.write(str(mrhat) + '\n')
             if not np.isnan(macl):
                 converged = np.all(acl * 50 < n)
                 converged &= np.all((np.abs(old_acl - acl) / acl) < 0.1)
+                if rhat is not None:
+                    converged &= mrhat < rhat
                 if converged:
                     break
             old_acl = acl

@@ -379,6 +379,31 @@ class _Ladder:
             tau = np.array([_host_tau(self.get_chain(t=r, discard=discard, thin=thin), c) for r in rungs])
         return _check_tau((tau if t is None else tau[0]) * thin, n, thin, tol, quiet)
 
+    def _moments(self, t, discard, thin, cols, cov):
+        """Series.moments' dict for rung t (t None: every rung, a leading axis T): from the device series with
+        autocorr='device' (one msx_series_moments call over all members), otherwise ``diagnostics`` on the host chain."""
+        from . import diagnostics
+        from .sampler import _device_moments, _selection
+        if self._series is not None:
+            out = _device_moments(self._series, len(self._chain), discard, thin, cols, cov)
+            return self._pick(self._owned({name: v for name, v in out.items() if v is not None}), t)
+        rungs = range(self.ntemps) if t is None else [int(t)]
+        x = np.concatenate([_selection(self.get_chain(t=r), discard, thin, cols) for r in rungs], axis=1)
+        out = diagnostics.split_parts(x, [self.nwalkers] * len(rungs))
+        if cov:
+            out.update(diagnostics.moments(x, [self.nwalkers] * len(rungs)))
+        return out if t is None else {name: v[0] for name, v in out.items()}
+
+    def get_rhat(self, t=0, discard=0, thin=1, cols=None):
+        """Rung t's split R-hat (ncols,) over its walkers -- rung 0 is the posterior -- or every rung's (T, ncols) for
+        ``t=None`` (``EnsembleSampler.get_rhat``'s keywords and rules)."""
+        return self._moments(t, discard, thin, cols, False)['rhat']
+
+    def get_moments(self, t=0, discard=0, thin=1, cols=None):
+        """Rung t's {'mean', 'cov', 'count'} (``EnsembleSampler.get_moments``); ``t=None``: every rung's."""
+        out = self._moments(t, discard, thin, cols, True)
+        return {name: out[name] for name in ('mean', 'cov', 'count')}
+
     def get_summary(self, t=0, q=(0.16, 0.5, 0.84), discard=0, thin=1, cols=None):
         """Rung t's posterior summary over its stored chain, flattened over its walkers (``DeviceEnsembleSampler.get_summary``'s
         dict and numbers: DESIGN.md section 14); ``t=None``: every rung's, the arrays with a leading axis T.  With

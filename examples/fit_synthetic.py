@@ -44,6 +44,8 @@ def main():
     ap.add_argument('--beta-min', type=float, default=0.02, help='the hottest rung of --tempered')
     ap.add_argument('--adaptive', type=int, default=0, metavar='N',
                     help='with --tempered: N adaptive iterations first (the rungs move towards equal swap rates), then the ladder is frozen')
+    ap.add_argument('--predictive', action='store_true',
+                    help='after the run: the posterior predictive check of the stored chain (chi^2 terms, worst pixels, largest mean residual)')
     ap.add_argument('--evidence', action='store_true',
                     help="with --tempered: print the cold rung's tau and ln Z +- mc_error (ladder ladder_error)")
     args = ap.parse_args()
@@ -124,6 +126,9 @@ def main():
     prod = sampler.get_products(['kep_contrast', 'pri_corr', 'sec_corr'])
     for nm, (lo, mid, hi) in zip(['dKep', 'f_pri', 'f_sec'], prod['quantiles']):
         print('  {:5s} {:.6g} / {:.6g} / {:.6g}'.format(nm, lo, mid, hi))
+    if args.predictive:   # does the model reproduce the data, and which data carry chi^2?  (mft6.py:2361-2438, on every sample)
+        from mcmc_spec_amd import predictive
+        predictive.print_report(predictive.check(eng, sampler.get_chain(flat=True)), wl_um)
     print('wrote', os.path.join(args.out, 'samples.txt'), samples.shape)
     return truth, med, samples
 

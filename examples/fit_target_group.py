@@ -109,6 +109,8 @@ def main():
     ap.add_argument('--beta-min', type=float, default=0.02, help='--tempered: the hottest rung (an evidence run wants it much smaller)')
     ap.add_argument('--adaptive', type=int, default=0, metavar='N', help='--tempered: adapt every ladder for N iterations first, then freeze')
     ap.add_argument('--evidence', action='store_true', help="--tempered: print every target's ln Z")
+    ap.add_argument('--predictive', action='store_true',
+                    help="after a plain run: every target's posterior predictive check (chi^2 terms, worst pixels, largest mean residual)")
     args = ap.parse_args()
     if (args.adaptive or args.evidence) and not args.tempered:
         ap.error('--adaptive and --evidence need --tempered T')
@@ -142,6 +144,7 @@ def main():
     kep_wl = np.linspace(4200.0, 9000.0, 200)   # a stand-in for bps/Kepler_Kepler.K.dat (get_transmission('kepler', res))
     kep_tm = np.exp(-0.5 * ((kep_wl - 6400.0) / 1100.0) ** 2)
     engines, truths = [], []
+    wls = []
     for k in range(args.targets):
         truth = synth.TRUTH_THETA.copy()
         truth[:2] = np.clip(truth[:2] + rng.uniform(-150.0, 150.0, size=2), tmin + 50.0, tmax - 50.0)
@@ -159,6 +162,7 @@ def main():
         eng.stage_products((kep_wl, kep_tm), matrix=matrix)
         engines.append(eng)
         truths.append(truth)
+        wls.append(wl_um)
 
     group = TargetGroup(engines)
     print('one launch:', group.launch_info([args.nwalkers] * args.targets)['kernel'])
@@ -206,6 +210,11 @@ def main():
     if args.device:
         print_summary(sampler.get_summary(discard=args.nsteps // 2), args.targets)
         print_products(sampler.get_products(['kep_contrast', 'pri_corr', 'sec_corr'], discard=args.nsteps // 2), args.targets)
+    if args.predictive:
+        from mcmc_spec_amd import predictive
+        for k in range(args.targets):
+            res = predictive.check(engines[k], sampler.get_chain(k, discard=args.nsteps // 2, flat=True))
+            predictive.print_report(res, wls[k], 'target {}: '.format(k))
     group.close()
     return sampler
 

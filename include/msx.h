@@ -846,6 +846,58 @@ int msx_products_spectra(msx_ctx *ctx, const double *theta, int64_t n, int32_t n
 int msx_composite_parts(msx_ctx *ctx, const double *teff, const double *logg, const double *rad, int32_t use_distance, double plx,
                         int64_t j0, int64_t n, double *comp_out, int32_t *status);
 
+/* ---- posterior predictive checks: bands, residuals and chi^2 terms of samples -----------------
+ * What the reference's all_spec figure shows of a finished run (mft6.py:2361-2438) and what its likelihood adds up
+ * (:1173-1191), for every sample of a chain and reduced per data pixel on the device.  For a sample theta (ndim = 2 nspec +
+ * 2) on a context with a staged problem and staged products:
+ *   ROWS 0 .. nspec are msx_products_spectra's rows with MSX_SPEC_MEDIAN_SCALE -- row 0 the composite times median(data) /
+ *     median(row 0), rows 1.. each star -- and carry the bits that call gives the sample;
+ *   data_n = data / P(u), P the quadratic least-squares fit of data / row 0 (norm_spec, :193-196, :1174);
+ *   z = (row 0 - data_n) / sigma, so that chisq (:115-120) is z^2;
+ *   TERMS chi_spec = sum(z^2) / npix (:1179), chi_contrast (:1182-1183), chi_phot with the magnitudes reddened as in
+ *     :1161-1166 (:1188-1189), chi_total = chi_spec (nc + np) + chi_contrast + chi_phot (:1191; a problem staged with
+ *     no_spectrum: chi_contrast + chi_phot).  A_V <= 0, or a problem staged without extinction: no reddening.
+ * No prior is applied.  Only samples whose status is MSX_W_OK enter the reductions, in their order; count is how many did.
+ * A sample that cannot be evaluated has NaN terms and its status is reported (msx_products_batch's codes).
+ *
+ * band  [4][1 + nspec][npix]: mean, variance (ddof = 1), min, max over the valid samples, per row and pixel, in PIXEL order;
+ * quant [nq][1 + nspec][npix], or NULL: np.quantile's default (linear) quantiles at q [nq] -- the device selects the elements
+ *   of ranks floor(h) and min(floor(h) + 1, N - 1), h = (N - 1) q, exactly (median.h's radix selection); the host
+ *   interpolates with NumPy's roundings;
+ * resid [3][npix]: the means over the valid samples of data_n, z and z^2;
+ * terms [n][4]: chi_spec, chi_contrast, chi_phot, chi_total;  status [n];  count [1].
+ * count == 0: every reduced output is NaN.  count == 1: the variance is NaN (np.var(ddof=1)).
+ *
+ * REPRODUCIBILITY.  Every reduced output is a function of the ordered list of the valid samples' values alone: a sum is
+ * formed by 256 partial sums over every 256th value, combined in one fixed order, and the variance is the second of two
+ * passes, sum (x - mean)^2 / (N - 1) in that order -- never from sums of squares of the raw values.  The bits do not depend
+ * on scratch_bytes, the pixel tiles or sample batches it leads to, the launch, thin, discard, the buffer's capacity, how the
+ * rows arrived, or on which of the two calls the samples came through.
+ *
+ * scratch_bytes bounds the temporary device memory of the two large buffers, which share it in turn: the sample pass's
+ * work rows (npix doubles per sample in flight) and the value buffer of a pixel tile ((nspec + 4) N doubles per pixel, N
+ * the samples selected); samples are evaluated in batches and pixels in tiles sized from it.  0: 256 MiB.  Beside it the
+ * call keeps a 192-byte record per sample and the outputs.  Host pointers; synchronous.
+ * MSX_ERR_RANGE: scratch_bytes below 8 * max(npix, (nspec + 4) N), a q outside [0, 1].  MSX_ERR_STATE: no products
+ * staged.  MSX_ERR_INVALID: null pointers, n < 1, ndim != 2 nspec + 2.  A refused call writes nothing.                   */
+int msx_predictive_batch(msx_ctx *ctx, const double *theta, int64_t n, int32_t ndim, const double *q, int32_t nq,
+                         int64_t scratch_bytes, double *band, double *quant, double *resid, double *terms, int32_t *status,
+                         int64_t *count);
+/* The same over the selection rows[0:n][discard::thin] of a device chain (msx_series_acf's selection): member m's walkers
+ * flattened in (row, walker) order -- get_chain(flat=True)'s -- and evaluated with ctxs[m] (k = the series' member count;
+ * the contexts live on the series' device and share nspec; their npix may differ).  band, quant and resid are member-major:
+ * member m's block is laid out as above, behind the blocks of the members before it.  count [k]; worst_status [k] (may be
+ * NULL): the worst sample status among the rows evaluated.  terms_dst: NULL, or a series of ndim = 4 with src's members,
+ * which receives the four terms of EVERY row 0 .. n - 1 (discard and thin only pick what is reduced; without it only the
+ * selection is evaluated); it grows as msx_series_derive's dst does, rows 0 .. n - 1 are overwritten and it then holds
+ * max(rows, n) rows, on which msx_series_order_stats / _hist / _acf / _moments work as on any series.  N above is the
+ * member's selected samples.  Synchronous, on src's stream; waits for nothing but the two series' latest growth copies.
+ * MSX_ERR_RANGE: n past the rows held, an empty selection, and the above.  MSX_ERR_STATE: a member without staged products,
+ * a run attached to terms_dst.  MSX_ERR_INVALID: series that do not match.  A refused call leaves both series as they were. */
+int msx_series_predictive(msx_series *src, msx_ctx **ctxs, int64_t n, int64_t discard, int64_t thin, const double *q, int32_t nq,
+                          int64_t scratch_bytes, double *band, double *quant, double *resid, msx_series *terms_dst,
+                          int64_t *count, int32_t *worst_status);
+
 /* ---- test hooks (used by tests/ only) ------------------------------------------------------------ */
 /* MSX_HOOK_LINKED_FAULT: value != 0 makes the workgroups of the linked form skip their signal -- and the walkers of an
  * overlapped sampler run the publication of their new version -- so that every in-kernel wait runs into its bound;

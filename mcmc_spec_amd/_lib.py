@@ -220,6 +220,10 @@ def load():
         'msx_group_ladder_adapt': (C.c_int, [vp, _dp, _dp, _ip]),
         'msx_group_ladder_betas': (C.c_int, [vp, C.c_int32, _dp]),
         'msx_group_ladder_current': (C.c_int, [vp, _dp, _ip, _ip]),
+        'msx_predictive_batch': (C.c_int, [vp, _dp, C.c_int64, C.c_int32, _dp, C.c_int32, C.c_int64, _dp, _dp, _dp, _dp,
+                                           C.POINTER(C.c_int32), _ip]),
+        'msx_series_predictive': (C.c_int, [vp, C.POINTER(vp), C.c_int64, C.c_int64, C.c_int64, _dp, C.c_int32, C.c_int64, _dp, _dp,
+                                            _dp, vp, _ip, C.POINTER(C.c_int32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = header/library skew, fail loudly
@@ -253,7 +257,7 @@ EXPORTED = ['msx_create', 'msx_destroy', 'msx_last_error', 'msx_device_info', 'm
             'msx_ladder_current', 'msx_ladder_step',
             'msx_group_tempered_begin', 'msx_group_tempered_enqueue', 'msx_group_tempered_enqueue_drawn', 'msx_group_tempered_collect',
             'msx_group_tempered_end', 'msx_group_tempered_attach_series', 'msx_group_ladder_adapt', 'msx_group_ladder_betas',
-            'msx_group_ladder_current', 'msx_series_moments']
+            'msx_group_ladder_current', 'msx_series_moments', 'msx_predictive_batch', 'msx_series_predictive']
 
 
 def as_f64(a):
@@ -495,6 +499,26 @@ class Context:
         self.check(self.lib.msx_products_spectra(self.h, dptr(theta), n, ndim, SPEC_MEDIAN_SCALE if median_scale else 0, dptr(out),
                                                  dptr(scale), status.ctypes.data_as(C.POINTER(C.c_int32))))
         return out, scale, status
+
+    def predictive_batch(self, theta, nspec, npix, q=None, scratch_bytes=0):
+        """msx_predictive_batch over the samples theta (n, ndim): (band (4, 1 + nspec, npix) = mean, var, min, max, quant
+        (len(q), 1 + nspec, npix) or None, resid (3, npix) = the means of data_n, z, z^2, terms (n, 4), status (n,), count),
+        reduced over the samples whose status is W_OK.  ``scratch_bytes``: the bound on the temporary device memory (0: the
+        library's default)."""
+        theta = as_f64(theta)
+        n, ndim = theta.shape
+        rows = 1 + int(nspec)
+        q = None if q is None else as_f64(np.atleast_1d(q))
+        band = np.empty((4, rows, int(npix)))
+        quant = None if q is None else np.empty((q.size, rows, int(npix)))
+        resid = np.empty((3, int(npix)))
+        terms = np.empty((n, 4))
+        status = np.zeros(n, dtype=np.int32)
+        count = np.zeros(1, dtype=np.int64)
+        self.check(self.lib.msx_predictive_batch(self.h, dptr(theta), n, ndim, None if q is None else dptr(q), 0 if q is None else q.size,
+                                                 int(scratch_bytes), dptr(band), None if quant is None else dptr(quant), dptr(resid),
+                                                 dptr(terms), status.ctypes.data_as(C.POINTER(C.c_int32)), iptr(count)))
+        return band, quant, resid, terms, status, int(count[0])
 
     def composite_parts(self, teff, logg, rad, use_distance, plx, j0, n):
         """(parts (nspec, n), status): each star's scaled blend over grid samples [j0, j0 + n) (msx_composite_parts)."""
@@ -1222,6 +1246,37 @@ class Series:
         self.check(self.lib.msx_series_derive(self.h, arr, uptr(cols), cols.size, int(row0), nrows, dst.h,
                                               worst.ctypes.data_as(C.POINTER(C.c_int32))))
         return worst
+
+    def predictive(self, contexts, npix, n, discard=0, thin=1, q=None, scratch_bytes=0, terms_dst=None):
+        """msx_series_predictive over rows[0:n][discard::thin]: per member m, evaluated with ``contexts[m]`` whose problem
+        has ``npix[m]`` pixels, the tuple (band (4, 1 + nspec, npix_m), quant (len(q), 1 + nspec, npix_m) or None, resid
+        (3, npix_m)); then counts (k,) and the members' worst sample status (k,).  ``terms_dst``: a series of ndim 4 with the
+        same members that receives the four chi^2 terms of every row 0 .. n - 1."""
+        contexts = list(contexts)
+        if len(contexts) != self.k or len(npix) != self.k:
+            raise ValueError('predictive: one context and one pixel count per member ({} members)'.format(self.k))
+        rows = self.ndim // 2   # 1 + nspec
+        npix = [int(x) for x in npix]
+        q = None if q is None else as_f64(np.atleast_1d(q))
+        tot = sum(npix)
+        band = np.empty(4 * rows * tot)
+        quant = None if q is None else np.empty(q.size * rows * tot)
+        resid = np.empty(3 * tot)
+        count = np.zeros(self.k, dtype=np.int64)
+        worst = np.zeros(self.k, dtype=np.int32)
+        arr = (C.c_void_p * self.k)(*[c.h for c in contexts])
+        self.check(self.lib.msx_series_predictive(self.h, arr, int(n), int(discard), int(thin), None if q is None else dptr(q),
+                                                  0 if q is None else q.size, int(scratch_bytes), dptr(band),
+                                                  None if quant is None else dptr(quant), dptr(resid),
+                                                  None if terms_dst is None else terms_dst.h, iptr(count),
+                                                  worst.ctypes.data_as(C.POINTER(C.c_int32))))
+        out, off = [], 0
+        for m in range(self.k):
+            b = band[4 * rows * off:4 * rows * (off + npix[m])].reshape(4, rows, npix[m])
+            qq = None if quant is None else quant[q.size * rows * off:q.size * rows * (off + npix[m])].reshape(q.size, rows, npix[m])
+            out.append((b, qq, resid[3 * off:3 * (off + npix[m])].reshape(3, npix[m])))
+            off += npix[m]
+        return out, count, worst
 
     def order_stats(self, n, discard, thin, cols, ranks):
         """(values (k, ncols, nranks), counts (k,)): the elements of zero-based ranks ``ranks`` (k, nranks; one row is

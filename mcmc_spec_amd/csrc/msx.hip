@@ -75,6 +75,7 @@
 #include "evidence_kernels.h"
 #include "diag_kernels.h"
 #include "product_kernels.h"
+#include "predictive_kernels.h"
 #include "opt_run_kernels.h"
 
 // ================================================================================================
@@ -141,6 +142,7 @@ struct msx_ctx {
     InpathRec *d_inp_rec = nullptr;
     double *d_inp_tmp = nullptr, *d_inp_given = nullptr;
     const int64_t *d_pix_lo = nullptr;
+    const double *d_pix_err = nullptr;  // sigma per pixel as staged (the predictive check's z; the hot path reads 1 / sigma^2)
     int64_t inp_rows = 0, inp_gstride = 0;  // walkers per sub-batch (0: the staged problem has no in-path form)
     // pair form (pair_kernel.h): binaries of <= 4096 pixels with the register-resident recipe
     int64_t pair_rows = 0;          // walkers per sub-batch = capacity of the planner's item lists (0: no pair form here)
@@ -1416,6 +1418,7 @@ int msx_stage_problem(msx_ctx *c, const msx_problem *p) {
         if ((rc = dev_alloc_copy(c, &tr, ivar.data(), p->npix, &d))) return rc;
         P.pix_ivar = d;
     }
+    if ((rc = dev_alloc_copy(c, &tr, p->pix_err, p->npix, &d))) return rc; c->d_pix_err = d;
     if ((rc = dev_alloc_copy(c, &tr, p->iso_teff, (int64_t)p->niso, &d))) return rc; P.iso_t = d;
     if ((rc = dev_alloc_copy(c, &tr, p->iso_logg, (int64_t)p->niso, &d))) return rc; P.iso_g = d;
     if ((rc = dev_alloc_copy(c, &tr, p->iso_lum, (int64_t)p->niso, &d))) return rc; P.iso_l = d;
@@ -4856,7 +4859,12 @@ int msx_stage_products(msx_ctx *c, const msx_products *p) {
     M.nt = P.nt; M.ng = P.ng; M.node_stride = P.node_stride; M.niso = P.niso; M.npiso = p->niso;
     M.nc = P.nc; M.np = P.np; M.npb = nb; M.nspec = P.nspec; M.dist_fit = P.dist_fit;
     M.grid = c->d_grid; M.kgrid = c->d_kgrid; M.pix_lo = c->d_pix_lo; M.pix_t = P.pix_t; M.nwl = c->nwl; M.npix = P.npix;
-    M.median_flux = P.median_flux; M.use_av = P.use_av;
+    M.median_flux = P.median_flux; M.use_av = P.use_av; M.no_spectrum = P.no_spectrum;
+    M.pix_flux = P.pix_flux; M.pix_err = c->d_pix_err; M.pix_u = P.pix_u;
+    memcpy(M.minv, P.minv, sizeof(M.minv));
+    for (int i = 0; i < MSX_MAX_BANDS; ++i) {
+        M.cmag[i] = P.cmag[i]; M.cerr[i] = P.cerr[i]; M.pmag[i] = P.pmag[i]; M.perr[i] = P.perr[i]; M.pk[i] = P.pk[i];
+    }
     if ((rc = dev_alloc_copy(c, &tr, &M, (int64_t)1, &c->d_prod_member))) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->products_staged = true;
@@ -5077,6 +5085,264 @@ int msx_series_derive(msx_series *src, msx_ctx **ctxs, const uint32_t *cols, int
     HIP_TRY(src, hipStreamSynchronize(st));
     if (worst_status) memcpy(worst_status, worst.data(), b_worst);
     dst->rows = std::max(dst->rows, row0 + nrows);
+    return MSX_OK;
+}
+
+// ---- posterior predictive checks (predictive_kernels.h) --------------------------------------------
+static constexpr size_t kPredDefaultBytes = (size_t)256 << 20;  // scratch_bytes == 0
+static size_t pred_align(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// one member's run: the samples of `src` (all of them get terms and a status), of which sample i is REDUCED when its row
+// index i / W is sel0 + j * selstep and its status is MSX_W_OK
+struct PredJob {
+    const msx_ctx *c;
+    PredSrc src;
+    int64_t nall, sel0, selstep, nsel;
+    double *d_terms;  // device; null: no terms wanted
+    int64_t t_sw, t_sr, t_sd;
+};
+struct PredSizes {
+    int64_t npix, nrows, nvr;  // nrows = 1 + nspec; nvr = rows of the value buffer (+ data_n, z, z^2)
+    size_t b_rec, b_status, b_vidx, b_ranks, b_band, b_ostat, b_resid, b_big, total;
+};
+// the smallest scratch a job can run in: one work row of the sample pass, or one pixel's values of every selected sample
+static size_t pred_min_bytes(int64_t npix, int nspec, int64_t nsel) {
+    return sizeof(double) * (size_t)std::max(npix, (int64_t)(1 + nspec + kPredExtra) * nsel);
+}
+static PredSizes pred_sizes(const PredJob &J, int32_t nq, size_t budget) {
+    PredSizes Z;
+    Z.npix = J.c->PM.npix; Z.nrows = 1 + J.c->PM.nspec; Z.nvr = Z.nrows + kPredExtra;
+    const size_t most = sizeof(double) * (size_t)Z.npix * (size_t)std::max(J.nall, Z.nvr * J.nsel);  // everything at once
+    Z.b_big = pred_align(std::min(budget, most));
+    Z.b_rec = pred_align(sizeof(PredRec) * (size_t)J.nall);
+    Z.b_status = pred_align(sizeof(int32_t) * (size_t)J.nall);
+    Z.b_vidx = pred_align(sizeof(int64_t) * (size_t)J.nsel);
+    Z.b_ranks = pred_align(sizeof(int64_t) * (size_t)std::max(1, 2 * nq));
+    Z.b_band = pred_align(sizeof(double) * (size_t)(4 * Z.nrows * Z.npix));
+    Z.b_ostat = pred_align(sizeof(double) * (size_t)std::max((int64_t)1, 2 * nq * Z.nrows * Z.npix));
+    Z.b_resid = pred_align(sizeof(double) * (size_t)(kPredExtra * Z.npix));
+    Z.total = Z.b_rec + Z.b_status + Z.b_vidx + Z.b_ranks + Z.b_band + Z.b_ostat + Z.b_resid + Z.b_big;
+    return Z;
+}
+
+// NumPy's interpolation of its default ('linear') quantile method, with its roundings (mcmc_spec_amd/summary.py, _lerp)
+static double pred_lerp(double a, double b, double t) {
+#pragma clang fp contract(off)
+    if (t == 0.0) return a;
+    const double d = b - a;
+    return t >= 0.5 ? b - d * (1.0 - t) : a + d * t;
+}
+
+// Runs the job on `st` inside d_arena (pred_sizes(...).total bytes) and waits for it.  status_out [nall] or null; band
+// [4][nrows][npix], quant [nq][nrows][npix] or null, resid [3][npix]: host.  *err gets the message of a failure.
+static int pred_run(const PredJob &J, hipStream_t st, char *d_arena, const PredSizes &Z, size_t budget, const double *q, int32_t nq,
+                    double *band, double *quant, double *resid, int32_t *status_out, int64_t *count_out, int32_t *worst_out,
+                    std::string *err) {
+#define PRED_TRY(expr)                                                                              \
+    do {                                                                                            \
+        hipError_t e__ = (expr);                                                                    \
+        if (e__ != hipSuccess) { *err = std::string(#expr) + ": " + hipGetErrorString(e__); return MSX_ERR_HIP; } \
+    } while (0)
+    const int ns = J.c->PM.nspec;
+    const int64_t npix = Z.npix, nrows = Z.nrows, nvr = Z.nvr;
+    char *at = d_arena;
+    PredRec *d_rec = reinterpret_cast<PredRec *>(at); at += Z.b_rec;
+    int32_t *d_status = reinterpret_cast<int32_t *>(at); at += Z.b_status;
+    int64_t *d_vidx = reinterpret_cast<int64_t *>(at); at += Z.b_vidx;
+    int64_t *d_ranks = reinterpret_cast<int64_t *>(at); at += Z.b_ranks;
+    double *d_band = reinterpret_cast<double *>(at); at += Z.b_band;
+    double *d_ostat = reinterpret_cast<double *>(at); at += Z.b_ostat;
+    double *d_resid = reinterpret_cast<double *>(at); at += Z.b_resid;
+    double *d_big = reinterpret_cast<double *>(at);
+    const size_t big = std::min(budget, Z.b_big);
+    // the sample pass, in batches of as many work rows as the scratch holds
+    const int64_t batch = std::max<int64_t>(1, std::min<int64_t>(J.nall, (int64_t)(big / (sizeof(double) * (size_t)npix))));
+    PredSampleLaunch SL;
+    memset(&SL, 0, sizeof(SL));
+    SL.M = J.c->d_prod_member; SL.src = J.src; SL.work = d_big; SL.rec = d_rec; SL.status = d_status;
+    SL.terms = J.d_terms; SL.t_sw = J.t_sw; SL.t_sr = J.t_sr; SL.t_sd = J.t_sd;
+    for (int64_t i0 = 0; i0 < J.nall; i0 += batch) {
+        SL.i0 = i0;
+        const dim3 grid((unsigned)std::min(batch, J.nall - i0));
+        if (ns == 2) hipLaunchKernelGGL(predictive_sample_kernel<2>, grid, dim3(kPredThreads), 0, st, SL);
+        else hipLaunchKernelGGL(predictive_sample_kernel<3>, grid, dim3(kPredThreads), 0, st, SL);
+        PRED_TRY(hipGetLastError());
+    }
+    std::vector<int32_t> status((size_t)J.nall);
+    PRED_TRY(hipMemcpyAsync(status.data(), d_status, sizeof(int32_t) * (size_t)J.nall, hipMemcpyDeviceToHost, st));
+    PRED_TRY(hipStreamSynchronize(st));
+    if (status_out) memcpy(status_out, status.data(), sizeof(int32_t) * (size_t)J.nall);
+    std::vector<int64_t> vidx;
+    vidx.reserve((size_t)J.nsel);
+    int32_t worst = 0;
+    for (int64_t i = 0; i < J.nall; ++i) {
+        worst = std::max(worst, status[(size_t)i]);
+        const int64_t ri = i / J.src.W;
+        if (ri >= J.sel0 && (ri - J.sel0) % J.selstep == 0 && status[(size_t)i] == MSX_W_OK) vidx.push_back(i);
+    }
+    const int64_t count = (int64_t)vidx.size();
+    *count_out = count;
+    if (worst_out) *worst_out = worst;
+    const double nan = (double)NAN;
+    const size_t plane = (size_t)(nrows * npix);
+    if (count == 0) {
+        std::fill(band, band + 4 * plane, nan);
+        if (quant) std::fill(quant, quant + (size_t)nq * plane, nan);
+        std::fill(resid, resid + (size_t)(kPredExtra * npix), nan);
+        return MSX_OK;
+    }
+    // ranks floor(h), min(floor(h) + 1, N - 1) of NumPy's virtual index h = (N - 1) q, and the weight h - floor(h)
+    const int nranks = quant ? 2 * nq : 0;
+    std::vector<int64_t> ranks((size_t)std::max(1, nranks), 0);
+    std::vector<double> wt((size_t)std::max(1, (int)nq), 0.0);
+    for (int r = 0; r < (quant ? nq : 0); ++r) {
+        const double h = (double)(count - 1) * q[r], fl = floor(h);
+        ranks[(size_t)(2 * r)] = (int64_t)fl;
+        ranks[(size_t)(2 * r + 1)] = std::min((int64_t)fl + 1, count - 1);
+        wt[(size_t)r] = h - fl;
+    }
+    PRED_TRY(hipMemcpyAsync(d_vidx, vidx.data(), sizeof(int64_t) * (size_t)count, hipMemcpyHostToDevice, st));
+    PRED_TRY(hipMemcpyAsync(d_ranks, ranks.data(), sizeof(int64_t) * ranks.size(), hipMemcpyHostToDevice, st));
+    // pixel tiles sized from the scratch by the SELECTED samples (not by how many turned out valid)
+    const int64_t tile = std::max<int64_t>(1, std::min<int64_t>(npix, (int64_t)(big / (sizeof(double) * (size_t)(nvr * J.nsel)))));
+    PredFillLaunch FL;
+    memset(&FL, 0, sizeof(FL));
+    FL.M = J.c->d_prod_member; FL.rec = d_rec; FL.vidx = d_vidx; FL.count = count; FL.vals = d_big;
+    PredReduceLaunch RL;
+    memset(&RL, 0, sizeof(RL));
+    RL.vals = d_big; RL.count = count; RL.npix = npix; RL.nrows = (int32_t)nrows; RL.nranks = nranks; RL.ranks = d_ranks;
+    RL.band = d_band; RL.ostat = d_ostat; RL.resid = d_resid;
+    for (int64_t p0 = 0; p0 < npix; p0 += tile) {
+        const int64_t tp = std::min(tile, npix - p0);
+        FL.p0 = RL.p0 = p0; FL.tp = RL.tp = tp;
+        const int64_t gx = (count + kPredTile - 1) / kPredTile, chunks = (tp + kPredTile - 1) / kPredTile;
+        const dim3 fgrid((unsigned)gx, (unsigned)std::max<int64_t>(1, std::min<int64_t>(chunks, 2048 / std::min<int64_t>(gx, 2048))));
+        if (ns == 2) hipLaunchKernelGGL(predictive_fill_kernel<2>, fgrid, dim3(kPredThreads), 0, st, FL);
+        else hipLaunchKernelGGL(predictive_fill_kernel<3>, fgrid, dim3(kPredThreads), 0, st, FL);
+        PRED_TRY(hipGetLastError());
+        hipLaunchKernelGGL(predictive_reduce_kernel, dim3((unsigned)tp, (unsigned)nvr), dim3(kPredThreads), 0, st, RL);
+        PRED_TRY(hipGetLastError());
+    }
+    std::vector<double> ostat((size_t)nranks * plane);
+    PRED_TRY(hipMemcpyAsync(band, d_band, sizeof(double) * 4 * plane, hipMemcpyDeviceToHost, st));
+    if (nranks) PRED_TRY(hipMemcpyAsync(ostat.data(), d_ostat, sizeof(double) * ostat.size(), hipMemcpyDeviceToHost, st));
+    PRED_TRY(hipMemcpyAsync(resid, d_resid, sizeof(double) * (size_t)(kPredExtra * npix), hipMemcpyDeviceToHost, st));
+    PRED_TRY(hipStreamSynchronize(st));
+    for (int r = 0; r < (quant ? nq : 0); ++r)
+        for (size_t e = 0; e < plane; ++e)
+            quant[(size_t)r * plane + e] = pred_lerp(ostat[(size_t)(2 * r) * plane + e], ostat[(size_t)(2 * r + 1) * plane + e], wt[(size_t)r]);
+    return MSX_OK;
+#undef PRED_TRY
+}
+
+static bool pred_q_ok(const double *q, int32_t nq) {
+    for (int32_t r = 0; r < nq; ++r)
+        if (!(q[r] >= 0.0 && q[r] <= 1.0)) return false;  // (a NaN fails the comparison too)
+    return true;
+}
+
+int msx_predictive_batch(msx_ctx *c, const double *theta, int64_t n, int32_t ndim, const double *q, int32_t nq, int64_t scratch_bytes,
+                         double *band, double *quant, double *resid, double *terms, int32_t *status, int64_t *count) {
+    if (!c) return MSX_ERR_INVALID;
+    if (!theta || !band || !resid || !terms || !status || !count || n < 1 || nq < 0 || scratch_bytes < 0 || (quant && (!q || nq < 1)))
+        return fail(c, MSX_ERR_INVALID, "msx_predictive_batch: bad arguments");
+    if (!c->problem_staged || !c->products_staged) return fail(c, MSX_ERR_STATE, "msx_predictive_batch: no products staged (msx_stage_products)");
+    if (ndim != 2 * c->P.nspec + 2) return fail(c, MSX_ERR_INVALID, "msx_predictive_batch: ndim must be 2 * nspec + 2");
+    if (c->P.npix > INT32_MAX || n > INT32_MAX) return fail(c, MSX_ERR_RANGE, "msx_predictive_batch: too many pixels or samples");
+    if (quant && !pred_q_ok(q, nq)) return fail(c, MSX_ERR_RANGE, "msx_predictive_batch: quantiles must lie in [0, 1]");
+    const size_t budget = scratch_bytes ? (size_t)scratch_bytes : kPredDefaultBytes;
+    if (budget < pred_min_bytes(c->P.npix, c->P.nspec, n))
+        return fail(c, MSX_ERR_RANGE, "msx_predictive_batch: scratch_bytes holds neither one model row nor one pixel's values of the n samples (8 * max(npix, (nspec + 4) * n) bytes)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    PredJob J;
+    memset(&J, 0, sizeof(J));
+    J.c = c; J.nall = n; J.sel0 = 0; J.selstep = 1; J.nsel = n;
+    const PredSizes Z = pred_sizes(J, quant ? nq : 0, budget);
+    const size_t b_theta = pred_align(sizeof(double) * (size_t)(n * ndim)), b_terms = pred_align(sizeof(double) * (size_t)(4 * n));
+    const size_t need = b_theta + b_terms + Z.total;
+    if (need > c->prod_buf_bytes) {
+        if (c->d_prod_buf) (void)hipFree(c->d_prod_buf);
+        c->d_prod_buf = nullptr; c->prod_buf_bytes = 0;
+        HIP_TRY(c, hipMalloc((void **)&c->d_prod_buf, need));
+        c->prod_buf_bytes = need;
+    }
+    double *d_theta = reinterpret_cast<double *>(c->d_prod_buf), *d_terms = reinterpret_cast<double *>(c->d_prod_buf + b_theta);
+    HIP_TRY(c, hipMemcpyAsync(d_theta, theta, sizeof(double) * (size_t)(n * ndim), hipMemcpyHostToDevice, c->stream));
+    J.src.base = d_theta; J.src.W = n; J.src.w0 = 0; J.src.sw = ndim; J.src.sr = 0; J.src.sd = 1; J.src.row0 = 0; J.src.rstep = 1;
+    J.d_terms = d_terms; J.t_sw = 4; J.t_sr = 0; J.t_sd = 1;
+    std::string err;
+    if (int rc = pred_run(J, c->stream, c->d_prod_buf + b_theta + b_terms, Z, budget, q, quant ? nq : 0, band, quant, resid, status, count,
+                          nullptr, &err))
+        return fail(c, rc, "msx_predictive_batch: " + err);
+    HIP_TRY(c, hipMemcpyAsync(terms, d_terms, sizeof(double) * (size_t)(4 * n), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return MSX_OK;
+}
+
+int msx_series_predictive(msx_series *src, msx_ctx **ctxs, int64_t n, int64_t discard, int64_t thin, const double *q, int32_t nq,
+                          int64_t scratch_bytes, double *band, double *quant, double *resid, msx_series *dst, int64_t *count,
+                          int32_t *worst_status) {
+    if (!src) return MSX_ERR_INVALID;
+    if (!ctxs || !band || !resid || !count || discard < 0 || thin < 1 || nq < 0 || scratch_bytes < 0 || (quant && (!q || nq < 1)))
+        return fail(src, MSX_ERR_INVALID, "msx_series_predictive: bad arguments (discard >= 0, thin >= 1, band, resid, count)");
+    if (dst && (dst == src || dst->device != src->device || dst->nw != src->nw || dst->off != src->off || dst->ndim != 4))
+        return fail(src, MSX_ERR_INVALID, "msx_series_predictive: the terms go to another series on the same device with src's members and ndim = 4");
+    if (dst && (dst->run || dst->trun || dst->gtrun)) return fail(src, MSX_ERR_STATE, "msx_series_predictive: a run in flight appends to the terms' series");
+    if (n < 1 || n > src->rows) return fail(src, MSX_ERR_RANGE, "msx_series_predictive: n must lie in 1 .. the rows the series holds");
+    const int64_t np = discard < n ? (n - discard + thin - 1) / thin : 0;
+    if (np < 1) return fail(src, MSX_ERR_RANGE, "msx_series_predictive: the selection rows[0:n][discard::thin] is empty");
+    if (quant && !pred_q_ok(q, nq)) return fail(src, MSX_ERR_RANGE, "msx_series_predictive: quantiles must lie in [0, 1]");
+    const int k = (int)src->off.size() - 1;
+    const size_t budget = scratch_bytes ? (size_t)scratch_bytes : kPredDefaultBytes;
+    const int32_t nqq = quant ? nq : 0;
+    int nspec = 0;
+    std::vector<PredJob> jobs((size_t)k);
+    size_t arena = 0;
+    for (int m = 0; m < k; ++m) {
+        const msx_ctx *c = ctxs[m];
+        const std::string who = "msx_series_predictive: member " + std::to_string(m);
+        if (!c) return fail(src, MSX_ERR_INVALID, who + " is null");
+        if (c->device != src->device) return fail(src, MSX_ERR_INVALID, who + " lives on another device");
+        if (!c->problem_staged || !c->products_staged) return fail(src, MSX_ERR_STATE, who + " has no staged products (msx_stage_products)");
+        if (m == 0) nspec = c->PM.nspec;
+        if (c->PM.nspec != nspec || src->ndim != 2 * nspec + 2)
+            return fail(src, MSX_ERR_INVALID, who + ": src's ndim must be 2 * nspec + 2 of every member");
+        const int64_t W = src->off[(size_t)m + 1] - src->off[(size_t)m];
+        PredJob &J = jobs[(size_t)m];
+        memset(&J, 0, sizeof(J));
+        J.c = c;
+        J.src.W = W; J.src.w0 = src->off[(size_t)m];
+        // with a terms series every row 0 .. n - 1 is evaluated and the selection picks among them; without, the selection alone
+        if (dst) { J.src.row0 = 0; J.src.rstep = 1; J.nall = n * W; J.sel0 = discard; J.selstep = thin; }
+        else { J.src.row0 = discard; J.src.rstep = thin; J.nall = np * W; J.sel0 = 0; J.selstep = 1; }
+        J.nsel = np * W;
+        if (c->PM.npix > INT32_MAX || J.nsel > INT32_MAX) return fail(src, MSX_ERR_RANGE, who + ": too many pixels or samples");
+        if (budget < pred_min_bytes(c->PM.npix, nspec, J.nsel))
+            return fail(src, MSX_ERR_RANGE, who + ": scratch_bytes holds neither one model row nor one pixel's values of its samples (8 * max(npix, (nspec + 4) * N_m) bytes)");
+        arena = std::max(arena, pred_sizes(J, nqq, budget).total);
+    }
+    HIP_TRY(src, hipSetDevice(src->device));
+    hipStream_t st = src->stream;
+    if (dst) HIP_TRY(src, series_reserve(dst, n, dst->rows, st));  // (grows the way append grows it)
+    HIP_TRY(src, series_scratch(src, arena));
+    HIP_TRY(src, series_wait_growth(src));
+    if (dst && dst->grown_set) HIP_TRY(src, hipStreamWaitEvent(st, dst->grown, 0));
+    size_t o_band = 0, o_quant = 0, o_resid = 0;
+    for (int m = 0; m < k; ++m) {
+        PredJob &J = jobs[(size_t)m];
+        J.src.base = src->d_rows; J.src.sw = src->cap; J.src.sr = 1; J.src.sd = src->nw * src->cap;
+        if (dst) { J.d_terms = dst->d_rows; J.t_sw = dst->cap; J.t_sr = 1; J.t_sd = dst->nw * dst->cap; }
+        const PredSizes Z = pred_sizes(J, nqq, budget);
+        const size_t plane = (size_t)(Z.nrows * Z.npix);
+        std::string err;
+        int32_t worst = 0;
+        if (int rc = pred_run(J, st, src->d_scratch, Z, budget, q, nqq, band + o_band, quant ? quant + o_quant : nullptr, resid + o_resid,
+                              nullptr, count + m, &worst, &err))
+            return fail(src, rc, "msx_series_predictive: member " + std::to_string(m) + ": " + err);
+        if (worst_status) worst_status[m] = worst;
+        o_band += 4 * plane; o_quant += (size_t)nqq * plane; o_resid += (size_t)(kPredExtra * Z.npix);
+    }
+    if (dst) dst->rows = std::max(dst->rows, n);
     return MSX_OK;
 }
 

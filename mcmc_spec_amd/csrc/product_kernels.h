@@ -30,7 +30,11 @@ struct ProdMember {
     const double *pix_t;
     int64_t nwl, npix;
     double median_flux;
-    int32_t use_av, pad;
+    int32_t use_av, no_spectrum;
+    // the posterior predictive check (predictive_kernels.h): what the likelihood compares the model with
+    const double *pix_flux, *pix_err, *pix_u;  // data, sigma, the fit abscissa                           mft6.py:195,:120
+    double minv[9];                            // the inverse Gram matrix of [1, u, u^2]
+    double cmag[MSX_MAX_BANDS], cerr[MSX_MAX_BANDS], pmag[MSX_MAX_BANDS], perr[MSX_MAX_BANDS], pk[MSX_MAX_BANDS];
 };
 
 // one launch: samples are (walker, row) of a [walkers][rows] rectangle per member; element d of sample (w, r) sits at
@@ -300,6 +304,33 @@ __global__ void __launch_bounds__(kProdThreads) products_kernel(const ProdLaunch
 // samples that bracket the pixel, e = 10^(-0.4 A_V k) there, m = e_lo y_lo + (e_hi y_hi - e_lo y_lo) t); row 0 their sum in
 // star order (:744, :751).  flags & MSX_SPEC_MEDIAN_SCALE: row 0 times median(data) / median(row 0) (:2409), the exact
 // median by median.h's radix_select.  A_V <= 0, or a problem staged without extinction: no reddening (mft6.py:1161).
+// one data pixel of a sample whose recipe is R: m [NS] each star's value, returned their sum in star order.  The one
+// statement of a pixel's arithmetic: products_spectra_kernel and the predictive kernels (predictive_kernels.h) both call
+// it, so a sample's pixel has the same bits wherever it is computed.
+template <int NS>
+__device__ __forceinline__ double spectra_pixel(const ProdMember *__restrict__ M, const ProdRecipe &R, int64_t nwl, bool redden,
+                                                double redc, int64_t p, double (&m)[NS]) {
+    const int64_t lo = M->pix_lo[p];
+    const double t = M->pix_t[p];
+    const double e_lo = redden ? exp2(redc * M->kgrid[lo]) : 1.0, e_hi = redden ? exp2(redc * M->kgrid[lo + 1]) : 1.0;
+    double tot = 0.0;
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        double y_lo = 0.0, y_hi = 0.0;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const double w = R.w[(4 * s + c) * kProdThreads];
+            const double *row = M->grid + (int64_t)R.node[(4 * s + c) * kProdThreads] * nwl + lo;
+            y_lo = fma(w, row[0], y_lo);
+            y_hi = fma(w, row[1], y_hi);
+        }
+        const double a = e_lo * y_lo, b = e_hi * y_hi;
+        m[s] = a + (b - a) * t;  // interp1d(ww, extinct(ww, star, e))(wl)   mft6.py:2395-2402
+        tot = s == 0 ? m[s] : tot + m[s];
+    }
+    return tot;
+}
+
 struct SpecLaunch {
     const ProdMember *M;
     const double *theta;
@@ -339,25 +370,10 @@ __global__ void __launch_bounds__(kProdThreads) products_spectra_kernel(const Sp
     const bool redden = M->use_av != 0 && a_v > 0.0;  // mft6.py:1161
     const double redc = -0.4 * kLog2Of10 * a_v;
     for (int64_t p = tid; p < npix; p += kProdThreads) {
-        const int64_t lo = M->pix_lo[p];
-        const double t = M->pix_t[p];
-        const double e_lo = redden ? exp2(redc * M->kgrid[lo]) : 1.0, e_hi = redden ? exp2(redc * M->kgrid[lo + 1]) : 1.0;
-        double tot = 0.0;
+        double m[NS];
+        const double tot = spectra_pixel<NS>(M, R, nwl, redden, redc, p, m);
 #pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            double y_lo = 0.0, y_hi = 0.0;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const double w = R.w[(4 * s + c) * kProdThreads];
-                const double *row = M->grid + (int64_t)R.node[(4 * s + c) * kProdThreads] * nwl + lo;
-                y_lo = fma(w, row[0], y_lo);
-                y_hi = fma(w, row[1], y_hi);
-            }
-            const double a = e_lo * y_lo, b = e_hi * y_hi;
-            const double m = a + (b - a) * t;  // interp1d(ww, extinct(ww, star, e))(wl)   mft6.py:2395-2402
-            out[(1 + s) * npix + p] = m;
-            tot = s == 0 ? m : tot + m;
-        }
+        for (int s = 0; s < NS; ++s) out[(1 + s) * npix + p] = m[s];
         out[p] = tot;
     }
     if (!(L.flags & MSX_SPEC_MEDIAN_SCALE)) {

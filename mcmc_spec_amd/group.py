@@ -468,6 +468,16 @@ class DeviceGroupSampler(GroupSampler):
                 out = products.summarize_chain(series, n, engines, cols, q, discard, thin)
         return out if k is None else {name: v[k] for name, v in out.items()}
 
+    def get_predictive(self, q=(0.16, 0.5, 0.84), discard=0, thin=1, k=None):
+        """Every target's posterior predictive check (``mcmc_spec_amd.predictive``) of its stored
+        chain, each target's samples evaluated with its own engine: a list of K dicts (the targets' pixel counts may
+        differ), or target ``k``'s dict.  With autocorr='device' on the chains held there, otherwise the host chains are
+        uploaded first; rows queued past the stored chains are not part of it."""
+        from . import predictive
+        out = predictive.of_chain(self._series, lambda: np.concatenate([np.array(s._chain) for s in self.samplers], axis=1),
+                                  len(self.samplers[0]._chain), self.group.engines, self.nwalkers, q, discard, thin)
+        return out if k is None else out[k]
+
 
 def run_group_protocol(sampler, pos, nburn, nsteps, nthin=10, dirname=None, fnames=None, rhat=None):
     """``sampler.run_reference_protocol`` (run_emcee's driver, mft6.py:1494-1529) applied to every target of a group

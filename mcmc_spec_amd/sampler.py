@@ -653,6 +653,17 @@ class DeviceEnsembleSampler(EnsembleSampler):
                 out = products.summarize_chain(series, n, [self.engine], cols, q, discard, thin)
         return {name: v[0] for name, v in out.items()}
 
+    def get_predictive(self, q=(0.16, 0.5, 0.84), discard=0, thin=1):
+        """The posterior predictive check of the stored chain (``mcmc_spec_amd.predictive``): every
+        sample of ``get_chain(discard=, thin=, flat=True)`` goes through the model once more and is reduced per data pixel
+        on the device -- ``predictive.check``'s dict (``worst_status`` in place of ``terms`` and ``status``).  With
+        autocorr='device' the chain held on the device is read, without a copy (rows past len(self._chain) -- queued chunks
+        not consumed yet -- are not part of it); otherwise the host chain is uploaded first.  The engine needs staged
+        products (``products.stage``)."""
+        from . import predictive
+        return predictive.of_chain(self._series, lambda: np.array(self._chain), len(self._chain), [self.engine], None, q, discard,
+                                   thin)[0]
+
 
 def _autocorr_1d(x):
     x = np.asarray(x, dtype=float)

@@ -435,6 +435,20 @@ class _Ladder:
         with summary.uploaded(self._flat_members(), self.engine.ctx, [self.nwalkers] * self.ntemps) as (series, n):
             return self._pick(products.summarize_chain(series, n, engines, cols, q, discard, thin), t)
 
+    def get_predictive(self, t=0, q=(0.16, 0.5, 0.84), discard=0, thin=1):
+        """Rung t's posterior predictive check (``mcmc_spec_amd.predictive``) of its stored chain --
+        rung 0 is the posterior --, ``predictive.check``'s dict (``worst_status`` in place of ``terms`` and ``status``);
+        ``t=None``: a list of every rung's.  With autocorr='device' from the chain held there, otherwise the host chain is
+        uploaded first (the sampler must have been built on an Engine with staged products)."""
+        from . import predictive
+        self._ctx()
+        if self._series is not None:
+            out = predictive.of_chain(self._series, None, len(self._chain), self._series_engines(), None, q, discard, thin)[self._own]
+        else:
+            out = predictive.of_chain(None, self._flat_members, len(self._chain), [self.engine] * self.ntemps,
+                                      [self.nwalkers] * self.ntemps, q, discard, thin)
+        return out if t is None else out[int(t)]
+
     def _evidence(self, discard, thin, db, blocks):
         """(mean, lme) (T, blocks + 1) of the stored ln L: ``host_evidence``, or msx_series_evidence on the device series."""
         n_total = len(self._ll)

@@ -15,7 +15,8 @@ burn-in, reset, production; the swap fractions and the cold rung's summary are p
 rung's autocorrelation time and ln Z by thermodynamic integration and the stepping stone (section 18), from the rows the
 run kept on the GPU with ``--autocorr device``; an evidence run wants a much smaller ``--beta-min`` than the default.
 ``--adaptive N`` first moves the rungs for N iterations until adjacent pairs swap at equal rates (section 19), prints the
-ladder before and after with the swap fractions, freezes it and goes on as above.
+ladder before and after with the swap fractions, freezes it and goes on as above.  ``--modes`` prints the posterior's modes
+(mcmc_spec_amd.modes; section 23): per mode its probability and the 16 / 50 / 84 percentiles of every coordinate.
 """
 import argparse
 import os
@@ -46,6 +47,9 @@ def main():
                     help='with --tempered: N adaptive iterations first (the rungs move towards equal swap rates), then the ladder is frozen')
     ap.add_argument('--predictive', action='store_true',
                     help='after the run: the posterior predictive check of the stored chain (chi^2 terms, worst pixels, largest mean residual)')
+    ap.add_argument('--modes', action='store_true',
+                    help="after the run: the posterior's modes (a two-component mixture over the six coordinates), each mode's "
+                         "probability and 16 / 50 / 84, and bic1 - bic2 (positive: two modes)")
     ap.add_argument('--evidence', action='store_true',
                     help="with --tempered: print the cold rung's tau and ln Z +- mc_error (ladder ladder_error)")
     args = ap.parse_args()
@@ -126,6 +130,9 @@ def main():
     prod = sampler.get_products(['kep_contrast', 'pri_corr', 'sec_corr'])
     for nm, (lo, mid, hi) in zip(['dKep', 'f_pri', 'f_sec'], prod['quantiles']):
         print('  {:5s} {:.6g} / {:.6g} / {:.6g}'.format(nm, lo, mid, hi))
+    if args.modes:   # which mode, with what probability?  (the reference's p_t1 and its siblings, mft6.py:2030-2194, jointly)
+        from mcmc_spec_amd import modes
+        modes.print_table(sampler.get_modes(), ['T1', 'T2', 'Av', 'R1', 'R2', 'plx'], sampler.get_modes(ncomp=1))
     if args.predictive:   # does the model reproduce the data, and which data carry chi^2?  (mft6.py:2361-2438, on every sample)
         from mcmc_spec_amd import predictive
         predictive.print_report(predictive.check(eng, sampler.get_chain(flat=True)), wl_um)
@@ -162,6 +169,9 @@ def tempered_run(args, eng, p0, truth, t2):
     print('posterior 16 / 50 / 84 of the cold rung ({} samples):'.format(int(summ['count'])))
     for nm, (lo, mid, hi) in zip(['T1', 'T2', 'Av', 'R1', 'R2', 'plx'], summ['quantiles']):
         print('  {:4s} {:.6g} / {:.6g} / {:.6g}'.format(nm, lo, mid, hi))
+    if args.modes:
+        from mcmc_spec_amd import modes
+        modes.print_table(sampler.get_modes(t=0), ['T1', 'T2', 'Av', 'R1', 'R2', 'plx'], sampler.get_modes(t=0, ncomp=1))
     if args.evidence:
         print('tau of the cold rung :', np.round(sampler.get_autocorr_time(t=0, quiet=True), 2))
         print('R-hat of the cold rung:', np.round(sampler.get_rhat(t=0), 3), '(split, over the walkers)')

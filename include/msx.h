@@ -898,6 +898,46 @@ int msx_series_predictive(msx_series *src, msx_ctx **ctxs, int64_t n, int64_t di
                           int64_t scratch_bytes, double *band, double *quant, double *resid, msx_series *terms_dst,
                           int64_t *count, int32_t *worst_status);
 
+/* ---- posterior modes of a series: mixture fit, labels, the samples by mode ----------------------
+ * A Gaussian mixture of ncomp components over ncols columns of every member, by EM; mcmc_spec_amd/modes.py is the definition
+ * (standardised units z = (x - center) / scale, E-step through the Cholesky factor, the M-step with ridge on the diagonal,
+ * the stopping rule, the statuses).  The selection rows[0:n][discard::thin] (n' rows) is msx_series_acf's; a sample with a
+ * non-finite selected value enters no sum.  cols [ncols]: coordinates < ndim, at most MSX_MAX_DIM; NULL: all (ncols = ndim).
+ * center, scale [k][ncols].  A JOB is a (member, start): start s assigns a sample to the component numbered by how many of
+ * split_at[m][s][0 .. ncomp - 2] (raw units, not descending; NULL with ncomp = 1) are <= its column cols[split_col[s]], and the
+ * M-step of that assignment gives the first parameters; then up to max_iter iterations, every job's queued back to back with
+ * no host read in between (two launches an iteration; a job that stopped is skipped on a flag in device memory).
+ * Out, components in start order: weight [k][nstarts][ncomp], mean [..][ncomp][ncols], cov [..][ncomp][ncols][ncols]
+ * (standardised units, ridge included), loglik, niter, status [k][nstarts] (MSX_MODES_*), nbad [k].  The order of every sum
+ * depends on (n', W_m) alone: the same input gives the same bits whatever thin, discard, the buffer's capacity, how the rows
+ * arrived and how many jobs share the call.  Synchronous, on the series' own stream, waits for nothing but the latest growth
+ * copy; reads no row at or past n.  Refused before any launch, the series as it was -- MSX_ERR_INVALID: a null series or
+ * output, thin < 1, discard < 0, ncols < 1, nstarts < 1, a scale that is not finite or not > 0, a center that is not finite,
+ * ridge < 0, tol < 0 (or NaN), max_iter < 1.  MSX_ERR_RANGE: n past the rows held, fewer than 4 rows selected, a column >=
+ * ndim, ncols over MSX_MAX_DIM (or not ndim with cols NULL), ncomp outside 1 .. MSX_MODES_MAX, nstarts over 64, a split_col
+ * outside 0 .. ncols - 1, thresholds that descend (or NaN), N_m = n' W_m <= ncomp (ncols + 1).                              */
+#define MSX_MODES_MAX 4
+#define MSX_MODES_CONVERGED 0 /* |loglik - previous| <= tol |loglik| after iteration niter >= 2 */
+#define MSX_MODES_MAXITER 1   /* max_iter iterations run                                         */
+#define MSX_MODES_COLLAPSED 2 /* an M-step found a component holding less than one sample        */
+int msx_series_modes(msx_series *s, int64_t n, int64_t discard, int64_t thin, const uint32_t *cols, int32_t ncols,
+                     const double *center, const double *scale, int32_t ncomp, int32_t nstarts, const int32_t *split_col,
+                     const double *split_at, int32_t max_iter, double tol, double ridge, double *weight, double *mean,
+                     double *cov, double *loglik, int32_t *niter, int32_t *status, int64_t *nbad);
+/* Labels under ONE mixture per member -- weight [k][ncomp], mean [k][ncomp][ncols], cov [k][ncomp][ncols][ncols], the
+ * caller's (the call keeps no state) -- of the same selection: label = argmax_k lp_k, the lowest k on ties, 255 for a sample
+ * with a non-finite selected value.  labels_out: host uint8 [n'][nw], or NULL; counts_out [k][ncomp].  dst: NULL, or
+ * k * ncomp series created by the caller on s's device with nw = 1, one member, s's ndim and no run attached: dst[m * ncomp +
+ * j] receives ALL ndim coordinates of member m's samples labelled j, walker ascending, then row ascending (per-tile counts, an
+ * exclusive scan, ballot prefixes inside a tile: the same order every time).  It grows as msx_series_append grows a series
+ * and ends holding exactly counts_out[m][j] rows, possibly none; msx_series_order_stats / _hist / _hist2d / _moments, and
+ * msx_series_derive where products are staged, then work on a mode as on any series.  Synchronous, on s's stream.
+ * msx_series_modes' refusals where they apply; also MSX_ERR_RANGE: a covariance without a Cholesky factor, a weight that is
+ * negative or NaN; MSX_ERR_INVALID: a dst that does not match or is listed twice; MSX_ERR_STATE: a run attached to a dst.  */
+int msx_series_mode_labels(msx_series *s, int64_t n, int64_t discard, int64_t thin, const uint32_t *cols, int32_t ncols,
+                           const double *center, const double *scale, int32_t ncomp, const double *weight, const double *mean,
+                           const double *cov, uint8_t *labels_out, int64_t *counts_out, msx_series **dst);
+
 /* ---- test hooks (used by tests/ only) ------------------------------------------------------------ */
 /* MSX_HOOK_LINKED_FAULT: value != 0 makes the workgroups of the linked form skip their signal -- and the walkers of an
  * overlapped sampler run the publication of their new version -- so that every in-kernel wait runs into its bound;

@@ -27,6 +27,7 @@ FORM_NAMES = {0: 'fused', 1: 'pair (planner + two walkers of one grid cell per w
               3: 'in-path broadening (recipe, composite + convolution, resample, then the fused kernel on the given model values)'}
 HOOK_LINKED_FAULT, HOOK_PAIR_LEASES = 1, 2  # include/msx.h MSX_HOOK_*
 MAX_SPEC, MAX_BANDS, MAX_DIM = 3, 8, 8
+MODES_MAX = 4  # MSX_MODES_MAX: the components of a mixture (msx_series_modes)
 MAX_GROUP = 64  # include/msx.h MSX_MAX_GROUP: members of a target group
 PB_TRAPZ, PB_SUM, PB_MEAN = 0, 1, 2  # include/msx.h MSX_PB_*: the kinds of a product band
 SPEC_MEDIAN_SCALE = 1  # include/msx.h MSX_SPEC_MEDIAN_SCALE
@@ -224,6 +225,11 @@ def load():
                                            C.POINTER(C.c_int32), _ip]),
         'msx_series_predictive': (C.c_int, [vp, C.POINTER(vp), C.c_int64, C.c_int64, C.c_int64, _dp, C.c_int32, C.c_int64, _dp, _dp,
                                             _dp, vp, _ip, C.POINTER(C.c_int32)]),
+        'msx_series_modes': (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, _up, C.c_int32, _dp, _dp, C.c_int32, C.c_int32,
+                                       C.POINTER(C.c_int32), _dp, C.c_int32, C.c_double, C.c_double, _dp, _dp, _dp, _dp,
+                                       C.POINTER(C.c_int32), C.POINTER(C.c_int32), _ip]),
+        'msx_series_mode_labels': (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, _up, C.c_int32, _dp, _dp, C.c_int32, _dp, _dp, _dp,
+                                             C.POINTER(C.c_uint8), _ip, C.POINTER(vp)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = header/library skew, fail loudly
@@ -257,7 +263,8 @@ EXPORTED = ['msx_create', 'msx_destroy', 'msx_last_error', 'msx_device_info', 'm
             'msx_ladder_current', 'msx_ladder_step',
             'msx_group_tempered_begin', 'msx_group_tempered_enqueue', 'msx_group_tempered_enqueue_drawn', 'msx_group_tempered_collect',
             'msx_group_tempered_end', 'msx_group_tempered_attach_series', 'msx_group_ladder_adapt', 'msx_group_ladder_betas',
-            'msx_group_ladder_current', 'msx_series_moments', 'msx_predictive_batch', 'msx_series_predictive']
+            'msx_group_ladder_current', 'msx_series_moments', 'msx_predictive_batch', 'msx_series_predictive',
+            'msx_series_modes', 'msx_series_mode_labels']
 
 
 def as_f64(a):
@@ -1231,6 +1238,59 @@ class Series:
             rhat = np.sqrt(var_plus / within)
         count = len(range(int(discard), int(n), int(thin))) * self.counts
         return {'within': within, 'var_plus': var_plus, 'between': between, 'rhat': rhat, 'mean': mean, 'cov': cv, 'count': count}
+
+    def modes(self, n, discard, thin, cols, center, scale, ncomp, split_col, split_at, max_iter=50, tol=1e-10, ridge=1e-6):
+        """The EM fits of msx_series_modes (``mcmc_spec_amd.modes`` is the definition) over
+        rows[0:n][discard::thin]: ({'weight' (k, S, K), 'mean' (k, S, K, d), 'cov' (k, S, K, d, d), 'loglik', 'niter',
+        'status' (k, S)}, nbad (k,)) in standardised units, components in start order.  ``center``, ``scale`` (k, d);
+        ``split_col`` (S,) positions in ``cols``; ``split_at`` (k, S, K - 1) raw thresholds."""
+        cols = _col_codes(cols)
+        d, K = int(cols.size), int(ncomp)
+        center, scale = as_f64(center), as_f64(scale)
+        split_col = np.ascontiguousarray(split_col, dtype=np.int32).reshape(-1)
+        S = int(split_col.size)
+        split_at = as_f64(split_at)
+        if center.shape != (self.k, d) or scale.shape != (self.k, d) or split_at.size != self.k * S * max(K - 1, 0):
+            raise ValueError('modes: center and scale must have shape (k, ncols), split_at (k, nstarts, ncomp - 1)')
+        i32p = C.POINTER(C.c_int32)
+        Kc = max(K, 0)
+        out = {'weight': np.empty((self.k, S, Kc)), 'mean': np.empty((self.k, S, Kc, d)), 'cov': np.empty((self.k, S, Kc, d, d)),
+               'loglik': np.empty((self.k, S)), 'niter': np.zeros((self.k, S), dtype=np.int32),
+               'status': np.zeros((self.k, S), dtype=np.int32)}
+        nbad = np.zeros(self.k, dtype=np.int64)
+        self.check(self.lib.msx_series_modes(self.h, int(n), int(discard), int(thin), uptr(cols), d, dptr(center), dptr(scale), K, S,
+                                             split_col.ctypes.data_as(i32p), dptr(split_at) if split_at.size else None, int(max_iter),
+                                             float(tol), float(ridge), dptr(out['weight']), dptr(out['mean']), dptr(out['cov']),
+                                             dptr(out['loglik']), out['niter'].ctypes.data_as(i32p), out['status'].ctypes.data_as(i32p),
+                                             iptr(nbad)))
+        return out, nbad
+
+    def mode_labels(self, n, discard, thin, cols, center, scale, weight, mean, cov, dst=None, want_labels=True):
+        """(labels uint8 (n', nw) -- None without ``want_labels`` --, counts (k, K)) under one mixture per member
+        (msx_series_mode_labels): ``weight`` (k, K), ``mean`` (k, K, d), ``cov`` (k, K, d, d) in standardised units.
+        ``dst``: k * K series of one walker and this series' ndim, member-major; dst[m * K + j] is filled with member m's
+        samples labelled j (all coordinates; walker ascending, then row ascending) and holds exactly counts[m, j] rows."""
+        cols = _col_codes(cols)
+        d = int(cols.size)
+        center, scale, weight, mean, cov = (as_f64(a) for a in (center, scale, weight, mean, cov))
+        K = int(weight.shape[-1]) if weight.ndim else 0
+        if (center.shape != (self.k, d) or scale.shape != (self.k, d) or weight.shape != (self.k, K) or mean.shape != (self.k, K, d)
+                or cov.shape != (self.k, K, d, d)):
+            raise ValueError('mode_labels: center, scale (k, ncols); weight (k, K); mean (k, K, ncols); cov (k, K, ncols, ncols)')
+        nrows = len(range(int(discard), int(n), int(thin)))
+        labels = np.empty((max(nrows, 0), self.nw), dtype=np.uint8) if want_labels else None
+        counts = np.zeros((self.k, K), dtype=np.int64)
+        arr = None
+        if dst is not None:
+            dst = list(dst)
+            if len(dst) != self.k * K:
+                raise ValueError('mode_labels: one dst series per member and mode ({})'.format(self.k * K))
+            arr = (C.c_void_p * len(dst))(*[s.h for s in dst])
+        self.check(self.lib.msx_series_mode_labels(self.h, int(n), int(discard), int(thin), uptr(cols), d, dptr(center), dptr(scale), K,
+                                                   dptr(weight), dptr(mean), dptr(cov),
+                                                   None if labels is None else labels.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                   iptr(counts), arr))
+        return labels, counts
 
     def derive(self, contexts, cols, dst, row0=0, nrows=None):
         """Rows row0 .. row0 + nrows - 1 of this series mapped to the derived columns ``cols`` (codes) and written to the

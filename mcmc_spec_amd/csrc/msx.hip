@@ -49,6 +49,8 @@
 
 #include <algorithm>
 #include <array>
+#include <cmath>
+#include <limits>
 #include <mutex>
 #include <type_traits>
 #include <string>
@@ -76,6 +78,7 @@
 #include "diag_kernels.h"
 #include "product_kernels.h"
 #include "predictive_kernels.h"
+#include "mode_kernels.h"
 #include "opt_run_kernels.h"
 
 // ================================================================================================
@@ -5345,6 +5348,251 @@ int msx_series_predictive(msx_series *src, msx_ctx **ctxs, int64_t n, int64_t di
     if (dst) dst->rows = std::max(dst->rows, n);
     return MSX_OK;
 }
+
+// ---- posterior modes: mixture fit, labels, the samples by mode (mode_kernels.h) -----------------------
+// what both calls check of the selection, the columns and the standardisation; fills S (rows and the device tables apart)
+static int modes_selection(msx_series *sr, const char *who, int64_t n, int64_t discard, int64_t thin, const uint32_t *cols, int32_t ncols,
+                           const double *center, const double *scale, int32_t ncomp, ModeSel *S) {
+    const std::string w(who);
+    if (!center || !scale || discard < 0 || thin < 1 || ncols < 1)
+        return fail(sr, MSX_ERR_INVALID, w + ": bad arguments (discard >= 0, thin >= 1, ncols >= 1, center and scale)");
+    if (n < 1 || n > sr->rows) return fail(sr, MSX_ERR_RANGE, w + ": n must lie in 1 .. the rows the series holds");
+    const int64_t np = n > discard ? (n - discard + thin - 1) / thin : 0;
+    if (np < 4) return fail(sr, MSX_ERR_RANGE, w + ": the selection rows[0:n][discard::thin] needs at least 4 rows");
+    if (ncols > MSX_MAX_DIM) return fail(sr, MSX_ERR_RANGE, w + ": more columns than a series is wide (MSX_MAX_DIM)");
+    if (ncomp < 1 || ncomp > MSX_MODES_MAX) return fail(sr, MSX_ERR_RANGE, w + ": ncomp must lie in 1 .. MSX_MODES_MAX");
+    memset(S, 0, sizeof(*S));
+    S->cols.n = ncols;
+    if (!cols && ncols != sr->ndim) return fail(sr, MSX_ERR_RANGE, w + ": cols == NULL means all columns (ncols = ndim)");
+    for (int32_t q = 0; q < ncols; ++q) {
+        const uint32_t c = cols ? cols[q] : (uint32_t)q;
+        if (c >= (uint32_t)sr->ndim) return fail(sr, MSX_ERR_RANGE, w + ": a column outside the series");
+        S->cols.c[q] = (int32_t)c;
+    }
+    const int k = (int)sr->off.size() - 1;
+    for (int64_t i = 0; i < (int64_t)k * ncols; ++i)
+        if (!std::isfinite(center[i]) || !std::isfinite(scale[i]) || !(scale[i] > 0.0))
+            return fail(sr, MSX_ERR_INVALID, w + ": every center must be finite, every scale finite and > 0");
+    for (int m = 0; m < k; ++m)
+        if ((sr->off[(size_t)m + 1] - sr->off[(size_t)m]) * np <= (int64_t)ncomp * (ncols + 1))
+            return fail(sr, MSX_ERR_RANGE, w + ": a member needs more than ncomp (ncols + 1) samples");
+    const int64_t ntiles = (np + kModeTile - 1) / kModeTile;
+    if (sr->nw * ntiles > 0x7fffffff) return fail(sr, MSX_ERR_RANGE, w + ": more rows than one launch covers");
+    S->cap = sr->cap; S->nw = sr->nw; S->np = np; S->discard = discard; S->thin = thin; S->k = k;
+    return MSX_OK;
+}
+
+static size_t mode_align(size_t b) { return (b + 15) & ~(size_t)15; }
+
+#define MODE_DISPATCH(D, KERNEL, ...)                                     \
+    switch (D) {                                                          \
+    case 1: hipLaunchKernelGGL(KERNEL<1>, __VA_ARGS__); break;            \
+    case 2: hipLaunchKernelGGL(KERNEL<2>, __VA_ARGS__); break;            \
+    case 3: hipLaunchKernelGGL(KERNEL<3>, __VA_ARGS__); break;            \
+    case 4: hipLaunchKernelGGL(KERNEL<4>, __VA_ARGS__); break;            \
+    case 5: hipLaunchKernelGGL(KERNEL<5>, __VA_ARGS__); break;            \
+    case 6: hipLaunchKernelGGL(KERNEL<6>, __VA_ARGS__); break;            \
+    case 7: hipLaunchKernelGGL(KERNEL<7>, __VA_ARGS__); break;            \
+    default: hipLaunchKernelGGL(KERNEL<8>, __VA_ARGS__); break;           \
+    }
+
+int msx_series_modes(msx_series *sr, int64_t n, int64_t discard, int64_t thin, const uint32_t *cols, int32_t ncols, const double *center,
+                     const double *scale, int32_t ncomp, int32_t nstarts, const int32_t *split_col, const double *split_at, int32_t max_iter,
+                     double tol, double ridge, double *weight, double *mean, double *cov, double *loglik, int32_t *niter, int32_t *status,
+                     int64_t *nbad) {
+    if (!sr) return MSX_ERR_INVALID;
+    const std::string who("msx_series_modes");
+    if (!weight || !mean || !cov || !loglik || !niter || !status || !nbad || !split_col || nstarts < 1 || max_iter < 1 || !(tol >= 0.0) ||
+        !(ridge >= 0.0) || !std::isfinite(ridge))
+        return fail(sr, MSX_ERR_INVALID, who + ": bad arguments (every output, split_col, nstarts >= 1, max_iter >= 1, tol >= 0, ridge >= 0)");
+    ModeSel S;
+    if (int rc = modes_selection(sr, "msx_series_modes", n, discard, thin, cols, ncols, center, scale, ncomp, &S)) return rc;
+    if (ncomp > 1 && !split_at) return fail(sr, MSX_ERR_INVALID, who + ": split_at is needed with ncomp > 1");
+    if (nstarts > 64) return fail(sr, MSX_ERR_RANGE, who + ": at most 64 starts");
+    const int k = S.k, d = ncols, nthr = ncomp - 1;
+    std::vector<int32_t> scol((size_t)nstarts);
+    for (int32_t s = 0; s < nstarts; ++s) {
+        if (split_col[s] < 0 || split_col[s] >= ncols) return fail(sr, MSX_ERR_RANGE, who + ": a split_col outside 0 .. ncols - 1");
+        scol[(size_t)s] = S.cols.c[split_col[s]];
+    }
+    const int64_t njobs = (int64_t)k * nstarts;
+    for (int64_t j = 0; j < njobs; ++j)
+        for (int i = 0; i < nthr; ++i) {
+            const double a = split_at[j * nthr + i];
+            if (std::isnan(a) || (i > 0 && !(split_at[j * nthr + i - 1] <= a))) return fail(sr, MSX_ERR_RANGE, who + ": a start's thresholds must not descend");
+        }
+    HIP_TRY(sr, hipSetDevice(sr->device));
+    const int64_t ntiles = (S.np + kModeTile - 1) / kModeTile, nwt = sr->nw * ntiles;
+    const int P = 1 + d + d * (d + 1) / 2, nacc = P + 1;
+    // scratch: [part | params | weight mean cov loglik (downloaded in one piece) | prev | ngood | center | scale | split_at |
+    //           niter status (one piece) | frozen | split columns]
+    const size_t b_part = mode_align(sizeof(double) * (size_t)(nstarts * ncomp) * (size_t)nwt * (size_t)nacc);
+    const size_t b_params = mode_align(sizeof(double) * (size_t)(njobs * ncomp * P));
+    const int64_t n_w = njobs * ncomp, n_mean = n_w * d, n_cov = n_mean * d, n_out = n_w + n_mean + n_cov + njobs;
+    const size_t b_out = mode_align(sizeof(double) * (size_t)n_out), b_job = mode_align(sizeof(double) * (size_t)njobs);
+    const size_t b_cs = mode_align(sizeof(double) * (size_t)(k * d)), b_at = mode_align(sizeof(double) * (size_t)std::max<int64_t>(njobs * nthr, 1));
+    const size_t b_ij = mode_align(sizeof(int32_t) * (size_t)(2 * njobs)), b_fr = mode_align(sizeof(int32_t) * (size_t)njobs);
+    const size_t b_sc = mode_align(sizeof(int32_t) * (size_t)nstarts);
+    HIP_TRY(sr, series_scratch(sr, b_part + b_params + b_out + 2 * b_job + 2 * b_cs + b_at + b_ij + b_fr + b_sc));
+    char *p = sr->d_scratch;
+    double *d_part = (double *)p; p += b_part;
+    double *d_params = (double *)p; p += b_params;
+    double *d_out = (double *)p; p += b_out;
+    double *d_weight = d_out, *d_mean = d_weight + n_w, *d_cov = d_mean + n_mean, *d_loglik = d_cov + n_cov;
+    double *d_prev = (double *)p; p += b_job;
+    double *d_ngood = (double *)p; p += b_job;
+    double *d_center = (double *)p; p += b_cs;
+    double *d_scale = (double *)p; p += b_cs;
+    double *d_at = (double *)p; p += b_at;
+    int32_t *d_niter = (int32_t *)p, *d_status = d_niter + njobs; p += b_ij;
+    int32_t *d_frozen = (int32_t *)p; p += b_fr;
+    int32_t *d_scol = (int32_t *)p;
+    hipStream_t st = sr->stream;
+    // the state every job starts from: no parameters (NaN), loglik NaN, niter 0, status collapsed until an iteration ran
+    std::vector<double> h_out((size_t)n_out, std::numeric_limits<double>::quiet_NaN());
+    std::vector<int32_t> h_ij((size_t)(2 * njobs), 0);
+    for (int64_t j = 0; j < njobs; ++j) h_ij[(size_t)(njobs + j)] = MSX_MODES_COLLAPSED;
+    HIP_TRY(sr, hipMemcpyAsync(d_out, h_out.data(), sizeof(double) * (size_t)n_out, hipMemcpyHostToDevice, st));
+    HIP_TRY(sr, hipMemcpyAsync(d_niter, h_ij.data(), sizeof(int32_t) * (size_t)(2 * njobs), hipMemcpyHostToDevice, st));
+    HIP_TRY(sr, hipMemsetAsync(d_frozen, 0, sizeof(int32_t) * (size_t)njobs, st));
+    HIP_TRY(sr, hipMemsetAsync(d_prev, 0, 2 * b_job, st));
+    HIP_TRY(sr, hipMemcpyAsync(d_center, center, sizeof(double) * (size_t)(k * d), hipMemcpyHostToDevice, st));
+    HIP_TRY(sr, hipMemcpyAsync(d_scale, scale, sizeof(double) * (size_t)(k * d), hipMemcpyHostToDevice, st));
+    if (nthr > 0) HIP_TRY(sr, hipMemcpyAsync(d_at, split_at, sizeof(double) * (size_t)(njobs * nthr), hipMemcpyHostToDevice, st));
+    HIP_TRY(sr, hipMemcpyAsync(d_scol, scol.data(), sizeof(int32_t) * (size_t)nstarts, hipMemcpyHostToDevice, st));
+    HIP_TRY(sr, series_wait_growth(sr));
+    S.rows = sr->d_rows; S.cap = sr->cap; S.member_off = sr->d_off; S.center = d_center; S.scale = d_scale;
+    const dim3 sgrid((unsigned)nwt, (unsigned)(nstarts * ncomp));
+    for (int32_t it = 0; it <= max_iter; ++it) {
+        MODE_DISPATCH(d, mode_stats_kernel, sgrid, dim3(kModeThreads), 0, st, S, nstarts, ncomp, (int32_t)(it == 0), (const int32_t *)d_scol,
+                      (const double *)d_at, (const double *)d_params, (const int32_t *)d_frozen, d_part);
+        HIP_TRY(sr, hipGetLastError());
+        hipLaunchKernelGGL(mode_mstep_kernel, dim3((unsigned)njobs), dim3(kModeThreads), 0, st, (const double *)d_part, (const int64_t *)sr->d_off,
+                           sr->nw, ntiles, nstarts, ncomp, (int32_t)d, it, max_iter, tol, ridge, d_params, d_weight, d_mean, d_cov, d_loglik, d_prev,
+                           d_ngood, d_niter, d_status, d_frozen);
+        HIP_TRY(sr, hipGetLastError());
+    }
+    std::vector<double> h_good((size_t)njobs);
+    HIP_TRY(sr, hipMemcpyAsync(h_out.data(), d_out, sizeof(double) * (size_t)n_out, hipMemcpyDeviceToHost, st));
+    HIP_TRY(sr, hipMemcpyAsync(h_ij.data(), d_niter, sizeof(int32_t) * (size_t)(2 * njobs), hipMemcpyDeviceToHost, st));
+    HIP_TRY(sr, hipMemcpyAsync(h_good.data(), d_ngood, sizeof(double) * (size_t)njobs, hipMemcpyDeviceToHost, st));
+    HIP_TRY(sr, hipStreamSynchronize(st));
+    memcpy(weight, h_out.data(), sizeof(double) * (size_t)n_w);
+    memcpy(mean, h_out.data() + n_w, sizeof(double) * (size_t)n_mean);
+    memcpy(cov, h_out.data() + n_w + n_mean, sizeof(double) * (size_t)n_cov);
+    memcpy(loglik, h_out.data() + n_w + n_mean + n_cov, sizeof(double) * (size_t)njobs);
+    memcpy(niter, h_ij.data(), sizeof(int32_t) * (size_t)njobs);
+    memcpy(status, h_ij.data() + njobs, sizeof(int32_t) * (size_t)njobs);
+    for (int m = 0; m < k; ++m)   // (start 0's count: every start of a member sees the same samples)
+        nbad[m] = (sr->off[(size_t)m + 1] - sr->off[(size_t)m]) * S.np - (int64_t)h_good[(size_t)m * nstarts];
+    return MSX_OK;
+}
+
+int msx_series_mode_labels(msx_series *sr, int64_t n, int64_t discard, int64_t thin, const uint32_t *cols, int32_t ncols, const double *center,
+                           const double *scale, int32_t ncomp, const double *weight, const double *mean, const double *cov, uint8_t *labels_out,
+                           int64_t *counts_out, msx_series **dst) {
+    if (!sr) return MSX_ERR_INVALID;
+    const std::string who("msx_series_mode_labels");
+    if (!weight || !mean || !cov || !counts_out) return fail(sr, MSX_ERR_INVALID, who + ": bad arguments (weight, mean, cov and counts_out)");
+    ModeSel S;
+    if (int rc = modes_selection(sr, "msx_series_mode_labels", n, discard, thin, cols, ncols, center, scale, ncomp, &S)) return rc;
+    const int k = S.k, d = ncols;
+    const int P = 1 + d + d * (d + 1) / 2;
+    const int64_t nmode = (int64_t)k * ncomp;
+    // every component's [c | mu | L by rows] from the caller's weight, mean and covariance
+    std::vector<double> prm((size_t)(nmode * P));
+    for (int64_t c = 0; c < nmode; ++c) {
+        double *pp = prm.data() + c * P, *L = pp + 1 + d;
+        const double *sg = cov + c * d * d;
+        if (!(weight[c] >= 0.0)) return fail(sr, MSX_ERR_RANGE, who + ": a weight that is negative or NaN");
+        double logdet = 0.0;
+        for (int r = 0; r < d; ++r)
+            for (int q = 0; q <= r; ++q) {
+                double s = sg[r * d + q];
+                for (int j = 0; j < q; ++j) s -= L[r * (r + 1) / 2 + j] * L[q * (q + 1) / 2 + j];
+                if (r == q) {
+                    if (!(s > 0.0) || !std::isfinite(s)) return fail(sr, MSX_ERR_RANGE, who + ": a covariance without a Cholesky factor");
+                    L[r * (r + 1) / 2 + q] = std::sqrt(s);
+                    logdet += std::log(L[r * (r + 1) / 2 + q]);
+                } else {
+                    L[r * (r + 1) / 2 + q] = s / L[q * (q + 1) / 2 + q];
+                }
+            }
+        pp[0] = std::log(weight[c]) - logdet - 0.5 * d * kModeLn2Pi;
+        for (int q = 0; q < d; ++q) {
+            if (!std::isfinite(mean[c * d + q])) return fail(sr, MSX_ERR_RANGE, who + ": a mean that is not finite");
+            pp[1 + q] = mean[c * d + q];
+        }
+    }
+    if (dst)
+        for (int64_t c = 0; c < nmode; ++c) {
+            msx_series *t = dst[c];
+            if (!t || t == sr || t->device != sr->device || t->nw != 1 || t->off.size() != 2 || t->ndim != sr->ndim)
+                return fail(sr, MSX_ERR_INVALID, who + ": every dst must be another series on the same device with one walker, one member and src's ndim");
+            for (int64_t e = 0; e < c; ++e)
+                if (dst[e] == t) return fail(sr, MSX_ERR_INVALID, who + ": a dst is listed twice");
+            if (t->run || t->trun || t->gtrun) return fail(sr, MSX_ERR_STATE, who + ": a run in flight appends to a dst");
+        }
+    HIP_TRY(sr, hipSetDevice(sr->device));
+    const int64_t ntiles = (S.np + kModeTile - 1) / kModeTile, nwt = sr->nw * ntiles;
+    // scratch: [params | center | scale | tilecount | base | total | dst table | labels]
+    const size_t b_prm = mode_align(sizeof(double) * prm.size()), b_cs = mode_align(sizeof(double) * (size_t)(k * d));
+    const size_t b_tc = mode_align(sizeof(int64_t) * (size_t)(nwt * MSX_MODES_MAX)), b_tot = mode_align(sizeof(int64_t) * (size_t)(k * MSX_MODES_MAX));
+    const size_t b_dst = mode_align(sizeof(ModeDst) * (size_t)nmode), b_lab = mode_align((size_t)(sr->nw * S.np));
+    HIP_TRY(sr, series_scratch(sr, b_prm + 2 * b_cs + 2 * b_tc + b_tot + b_dst + b_lab));
+    char *p = sr->d_scratch;
+    double *d_prm = (double *)p; p += b_prm;
+    double *d_center = (double *)p; p += b_cs;
+    double *d_scale = (double *)p; p += b_cs;
+    int64_t *d_tc = (int64_t *)p; p += b_tc;
+    int64_t *d_base = (int64_t *)p; p += b_tc;
+    int64_t *d_total = (int64_t *)p; p += b_tot;
+    ModeDst *d_dst = (ModeDst *)p; p += b_dst;
+    uint8_t *d_lab = (uint8_t *)p;
+    hipStream_t st = sr->stream;
+    HIP_TRY(sr, hipMemcpyAsync(d_prm, prm.data(), sizeof(double) * prm.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(sr, hipMemcpyAsync(d_center, center, sizeof(double) * (size_t)(k * d), hipMemcpyHostToDevice, st));
+    HIP_TRY(sr, hipMemcpyAsync(d_scale, scale, sizeof(double) * (size_t)(k * d), hipMemcpyHostToDevice, st));
+    HIP_TRY(sr, series_wait_growth(sr));
+    S.rows = sr->d_rows; S.cap = sr->cap; S.member_off = sr->d_off; S.center = d_center; S.scale = d_scale;
+    MODE_DISPATCH(d, mode_label_kernel, dim3((unsigned)nwt), dim3(kModeThreads), 0, st, S, ncomp, (const double *)d_prm, d_lab, d_tc);
+    HIP_TRY(sr, hipGetLastError());
+    hipLaunchKernelGGL(mode_scan_kernel, dim3((unsigned)k), dim3(MSX_MODES_MAX), 0, st, (const int64_t *)d_tc, (const int64_t *)sr->d_off, ntiles,
+                       d_base, d_total);
+    HIP_TRY(sr, hipGetLastError());
+    std::vector<int64_t> total((size_t)(k * MSX_MODES_MAX));
+    std::vector<uint8_t> lab;
+    HIP_TRY(sr, hipMemcpyAsync(total.data(), d_total, sizeof(int64_t) * total.size(), hipMemcpyDeviceToHost, st));
+    if (labels_out) {
+        lab.resize((size_t)(sr->nw * S.np));
+        HIP_TRY(sr, hipMemcpyAsync(lab.data(), d_lab, lab.size(), hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(sr, hipStreamSynchronize(st));
+    for (int m = 0; m < k; ++m)
+        for (int j = 0; j < ncomp; ++j) counts_out[m * ncomp + j] = total[(size_t)(m * MSX_MODES_MAX + j)];
+    if (labels_out)   // device [nw][n'] -> host [n'][nw]
+        for (int64_t w = 0; w < sr->nw; ++w)
+            for (int64_t t = 0; t < S.np; ++t) labels_out[t * sr->nw + w] = lab[(size_t)(w * S.np + t)];
+    if (!dst) return MSX_OK;
+    // every dst holds exactly its label's rows: grown the way append grows a series (nothing carried over), then filled
+    std::vector<ModeDst> table((size_t)nmode);
+    for (int64_t c = 0; c < nmode; ++c) {
+        msx_series *t = dst[c];
+        HIP_TRY(sr, series_reserve(t, counts_out[c], 0, st));
+        table[(size_t)c].rows = t->d_rows;
+        table[(size_t)c].cap = t->cap;
+    }
+    HIP_TRY(sr, hipMemcpyAsync(d_dst, table.data(), sizeof(ModeDst) * (size_t)nmode, hipMemcpyHostToDevice, st));
+    for (int64_t c = 0; c < nmode; ++c)
+        if (dst[c]->grown_set) HIP_TRY(sr, hipStreamWaitEvent(st, dst[c]->grown, 0));
+    hipLaunchKernelGGL(mode_scatter_kernel, dim3((unsigned)nwt), dim3(kModeThreads), 0, st, S, (int32_t)sr->ndim, ncomp, (const uint8_t *)d_lab,
+                       (const int64_t *)d_base, (const ModeDst *)d_dst);
+    HIP_TRY(sr, hipGetLastError());
+    HIP_TRY(sr, hipStreamSynchronize(st));
+    for (int64_t c = 0; c < nmode; ++c) dst[c]->rows = counts_out[c];
+    return MSX_OK;
+}
+#undef MODE_DISPATCH
 
 int msx_test_hook(msx_ctx *c, int32_t what, int32_t value) {
     if (!c) return MSX_ERR_INVALID;

@@ -232,6 +232,17 @@ class GroupSampler:
         outs = [s.get_moments(**kw) for s in self.samplers]
         return {name: np.array([o[name] for o in outs]) for name in _MOMENTS}
 
+    def _host_members(self):
+        """The targets' stored chains side by side: (n, sum of the walkers, ndim)."""
+        return np.concatenate([np.array(s._chain) for s in self.samplers], axis=1)
+
+    def get_modes(self, k=None, ncomp=2, discard=0, thin=1, cols=None, **fit_kw):
+        """Every target's posterior modes (EnsembleSampler.get_modes: a ``modes.ModeFit`` with one member per target), or
+        target k's alone (the same object cut to that member)."""
+        from . import modes
+        out = modes.fit(self._host_members(), list(self.nwalkers), cols, ncomp, discard=discard, thin=thin, **fit_kw)
+        return out if k is None else out.select([k])
+
 
 class DeviceGroupSampler(GroupSampler):
     """``GroupSampler`` with the K ensembles resident in HBM (``msx_group_sampler_*``, include/msx.h): ``chunk`` iterations
@@ -419,6 +430,14 @@ class DeviceGroupSampler(GroupSampler):
             return super().get_moments(k, discard=discard, thin=thin, cols=cols)
         out = _device_moments(self._series, len(self.samplers[0]._chain), discard, thin, cols, True)
         return {name: out[name] if k is None else out[name][k] for name in _MOMENTS}
+
+    def get_modes(self, k=None, ncomp=2, discard=0, thin=1, cols=None, **fit_kw):
+        """GroupSampler.get_modes on the device, every target's EM jobs in ONE msx_series_modes call: with autocorr='device'
+        on the chains held there, otherwise the host chains are uploaded first (DeviceEnsembleSampler.get_modes' rules)."""
+        from . import modes
+        out = modes.of_sampler(self._series, self._host_members, len(self.samplers[0]._chain), self.group.engines[0].ctx,
+                               list(self.nwalkers), ncomp, discard, thin, cols, fit_kw)
+        return out if k is None else out.select([k])
 
     def get_summary(self, k=None, q=(0.16, 0.5, 0.84), discard=0, thin=1, cols=None):
         """Every target's posterior summary from its stored chain, flattened over its walkers: {'count' (K,), 'min', 'max'

@@ -288,6 +288,14 @@ class EnsembleSampler:
         from . import diagnostics
         return diagnostics.moments(_selection(self._chain, discard, thin, cols))
 
+    def get_modes(self, ncomp=2, discard=0, thin=1, cols=None, **fit_kw):
+        """The posterior's modes: a joint Gaussian mixture of ``ncomp`` components over the columns ``cols`` (None: all)
+        of ``get_chain(discard=, thin=, flat=True)``, as a ``modes.ModeFit`` (one member) whose ``labels()``, ``split()``
+        and ``summary()`` give every sample's mode and the per-mode quantiles (``mcmc_spec_amd.modes``; DESIGN.md section
+        23).  ``fit_kw``: ``modes.fit``'s max_iter, tol, ridge, center, scale, split_col, split_at."""
+        from . import modes
+        return modes.fit(np.array(self._chain), None, cols, ncomp, discard=discard, thin=thin, **fit_kw)
+
 
 def _selection(rows, discard, thin, cols):
     """Stored rows (a list of (nw, ndim) arrays, or an array) as the selection (n', nw, ncols) of get_rhat / get_moments."""
@@ -613,6 +621,14 @@ class DeviceEnsembleSampler(EnsembleSampler):
             return super().get_moments(discard=discard, thin=thin, cols=cols)
         out = _device_moments(self._series, len(self._chain), discard, thin, cols, True)
         return {name: out[name][0] for name in _MOMENTS}
+
+    def get_modes(self, ncomp=2, discard=0, thin=1, cols=None, **fit_kw):
+        """EnsembleSampler.get_modes on the device (msx_series_modes, msx_series_mode_labels): with autocorr='device' on
+        the chain held there, without a download (rows past len(self._chain) are not part of it); otherwise the host chain
+        is uploaded first and the result keeps that copy until its ``close()``."""
+        from . import modes
+        return modes.of_sampler(self._series, lambda: np.array(self._chain), len(self._chain), self.engine.ctx, None, ncomp, discard,
+                                thin, cols, fit_kw)
 
     def get_summary(self, q=(0.16, 0.5, 0.84), discard=0, thin=1, cols=None):
         """The posterior summary of the stored chain, flattened over the walkers: {'count': N, 'min', 'max' (ncols,),

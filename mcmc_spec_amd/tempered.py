@@ -404,6 +404,23 @@ class _Ladder:
         out = self._moments(t, discard, thin, cols, True)
         return {name: out[name] for name in ('mean', 'cov', 'count')}
 
+    _device_modes = False    # get_modes: the device calls (the device samplers) or the definition (TemperedSampler)
+
+    def get_modes(self, t=0, ncomp=2, discard=0, thin=1, cols=None, **fit_kw):
+        """Rung t's posterior modes -- rung 0 is the posterior -- as ``EnsembleSampler.get_modes`` gives them (a
+        ``modes.ModeFit`` cut to that rung); ``t=None``: every rung's, one member per rung.  TemperedSampler uses the
+        definition on the host chain; the device samplers the chain held on the device with autocorr='device' (every rung's
+        jobs in one msx_series_modes call) and upload the host chain otherwise."""
+        from . import modes
+        rungs = list(range(self.ntemps)) if t is None else [int(t)]
+        if not self._device_modes:
+            out = modes.fit(self._flat_members(), [self.nwalkers] * self.ntemps, cols, ncomp, discard=discard, thin=thin, **fit_kw)
+            return out.select(rungs)
+        out = modes.of_sampler(self._series, self._flat_members, len(self._chain), self._ctx(), [self.nwalkers] * self.ntemps, ncomp,
+                               discard, thin, cols, fit_kw)
+        own = list(range(out.k))[self._own] if self._series is not None else list(range(self.ntemps))
+        return out.select([own[r] for r in rungs])
+
     def get_summary(self, t=0, q=(0.16, 0.5, 0.84), discard=0, thin=1, cols=None):
         """Rung t's posterior summary over its stored chain, flattened over its walkers (``DeviceEnsembleSampler.get_summary``'s
         dict and numbers: DESIGN.md section 14); ``t=None``: every rung's, the arrays with a leading axis T.  With
@@ -705,6 +722,8 @@ class DeviceTemperedSampler(_Ladder):
     planned, when known); the series grow by doubling otherwise.  ``reset()`` drops the rows.  The chain is the same, bit
     for bit, whatever ``autocorr`` is."""
 
+    _device_modes = True
+
     def __init__(self, nwalkers, ndim, engine, ntemps=None, betas=None, beta_min=0.02, seed=None, seeds=None, chunk=64, rng='host',
                  moves=None, autocorr='host', cap_hint=0, adaptive=False, adaptation_lag=10000.0, adaptation_time=100.0):
         if rng not in ('host', 'device'):
@@ -988,6 +1007,7 @@ class _TargetLadder(_Ladder):
 
     _series = property(lambda self: self.parent._series)
     _dens = property(lambda self: self.parent._dens)
+    _device_modes = True
     _evaluate = DeviceTemperedSampler._evaluate
 
     def _series_engines(self):

@@ -17,6 +17,9 @@ run kept on the GPU with ``--autocorr device``; an evidence run wants a much sma
 ``--adaptive N`` first moves the rungs for N iterations until adjacent pairs swap at equal rates (section 19), prints the
 ladder before and after with the swap fractions, freezes it and goes on as above.  ``--modes`` prints the posterior's modes
 (mcmc_spec_amd.modes; section 23): per mode its probability and the 16 / 50 / 84 percentiles of every coordinate.
+``--reweight`` asks the finished chain a second question without a second run (mcmc_spec_amd.reweight; section 24): the
+same data staged under a second parallax prior, the effective sample size of the reweighted chain and both sets of
+16 / 50 / 84.
 """
 import argparse
 import os
@@ -50,6 +53,9 @@ def main():
     ap.add_argument('--modes', action='store_true',
                     help="after the run: the posterior's modes (a two-component mixture over the six coordinates), each mode's "
                          "probability and 16 / 50 / 84, and bic1 - bic2 (positive: two modes)")
+    ap.add_argument('--reweight', type=float, default=None, metavar='SIGMAS', nargs='?', const=1.0,
+                    help="after the run: the posterior under a second parallax prior whose mean lies SIGMAS (default 1) of its "
+                         "width higher, by importance reweighting of the stored chain: the ESS and both sets of 16 / 50 / 84")
     ap.add_argument('--evidence', action='store_true',
                     help="with --tempered: print the cold rung's tau and ln Z +- mc_error (ladder ladder_error)")
     args = ap.parse_args()
@@ -136,6 +142,24 @@ def main():
     if args.predictive:   # does the model reproduce the data, and which data carry chi^2?  (mft6.py:2361-2438, on every sample)
         from mcmc_spec_amd import predictive
         predictive.print_report(predictive.check(eng, sampler.get_chain(flat=True)), wl_um)
+    if args.reweight is not None:   # what would another parallax prior have given?  One chain, two questions: a paired comparison
+        from mcmc_spec_amd import summary
+        from mcmc_spec_amd.engine import Engine
+        eng2 = Engine(0)
+        eng2.stage_specs(specs)
+        prior2 = [*np.zeros(10), plx + args.reweight * plx_err, plx_err]
+        eng2.stage_problem(data, err, fr, [wl_um.min(), wl_um.max()], ctm, ptm, tmi, tma, matrix, nspec=2, bands=gpu._BANDS,
+                           av_table=gpu._AV_TABLE, tmin=3000.0, tmax=4200.0, prior=prior2, use_av=True, dist_fit=True, rad_prior=False)
+        with sampler.get_reweighted(eng2) as rw_:
+            n = int(rw_.stats['count'][0])
+            print('reweighted to the parallax prior {:.5g} +- {:.2g} (was {:.5g}): ESS {:.1f} of {} samples, {} bad'.format(
+                prior2[-2], plx_err, plx, rw_.stats['ess'][0], n, int(rw_.stats['nbad'][0])))
+            (resampled,) = rw_.resample()
+            second = summary.summary_of(resampled, resampled.rows)
+            resampled.close()
+        print('posterior 16 / 50 / 84 under the first prior | under the second:')
+        for nm, a3, b3 in zip(['T1', 'T2', 'Av', 'R1', 'R2', 'plx'], summ['quantiles'], second['quantiles'][0]):
+            print('  {:4s} {:.6g} / {:.6g} / {:.6g}  |  {:.6g} / {:.6g} / {:.6g}'.format(nm, *a3, *b3))
     print('wrote', os.path.join(args.out, 'samples.txt'), samples.shape)
     return truth, med, samples
 

@@ -938,6 +938,69 @@ int msx_series_mode_labels(msx_series *s, int64_t n, int64_t discard, int64_t th
                            const double *center, const double *scale, int32_t ncomp, const double *weight, const double *mean,
                            const double *cov, uint8_t *labels_out, int64_t *counts_out, msx_series **dst);
 
+/* ---- importance reweighting of a series: re-scored rows, weights, weighted moments, resampling ----
+ * Asking a finished chain another question -- another prior, another likelihood term, a ladder's rung -- without a second
+ * run: the chain's rows are scored again, the difference of two log-densities is a log-weight, and the weighted chain is
+ * summarised or resampled; mcmc_spec_amd/reweight.py is the NumPy definition of all but the first call.  Host pointers;
+ * synchronous, on the named series' own stream; every call waits for nothing but the latest growth copies of the series it
+ * touches: the rows read must be in place.  The selection rows[0:n][discard::thin] (n' rows) is msx_series_acf's; member m's
+ * FLAT sample is in (row, walker) order -- get_chain(flat=True)'s --, flat index i = t W_m + walker, N_m = n' W_m.  A
+ * "weights" series has ndim = 1 and the members of the series it weighs.  SUMS are formed per walker (element i, i + 256, ..
+ * one after the other, then a fixed tree over the 256 partial sums) and then over the member's walkers in walker order:
+ * float64 + - * / in an order fixed by (n', W_m) alone, so the same input gives the same bits whatever thin, discard, the
+ * buffer's capacity and how the rows arrived.  A refused call leaves every series as it was.  Common refusals --
+ * MSX_ERR_INVALID: null pointers, discard < 0, thin < 1, series that do not match (device, members, ndim); MSX_ERR_RANGE: n
+ * or rows past the ones a series holds, an empty selection, a column outside its series; MSX_ERR_STATE: a run attached to a
+ * series that would be written.                                                                                            */
+
+/* Rows row0 .. row0 + nrows - 1 of src (ndim = 2 nspec + 2) through the unchanged evaluation (msx_logprob_batch_dev) with
+ * ctxs[m]'s staged problem for member m, in `mode` (MSX_MODE_LOGPOST, MSX_MODE_LOGPRIOR or MSX_MODE_LOGLIKE), into the same
+ * rows of dst: a series with src's members and ndim = 1, which grows and is overwritten as msx_series_derive's dst is.  A
+ * value carries the bits msx_logprob_batch gives that theta on that context; a rejected sample (MSX_W_REJECT) gives -inf; a
+ * sample with an error status gives NaN and its status is reported: worst_status [k] (may be NULL), the worst per member.
+ * Rows are gathered and evaluated member by member in batches of at most 65,536 samples from the series' scratch; a sample's
+ * bits do not depend on the launch it shares, so not on the batch.  No products need be staged.  MSX_ERR_STATE: a member
+ * without a staged problem, or with a run of its own in flight.  MSX_ERR_INVALID: another mode, ndim != 2 nspec + 2.        */
+int msx_series_logprob(msx_series *src, msx_ctx **ctxs, int32_t mode, int64_t row0, int64_t nrows, msx_series *dst,
+                       int32_t *worst_status);
+/* dst[row][walker] = ((coef[0] x_0) + coef[1] x_1) + ..., x_j = srcs[j][row][walker][cols[j]], for rows row0 .. row0 + nrows
+ * - 1: each product rounded, then the additions in j order, no FMA contraction -- NumPy's bits for coef[0] * x0 + coef[1] * x1
+ * + ...  IEEE special values pass through.  nsrc 1 .. 8; dst (ndim = 1) is none of the sources and shares their members; it
+ * grows and is overwritten as msx_series_derive's dst is.  The result is a log-weight: lp_new - lp_old, (1 - beta) ll of a
+ * ladder's dens series, +0.5 chi_contrast of a terms series, or any mixture.  On dst's stream; dst carries the error text.  */
+int msx_series_lincomb(int32_t nsrc, msx_series **srcs, const int32_t *cols, const double *coef, int64_t row0, int64_t nrows,
+                       msx_series *dst);
+/* The weights of the log-weights logw (ndim = 1): per member M_m = the maximum over rows [0, n) of the values that are finite
+ * or -inf, and w = exp(logw - M_m) into rows [0, n) of w_dst (it grows as above and then holds max(rows, n) rows).  A NaN or
+ * +inf log-weight is BAD and weighs 0; -inf weighs 0; a member without a finite value has all weights 0.  stats [k][6] over
+ * the SELECTION: count N_m, nbad, nzero (weights == 0 that are not bad), sum w, sum w^2 and Kish's effective sample size
+ * (sum w)^2 / sum w^2 (0 when nothing weighs), the sums in the order above.  exp is the device library's.                 */
+int msx_series_weights(msx_series *logw, int64_t n, int64_t discard, int64_t thin, msx_series *w_dst, double *stats);
+/* Weighted moments of the selection of src under the weights w: per member sumw [k] = sum w (msx_series_weights' sum, its
+ * bits), mean [k][ncols] = sum (w x) / sum w, and cov [k][ncols][ncols] (or NULL) = sum (w ((x_d - mean_d)(x_e - mean_e))) /
+ * sum w -- the second of two passes, for d <= e and mirrored.  cols as msx_series_moments'.  A sample of zero weight enters
+ * no sum, whatever its values; with a non-zero weight a non-finite value poisons its column, as IEEE arithmetic does.       */
+int msx_series_wmoments(msx_series *src, msx_series *w, int64_t n, int64_t discard, int64_t thin, const uint32_t *cols,
+                        int32_t ncols, double *sumw, double *mean, double *cov);
+/* Systematic resampling.  Member m's selected samples have the weights w_0 .. w_{N-1} in flat order; their inclusive prefix
+ * sums C_i come from a three-phase scan over tiles of MSX_RESAMPLE_TILE consecutive samples:
+ *   1. inside a tile, lane l of 256 adds its MSX_RESAMPLE_TILE / 256 consecutive values one after the other, and the lanes'
+ *      totals are scanned serially in lane order: local_i = E_l + s_e; the tile's sum is the last of them;
+ *   2. the tiles' sums are scanned serially in tile order: B_0 = 0, B_{j+1} = B_j + sum_j;
+ *   3. C_i = B_tile + local_i.
+ * The bits of C depend on N and the values alone, and C never decreases: each level's last value is exactly the next base.
+ * W = C_{N-1}, step = W / nout[m], u0 = one uniform of the counter generator (stream 15, index 0, with the member's number
+ * in the iteration's place), t_j = (j + u0) * step in two roundings for j < nout[m], and sample j is the first i with C_i >
+ * t_j, clamped to the last i with w_i > 0: a sample of zero weight is never drawn.  dst [k]: caller-created series on src's
+ * device with one walker, one member and src's ndim (msx_series_mode_labels' dst); dst[m] receives all ndim coordinates of
+ * the drawn samples in j order and ends holding exactly nout[m] rows, possibly none.  index_out: NULL, or sum nout int64,
+ * member after member: the drawn flat indices.  MSX_ERR_RANGE, before anything is written to a dst: a weight that is
+ * negative, NaN or infinite; W == 0 (or not finite) for a member with nout > 0.  MSX_ERR_INVALID: a negative nout, a dst
+ * that does not match or is listed twice.                                                                                  */
+#define MSX_RESAMPLE_TILE 1024
+int msx_series_resample(msx_series *src, msx_series *w, int64_t n, int64_t discard, int64_t thin, uint64_t seed,
+                        const int64_t *nout, msx_series **dst, int64_t *index_out);
+
 /* ---- test hooks (used by tests/ only) ------------------------------------------------------------ */
 /* MSX_HOOK_LINKED_FAULT: value != 0 makes the workgroups of the linked form skip their signal -- and the walkers of an
  * overlapped sampler run the publication of their new version -- so that every in-kernel wait runs into its bound;

@@ -29,6 +29,7 @@ HOOK_LINKED_FAULT, HOOK_PAIR_LEASES = 1, 2  # include/msx.h MSX_HOOK_*
 MAX_SPEC, MAX_BANDS, MAX_DIM = 3, 8, 8
 MODES_MAX = 4  # MSX_MODES_MAX: the components of a mixture (msx_series_modes)
 MAX_GROUP = 64  # include/msx.h MSX_MAX_GROUP: members of a target group
+RESAMPLE_TILE = 1024  # include/msx.h MSX_RESAMPLE_TILE: the samples of one tile of msx_series_resample's prefix scan
 PB_TRAPZ, PB_SUM, PB_MEAN = 0, 1, 2  # include/msx.h MSX_PB_*: the kinds of a product band
 SPEC_MEDIAN_SCALE = 1  # include/msx.h MSX_SPEC_MEDIAN_SCALE
 MAX_PCOLS = 64  # include/msx.h MSX_MAX_PCOLS: derived columns of one products_batch call
@@ -230,6 +231,11 @@ def load():
                                        C.POINTER(C.c_int32), C.POINTER(C.c_int32), _ip]),
         'msx_series_mode_labels': (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, _up, C.c_int32, _dp, _dp, C.c_int32, _dp, _dp, _dp,
                                              C.POINTER(C.c_uint8), _ip, C.POINTER(vp)]),
+        'msx_series_logprob': (C.c_int, [vp, C.POINTER(vp), C.c_int32, C.c_int64, C.c_int64, vp, C.POINTER(C.c_int32)]),
+        'msx_series_lincomb': (C.c_int, [C.c_int32, C.POINTER(vp), C.POINTER(C.c_int32), _dp, C.c_int64, C.c_int64, vp]),
+        'msx_series_weights': (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, vp, _dp]),
+        'msx_series_wmoments': (C.c_int, [vp, vp, C.c_int64, C.c_int64, C.c_int64, _up, C.c_int32, _dp, _dp, _dp]),
+        'msx_series_resample': (C.c_int, [vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_uint64, _ip, C.POINTER(vp), _ip]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = header/library skew, fail loudly
@@ -264,7 +270,8 @@ EXPORTED = ['msx_create', 'msx_destroy', 'msx_last_error', 'msx_device_info', 'm
             'msx_group_tempered_begin', 'msx_group_tempered_enqueue', 'msx_group_tempered_enqueue_drawn', 'msx_group_tempered_collect',
             'msx_group_tempered_end', 'msx_group_tempered_attach_series', 'msx_group_ladder_adapt', 'msx_group_ladder_betas',
             'msx_group_ladder_current', 'msx_series_moments', 'msx_predictive_batch', 'msx_series_predictive',
-            'msx_series_modes', 'msx_series_mode_labels']
+            'msx_series_modes', 'msx_series_mode_labels',
+            'msx_series_logprob', 'msx_series_lincomb', 'msx_series_weights', 'msx_series_wmoments', 'msx_series_resample']
 
 
 def as_f64(a):
@@ -1152,6 +1159,7 @@ class Series:
         h = C.c_void_p()
         ctx.check(self.lib.msx_series_create(ctx.h, int(nw), int(ndim), counts.size, iptr(counts), int(cap_hint), C.byref(h)))
         self.h = h
+        self.ctx = ctx   # (whoever makes a sibling series -- mcmc_spec_amd.reweight -- makes it on the same device)
         self.nw, self.ndim, self.k = int(nw), int(ndim), int(counts.size)
         self.counts = counts
 
@@ -1291,6 +1299,71 @@ class Series:
                                                    None if labels is None else labels.ctypes.data_as(C.POINTER(C.c_uint8)),
                                                    iptr(counts), arr))
         return labels, counts
+
+    def logprob(self, contexts, dst, mode=MODE_LOGPOST, row0=0, nrows=None):
+        """Rows row0 .. row0 + nrows - 1 of this series scored once more: member m with ``contexts[m]``'s staged problem in
+        ``mode`` (MODE_LOGPOST, MODE_LOGPRIOR or MODE_LOGLIKE), into the same rows of ``dst`` (ndim = 1, the same members;
+        msx_series_logprob).  A rejected sample gives -inf, one with an error status NaN.  Returns the members' worst
+        sample status (k,)."""
+        contexts = list(contexts)
+        if len(contexts) != self.k:
+            raise ValueError('logprob: one context per member ({} members, {} contexts)'.format(self.k, len(contexts)))
+        nrows = self.rows - int(row0) if nrows is None else int(nrows)
+        arr = (C.c_void_p * self.k)(*[c.h for c in contexts])
+        worst = np.zeros(self.k, dtype=np.int32)
+        self.check(self.lib.msx_series_logprob(self.h, arr, int(mode), int(row0), nrows, dst.h, worst.ctypes.data_as(C.POINTER(C.c_int32))))
+        return worst
+
+    @staticmethod
+    def lincomb(terms, dst, row0=0, nrows=None):
+        """``dst[row][walker] = coef_0 * x_0 + coef_1 * x_1 + ...`` for ``terms`` = [(series, col, coef), ...] (1 .. 8 of
+        them; NumPy's bits for that expression), rows row0 .. row0 + nrows - 1 (None: all the first term's series holds);
+        ``dst`` has ndim = 1 and the terms' members (msx_series_lincomb)."""
+        terms = list(terms)
+        if not terms:
+            raise ValueError('lincomb: at least one term (series, col, coef)')
+        nrows = terms[0][0].rows - int(row0) if nrows is None else int(nrows)
+        arr = (C.c_void_p * len(terms))(*[t[0].h for t in terms])
+        cols = np.ascontiguousarray([int(t[1]) for t in terms], dtype=np.int32)
+        coef = as_f64([float(t[2]) for t in terms])
+        dst.check(dst.lib.msx_series_lincomb(len(terms), arr, cols.ctypes.data_as(C.POINTER(C.c_int32)), dptr(coef), int(row0), nrows, dst.h))
+
+    def weights(self, n, w_dst, discard=0, thin=1):
+        """This series (ndim = 1) read as log-weights: ``w = exp(logw - M_m)`` of rows [0, n) into ``w_dst`` (ndim = 1, the
+        same members), M_m the member's largest value that is finite or -inf; NaN and +inf are bad and weigh 0
+        (msx_series_weights).  Returns {'count', 'nbad', 'nzero' (k,) ints, 'sumw', 'sumw2', 'ess' (k,)} over
+        rows[0:n][discard::thin]."""
+        stats = np.empty((self.k, 6))
+        self.check(self.lib.msx_series_weights(self.h, int(n), int(discard), int(thin), w_dst.h, dptr(stats)))
+        out = {name: stats[:, i].astype(np.int64) for i, name in enumerate(('count', 'nbad', 'nzero'))}
+        out.update(sumw=stats[:, 3].copy(), sumw2=stats[:, 4].copy(), ess=stats[:, 5].copy())
+        return out
+
+    def wmoments(self, w, n, discard=0, thin=1, cols=None, cov=True):
+        """{'sumw' (k,), 'mean' (k, ncols), 'cov' (k, ncols, ncols) or None}: the moments of rows[0:n][discard::thin] under
+        the weights series ``w`` (msx_series_wmoments): mean = sum w x / sum w, cov = sum w (x - mean)(x - mean)^T / sum w."""
+        cols = _col_codes(range(self.ndim) if cols is None else cols)
+        nc = int(cols.size)
+        sumw, mean = np.empty(self.k), np.empty((self.k, nc))
+        cv = np.empty((self.k, nc, nc)) if cov else None
+        self.check(self.lib.msx_series_wmoments(self.h, w.h, int(n), int(discard), int(thin), uptr(cols), nc, dptr(sumw), dptr(mean),
+                                                None if cv is None else dptr(cv)))
+        return {'sumw': sumw, 'mean': mean, 'cov': cv}
+
+    def resample(self, w, n, nout, dst, discard=0, thin=1, seed=0):
+        """Systematic resampling of rows[0:n][discard::thin] under the weights series ``w`` (msx_series_resample):
+        ``dst[m]`` -- a series of one walker and this series' ndim -- receives member m's ``nout[m]`` drawn samples, all
+        coordinates, and holds exactly that many rows.  Returns the drawn flat indices, a list of k int64 arrays."""
+        nout = np.ascontiguousarray(nout, dtype=np.int64).reshape(-1)
+        dst = list(dst)
+        if nout.size != self.k or len(dst) != self.k:
+            raise ValueError('resample: one nout and one dst series per member ({})'.format(self.k))
+        arr = (C.c_void_p * self.k)(*[s.h for s in dst])
+        idx = np.zeros(max(int(np.sum(np.maximum(nout, 0))), 1), dtype=np.int64)
+        self.check(self.lib.msx_series_resample(self.h, w.h, int(n), int(discard), int(thin), int(seed) & 0xffffffffffffffff, iptr(nout),
+                                                arr, iptr(idx)))
+        cuts = np.concatenate([[0], np.cumsum(nout)])
+        return [idx[cuts[m]:cuts[m + 1]].copy() for m in range(self.k)]
 
     def derive(self, contexts, cols, dst, row0=0, nrows=None):
         """Rows row0 .. row0 + nrows - 1 of this series mapped to the derived columns ``cols`` (codes) and written to the

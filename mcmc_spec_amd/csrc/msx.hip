@@ -79,6 +79,7 @@
 #include "product_kernels.h"
 #include "predictive_kernels.h"
 #include "mode_kernels.h"
+#include "reweight_kernels.h"
 #include "opt_run_kernels.h"
 
 // ================================================================================================
@@ -5593,6 +5594,327 @@ int msx_series_mode_labels(msx_series *sr, int64_t n, int64_t discard, int64_t t
     return MSX_OK;
 }
 #undef MODE_DISPATCH
+
+// ---- importance reweighting of a series (reweight_kernels.h) ----------------------------------------
+static constexpr int64_t kRwEvalBatch = (int64_t)1 << 16;   // samples per evaluation launch of msx_series_logprob (its scratch's bound)
+
+static bool rw_same_members(const msx_series *a, const msx_series *b) { return a->device == b->device && a->nw == b->nw && a->off == b->off; }
+static bool rw_attached(const msx_series *s) { return s->run || s->trun || s->gtrun; }
+static size_t rw_align(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// the selection rows[0:n][discard::thin] -> n' (msx_series_moments' codes)
+static int rw_selection(msx_series *sr, const std::string &who, int64_t n, int64_t discard, int64_t thin, int64_t *np_out) {
+    if (discard < 0 || thin < 1) return fail(sr, MSX_ERR_INVALID, who + ": bad arguments (discard >= 0, thin >= 1)");
+    if (n < 1 || n > sr->rows) return fail(sr, MSX_ERR_RANGE, who + ": n must lie in 1 .. the rows the series holds");
+    const int64_t np = n > discard ? (n - discard + thin - 1) / thin : 0;
+    if (np < 1) return fail(sr, MSX_ERR_RANGE, who + ": the selection rows[0:n][discard::thin] is empty");
+    *np_out = np;
+    return MSX_OK;
+}
+
+// a weights series beside `sr`: one column, sr's members, the rows of the selection
+static int rw_weights_ok(msx_series *sr, const std::string &who, const msx_series *w, int64_t n) {
+    if (!w || w == sr || !rw_same_members(sr, w) || w->ndim != 1)
+        return fail(sr, MSX_ERR_INVALID, who + ": the weights must be another series on the same device with ndim = 1 and the same members");
+    if (n > w->rows) return fail(sr, MSX_ERR_RANGE, who + ": n past the rows the weights hold");
+    return MSX_OK;
+}
+
+int msx_series_logprob(msx_series *src, msx_ctx **ctxs, int32_t mode, int64_t row0, int64_t nrows, msx_series *dst, int32_t *worst_status) {
+    if (!src) return MSX_ERR_INVALID;
+    const std::string who("msx_series_logprob");
+    if (!dst || !ctxs || row0 < 0 || nrows < 1) return fail(src, MSX_ERR_INVALID, who + ": bad arguments");
+    if (mode != MSX_MODE_LOGPOST && mode != MSX_MODE_LOGPRIOR && mode != MSX_MODE_LOGLIKE)
+        return fail(src, MSX_ERR_INVALID, who + ": mode must be MSX_MODE_LOGPOST, MSX_MODE_LOGPRIOR or MSX_MODE_LOGLIKE");
+    if (dst == src || !rw_same_members(src, dst) || dst->ndim != 1)
+        return fail(src, MSX_ERR_INVALID, who + ": dst must be another series on the same device with src's members and ndim = 1");
+    if (rw_attached(dst)) return fail(src, MSX_ERR_STATE, who + ": a run in flight appends to dst");
+    if (row0 + nrows > src->rows) return fail(src, MSX_ERR_RANGE, who + ": rows past the ones src holds");
+    if (row0 > dst->rows) return fail(src, MSX_ERR_RANGE, who + ": row0 past the rows dst holds (it would leave a gap)");
+    const int k = (int)src->off.size() - 1;
+    int64_t maxW = 0;
+    for (int m = 0; m < k; ++m) {
+        const msx_ctx *c = ctxs[m];
+        const std::string mem = who + ": member " + std::to_string(m);
+        if (!c) return fail(src, MSX_ERR_INVALID, mem + " is null");
+        if (c->device != src->device) return fail(src, MSX_ERR_INVALID, mem + " lives on another device");
+        if (!c->problem_staged) return fail(src, MSX_ERR_STATE, mem + " has no staged problem");
+        if (c->smp || c->tmp || c->opt_run) return fail(src, MSX_ERR_STATE, mem + " has a run in flight (end it first)");
+        if (src->ndim != 2 * c->P.nspec + 2) return fail(src, MSX_ERR_INVALID, mem + ": src's ndim must be 2 * nspec + 2");
+        maxW = std::max(maxW, src->off[(size_t)m + 1] - src->off[(size_t)m]);
+    }
+    HIP_TRY(src, hipSetDevice(src->device));
+    hipStream_t st = src->stream;
+    HIP_TRY(src, series_reserve(dst, row0 + nrows, dst->rows, st));
+    // scratch, bounded by the batch: [theta | logp | status | worst]
+    const int64_t rows_per = std::min(nrows, std::max<int64_t>(1, kRwEvalBatch / maxW)), cap_s = rows_per * maxW;
+    const size_t b_theta = rw_align(sizeof(double) * (size_t)(cap_s * src->ndim)), b_logp = rw_align(sizeof(double) * (size_t)cap_s);
+    const size_t b_status = rw_align(sizeof(int32_t) * (size_t)cap_s), b_worst = sizeof(int32_t) * (size_t)k;
+    HIP_TRY(src, series_scratch(src, b_theta + b_logp + b_status + b_worst));
+    double *d_theta = (double *)src->d_scratch, *d_logp = (double *)(src->d_scratch + b_theta);
+    int32_t *d_status = (int32_t *)(src->d_scratch + b_theta + b_logp), *d_worst = (int32_t *)(src->d_scratch + b_theta + b_logp + b_status);
+    HIP_TRY(src, hipMemsetAsync(d_worst, 0, b_worst, st));
+    HIP_TRY(src, series_wait_growth(src));
+    if (dst->grown_set) HIP_TRY(src, hipStreamWaitEvent(st, dst->grown, 0));
+    for (int m = 0; m < k; ++m) {
+        const int64_t w0 = src->off[(size_t)m], W = src->off[(size_t)m + 1] - w0;
+        for (int64_t rb = 0; rb < nrows; rb += rows_per) {
+            const int64_t cnt = std::min(rows_per, nrows - rb), ns = cnt * W, total = ns * src->ndim;
+            hipLaunchKernelGGL(rw_gather_theta_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const double *)src->d_rows,
+                               src->cap, src->nw, (int32_t)src->ndim, w0, W, row0 + rb, cnt, d_theta);
+            HIP_TRY(src, hipGetLastError());
+            if (int rc = msx_logprob_batch_dev(ctxs[m], mode, d_theta, ns, src->ndim, d_logp, d_status, st, 0)) {
+                (void)hipStreamSynchronize(st);
+                return fail(src, rc, who + ": member " + std::to_string(m) + ": " + ctxs[m]->err);
+            }
+            hipLaunchKernelGGL(rw_put_logp_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, st, (const double *)d_logp,
+                               (const int32_t *)d_status, W, cnt, w0, row0 + rb, dst->d_rows, dst->cap, d_worst + m);
+            HIP_TRY(src, hipGetLastError());
+        }
+    }
+    std::vector<int32_t> worst((size_t)k, 0);
+    HIP_TRY(src, hipMemcpyAsync(worst.data(), d_worst, b_worst, hipMemcpyDeviceToHost, st));
+    HIP_TRY(src, hipStreamSynchronize(st));
+    if (worst_status) memcpy(worst_status, worst.data(), b_worst);
+    dst->rows = std::max(dst->rows, row0 + nrows);
+    return MSX_OK;
+}
+
+int msx_series_lincomb(int32_t nsrc, msx_series **srcs, const int32_t *cols, const double *coef, int64_t row0, int64_t nrows, msx_series *dst) {
+    if (!dst) return MSX_ERR_INVALID;
+    const std::string who("msx_series_lincomb");
+    if (!srcs || !cols || !coef || nsrc < 1 || nsrc > kRwMaxSrc || row0 < 0 || nrows < 1)
+        return fail(dst, MSX_ERR_INVALID, who + ": bad arguments (1 .. 8 terms, row0 >= 0, nrows >= 1)");
+    if (dst->ndim != 1) return fail(dst, MSX_ERR_INVALID, who + ": dst needs ndim = 1");
+    if (rw_attached(dst)) return fail(dst, MSX_ERR_STATE, who + ": a run in flight appends to dst");
+    for (int j = 0; j < nsrc; ++j) {
+        const msx_series *s = srcs[j];
+        if (!s || s == dst || !rw_same_members(dst, s))
+            return fail(dst, MSX_ERR_INVALID, who + ": every source must be another series on dst's device with dst's members");
+        if (cols[j] < 0 || cols[j] >= s->ndim) return fail(dst, MSX_ERR_RANGE, who + ": a column outside its series");
+        if (row0 + nrows > s->rows) return fail(dst, MSX_ERR_RANGE, who + ": rows past the ones a source holds");
+    }
+    if (row0 > dst->rows) return fail(dst, MSX_ERR_RANGE, who + ": row0 past the rows dst holds (it would leave a gap)");
+    if (dst->nw > 65535) return fail(dst, MSX_ERR_RANGE, who + ": more walkers than one launch covers");
+    HIP_TRY(dst, hipSetDevice(dst->device));
+    hipStream_t st = dst->stream;
+    HIP_TRY(dst, series_reserve(dst, row0 + nrows, dst->rows, st));
+    RwTerms T;
+    memset(&T, 0, sizeof(T));
+    T.n = nsrc;
+    for (int j = 0; j < nsrc; ++j) {
+        msx_series *s = srcs[j];
+        if (s->grown_set) HIP_TRY(dst, hipStreamWaitEvent(st, s->grown, 0));
+        T.p[j] = s->d_rows + (int64_t)cols[j] * s->nw * s->cap;
+        T.cap[j] = s->cap;
+        T.coef[j] = coef[j];
+    }
+    HIP_TRY(dst, series_wait_growth(dst));
+    hipLaunchKernelGGL(rw_lincomb_kernel, dim3((unsigned)((nrows + kRwThreads - 1) / kRwThreads), (unsigned)dst->nw), dim3(kRwThreads), 0, st, T,
+                       row0, nrows, dst->d_rows, dst->cap);
+    HIP_TRY(dst, hipGetLastError());
+    HIP_TRY(dst, hipStreamSynchronize(st));
+    dst->rows = std::max(dst->rows, row0 + nrows);
+    return MSX_OK;
+}
+
+int msx_series_weights(msx_series *logw, int64_t n, int64_t discard, int64_t thin, msx_series *w_dst, double *stats) {
+    if (!logw) return MSX_ERR_INVALID;
+    const std::string who("msx_series_weights");
+    if (!w_dst || !stats) return fail(logw, MSX_ERR_INVALID, who + ": bad arguments (w_dst and stats)");
+    if (logw->ndim != 1 || w_dst == logw || !rw_same_members(logw, w_dst) || w_dst->ndim != 1)
+        return fail(logw, MSX_ERR_INVALID, who + ": the log-weights and w_dst must be two series of ndim = 1 on one device with the same members");
+    if (rw_attached(w_dst)) return fail(logw, MSX_ERR_STATE, who + ": a run in flight appends to w_dst");
+    int64_t np = 0;
+    if (int rc = rw_selection(logw, who, n, discard, thin, &np)) return rc;
+    if (logw->nw > 65535) return fail(logw, MSX_ERR_RANGE, who + ": more walkers than one launch covers");
+    HIP_TRY(logw, hipSetDevice(logw->device));
+    hipStream_t st = logw->stream;
+    HIP_TRY(logw, series_reserve(w_dst, n, w_dst->rows, st));
+    const int k = (int)logw->off.size() - 1;
+    const int64_t nw = logw->nw;
+    // scratch: [pmax nw | psum 2 nw | stats 6 k | pcnt 2 nw]
+    HIP_TRY(logw, series_scratch(logw, sizeof(double) * (size_t)(3 * nw + 6 * k) + sizeof(long long) * (size_t)(2 * nw)));
+    double *d_pmax = (double *)logw->d_scratch, *d_psum = d_pmax + nw, *d_stats = d_psum + 2 * nw;
+    long long *d_pcnt = (long long *)(d_stats + 6 * k);
+    HIP_TRY(logw, series_wait_growth(logw));
+    if (w_dst->grown_set) HIP_TRY(logw, hipStreamWaitEvent(st, w_dst->grown, 0));
+    hipLaunchKernelGGL(rw_max_kernel, dim3((unsigned)nw), dim3(kRwThreads), 0, st, (const double *)logw->d_rows, logw->cap, n, d_pmax);
+    HIP_TRY(logw, hipGetLastError());
+    hipLaunchKernelGGL(rw_exp_kernel, dim3((unsigned)((n + kRwThreads - 1) / kRwThreads), (unsigned)nw), dim3(kRwThreads), 0, st,
+                       (const double *)logw->d_rows, logw->cap, n, (const int64_t *)logw->d_off, (int32_t)k, (const double *)d_pmax, w_dst->d_rows,
+                       w_dst->cap);
+    HIP_TRY(logw, hipGetLastError());
+    hipLaunchKernelGGL(rw_stat_kernel, dim3((unsigned)nw), dim3(kRwThreads), 0, st, (const double *)logw->d_rows, logw->cap,
+                       (const double *)w_dst->d_rows, w_dst->cap, nw, np, discard, thin, d_pcnt, d_psum);
+    HIP_TRY(logw, hipGetLastError());
+    hipLaunchKernelGGL(rw_stat_combine_kernel, dim3(1), dim3(MSX_MAX_GROUP), 0, st, (const long long *)d_pcnt, (const double *)d_psum,
+                       (const int64_t *)logw->d_off, (int32_t)k, nw, np, d_stats);
+    HIP_TRY(logw, hipGetLastError());
+    HIP_TRY(logw, hipMemcpyAsync(stats, d_stats, sizeof(double) * (size_t)(6 * k), hipMemcpyDeviceToHost, st));
+    HIP_TRY(logw, hipStreamSynchronize(st));
+    w_dst->rows = std::max(w_dst->rows, n);
+    return MSX_OK;
+}
+
+int msx_series_wmoments(msx_series *src, msx_series *w, int64_t n, int64_t discard, int64_t thin, const uint32_t *cols, int32_t ncols,
+                        double *sumw, double *mean, double *cov) {
+    if (!src) return MSX_ERR_INVALID;
+    const std::string who("msx_series_wmoments");
+    if (!sumw || !mean || ncols < 1) return fail(src, MSX_ERR_INVALID, who + ": bad arguments (ncols >= 1, every output but cov)");
+    int64_t np = 0;
+    if (int rc = rw_selection(src, who, n, discard, thin, &np)) return rc;
+    if (int rc = rw_weights_ok(src, who, w, n)) return rc;
+    if (ncols > MSX_MAX_DIM) return fail(src, MSX_ERR_RANGE, who + ": more columns than a series is wide (MSX_MAX_DIM)");
+    if (!cols && ncols != src->ndim) return fail(src, MSX_ERR_RANGE, who + ": cols == NULL means all columns (ncols = ndim)");
+    RwCols C;
+    memset(&C, 0, sizeof(C));
+    C.n = ncols;
+    for (int32_t q = 0; q < ncols; ++q) {
+        const uint32_t c = cols ? cols[q] : (uint32_t)q;
+        if (c >= (uint32_t)src->ndim) return fail(src, MSX_ERR_RANGE, who + ": a column outside the series");
+        C.c[q] = (int32_t)c;
+    }
+    HIP_TRY(src, hipSetDevice(src->device));
+    const int k = (int)src->off.size() - 1;
+    const int64_t nc = ncols, npairs = cov ? nc * (nc + 1) / 2 : 0, nw = src->nw, kc = (int64_t)k * nc, ncov = cov ? kc * nc : 0;
+    // scratch: [psum (nc + 1) nw | pcross npairs nw | sumw k | mean k nc | cov k nc nc]
+    HIP_TRY(src, series_scratch(src, sizeof(double) * (size_t)((nc + 1 + npairs) * nw + k + kc + ncov)));
+    double *d_psum = (double *)src->d_scratch, *d_pcross = d_psum + (nc + 1) * nw, *d_sumw = d_pcross + npairs * nw;
+    double *d_mean = d_sumw + k, *d_cov = d_mean + kc;
+    hipStream_t st = src->stream;
+    HIP_TRY(src, series_wait_growth(src));
+    if (w->grown_set) HIP_TRY(src, hipStreamWaitEvent(st, w->grown, 0));
+    hipLaunchKernelGGL(rw_wsum_kernel, dim3((unsigned)nw, (unsigned)(nc + 1)), dim3(kRwThreads), 0, st, (const double *)src->d_rows, src->cap, nw,
+                       C, (const double *)w->d_rows, w->cap, np, discard, thin, d_psum);
+    HIP_TRY(src, hipGetLastError());
+    hipLaunchKernelGGL(rw_wmean_kernel, dim3((unsigned)k), dim3(MSX_MAX_DIM + 1), 0, st, (const double *)d_psum, (const int64_t *)src->d_off, nw,
+                       (int32_t)nc, d_sumw, d_mean);
+    HIP_TRY(src, hipGetLastError());
+    if (cov) {
+        hipLaunchKernelGGL(rw_wcross_kernel, dim3((unsigned)nw, (unsigned)npairs), dim3(kRwThreads), 0, st, (const double *)src->d_rows, src->cap,
+                           nw, C, (const double *)w->d_rows, w->cap, np, discard, thin, (const int64_t *)src->d_off, (int32_t)k,
+                           (const double *)d_mean, d_pcross);
+        HIP_TRY(src, hipGetLastError());
+        hipLaunchKernelGGL(rw_wcov_kernel, dim3((unsigned)k), dim3(MSX_MAX_DIM * (MSX_MAX_DIM + 1) / 2), 0, st, (const double *)d_pcross,
+                           (const int64_t *)src->d_off, nw, (int32_t)nc, (const double *)d_sumw, d_cov);
+        HIP_TRY(src, hipGetLastError());
+        HIP_TRY(src, hipMemcpyAsync(cov, d_cov, sizeof(double) * (size_t)ncov, hipMemcpyDeviceToHost, st));
+    }
+    std::vector<double> hbuf((size_t)(k + kc));   // (sumw and mean lie side by side: one copy)
+    HIP_TRY(src, hipMemcpyAsync(hbuf.data(), d_sumw, sizeof(double) * hbuf.size(), hipMemcpyDeviceToHost, st));
+    HIP_TRY(src, hipStreamSynchronize(st));
+    memcpy(sumw, hbuf.data(), sizeof(double) * (size_t)k);
+    memcpy(mean, hbuf.data() + k, sizeof(double) * (size_t)kc);
+    return MSX_OK;
+}
+
+int msx_series_resample(msx_series *src, msx_series *w, int64_t n, int64_t discard, int64_t thin, uint64_t seed, const int64_t *nout,
+                        msx_series **dst, int64_t *index_out) {
+    if (!src) return MSX_ERR_INVALID;
+    const std::string who("msx_series_resample");
+    if (!nout || !dst) return fail(src, MSX_ERR_INVALID, who + ": bad arguments (nout and dst)");
+    int64_t np = 0;
+    if (int rc = rw_selection(src, who, n, discard, thin, &np)) return rc;
+    if (int rc = rw_weights_ok(src, who, w, n)) return rc;
+    const int k = (int)src->off.size() - 1;
+    int64_t max_out = 0, sum_out = 0;
+    for (int m = 0; m < k; ++m) {
+        if (nout[m] < 0) return fail(src, MSX_ERR_INVALID, who + ": a negative nout");
+        max_out = std::max(max_out, nout[m]);
+        sum_out += nout[m];
+        msx_series *t = dst[m];
+        if (!t || t == src || t == w || t->device != src->device || t->nw != 1 || t->off.size() != 2 || t->ndim != src->ndim)
+            return fail(src, MSX_ERR_INVALID, who + ": every dst must be another series on the same device with one walker, one member and src's ndim");
+        for (int e = 0; e < m; ++e)
+            if (dst[e] == t) return fail(src, MSX_ERR_INVALID, who + ": a dst is listed twice");
+        if (rw_attached(t)) return fail(src, MSX_ERR_STATE, who + ": a run in flight appends to a dst");
+    }
+    HIP_TRY(src, hipSetDevice(src->device));
+    std::vector<int64_t> tile_off((size_t)k + 1, 0), samp_off((size_t)k + 1, 0);
+    for (int m = 0; m < k; ++m) {
+        const int64_t N = np * (src->off[(size_t)m + 1] - src->off[(size_t)m]);
+        tile_off[(size_t)m + 1] = tile_off[(size_t)m] + (N + kRwTile - 1) / kRwTile;
+        samp_off[(size_t)m + 1] = samp_off[(size_t)m] + N;
+    }
+    const int64_t tiles = tile_off[(size_t)k], sumN = samp_off[(size_t)k];
+    if (tiles > 0x7fffffff) return fail(src, MSX_ERR_RANGE, who + ": more samples than one launch covers");
+    // scratch: [C sumN | tsum tiles | total k | tlast tiles | tbad tiles | mlast k | mbad k | tile_off k + 1 | samp_off k + 1 | idx sum_out | draws k]
+    const size_t b_C = rw_align(sizeof(double) * (size_t)sumN), b_t = rw_align(sizeof(double) * (size_t)tiles), b_k = rw_align(8 * ((size_t)k + 1));
+    const size_t b_idx = rw_align(sizeof(long long) * (size_t)std::max<int64_t>(sum_out, 1)), b_draw = rw_align(sizeof(RwDraw) * (size_t)k);
+    HIP_TRY(src, series_scratch(src, b_C + 3 * b_t + 5 * b_k + b_idx + b_draw));
+    char *p = src->d_scratch;
+    double *d_C = (double *)p; p += b_C;
+    double *d_tsum = (double *)p; p += b_t;
+    double *d_total = (double *)p; p += b_k;
+    long long *d_tlast = (long long *)p; p += b_t;
+    long long *d_tbad = (long long *)p; p += b_t;
+    long long *d_mlast = (long long *)p; p += b_k;
+    long long *d_mbad = (long long *)p; p += b_k;
+    int64_t *d_tile_off = (int64_t *)p; p += b_k;
+    int64_t *d_samp_off = (int64_t *)p; p += b_k;
+    long long *d_idx = (long long *)p; p += b_idx;
+    RwDraw *d_draws = (RwDraw *)p;
+    hipStream_t st = src->stream;
+    HIP_TRY(src, hipMemcpyAsync(d_tile_off, tile_off.data(), sizeof(int64_t) * tile_off.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(src, hipMemcpyAsync(d_samp_off, samp_off.data(), sizeof(int64_t) * samp_off.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(src, series_wait_growth(src));
+    if (w->grown_set) HIP_TRY(src, hipStreamWaitEvent(st, w->grown, 0));
+    RwScan S;
+    memset(&S, 0, sizeof(S));
+    S.wt = w->d_rows; S.wcap = w->cap; S.np = np; S.discard = discard; S.thin = thin;
+    S.member_off = src->d_off; S.tile_off = d_tile_off; S.samp_off = d_samp_off; S.k = k;
+    hipLaunchKernelGGL(rw_scan_local_kernel, dim3((unsigned)tiles), dim3(kRwThreads), 0, st, S, d_C, d_tsum, d_tlast, d_tbad);
+    HIP_TRY(src, hipGetLastError());
+    hipLaunchKernelGGL(rw_scan_tiles_kernel, dim3((unsigned)k), dim3(kRwThreads), 0, st, (const int64_t *)d_tile_off, d_tsum,
+                       (const long long *)d_tlast, (const long long *)d_tbad, d_total, d_mlast, d_mbad);
+    HIP_TRY(src, hipGetLastError());
+    std::vector<double> total((size_t)k);
+    std::vector<long long> mlast((size_t)k), mbad((size_t)k);
+    HIP_TRY(src, hipMemcpyAsync(total.data(), d_total, sizeof(double) * (size_t)k, hipMemcpyDeviceToHost, st));
+    HIP_TRY(src, hipMemcpyAsync(mlast.data(), d_mlast, sizeof(long long) * (size_t)k, hipMemcpyDeviceToHost, st));
+    HIP_TRY(src, hipMemcpyAsync(mbad.data(), d_mbad, sizeof(long long) * (size_t)k, hipMemcpyDeviceToHost, st));
+    HIP_TRY(src, hipStreamSynchronize(st));
+    // refused before anything is written to a dst
+    for (int m = 0; m < k; ++m) {
+        if (mbad[(size_t)m] > 0) return fail(src, MSX_ERR_RANGE, who + ": member " + std::to_string(m) + " has a weight that is negative, NaN or infinite");
+        if (nout[m] > 0 && (!(total[(size_t)m] > 0.0) || !std::isfinite(total[(size_t)m]) || mlast[(size_t)m] < 0))
+            return fail(src, MSX_ERR_RANGE, who + ": member " + std::to_string(m) + "'s weights sum to zero (or overflow): nothing to draw from");
+    }
+    if (sum_out == 0) {
+        for (int m = 0; m < k; ++m) dst[m]->rows = 0;
+        return MSX_OK;
+    }
+    hipLaunchKernelGGL(rw_scan_add_kernel, dim3((unsigned)tiles), dim3(kRwThreads), 0, st, S, (const double *)d_tsum, d_C);
+    HIP_TRY(src, hipGetLastError());
+    std::vector<RwDraw> draws((size_t)k);
+    int64_t at = 0;
+    for (int m = 0; m < k; ++m) {
+        msx_series *t = dst[m];
+        RwDraw &D = draws[(size_t)m];
+        memset(&D, 0, sizeof(D));
+        D.nout = nout[m];
+        D.out_off = at;
+        at += nout[m];
+        if (nout[m] == 0) continue;
+        HIP_TRY(src, series_reserve(t, nout[m], 0, st));   // (grown the way append grows a series; nothing carried over)
+        D.step = total[(size_t)m] / (double)nout[m];
+        D.u0 = counter_uniform(seed, (unsigned long long)m, kRwStream, 0u);
+        D.last = mlast[(size_t)m];
+        D.dst = t->d_rows;
+        D.dcap = t->cap;
+    }
+    HIP_TRY(src, hipMemcpyAsync(d_draws, draws.data(), sizeof(RwDraw) * (size_t)k, hipMemcpyHostToDevice, st));
+    for (int m = 0; m < k; ++m)
+        if (dst[m]->grown_set) HIP_TRY(src, hipStreamWaitEvent(st, dst[m]->grown, 0));
+    hipLaunchKernelGGL(rw_draw_kernel, dim3((unsigned)((max_out + kRwThreads - 1) / kRwThreads), (unsigned)k), dim3(kRwThreads), 0, st, S,
+                       (const double *)d_C, (const RwDraw *)d_draws, (const double *)src->d_rows, src->cap, src->nw, (int32_t)src->ndim, d_idx);
+    HIP_TRY(src, hipGetLastError());
+    if (index_out) HIP_TRY(src, hipMemcpyAsync(index_out, d_idx, sizeof(int64_t) * (size_t)sum_out, hipMemcpyDeviceToHost, st));
+    HIP_TRY(src, hipStreamSynchronize(st));
+    for (int m = 0; m < k; ++m) dst[m]->rows = nout[m];
+    return MSX_OK;
+}
 
 int msx_test_hook(msx_ctx *c, int32_t what, int32_t value) {
     if (!c) return MSX_ERR_INVALID;

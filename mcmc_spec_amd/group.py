@@ -497,6 +497,18 @@ class DeviceGroupSampler(GroupSampler):
                                   len(self.samplers[0]._chain), self.group.engines, self.nwalkers, q, discard, thin)
         return out if k is None else out[k]
 
+    def get_reweighted(self, engines_new, mode='logposterior', discard=0, thin=1):
+        """``DeviceEnsembleSampler.get_reweighted`` for every target at once: ``engines_new`` holds one staged Engine per
+        target (a target's own engine leaves its weights at 1), and the ``reweight.Reweighted`` it returns has one member
+        per target.  With autocorr='device' on the chains held there, otherwise the host chains are uploaded first."""
+        from . import reweight
+        engines_new = list(engines_new)
+        if len(engines_new) != len(self.group.engines):
+            raise ValueError('get_reweighted: one engine per target ({})'.format(len(self.group.engines)))
+        return reweight.of_sampler(self._series, lambda: np.concatenate([np.array(s._chain) for s in self.samplers], axis=1),
+                                   len(self.samplers[0]._chain), self.group.engines, engines_new, self.nwalkers, mode=mode,
+                                   mode_old=self.mode, discard=discard, thin=thin)
+
 
 def run_group_protocol(sampler, pos, nburn, nsteps, nthin=10, dirname=None, fnames=None, rhat=None):
     """``sampler.run_reference_protocol`` (run_emcee's driver, mft6.py:1494-1529) applied to every target of a group

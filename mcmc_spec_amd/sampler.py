@@ -680,6 +680,20 @@ class DeviceEnsembleSampler(EnsembleSampler):
         return predictive.of_chain(self._series, lambda: np.array(self._chain), len(self._chain), [self.engine], None, q, discard,
                                    thin)[0]
 
+    def get_reweighted(self, engines_new, mode='logposterior', discard=0, thin=1):
+        """The stored chain asked another question without a second run (``mcmc_spec_amd.reweight``):
+        a ``reweight.Reweighted`` whose log-weight is ``lp_new - lp_old`` -- ``lp_new`` the ``mode`` of ``engines_new`` (one
+        staged Engine: the same data under another prior, with ``rad_prior``, without the contrasts, ...), ``lp_old`` the
+        sampler's own density under its own engine, both scored once more on the device.  Its ``stats['ess']`` says how far
+        the second question is from the first; ``moments()`` and ``resample()`` answer it.  With autocorr='device' on the
+        chain held there (rows past len(self._chain) are not part of it); otherwise the host chain is uploaded first.  The
+        caller ``close()``s the result."""
+        from . import reweight
+        e_new = engines_new[0] if isinstance(engines_new, (list, tuple)) else engines_new
+        own = 'logposterior' if self._mode == 1 else 'loglikelihood'
+        return reweight.of_sampler(self._series, lambda: np.array(self._chain), len(self._chain), [self.engine], [e_new], None,
+                                   mode=mode, mode_old=own, discard=discard, thin=thin)
+
 
 def _autocorr_1d(x):
     x = np.asarray(x, dtype=float)

@@ -466,6 +466,32 @@ class _Ladder:
                                       [self.nwalkers] * self.ntemps, q, discard, thin)
         return out if t is None else out[int(t)]
 
+    def get_reweighted(self, engines_new=None, t=0, mode='logposterior', discard=0, thin=1):
+        """What rung t's stored chain says about another density (``mcmc_spec_amd.reweight``): a
+        ``reweight.Reweighted`` of one member whose log-weight is ``lp_new - lpr - betas[t] * ll`` -- ``lp_new`` the
+        ``mode`` of ``engines_new`` (one staged Engine; None: this sampler's own, and the weights are then those of the
+        rung against the posterior, ``(1 - beta) * ll``), ``lpr`` and ``ll`` the chain scored once more under the sampler's
+        own engine.  With autocorr='device' on the chain held there; otherwise the host chain is uploaded first.  The
+        selected rows must all have been run with the ladder ``self.betas``."""
+        from . import reweight
+        self._ctx()
+        if np.any(self.get_betas(discard=discard, thin=thin) != self.betas):
+            raise ValueError('get_reweighted: the selected rows were not all run with the ladder self.betas (an adaptive run moved it): '
+                             'freeze the ladder (adapt=False) and discard= the adaptive rows')
+        if self._series is not None:
+            engines = self._series_engines()
+            own, host, counts = list(range(len(engines)))[self._own], None, None
+        else:
+            engines = [self.engine] * self.ntemps
+            own, host, counts = list(range(self.ntemps)), self._flat_members, [self.nwalkers] * self.ntemps
+        new = list(engines)
+        for m in own:
+            new[m] = self.engine if engines_new is None else engines_new
+        betas = np.ones(len(engines))
+        betas[own] = self.betas
+        return reweight.of_sampler(self._series, host, len(self._chain), engines, new, counts, mode=mode, discard=discard, thin=thin,
+                                   members=[own[int(t)]], betas=betas)
+
     def _evidence(self, discard, thin, db, blocks):
         """(mean, lme) (T, blocks + 1) of the stored ln L: ``host_evidence``, or msx_series_evidence on the device series."""
         n_total = len(self._ll)

@@ -19,7 +19,9 @@ ladder before and after with the swap fractions, freezes it and goes on as above
 (mcmc_spec_amd.modes; section 23): per mode its probability and the 16 / 50 / 84 percentiles of every coordinate.
 ``--reweight`` asks the finished chain a second question without a second run (mcmc_spec_amd.reweight; section 24): the
 same data staged under a second parallax prior, the effective sample size of the reweighted chain and both sets of
-16 / 50 / 84.
+16 / 50 / 84, and the Pareto shape khat of the weights' tail (mcmc_spec_amd.psis; section 25).  ``--loo`` prints PSIS-LOO and
+WAIC of the stored chain over the likelihood's own terms: the totals with their standard errors, how many observations have
+khat > 0.7 and the worst pixels.
 """
 import argparse
 import os
@@ -50,6 +52,8 @@ def main():
                     help='with --tempered: N adaptive iterations first (the rungs move towards equal swap rates), then the ladder is frozen')
     ap.add_argument('--predictive', action='store_true',
                     help='after the run: the posterior predictive check of the stored chain (chi^2 terms, worst pixels, largest mean residual)')
+    ap.add_argument('--loo', action='store_true',
+                    help='after the run: PSIS-LOO and WAIC of the stored chain per pixel and filter (totals, how many khat > 0.7, the worst pixels)')
     ap.add_argument('--modes', action='store_true',
                     help="after the run: the posterior's modes (a two-component mixture over the six coordinates), each mode's "
                          "probability and 16 / 50 / 84, and bic1 - bic2 (positive: two modes)")
@@ -142,6 +146,9 @@ def main():
     if args.predictive:   # does the model reproduce the data, and which data carry chi^2?  (mft6.py:2361-2438, on every sample)
         from mcmc_spec_amd import predictive
         predictive.print_report(predictive.check(eng, sampler.get_chain(flat=True)), wl_um)
+    if args.loo:   # which data can one sample not stand in for, and a score to compare a second model's chain with on the same data
+        from mcmc_spec_amd import psis
+        psis.print_report(psis.loo(eng, sampler.get_chain(flat=True), wl=wl_um))
     if args.reweight is not None:   # what would another parallax prior have given?  One chain, two questions: a paired comparison
         from mcmc_spec_amd import summary
         from mcmc_spec_amd.engine import Engine
@@ -154,6 +161,9 @@ def main():
             n = int(rw_.stats['count'][0])
             print('reweighted to the parallax prior {:.5g} +- {:.2g} (was {:.5g}): ESS {:.1f} of {} samples, {} bad'.format(
                 prior2[-2], plx_err, plx, rw_.stats['ess'][0], n, int(rw_.stats['nbad'][0])))
+            with rw_.smooth() as sm:   # can these weights be trusted?  Kish's ESS cannot say; the Pareto shape of their tail can
+                print('  Pareto-smoothed: khat {:.3f} ({}) from a tail of {}, ESS {:.1f}'.format(
+                    sm.khat[0], 'reliable' if sm.khat[0] <= 0.7 else 'NOT reliable: khat > 0.7', int(sm.ntail[0]), sm.stats['ess'][0]))
             (resampled,) = rw_.resample()
             second = summary.summary_of(resampled, resampled.rows)
             resampled.close()

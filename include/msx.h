@@ -1001,6 +1001,81 @@ int msx_series_wmoments(msx_series *src, msx_series *w, int64_t n, int64_t disca
 int msx_series_resample(msx_series *src, msx_series *w, int64_t n, int64_t discard, int64_t thin, uint64_t seed,
                         const int64_t *nout, msx_series **dst, int64_t *index_out);
 
+/* ---- Pareto-smoothed importance sampling of a log-weight series -----------------------------------
+ * Kish's effective sample size looks healthy while the variance of the weights is infinite.  PSIS (Vehtari, Simpson, Gelman,
+ * Yao & Gabry 2024) fits a generalised Pareto distribution to the largest weights by Zhang & Stephens' (2009) profile
+ * posterior mean, reports its shape khat -- below about 0.7 the weighted estimates are reliable -- and replaces those weights
+ * by the fitted quantiles.  mcmc_spec_amd/psis.py is the NumPy definition; the reference project has no counterpart.
+ *
+ * Per member, over the FLAT selection of logw (ndim = 1; the family's selection and flat order above), N_m values:
+ *   bad      NaN and +inf are BAD as in msx_series_weights: they weigh 0 and do not count; S = N_m - nbad.  -inf weighs 0 and
+ *            counts.
+ *   shift    x = logw - max (the maximum of the values that are not bad, over the selection).
+ *   cutoff   the element of ascending rank S - tail_len[m] - 1 (0-based) of x, by the radix selection of
+ *            msx_series_order_stats over all of the member's workgroups, and not below MSX_PSIS_LOG_TINY.  tail_len comes from
+ *            the host (ceil(min(S / 5, 3 sqrt(S / reff))) is the papers'); the device never recomputes it.
+ *   tail     the samples with x strictly above the cutoff, ordered by (x, flat index): at most tail_len of them, fewer with
+ *            ties across the cutoff.  Fewer than MSX_PSIS_MIN_TAIL: nothing is smoothed, khat = +inf, MSX_PSIS_SHORT_TAIL (a
+ *            constant log-weight ends here, and so does a member without a finite value, whose weights are all 0).
+ *   fit      t_j = exp(x_j) - exp(cutoff) ascending, n of them; m = 30 + floor(sqrt(n)); b_i = 1 / t_{n-1} + (1 - sqrt(m / (i -
+ *            0.5))) / (3 t_q), i = 1 .. m, t_q = t[int(n / 4 + 0.5) - 1]; k_i = mean_j log1p(-b_i t_j); L_i = n (log(-b_i / k_i)
+ *            - k_i - 1); w_i = 1 / sum_l exp(L_l - L_i); b = sum b_i w_i / sum w_i; k = mean_j log1p(-b t_j); sigma = -k / b;
+ *            khat = (n k + 5) / (n + 10).
+ *   replace  the tail's j-th value becomes min(log(exp(cutoff) + sigma expm1(-khat log1p(-p_j)) / khat), 0), p_j = (j + 0.5) /
+ *            n (the limit -sigma log1p(-p_j) for |khat| < 1e-30).
+ *   weights  w = exp(value - the largest value) into the selected rows of w_dst; every other row of [0, n) weighs 0.  lw_dst
+ *            (may be NULL; as w_dst) receives value - logsumexp(values), the normalised log-weights, -inf elsewhere.
+ * One workgroup per member compacts the tail (value and 32-bit flat index) into LDS, sorts it there, fits and replaces.  Sums
+ * over the tail: lane l of 256 adds elements l, l + 256, .. one after the other, then a fixed tree; sums over the member: lane
+ * l adds, walker after walker, rows l, l + 256, .., then the tree -- an order fixed by (n', W_m) and the tail's length alone.
+ * No float atomics; no workgroup waits for another.  exp, log, log1p, expm1 and sqrt are the device library's.
+ * Outputs per member: khat [k], status [k], tail_count [k], stats [k][6] (msx_series_weights' statistics of the smoothed
+ * weights), tail_index (NULL, or [k][MSX_PSIS_TAIL_MAX]: the tail's flat indices in order, -1 past tail_count).  w_dst then
+ * serves msx_series_wmoments and msx_series_resample as any weights series does.
+ * Refusals, nothing written -- the family's, and MSX_ERR_RANGE: tail_len[m] outside 1 .. min(S - 1, MSX_PSIS_TAIL_MAX) (so
+ * every member needs S >= 2), a member of 2^31 samples or more.                                                            */
+#define MSX_PSIS_TAIL_MAX 4096
+#define MSX_PSIS_MIN_TAIL 5
+#define MSX_PSIS_LOG_TINY (-708.3964185322641) /* log of the smallest normal double */
+#define MSX_PSIS_OK 0
+#define MSX_PSIS_SHORT_TAIL 1
+int msx_series_psis(msx_series *logw, int64_t n, int64_t discard, int64_t thin, const int64_t *tail_len, msx_series *w_dst,
+                    msx_series *lw_dst, double *khat, int32_t *status, int64_t *tail_count, double *stats, int64_t *tail_index);
+
+/* ---- pointwise model checks: PSIS-LOO, WAIC and khat per observation -----------------------------------
+ * "Binary or triple?" for a user who ran a plain chain, and "which data can one sample not stand in for?".  The reference
+ * project has no counterpart; the estimates are those of Vehtari, Gelman & Gabry (2017) with the PSIS above, and
+ * mcmc_spec_amd/psis.py (pointwise_stats) is the NumPy definition.
+ * OBSERVATIONS.  loglikelihood is -0.5 [(nc + np) sum_p z_p^2 / npix + sum_f chi_contrast,f + sum_f chi_phot,f] (mft6.py:1179-1191):
+ * the observations are the npix pixels, then the nc contrast filters, then the np photometry bands, n_obs = npix + nc + np (nc +
+ * np for a problem staged with no_spectrum).  A pixel's term is coef * z^2 with coef = (-0.5 (nc + np)) / npix rounded once and
+ * z^2 the bits the predictive check forms; a filter's term is -0.5 s with s = (z z) / (err err) the summand of the predictive
+ * check's chi_contrast / chi_phot in its roundings.  A sample's terms add up to its MSX_MODE_LOGLIKE value up to the order of
+ * the sum.  These are the terms of the likelihood the reference SAMPLES, its (nc + np) / npix weighting and all, and pixels are
+ * coupled through the continuum fit and the broadening: elpd_loo here is a per-term influence and a RELATIVE score between
+ * models on identical data, errors and pixels -- not an absolute predictive density.
+ * Per observation over the `count` samples that can be evaluated (the others are left out, as in the predictive check), out
+ * [6][n_obs]: lppd = logsumexp_s(ll) - log count; p_waic = var_s(ll) (ddof 1, two passes); elpd_waic = lppd - p_waic; elpd_loo =
+ * logsumexp_s(lw_s + ll_s) with lw the PSIS log-weights of the ratios -ll; p_loo = lppd - elpd_loo; khat.  The tail length is
+ * min(ceil(min(count / 5, 3 sqrt(count / reff))), count - 1), computed on the host once (*tail_len); the cutoff is an exact order
+ * statistic (radix selection).  A term that is NaN or -inf is a BAD ratio: with fewer than tail_len + 1 others khat, elpd_loo
+ * and p_loo are NaN.  count < 2: every output NaN.  One workgroup per observation; sums in an order fixed by the ordered list of
+ * valid samples alone; the bits do not depend on scratch_bytes.
+ * status [n], count as msx_predictive_batch's.  ll_out: NULL, or [n_obs][count] -- the pointwise matrix itself, refused
+ * (MSX_ERR_RANGE) above MSX_POINTWISE_MATRIX_MAX bytes for n_obs x n.  scratch_bytes: 0 (256 MiB) or at least 8 * max(npix, n).
+ * MSX_ERR_RANGE also: a tail over MSX_PSIS_TAIL_MAX (more than 1.8 M samples).  MSX_ERR_STATE: no products staged.
+ * MSX_ERR_INVALID: null pointers, n < 1, ndim != 2 nspec + 2, reff not > 0.  A refused call writes nothing.                   */
+#define MSX_POINTWISE_MATRIX_MAX 1073741824
+int msx_pointwise_nobs(msx_ctx *ctx, int64_t *npix, int32_t *n_contrast, int32_t *n_phot);
+int msx_predictive_pointwise(msx_ctx *ctx, const double *theta, int64_t n, int32_t ndim, double reff, int64_t scratch_bytes,
+                             double *out, int32_t *status, int64_t *count, int64_t *tail_len, double *ll_out);
+/* The same over rows[0:n][discard::thin] of a device chain, member m's flat sample (N_m = n' W_m) evaluated with ctxs[m] as in
+ * msx_series_predictive: out holds the members' [6][n_obs_m] one after the other, count / tail_len / worst_status [k] (the
+ * latter two may be NULL), ll_out (or NULL) member m's [n_obs_m][count_m] at the start of its slot of n_obs_m * N_m doubles.
+ * The bits are msx_predictive_pointwise's for the same samples.  MSX_ERR_RANGE: n past the rows held, an empty selection.      */
+int msx_series_pointwise(msx_series *src, msx_ctx **ctxs, int64_t n, int64_t discard, int64_t thin, double reff,
+                         int64_t scratch_bytes, double *out, int64_t *count, int64_t *tail_len, int32_t *worst_status, double *ll_out);
+
 /* ---- test hooks (used by tests/ only) ------------------------------------------------------------ */
 /* MSX_HOOK_LINKED_FAULT: value != 0 makes the workgroups of the linked form skip their signal -- and the walkers of an
  * overlapped sampler run the publication of their new version -- so that every in-kernel wait runs into its bound;

@@ -30,6 +30,10 @@ MAX_SPEC, MAX_BANDS, MAX_DIM = 3, 8, 8
 MODES_MAX = 4  # MSX_MODES_MAX: the components of a mixture (msx_series_modes)
 MAX_GROUP = 64  # include/msx.h MSX_MAX_GROUP: members of a target group
 RESAMPLE_TILE = 1024  # include/msx.h MSX_RESAMPLE_TILE: the samples of one tile of msx_series_resample's prefix scan
+PSIS_TAIL_MAX, PSIS_MIN_TAIL = 4096, 5  # include/msx.h MSX_PSIS_TAIL_MAX, MSX_PSIS_MIN_TAIL: the longest tail msx_series_psis fits, the shortest
+PSIS_LOG_TINY = -708.3964185322641  # include/msx.h MSX_PSIS_LOG_TINY: log of the smallest normal double
+POINTWISE_MATRIX_MAX = 1 << 30  # include/msx.h MSX_POINTWISE_MATRIX_MAX: the largest pointwise matrix the calls hand back, bytes
+PSIS_OK, PSIS_SHORT_TAIL = 0, 1  # include/msx.h MSX_PSIS_*: a member's status
 PB_TRAPZ, PB_SUM, PB_MEAN = 0, 1, 2  # include/msx.h MSX_PB_*: the kinds of a product band
 SPEC_MEDIAN_SCALE = 1  # include/msx.h MSX_SPEC_MEDIAN_SCALE
 MAX_PCOLS = 64  # include/msx.h MSX_MAX_PCOLS: derived columns of one products_batch call
@@ -236,6 +240,11 @@ def load():
         'msx_series_weights': (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, vp, _dp]),
         'msx_series_wmoments': (C.c_int, [vp, vp, C.c_int64, C.c_int64, C.c_int64, _up, C.c_int32, _dp, _dp, _dp]),
         'msx_series_resample': (C.c_int, [vp, vp, C.c_int64, C.c_int64, C.c_int64, C.c_uint64, _ip, C.POINTER(vp), _ip]),
+        'msx_pointwise_nobs': (C.c_int, [vp, _ip, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+        'msx_predictive_pointwise': (C.c_int, [vp, _dp, C.c_int64, C.c_int32, C.c_double, C.c_int64, _dp, C.POINTER(C.c_int32), _ip, _ip, _dp]),
+        'msx_series_pointwise': (C.c_int, [vp, C.POINTER(vp), C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_int64, _dp, _ip, _ip,
+                                           C.POINTER(C.c_int32), _dp]),
+        'msx_series_psis': (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, _ip, vp, vp, _dp, C.POINTER(C.c_int32), _ip, _dp, _ip]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = header/library skew, fail loudly
@@ -271,7 +280,8 @@ EXPORTED = ['msx_create', 'msx_destroy', 'msx_last_error', 'msx_device_info', 'm
             'msx_group_tempered_end', 'msx_group_tempered_attach_series', 'msx_group_ladder_adapt', 'msx_group_ladder_betas',
             'msx_group_ladder_current', 'msx_series_moments', 'msx_predictive_batch', 'msx_series_predictive',
             'msx_series_modes', 'msx_series_mode_labels',
-            'msx_series_logprob', 'msx_series_lincomb', 'msx_series_weights', 'msx_series_wmoments', 'msx_series_resample']
+            'msx_series_logprob', 'msx_series_lincomb', 'msx_series_weights', 'msx_series_wmoments', 'msx_series_resample',
+            'msx_series_psis', 'msx_pointwise_nobs', 'msx_predictive_pointwise', 'msx_series_pointwise']
 
 
 def as_f64(a):
@@ -533,6 +543,29 @@ class Context:
                                                  int(scratch_bytes), dptr(band), None if quant is None else dptr(quant), dptr(resid),
                                                  dptr(terms), status.ctypes.data_as(C.POINTER(C.c_int32)), iptr(count)))
         return band, quant, resid, terms, status, int(count[0])
+
+    def pointwise_nobs(self):
+        """(npix, nc, np): the observations of the staged problem in the pointwise calls' order -- its pixels (0 for a problem
+        staged with no_spectrum), contrast filters and photometry bands (msx_pointwise_nobs)."""
+        npix, nc, nph = C.c_int64(), C.c_int32(), C.c_int32()
+        self.check(self.lib.msx_pointwise_nobs(self.h, C.byref(npix), C.byref(nc), C.byref(nph)))
+        return int(npix.value), int(nc.value), int(nph.value)
+
+    def predictive_pointwise(self, theta, reff=1.0, scratch_bytes=0, want_matrix=False):
+        """msx_predictive_pointwise over the samples theta (n, ndim): (out (6, n_obs) = lppd, p_waic, elpd_waic, elpd_loo, p_loo,
+        khat per observation, status (n,), count, tail_len, the pointwise matrix (n_obs, count) or None)."""
+        theta = as_f64(theta)
+        n, ndim = theta.shape
+        nobs = sum(self.pointwise_nobs())
+        out = np.empty((6, nobs))
+        status = np.zeros(n, dtype=np.int32)
+        count, tail = np.zeros(1, dtype=np.int64), np.zeros(1, dtype=np.int64)
+        ll = np.empty(nobs * n) if want_matrix else None
+        self.check(self.lib.msx_predictive_pointwise(self.h, dptr(theta), n, ndim, float(reff), int(scratch_bytes), dptr(out),
+                                                     status.ctypes.data_as(C.POINTER(C.c_int32)), iptr(count), iptr(tail),
+                                                     None if ll is None else dptr(ll)))
+        cnt = int(count[0])
+        return out, status, cnt, int(tail[0]), None if ll is None else ll[:nobs * cnt].reshape(nobs, cnt).copy()
 
     def composite_parts(self, teff, logg, rad, use_distance, plx, j0, n):
         """(parts (nspec, n), status): each star's scaled blend over grid samples [j0, j0 + n) (msx_composite_parts)."""
@@ -1339,6 +1372,27 @@ class Series:
         out.update(sumw=stats[:, 3].copy(), sumw2=stats[:, 4].copy(), ess=stats[:, 5].copy())
         return out
 
+    def psis(self, n, tail_len, w_dst, lw_dst=None, discard=0, thin=1, want_tail=False):
+        """This series (ndim = 1) read as log-weights and Pareto-smoothed over rows[0:n][discard::thin] (msx_series_psis):
+        ``tail_len`` (k,) samples per member form the tail; the smoothed, max-normalised weights go to ``w_dst`` and the
+        normalised log-weights to ``lw_dst`` (or None), both of ndim = 1 with the same members.  Returns {'khat' (k,), 'status'
+        (k,), 'ntail' (k,), 'stats': ``weights``' dict for the smoothed weights, 'tail': with ``want_tail`` the tails' flat
+        indices in (value, index) order, a list of k arrays}."""
+        tail_len = np.ascontiguousarray(tail_len, dtype=np.int64).reshape(-1)
+        if tail_len.size != self.k:
+            raise ValueError('psis: one tail_len per member ({})'.format(self.k))
+        khat, status, ntail, stats = np.empty(self.k), np.zeros(self.k, dtype=np.int32), np.zeros(self.k, dtype=np.int64), np.empty((self.k, 6))
+        tail = np.zeros((self.k, PSIS_TAIL_MAX), dtype=np.int64) if want_tail else None
+        self.check(self.lib.msx_series_psis(self.h, int(n), int(discard), int(thin), iptr(tail_len), w_dst.h, None if lw_dst is None else lw_dst.h,
+                                            dptr(khat), status.ctypes.data_as(C.POINTER(C.c_int32)), iptr(ntail), dptr(stats),
+                                            None if tail is None else iptr(tail)))
+        st = {name: stats[:, i].astype(np.int64) for i, name in enumerate(('count', 'nbad', 'nzero'))}
+        st.update(sumw=stats[:, 3].copy(), sumw2=stats[:, 4].copy(), ess=stats[:, 5].copy())
+        out = {'khat': khat, 'status': status.astype(np.int64), 'ntail': ntail, 'stats': st}
+        if want_tail:
+            out['tail'] = [tail[m, :ntail[m]].copy() for m in range(self.k)]
+        return out
+
     def wmoments(self, w, n, discard=0, thin=1, cols=None, cov=True):
         """{'sumw' (k,), 'mean' (k, ncols), 'cov' (k, ncols, ncols) or None}: the moments of rows[0:n][discard::thin] under
         the weights series ``w`` (msx_series_wmoments): mean = sum w x / sum w, cov = sum w (x - mean)(x - mean)^T / sum w."""
@@ -1410,6 +1464,31 @@ class Series:
             out.append((b, qq, resid[3 * off:3 * (off + npix[m])].reshape(3, npix[m])))
             off += npix[m]
         return out, count, worst
+
+    def pointwise(self, contexts, n, discard=0, thin=1, reff=1.0, scratch_bytes=0, want_matrix=False):
+        """msx_series_pointwise over rows[0:n][discard::thin]: per member m, evaluated with ``contexts[m]``, the tuple (out (6,
+        n_obs_m), the pointwise matrix (n_obs_m, count_m) or None); then counts, tail lengths and the members' worst sample
+        status, each (k,)."""
+        contexts = list(contexts)
+        if len(contexts) != self.k:
+            raise ValueError('pointwise: one context per member ({} members)'.format(self.k))
+        nobs = [sum(c.pointwise_nobs()) for c in contexts]
+        nsel = len(range(int(discard), int(n), int(thin))) * np.asarray(self.counts, dtype=np.int64) if int(thin) >= 1 else np.zeros(self.k, dtype=np.int64)
+        out = np.empty(6 * sum(nobs))
+        slots = [int(nobs[m] * nsel[m]) for m in range(self.k)]
+        ll = np.empty(max(sum(slots), 1)) if want_matrix else None
+        count, tail, worst = np.zeros(self.k, dtype=np.int64), np.zeros(self.k, dtype=np.int64), np.zeros(self.k, dtype=np.int32)
+        arr = (C.c_void_p * self.k)(*[c.h for c in contexts])
+        self.check(self.lib.msx_series_pointwise(self.h, arr, int(n), int(discard), int(thin), float(reff), int(scratch_bytes), dptr(out),
+                                                 iptr(count), iptr(tail), worst.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                 None if ll is None else dptr(ll)))
+        parts, o, l = [], 0, 0
+        for m in range(self.k):
+            mat = None if ll is None else ll[l:l + nobs[m] * int(count[m])].reshape(nobs[m], int(count[m])).copy()
+            parts.append((out[o:o + 6 * nobs[m]].reshape(6, nobs[m]), mat))
+            o += 6 * nobs[m]
+            l += slots[m]
+        return parts, count, tail, worst
 
     def order_stats(self, n, discard, thin, cols, ranks):
         """(values (k, ncols, nranks), counts (k,)): the elements of zero-based ranks ``ranks`` (k, nranks; one row is

@@ -80,6 +80,8 @@
 #include "predictive_kernels.h"
 #include "mode_kernels.h"
 #include "reweight_kernels.h"
+#include "psis_kernels.h"
+#include "pointwise_kernels.h"
 #include "opt_run_kernels.h"
 
 // ================================================================================================
@@ -5913,6 +5915,317 @@ int msx_series_resample(msx_series *src, msx_series *w, int64_t n, int64_t disca
     if (index_out) HIP_TRY(src, hipMemcpyAsync(index_out, d_idx, sizeof(int64_t) * (size_t)sum_out, hipMemcpyDeviceToHost, st));
     HIP_TRY(src, hipStreamSynchronize(st));
     for (int m = 0; m < k; ++m) dst[m]->rows = nout[m];
+    return MSX_OK;
+}
+
+// ---- Pareto-smoothed importance sampling (psis_kernels.h) -------------------------------------------
+int msx_series_psis(msx_series *logw, int64_t n, int64_t discard, int64_t thin, const int64_t *tail_len, msx_series *w_dst,
+                    msx_series *lw_dst, double *khat, int32_t *status, int64_t *tail_count, double *stats, int64_t *tail_index) {
+    if (!logw) return MSX_ERR_INVALID;
+    const std::string who("msx_series_psis");
+    if (!tail_len || !w_dst || !khat || !status || !tail_count || !stats)
+        return fail(logw, MSX_ERR_INVALID, who + ": bad arguments (tail_len, w_dst, khat, status, tail_count and stats)");
+    if (logw->ndim != 1 || w_dst == logw || !rw_same_members(logw, w_dst) || w_dst->ndim != 1)
+        return fail(logw, MSX_ERR_INVALID, who + ": the log-weights and w_dst must be two series of ndim = 1 on one device with the same members");
+    if (lw_dst && (lw_dst == logw || lw_dst == w_dst || !rw_same_members(logw, lw_dst) || lw_dst->ndim != 1))
+        return fail(logw, MSX_ERR_INVALID, who + ": lw_dst must be a third series of ndim = 1 on the same device with the same members");
+    if (rw_attached(w_dst) || (lw_dst && rw_attached(lw_dst))) return fail(logw, MSX_ERR_STATE, who + ": a run in flight appends to a destination");
+    int64_t np = 0;
+    if (int rc = rw_selection(logw, who, n, discard, thin, &np)) return rc;
+    if (logw->nw > 65535) return fail(logw, MSX_ERR_RANGE, who + ": more walkers than one launch covers");
+    const int k = (int)logw->off.size() - 1;
+    const int64_t nw = logw->nw;
+    for (int m = 0; m < k; ++m) {
+        if (np * (logw->off[(size_t)m + 1] - logw->off[(size_t)m]) > 0x7fffffffll)
+            return fail(logw, MSX_ERR_RANGE, who + ": a member of 2^31 samples or more");
+        if (tail_len[m] < 1 || tail_len[m] > MSX_PSIS_TAIL_MAX)
+            return fail(logw, MSX_ERR_RANGE, who + ": member " + std::to_string(m) + "'s tail_len lies outside 1 .. MSX_PSIS_TAIL_MAX");
+    }
+    HIP_TRY(logw, hipSetDevice(logw->device));
+    hipStream_t st = logw->stream;
+    // scratch, w_dst's (the selection below uses logw's): [pmax nw | psum 2 nw | cut k | res 3 k | stats 6 k | pcnt 2 nw | nbad k | tail k TAIL_MAX]
+    const size_t b_tail = tail_index ? sizeof(long long) * (size_t)k * MSX_PSIS_TAIL_MAX : 0;
+    HIP_TRY(logw, series_scratch(w_dst, sizeof(double) * (size_t)(3 * nw + 10 * k) + sizeof(long long) * (size_t)(2 * nw + k) + b_tail));
+    double *d_pmax = (double *)w_dst->d_scratch, *d_psum = d_pmax + nw, *d_cut = d_psum + 2 * nw, *d_res = d_cut + k, *d_stats = d_res + 3 * k;
+    long long *d_pcnt = (long long *)(d_stats + 6 * k);
+    unsigned long long *d_nbad = (unsigned long long *)(d_pcnt + 2 * nw);
+    long long *d_tail = tail_index ? (long long *)(d_nbad + k) : nullptr;
+    HIP_TRY(logw, series_wait_growth(logw));
+    HIP_TRY(logw, hipMemsetAsync(d_nbad, 0, sizeof(unsigned long long) * (size_t)k, st));
+    hipLaunchKernelGGL(psis_scan_kernel, dim3((unsigned)nw), dim3(kPsThreads), 0, st, (const double *)logw->d_rows, logw->cap, np, discard, thin,
+                       (const int64_t *)logw->d_off, (int32_t)k, d_pmax, d_nbad);
+    HIP_TRY(logw, hipGetLastError());
+    std::vector<unsigned long long> nbad((size_t)k);
+    HIP_TRY(logw, hipMemcpyAsync(nbad.data(), d_nbad, sizeof(unsigned long long) * (size_t)k, hipMemcpyDeviceToHost, st));
+    HIP_TRY(logw, hipStreamSynchronize(st));
+    std::vector<int64_t> ranks((size_t)k);
+    for (int m = 0; m < k; ++m) {
+        const int64_t S = np * (logw->off[(size_t)m + 1] - logw->off[(size_t)m]) - (int64_t)nbad[(size_t)m];
+        if (tail_len[m] > S - 1)
+            return fail(logw, MSX_ERR_RANGE, who + ": member " + std::to_string(m) + "'s tail_len lies outside 1 .. S - 1 (S = " + std::to_string(S) +
+                                                 " samples that are not NaN or +inf)");
+        ranks[(size_t)m] = S - tail_len[m] - 1;   // (NaN and +inf take the top keys of the selection: the bad values lie above every rank < S)
+    }
+    std::vector<double> cut((size_t)k);
+    const uint32_t col0 = 0;
+    if (int rc = msx_series_order_stats(logw, n, discard, thin, &col0, 1, ranks.data(), 1, cut.data(), nullptr)) return rc;
+    HIP_TRY(logw, series_reserve(w_dst, n, w_dst->rows, st));
+    if (lw_dst) HIP_TRY(logw, series_reserve(lw_dst, n, lw_dst->rows, st));
+    if (w_dst->grown_set) HIP_TRY(logw, hipStreamWaitEvent(st, w_dst->grown, 0));
+    if (lw_dst && lw_dst->grown_set) HIP_TRY(logw, hipStreamWaitEvent(st, lw_dst->grown, 0));
+    HIP_TRY(logw, hipMemcpyAsync(d_cut, cut.data(), sizeof(double) * (size_t)k, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(psis_fill_kernel, dim3((unsigned)((n + kPsThreads - 1) / kPsThreads), (unsigned)nw), dim3(kPsThreads), 0, st, n, w_dst->d_rows,
+                       w_dst->cap, lw_dst ? lw_dst->d_rows : nullptr, lw_dst ? lw_dst->cap : 0);
+    HIP_TRY(logw, hipGetLastError());
+    PsisArgs A;
+    memset(&A, 0, sizeof(A));
+    A.logw = logw->d_rows; A.cap = logw->cap; A.np = np; A.discard = discard; A.thin = thin;
+    A.member_off = logw->d_off; A.pmax = d_pmax; A.cut = d_cut;
+    A.wt = w_dst->d_rows; A.wcap = w_dst->cap;
+    A.lwt = lw_dst ? lw_dst->d_rows : nullptr; A.lcap = lw_dst ? lw_dst->cap : 0;
+    A.res = d_res; A.tail_index = d_tail;
+    hipLaunchKernelGGL(psis_reduce_kernel, dim3((unsigned)k), dim3(kPsThreads), 0, st, A);
+    HIP_TRY(logw, hipGetLastError());
+    hipLaunchKernelGGL(rw_stat_kernel, dim3((unsigned)nw), dim3(kRwThreads), 0, st, (const double *)logw->d_rows, logw->cap,
+                       (const double *)w_dst->d_rows, w_dst->cap, nw, np, discard, thin, d_pcnt, d_psum);
+    HIP_TRY(logw, hipGetLastError());
+    hipLaunchKernelGGL(rw_stat_combine_kernel, dim3(1), dim3(MSX_MAX_GROUP), 0, st, (const long long *)d_pcnt, (const double *)d_psum,
+                       (const int64_t *)logw->d_off, (int32_t)k, nw, np, d_stats);
+    HIP_TRY(logw, hipGetLastError());
+    std::vector<double> hbuf((size_t)(9 * k));   // (res and stats lie side by side: one copy)
+    HIP_TRY(logw, hipMemcpyAsync(hbuf.data(), d_res, sizeof(double) * hbuf.size(), hipMemcpyDeviceToHost, st));
+    if (tail_index) HIP_TRY(logw, hipMemcpyAsync(tail_index, d_tail, b_tail, hipMemcpyDeviceToHost, st));
+    HIP_TRY(logw, hipStreamSynchronize(st));
+    for (int m = 0; m < k; ++m) {
+        khat[m] = hbuf[(size_t)m * 3];
+        status[m] = (int32_t)hbuf[(size_t)m * 3 + 1];
+        tail_count[m] = (int64_t)hbuf[(size_t)m * 3 + 2];
+    }
+    memcpy(stats, hbuf.data() + 3 * k, sizeof(double) * (size_t)(6 * k));
+    w_dst->rows = std::max(w_dst->rows, n);
+    if (lw_dst) lw_dst->rows = std::max(lw_dst->rows, n);
+    return MSX_OK;
+}
+
+// ---- pointwise model checks: PSIS-LOO, WAIC, khat per observation (pointwise_kernels.h) -------------
+static int64_t pw_nobs(const msx_ctx *c) { return (c->PM.no_spectrum ? 0 : c->PM.npix) + c->PM.nc + c->PM.np; }
+// the smallest scratch a job can run in: one work row of the sample pass, or one observation's terms of every selected sample
+static size_t pw_min_bytes(int64_t npix, int64_t nsel) { return sizeof(double) * (size_t)std::max(npix, nsel); }
+// ceil(min(S / 5, 3 sqrt(S / reff))): the papers' tail length, computed here on the host, once (psis.tail_len's expression)
+static int64_t pw_tail_len(int64_t S, double reff) {
+    const double dS = (double)S;
+    return (int64_t)ceil(std::min(dS / 5.0, 3.0 * sqrt(dS / reff)));
+}
+struct PwSizes {
+    size_t b_rec, b_status, b_vidx, b_out, b_big, total;
+};
+static PwSizes pw_sizes(const PredJob &J, size_t budget) {
+    PwSizes Z;
+    const int64_t npix = J.c->PM.npix, nobs = pw_nobs(J.c);
+    const size_t most = sizeof(double) * (size_t)std::max(npix * J.nall, nobs * J.nsel);  // everything at once
+    Z.b_big = pred_align(std::min(budget, most));
+    Z.b_rec = pred_align(sizeof(PredRec) * (size_t)J.nall);
+    Z.b_status = pred_align(sizeof(int32_t) * (size_t)J.nall);
+    Z.b_vidx = pred_align(sizeof(int64_t) * (size_t)J.nsel);
+    Z.b_out = pred_align(sizeof(double) * (size_t)(kPwOut * nobs));
+    Z.total = Z.b_rec + Z.b_status + Z.b_vidx + Z.b_out + Z.b_big;
+    return Z;
+}
+
+// Runs the job on `st` inside d_arena (pw_sizes(...).total bytes) and waits for it.  out [6][n_obs], status_out [nall] or null,
+// ll_out [n_obs][count] or null: host; nothing is written to them before the job has succeeded up to the tail's check.
+static int pw_run(const PredJob &J, hipStream_t st, char *d_arena, const PwSizes &Z, size_t budget, double reff, double *out,
+                  int32_t *status_out, int64_t *count_out, int64_t *tail_out, int32_t *worst_out, double *ll_out, std::string *err) {
+#define PW_TRY(expr)                                                                                \
+    do {                                                                                            \
+        hipError_t e__ = (expr);                                                                    \
+        if (e__ != hipSuccess) { *err = std::string(#expr) + ": " + hipGetErrorString(e__); return MSX_ERR_HIP; } \
+    } while (0)
+    const int ns = J.c->PM.nspec;
+    const int64_t npix = J.c->PM.npix, nobs = pw_nobs(J.c), nb = J.c->PM.nc + J.c->PM.np, npx = nobs - nb;
+    char *at = d_arena;
+    PredRec *d_rec = reinterpret_cast<PredRec *>(at); at += Z.b_rec;
+    int32_t *d_status = reinterpret_cast<int32_t *>(at); at += Z.b_status;
+    int64_t *d_vidx = reinterpret_cast<int64_t *>(at); at += Z.b_vidx;
+    double *d_out = reinterpret_cast<double *>(at); at += Z.b_out;
+    double *d_big = reinterpret_cast<double *>(at);
+    const size_t big = std::min(budget, Z.b_big);
+    // the unchanged sample pass of the predictive check, without its terms
+    const int64_t batch = std::max<int64_t>(1, std::min<int64_t>(J.nall, (int64_t)(big / (sizeof(double) * (size_t)std::max<int64_t>(npix, 1)))));
+    PredSampleLaunch SL;
+    memset(&SL, 0, sizeof(SL));
+    SL.M = J.c->d_prod_member; SL.src = J.src; SL.work = d_big; SL.rec = d_rec; SL.status = d_status;
+    for (int64_t i0 = 0; i0 < J.nall; i0 += batch) {
+        SL.i0 = i0;
+        const dim3 grid((unsigned)std::min(batch, J.nall - i0));
+        if (ns == 2) hipLaunchKernelGGL(predictive_sample_kernel<2>, grid, dim3(kPredThreads), 0, st, SL);
+        else hipLaunchKernelGGL(predictive_sample_kernel<3>, grid, dim3(kPredThreads), 0, st, SL);
+        PW_TRY(hipGetLastError());
+    }
+    std::vector<int32_t> status((size_t)J.nall);
+    PW_TRY(hipMemcpyAsync(status.data(), d_status, sizeof(int32_t) * (size_t)J.nall, hipMemcpyDeviceToHost, st));
+    PW_TRY(hipStreamSynchronize(st));
+    std::vector<int64_t> vidx;
+    vidx.reserve((size_t)J.nsel);
+    int32_t worst = 0;
+    for (int64_t i = 0; i < J.nall; ++i) {
+        worst = std::max(worst, status[(size_t)i]);
+        const int64_t ri = i / J.src.W;
+        if (ri >= J.sel0 && (ri - J.sel0) % J.selstep == 0 && status[(size_t)i] == MSX_W_OK) vidx.push_back(i);
+    }
+    const int64_t count = (int64_t)vidx.size();
+    const int64_t tail = count >= 2 ? std::min(pw_tail_len(count, reff), count - 1) : 0;
+    if (tail > MSX_PSIS_TAIL_MAX) {
+        *err = "the tail of " + std::to_string(count) + " samples is longer than MSX_PSIS_TAIL_MAX";
+        return MSX_ERR_RANGE;
+    }
+    if (status_out) memcpy(status_out, status.data(), sizeof(int32_t) * (size_t)J.nall);
+    *count_out = count;
+    if (tail_out) *tail_out = tail;
+    if (worst_out) *worst_out = worst;
+    if (count < 2 || tail < 1) {   // nothing to leave out
+        std::fill(out, out + kPwOut * nobs, (double)NAN);
+        return MSX_OK;
+    }
+    PW_TRY(hipMemcpyAsync(d_vidx, vidx.data(), sizeof(int64_t) * (size_t)count, hipMemcpyHostToDevice, st));
+    // observation tiles sized from the scratch by the SELECTED samples (not by how many turned out valid)
+    const int64_t tile = std::max<int64_t>(1, (int64_t)(big / (sizeof(double) * (size_t)J.nsel)));
+    PwPixelLaunch XL;
+    memset(&XL, 0, sizeof(XL));
+    XL.M = J.c->d_prod_member; XL.rec = d_rec; XL.vidx = d_vidx; XL.count = count; XL.vals = d_big;
+    XL.coef = (-0.5 * (double)nb) / (double)npix;
+    PwBandLaunch BL;
+    memset(&BL, 0, sizeof(BL));
+    BL.M = J.c->d_prod_member; BL.rec = d_rec; BL.vidx = d_vidx; BL.src = J.src; BL.count = count; BL.vals = d_big;
+    PwReduceLaunch RL;
+    memset(&RL, 0, sizeof(RL));
+    RL.vals = d_big; RL.count = count; RL.n_obs = nobs; RL.tail_len = tail; RL.out = d_out;
+    for (int64_t o0 = 0; o0 < nobs;) {
+        const bool pixels = o0 < npx;
+        const int64_t to = std::min(tile, (pixels ? npx : nobs) - o0);   // (a tile holds pixels or filters, not both)
+        if (pixels) {
+            XL.p0 = o0; XL.tp = to;
+            const int64_t gx = (count + kPredTile - 1) / kPredTile, chunks = (to + kPredTile - 1) / kPredTile;
+            const dim3 fgrid((unsigned)gx, (unsigned)std::max<int64_t>(1, std::min<int64_t>(chunks, 2048 / std::min<int64_t>(gx, 2048))));
+            if (ns == 2) hipLaunchKernelGGL(pointwise_pixel_kernel<2>, fgrid, dim3(kPredThreads), 0, st, XL);
+            else hipLaunchKernelGGL(pointwise_pixel_kernel<3>, fgrid, dim3(kPredThreads), 0, st, XL);
+        } else {
+            BL.f0 = (int32_t)(o0 - npx); BL.tf = (int32_t)to;
+            const dim3 bgrid((unsigned)((count + kPredThreads - 1) / kPredThreads));
+            if (ns == 2) hipLaunchKernelGGL(pointwise_band_kernel<2>, bgrid, dim3(kPredThreads), 0, st, BL);
+            else hipLaunchKernelGGL(pointwise_band_kernel<3>, bgrid, dim3(kPredThreads), 0, st, BL);
+        }
+        PW_TRY(hipGetLastError());
+        RL.o0 = o0;
+        hipLaunchKernelGGL(pointwise_reduce_kernel, dim3((unsigned)to), dim3(kPredThreads), 0, st, RL);
+        PW_TRY(hipGetLastError());
+        if (ll_out) PW_TRY(hipMemcpyAsync(ll_out + o0 * count, d_big, sizeof(double) * (size_t)(to * count), hipMemcpyDeviceToHost, st));
+        o0 += to;
+    }
+    PW_TRY(hipMemcpyAsync(out, d_out, sizeof(double) * (size_t)(kPwOut * nobs), hipMemcpyDeviceToHost, st));
+    PW_TRY(hipStreamSynchronize(st));
+    return MSX_OK;
+#undef PW_TRY
+}
+
+int msx_pointwise_nobs(msx_ctx *c, int64_t *npix, int32_t *n_contrast, int32_t *n_phot) {
+    if (!c) return MSX_ERR_INVALID;
+    if (!npix || !n_contrast || !n_phot) return fail(c, MSX_ERR_INVALID, "msx_pointwise_nobs: bad arguments");
+    if (!c->problem_staged || !c->products_staged) return fail(c, MSX_ERR_STATE, "msx_pointwise_nobs: no products staged (msx_stage_products)");
+    *npix = c->PM.no_spectrum ? 0 : c->PM.npix;
+    *n_contrast = c->PM.nc;
+    *n_phot = c->PM.np;
+    return MSX_OK;
+}
+
+int msx_predictive_pointwise(msx_ctx *c, const double *theta, int64_t n, int32_t ndim, double reff, int64_t scratch_bytes, double *out,
+                             int32_t *status, int64_t *count, int64_t *tail_len, double *ll_out) {
+    if (!c) return MSX_ERR_INVALID;
+    const std::string who("msx_predictive_pointwise");
+    if (!theta || !out || !status || !count || n < 1 || scratch_bytes < 0 || !(reff > 0.0) || !std::isfinite(reff))
+        return fail(c, MSX_ERR_INVALID, who + ": bad arguments (theta, out, status, count, n >= 1, scratch_bytes >= 0, reff > 0)");
+    if (!c->problem_staged || !c->products_staged) return fail(c, MSX_ERR_STATE, who + ": no products staged (msx_stage_products)");
+    if (ndim != 2 * c->P.nspec + 2) return fail(c, MSX_ERR_INVALID, who + ": ndim must be 2 * nspec + 2");
+    if (c->P.npix > INT32_MAX || n > INT32_MAX) return fail(c, MSX_ERR_RANGE, who + ": too many pixels or samples");
+    const size_t budget = scratch_bytes ? (size_t)scratch_bytes : kPredDefaultBytes;
+    if (budget < pw_min_bytes(c->P.npix, n))
+        return fail(c, MSX_ERR_RANGE, who + ": scratch_bytes holds neither one model row nor one observation's terms of the n samples (8 * max(npix, n) bytes)");
+    if (ll_out && sizeof(double) * (size_t)pw_nobs(c) * (size_t)n > (size_t)MSX_POINTWISE_MATRIX_MAX)
+        return fail(c, MSX_ERR_RANGE, who + ": the pointwise matrix is larger than MSX_POINTWISE_MATRIX_MAX bytes");
+    HIP_TRY(c, hipSetDevice(c->device));
+    PredJob J;
+    memset(&J, 0, sizeof(J));
+    J.c = c; J.nall = n; J.sel0 = 0; J.selstep = 1; J.nsel = n;
+    const PwSizes Z = pw_sizes(J, budget);
+    const size_t b_theta = pred_align(sizeof(double) * (size_t)(n * ndim));
+    const size_t need = b_theta + Z.total;
+    if (need > c->prod_buf_bytes) {
+        if (c->d_prod_buf) (void)hipFree(c->d_prod_buf);
+        c->d_prod_buf = nullptr; c->prod_buf_bytes = 0;
+        HIP_TRY(c, hipMalloc((void **)&c->d_prod_buf, need));
+        c->prod_buf_bytes = need;
+    }
+    double *d_theta = reinterpret_cast<double *>(c->d_prod_buf);
+    HIP_TRY(c, hipMemcpyAsync(d_theta, theta, sizeof(double) * (size_t)(n * ndim), hipMemcpyHostToDevice, c->stream));
+    J.src.base = d_theta; J.src.W = n; J.src.w0 = 0; J.src.sw = ndim; J.src.sr = 0; J.src.sd = 1; J.src.row0 = 0; J.src.rstep = 1;
+    std::string err;
+    if (int rc = pw_run(J, c->stream, c->d_prod_buf + b_theta, Z, budget, reff, out, status, count, tail_len, nullptr, ll_out, &err))
+        return fail(c, rc, who + ": " + err);
+    return MSX_OK;
+}
+
+int msx_series_pointwise(msx_series *src, msx_ctx **ctxs, int64_t n, int64_t discard, int64_t thin, double reff, int64_t scratch_bytes,
+                         double *out, int64_t *count, int64_t *tail_len, int32_t *worst_status, double *ll_out) {
+    if (!src) return MSX_ERR_INVALID;
+    const std::string who("msx_series_pointwise");
+    if (!ctxs || !out || !count || discard < 0 || thin < 1 || scratch_bytes < 0 || !(reff > 0.0) || !std::isfinite(reff))
+        return fail(src, MSX_ERR_INVALID, who + ": bad arguments (ctxs, out, count, discard >= 0, thin >= 1, scratch_bytes >= 0, reff > 0)");
+    if (n < 1 || n > src->rows) return fail(src, MSX_ERR_RANGE, who + ": n must lie in 1 .. the rows the series holds");
+    const int64_t np = discard < n ? (n - discard + thin - 1) / thin : 0;
+    if (np < 1) return fail(src, MSX_ERR_RANGE, who + ": the selection rows[0:n][discard::thin] is empty");
+    const int k = (int)src->off.size() - 1;
+    const size_t budget = scratch_bytes ? (size_t)scratch_bytes : kPredDefaultBytes;
+    int nspec = 0;
+    std::vector<PredJob> jobs((size_t)k);
+    size_t arena = 0, matrix = 0;
+    for (int m = 0; m < k; ++m) {
+        const msx_ctx *c = ctxs[m];
+        const std::string mem = who + ": member " + std::to_string(m);
+        if (!c) return fail(src, MSX_ERR_INVALID, mem + " is null");
+        if (c->device != src->device) return fail(src, MSX_ERR_INVALID, mem + " lives on another device");
+        if (!c->problem_staged || !c->products_staged) return fail(src, MSX_ERR_STATE, mem + " has no staged products (msx_stage_products)");
+        if (m == 0) nspec = c->PM.nspec;
+        if (c->PM.nspec != nspec || src->ndim != 2 * nspec + 2) return fail(src, MSX_ERR_INVALID, mem + ": src's ndim must be 2 * nspec + 2 of every member");
+        const int64_t W = src->off[(size_t)m + 1] - src->off[(size_t)m];
+        PredJob &J = jobs[(size_t)m];
+        memset(&J, 0, sizeof(J));
+        J.c = c;
+        J.src.W = W; J.src.w0 = src->off[(size_t)m];
+        J.src.row0 = discard; J.src.rstep = thin; J.nall = np * W; J.sel0 = 0; J.selstep = 1; J.nsel = np * W;
+        if (c->PM.npix > INT32_MAX || J.nsel > INT32_MAX) return fail(src, MSX_ERR_RANGE, mem + ": too many pixels or samples");
+        if (budget < pw_min_bytes(c->PM.npix, J.nsel))
+            return fail(src, MSX_ERR_RANGE, mem + ": scratch_bytes holds neither one model row nor one observation's terms of its samples (8 * max(npix, N_m) bytes)");
+        matrix += sizeof(double) * (size_t)pw_nobs(c) * (size_t)J.nsel;
+        arena = std::max(arena, pw_sizes(J, budget).total);
+    }
+    if (ll_out && matrix > (size_t)MSX_POINTWISE_MATRIX_MAX) return fail(src, MSX_ERR_RANGE, who + ": the pointwise matrices are larger than MSX_POINTWISE_MATRIX_MAX bytes");
+    HIP_TRY(src, hipSetDevice(src->device));
+    hipStream_t st = src->stream;
+    HIP_TRY(src, series_scratch(src, arena));
+    HIP_TRY(src, series_wait_growth(src));
+    size_t o_out = 0, o_ll = 0;
+    for (int m = 0; m < k; ++m) {
+        PredJob &J = jobs[(size_t)m];
+        J.src.base = src->d_rows; J.src.sw = src->cap; J.src.sr = 1; J.src.sd = src->nw * src->cap;
+        const PwSizes Z = pw_sizes(J, budget);
+        std::string err;
+        int32_t worst = 0;
+        if (int rc = pw_run(J, st, src->d_scratch, Z, budget, reff, out + o_out, nullptr, count + m, tail_len ? tail_len + m : nullptr, &worst,
+                            ll_out ? ll_out + o_ll : nullptr, &err))
+            return fail(src, rc, who + ": member " + std::to_string(m) + ": " + err);
+        if (worst_status) worst_status[m] = worst;
+        o_out += (size_t)(kPwOut * pw_nobs(J.c)); o_ll += (size_t)pw_nobs(J.c) * (size_t)J.nsel;
+    }
     return MSX_OK;
 }
 

@@ -497,6 +497,15 @@ class DeviceGroupSampler(GroupSampler):
                                   len(self.samplers[0]._chain), self.group.engines, self.nwalkers, q, discard, thin)
         return out if k is None else out[k]
 
+    def get_loo(self, discard=0, thin=1, reff=1.0, k=None):
+        """Every target's PSIS-LOO, WAIC and khat per observation (``mcmc_spec_amd.psis``) of its
+        stored chain, each target's samples evaluated with its own engine: a list of K ``psis.loo`` dicts, or target
+        ``k``'s.  With autocorr='device' on the chains held there, otherwise the host chains are uploaded first."""
+        from . import psis
+        out = psis.of_chain(self._series, lambda: np.concatenate([np.array(s._chain) for s in self.samplers], axis=1),
+                            len(self.samplers[0]._chain), self.group.engines, self.nwalkers, discard, thin, reff)
+        return out if k is None else out[k]
+
     def get_reweighted(self, engines_new, mode='logposterior', discard=0, thin=1):
         """``DeviceEnsembleSampler.get_reweighted`` for every target at once: ``engines_new`` holds one staged Engine per
         target (a target's own engine leaves its weights at 1), and the ``reweight.Reweighted`` it returns has one member

@@ -282,6 +282,14 @@ class Reweighted:
         out = [dst[m] for m in self.members]
         return (out, [idx[m] for m in self.members]) if want_indices else out
 
+    def smooth(self, reff=1.0):
+        """The same chain under the Pareto-smoothed weights (``psis.Smoothed``; msx_series_psis): this object's interface, and
+        ``khat`` / ``status`` per member -- khat above about 0.7 says the weights cannot be trusted, whatever ``stats['ess']``
+        shows.  ``reff``: the chain's relative efficiency, for the tail's length.  This object and its ``stats`` stay as they
+        are; close the result before this."""
+        from .psis import Smoothed
+        return Smoothed(self, reff)
+
     def close(self):
         for s in self._owned:
             s.close()

@@ -680,6 +680,15 @@ class DeviceEnsembleSampler(EnsembleSampler):
         return predictive.of_chain(self._series, lambda: np.array(self._chain), len(self._chain), [self.engine], None, q, discard,
                                    thin)[0]
 
+    def get_loo(self, discard=0, thin=1, reff=1.0):
+        """PSIS-LOO, WAIC and khat per observation of the stored chain (``mcmc_spec_amd.psis``):
+        ``psis.loo``'s dict (``worst_status`` in place of ``status``) over ``get_chain(discard=, thin=, flat=True)``, from
+        the chain held on the device with autocorr='device', otherwise from the host chain uploaded first.  A relative score
+        between models on identical data (``psis.compare``), and the observations one sample cannot stand in for (khat >
+        0.7).  The engine needs staged products (``products.stage``)."""
+        from . import psis
+        return psis.of_chain(self._series, lambda: np.array(self._chain), len(self._chain), [self.engine], None, discard, thin, reff)[0]
+
     def get_reweighted(self, engines_new, mode='logposterior', discard=0, thin=1):
         """The stored chain asked another question without a second run (``mcmc_spec_amd.reweight``):
         a ``reweight.Reweighted`` whose log-weight is ``lp_new - lp_old`` -- ``lp_new`` the ``mode`` of ``engines_new`` (one

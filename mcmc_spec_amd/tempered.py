@@ -466,6 +466,19 @@ class _Ladder:
                                       [self.nwalkers] * self.ntemps, q, discard, thin)
         return out if t is None else out[int(t)]
 
+    def get_loo(self, t=0, discard=0, thin=1, reff=1.0):
+        """Rung t's PSIS-LOO, WAIC and khat per observation (``mcmc_spec_amd.psis``) of its stored
+        chain -- rung 0 is the posterior --, ``psis.loo``'s dict; ``t=None``: a list of every rung's.  With autocorr='device'
+        from the chain held there, otherwise the host chain is uploaded first."""
+        from . import psis
+        self._ctx()
+        if self._series is not None:
+            out = psis.of_chain(self._series, None, len(self._chain), self._series_engines(), None, discard, thin, reff)[self._own]
+        else:
+            out = psis.of_chain(None, self._flat_members, len(self._chain), [self.engine] * self.ntemps, [self.nwalkers] * self.ntemps,
+                                discard, thin, reff)
+        return out if t is None else out[int(t)]
+
     def get_reweighted(self, engines_new=None, t=0, mode='logposterior', discard=0, thin=1):
         """What rung t's stored chain says about another density (``mcmc_spec_amd.reweight``): a
         ``reweight.Reweighted`` of one member whose log-weight is ``lp_new - lpr - betas[t] * ll`` -- ``lp_new`` the

@@ -248,6 +248,8 @@ rot_broaden_kernel(const double *__restrict__ in, int64_t in_stride, const doubl
 // np.interp / scipy interp1d(kind='linear') arithmetic (mft6.py:369-371): one thread per query.
 __global__ void resample_kernel(const double *__restrict__ xs, const double *__restrict__ ys, int64_t n,
                                 const double *__restrict__ xq, int64_t m, double *__restrict__ out) {
+#pragma clang fp contract(off)
+    // slope * (x - xs[j]) + ys[j] rounds the product, as NumPy does: a fused multiply-add is an ulp away on most queries
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= m) return;
     const double x = xq[i];

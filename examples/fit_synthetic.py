@@ -52,6 +52,8 @@ def main():
                     help='with --tempered: N adaptive iterations first (the rungs move towards equal swap rates), then the ladder is frozen')
     ap.add_argument('--predictive', action='store_true',
                     help='after the run: the posterior predictive check of the stored chain (chi^2 terms, worst pixels, largest mean residual)')
+    ap.add_argument('--ess', action='store_true',
+                    help='rank-normalised R-hat, bulk / tail ESS and the MCSE of the 16 / 50 / 84 percentiles (DESIGN.md section 26)')
     ap.add_argument('--loo', action='store_true',
                     help='after the run: PSIS-LOO and WAIC of the stored chain per pixel and filter (totals, how many khat > 0.7, the worst pixels)')
     ap.add_argument('--modes', action='store_true',
@@ -140,6 +142,12 @@ def main():
     prod = sampler.get_products(['kep_contrast', 'pri_corr', 'sec_corr'])
     for nm, (lo, mid, hi) in zip(['dKep', 'f_pri', 'f_sec'], prod['quantiles']):
         print('  {:5s} {:.6g} / {:.6g} / {:.6g}'.format(nm, lo, mid, hi))
+    if args.ess:   # how far can the numbers above be trusted?  (Vehtari et al. 2021: want R-hat < 1.01, bulk and tail ESS > 400)
+        rr, mc = sampler.get_rank_rhat()['rhat'], sampler.get_mcse()
+        bulk, tail = sampler.get_ess(kind='bulk'), sampler.get_ess(kind='tail')
+        print('        R-hat (rank)  ESS bulk  ESS tail   MCSE of 16 / 50 / 84')
+        for i, nm in enumerate(['T1', 'T2', 'Av', 'R1', 'R2', 'plx']):
+            print('  {:5s} {:12.4f} {:9.1f} {:9.1f}   {:.3g} / {:.3g} / {:.3g}'.format(nm, rr[i], bulk[i], tail[i], *mc['quantiles'][i]))
     if args.modes:   # which mode, with what probability?  (the reference's p_t1 and its siblings, mft6.py:2030-2194, jointly)
         from mcmc_spec_amd import modes
         modes.print_table(sampler.get_modes(), ['T1', 'T2', 'Av', 'R1', 'R2', 'plx'], sampler.get_modes(ncomp=1))

@@ -1076,6 +1076,52 @@ int msx_predictive_pointwise(msx_ctx *ctx, const double *theta, int64_t n, int32
 int msx_series_pointwise(msx_series *src, msx_ctx **ctxs, int64_t n, int64_t discard, int64_t thin, double reff,
                          int64_t scratch_bytes, double *out, int64_t *count, int64_t *tail_len, int32_t *worst_status, double *ll_out);
 
+/* ---- the split pool, transformed: ranks, normal scores, folding, indicators ----------------------------
+ * What rank-normalised R-hat, bulk / tail ESS and the Monte-Carlo standard errors (Vehtari et al. 2021) are made of;
+ * mcmc_spec_amd/diagnostics.py is the definition.  The selection x = rows[0:n][discard::thin] (n' >= 4 rows) of src is
+ * msx_series_acf's; h = n' / 2.  dst is another series on src's device with 2 nw walkers, ndim = ncols and members of 2 W_m
+ * walkers: walker 2 w + half of dst receives, in rows 0 .. h - 1, the transformed rows [0, h) (half 0) or [n' - h, n') (half 1)
+ * of source walker w -- msx_series_moments' half-chains as chains of their own; an odd n' leaves the middle row out.  dst grows
+ * as msx_series_append grows a series and then holds exactly h rows, on which msx_series_order_stats (the IDENTITY series is
+ * the split pool: its medians and quantiles), _hist, _read, _acf and msx_series_chain_acov work as on any series.  A member's
+ * column is a SEGMENT of S = 2 W_m h values.  cols: coordinates or MSX_COL_RATIO codes, at most MSX_MAX_DIM.  Transforms:
+ *   MSX_SPLIT_IDENTITY       x;
+ *   MSX_SPLIT_RANKNORM       z = ndtri((r - 3/8) / (S + 1/4)), r the 1-based rank of x in its segment, ties sharing the mean of
+ *                            their positions (twice a rank is an integer), -0 and +0 tied; ndtri is AS 241's PPND16 in
+ *                            float64 + - * /, log and sqrt, the coefficients in diagnostics.ndtri's order;
+ *   MSX_SPLIT_FOLD_RANKNORM  the same of |x - param[m * ncols + j]| (the caller's median of the segment);
+ *   MSX_SPLIT_INDICATOR      1 where x <= param[m * ncols + j], 0 elsewhere, NaN for a NaN;
+ *   MSX_SPLIT_RANK2          twice the rank itself, as a double (what the tests compare with 2 * rankdata).
+ * A ranked segment that holds a non-finite value, or one distinct value, is NaN all over; nothing else is touched by it.  Ranks
+ * come from a segmented radix sort of (key, position) pairs -- keys as msx_series_order_stats' -- in 8-bit passes of three
+ * launches each (per-tile digit counts, scan, stable scatter); passes whose digit is the same all over every segment of a round
+ * are dropped.  Ranks depend on the keys alone: the result has the same bits whatever the launch, the budget, or how the rows
+ * arrived.  Scratch comes from src's scratch buffer: scratch_bytes (0: 256 MiB) bounds it, segments are sorted in as many rounds
+ * as that needs, and MSX_ERR_RANGE refuses a budget below the largest segment's need (24 S bytes and its tables:
+ * msx_split_scratch_bytes).  Synchronous, on src's stream; waits for nothing but the latest growth copies.
+ * MSX_ERR_INVALID: a null series, dst == src or on another device, discard < 0, thin < 1, ncols < 1, cols NULL, an unknown
+ * transform, param NULL where the transform reads it, scratch_bytes < 0.  MSX_ERR_STATE: a run in flight appends to dst.
+ * MSX_ERR_RANGE: n past the rows held, fewer than 4 rows selected, an unknown column, more than MSX_MAX_DIM columns, a dst whose
+ * walkers, members or ndim are not 2 nw, 2 W_m and ncols, a segment of 2^31 values or more, over 65,535 segments.  A refused call writes nothing.   */
+#define MSX_SPLIT_IDENTITY 0
+#define MSX_SPLIT_RANKNORM 1
+#define MSX_SPLIT_FOLD_RANKNORM 2
+#define MSX_SPLIT_INDICATOR 3
+#define MSX_SPLIT_RANK2 4
+int msx_series_split_transform(msx_series *src, int64_t n, int64_t discard, int64_t thin, const uint32_t *cols, int32_t ncols,
+                               int32_t transform, const double *param, int64_t scratch_bytes, msx_series *dst);
+/* the scratch one segment of S values needs (the smallest scratch_bytes msx_series_split_transform accepts for it)             */
+int64_t msx_split_scratch_bytes(int64_t S);
+/* The autocovariance of a series whose every walker is a chain (a dst of the call above), rows[0:n] (h = n >= 2), averaged over
+ * each member's J chains: acov_out[(m * ncols + j) * nlag + t] = A(lag0 + t), A(t) = (1 / J) sum_chains (1 / h) sum_{i < h - t}
+ * (y_i - m_c)(y_{i+t} - m_c); meanvar_out[m * ncols + j] = A(0) h / (h - 1); between_out = var (ddof 1) of the chains' means
+ * m_c.  The sums are msx_series_acf's (the same kernels, the same order, fixed by h alone: identical bits for any lag tiling);
+ * a chain's sums are then added in walker order.  cols: coordinates < ndim (no ratios), ncols <= MSX_MAX_DIM.  Needs
+ * lag0 + nlag <= h.  MSX_ERR_INVALID: a null series or output, lag0 < 0, nlag < 1, ncols < 1, cols NULL.  MSX_ERR_RANGE: n past
+ * the rows held or below 2, lags past h, a column >= ndim, more than MSX_MAX_DIM columns.                                       */
+int msx_series_chain_acov(msx_series *s, int64_t n, int64_t lag0, int64_t nlag, const uint32_t *cols, int32_t ncols,
+                          double *acov_out, double *meanvar_out, double *between_out);
+
 /* ---- test hooks (used by tests/ only) ------------------------------------------------------------ */
 /* MSX_HOOK_LINKED_FAULT: value != 0 makes the workgroups of the linked form skip their signal -- and the walkers of an
  * overlapped sampler run the publication of their new version -- so that every in-kernel wait runs into its bound;

@@ -245,6 +245,9 @@ def load():
         'msx_series_pointwise': (C.c_int, [vp, C.POINTER(vp), C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_int64, _dp, _ip, _ip,
                                            C.POINTER(C.c_int32), _dp]),
         'msx_series_psis': (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, _ip, vp, vp, _dp, C.POINTER(C.c_int32), _ip, _dp, _ip]),
+        'msx_series_split_transform': (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, _up, C.c_int32, C.c_int32, _dp, C.c_int64, vp]),
+        'msx_split_scratch_bytes': (C.c_int64, [C.c_int64]),
+        'msx_series_chain_acov': (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, _up, C.c_int32, _dp, _dp, _dp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = header/library skew, fail loudly
@@ -281,7 +284,11 @@ EXPORTED = ['msx_create', 'msx_destroy', 'msx_last_error', 'msx_device_info', 'm
             'msx_group_ladder_current', 'msx_series_moments', 'msx_predictive_batch', 'msx_series_predictive',
             'msx_series_modes', 'msx_series_mode_labels',
             'msx_series_logprob', 'msx_series_lincomb', 'msx_series_weights', 'msx_series_wmoments', 'msx_series_resample',
-            'msx_series_psis', 'msx_pointwise_nobs', 'msx_predictive_pointwise', 'msx_series_pointwise']
+            'msx_series_psis', 'msx_pointwise_nobs', 'msx_predictive_pointwise', 'msx_series_pointwise',
+            'msx_series_split_transform', 'msx_split_scratch_bytes', 'msx_series_chain_acov']
+
+
+SPLIT_IDENTITY, SPLIT_RANKNORM, SPLIT_FOLD_RANKNORM, SPLIT_INDICATOR, SPLIT_RANK2 = range(5)   # MSX_SPLIT_* (include/msx.h)
 
 
 def as_f64(a):
@@ -1489,6 +1496,143 @@ class Series:
             o += 6 * nobs[m]
             l += slots[m]
         return parts, count, tail, worst
+
+    # ---- the split pool, transformed: rank-normalised R-hat, bulk / tail ESS, MCSE ----------------
+    def split_sibling(self, ncols):
+        """An empty series for ``split_transform``'s results: 2 nw walkers, members of 2 W_m, ``ncols`` columns."""
+        return Series(self.ctx, 2 * self.nw, int(ncols), 2 * self.counts)
+
+    def split_transform(self, n, discard, thin, cols, transform, dst, param=None, scratch_bytes=0):
+        """The split pool of rows[0:n][discard::thin] (n' >= 4 rows), transformed, into ``dst`` (``split_sibling``), which then
+        holds h = n' // 2 rows: half-chain 2 w + half of walker w is walker 2 w + half of dst (msx_series_split_transform).
+        ``transform``: SPLIT_IDENTITY, SPLIT_RANKNORM, SPLIT_FOLD_RANKNORM (``param`` (k, ncols): the medians), SPLIT_INDICATOR
+        (``param``: the thresholds) or SPLIT_RANK2 (twice the average rank).  ``cols``: coordinates or ``col_ratio`` codes.
+        ``scratch_bytes``: the sort's budget (0: 256 MiB); the result does not depend on it."""
+        cols = _col_codes(cols)
+        if param is not None:
+            param = as_f64(param)
+            if param.shape != (self.k, cols.size):
+                raise ValueError('split_transform: param must have shape (k, ncols)')
+        self.check(self.lib.msx_series_split_transform(self.h, int(n), int(discard), int(thin), uptr(cols), cols.size, int(transform),
+                                                       None if param is None else dptr(param), int(scratch_bytes), dst.h))
+
+    def chain_acov(self, n, lag0=0, nlag=None, cols=None):
+        """(A (k, ncols, nlag), mean_var (k, ncols), between (k, ncols)) of rows[0:n] with every walker a chain
+        (msx_series_chain_acov): the chain-averaged biased autocovariance at lags lag0 .. lag0 + nlag - 1, A(0) n / (n - 1) and
+        the variance (ddof 1) of the chains' means."""
+        cols = _col_codes(range(self.ndim) if cols is None else cols)
+        nlag = int(n) - int(lag0) if nlag is None else int(nlag)
+        A = np.empty((self.k, cols.size, max(nlag, 0)))
+        mv, bt = np.empty((self.k, cols.size)), np.empty((self.k, cols.size))
+        self.check(self.lib.msx_series_chain_acov(self.h, int(n), int(lag0), nlag, uptr(cols), cols.size, dptr(A), dptr(mv), dptr(bt)))
+        return A, mv, bt
+
+    def chain_ess(self, n, lag_tile=320):
+        """{'ess', 'rhat', 'mean_var', 'between', 'max_t'}, each (k, ndim), of rows[0:n] with every walker a chain: Geyer's
+        sequences (``diagnostics.geyer_tau``) over lag tiles of ``lag_tile``, 2 ``lag_tile``, ... asked for until every column's
+        sequence has ended -- the loop is sequential, so an end found in a prefix is the end the full length gives -- and the
+        plain R-hat of the chains, sqrt(((n - 1) / n mean_var + between) / mean_var)."""
+        from . import diagnostics
+        n, k, nd = int(n), self.k, self.ndim
+        S = n * self.counts
+        ess, max_t = np.full((k, nd), np.nan), np.zeros((k, nd), dtype=np.int64)
+        mv, bt = np.empty((k, nd)), np.empty((k, nd))
+        prefix = np.empty((k, nd, 0))
+        pending = {(m, d) for m in range(k) for d in range(nd)}
+        lag0, tile = 0, int(lag_tile)
+        while pending:
+            nlag = min(tile, n - lag0)
+            cols = sorted({d for _, d in pending})
+            A, v, b = self.chain_acov(n, lag0, nlag, cols)
+            full = np.full((k, nd, nlag), np.nan)
+            full[:, cols] = A
+            prefix = np.concatenate([prefix, full], axis=2)
+            if lag0 == 0:
+                mv, bt = v, b
+            lag0 += nlag
+            tile *= 2
+            for m, d in sorted(pending):
+                tau, cut = diagnostics.geyer_tau(prefix[m, d], mv[m, d], bt[m, d], n, int(S[m]))
+                if tau is None:
+                    continue
+                ess[m, d], max_t[m, d] = S[m] / tau, cut
+                pending.discard((m, d))
+        with np.errstate(invalid='ignore', divide='ignore'):
+            rhat = np.sqrt(((n - 1) / n * mv + bt) / mv)
+        return {'ess': ess, 'rhat': rhat, 'mean_var': mv, 'between': bt, 'max_t': max_t}
+
+    def rank_stats(self, n, discard=0, thin=1, cols=None, q=(0.16, 0.5, 0.84), want=('rhat', 'bulk', 'tail', 'mean', 'mcse'),
+                   scratch_bytes=0, lag_tile=320):
+        """``diagnostics.rank_rhat`` / ``ess`` / ``mcse`` of rows[0:n][discard::thin] (n' >= 4 rows) per member and column, from
+        the series itself: the split pool's transforms (``split_transform``) go to two sibling series, their autocovariances
+        come back in lag tiles (``chain_ess``), the pool's median and quantiles are exact order statistics of the IDENTITY
+        series, and Geyer's loop, the maxima, the Beta quantiles and the square roots are the host's.  -> a dict of (k, ncols)
+        arrays, as ``want`` names them: 'rhat' -> 'bulk', 'folded', 'rhat'; 'bulk' / 'tail' / 'mean' -> 'ess_bulk' / 'ess_tail'
+        / 'ess_mean'; 'mcse' -> 'mcse_mean', 'ess_quantile' and 'mcse_quantile' (k, ncols, len(q)).  A column with a non-finite
+        value or one distinct value is NaN everywhere."""
+        from . import diagnostics, summary
+        cols = list(range(self.ndim)) if cols is None else [int(c) for c in np.atleast_1d(cols)]
+        q = [float(p) for p in np.atleast_1d(q)] if 'mcse' in want else []
+        if any(not 0.0 < p < 1.0 for p in q):
+            raise ValueError('every q must lie in (0, 1)')
+        nc, h = len(cols), len(range(int(discard), int(n), int(thin))) // 2
+        if h < 2:
+            raise ValueError('chain too short')
+        S = 2 * h * self.counts
+        out = {}
+        ident, work = self.split_sibling(nc), self.split_sibling(nc)
+        try:
+            def ess_of(transform, param=None):
+                self.split_transform(n, discard, thin, cols, transform, work, param, scratch_bytes)
+                return work.chain_ess(h, lag_tile)
+            self.split_transform(n, discard, thin, cols, SPLIT_IDENTITY, ident)
+            pool = summary.summary_of(ident, h, [0.05, 0.95] + q)
+            # NaN sorts last and the infinities to the ends: the pool's extremes say whether it has an answer at all
+            bad = ~(np.isfinite(pool['min']) & np.isfinite(pool['max'])) | (pool['min'] == pool['max'])
+            z = ess_of(SPLIT_RANKNORM) if 'rhat' in want or 'bulk' in want else None
+            if 'rhat' in want:
+                self.split_transform(n, discard, thin, cols, SPLIT_FOLD_RANKNORM, work, pool['median'], scratch_bytes)
+                _, mv, bt = work.chain_acov(h, 0, 1)
+                with np.errstate(invalid='ignore', divide='ignore'):
+                    out['bulk'], out['folded'] = z['rhat'], np.sqrt(((h - 1) / h * mv + bt) / mv)
+                    out['rhat'] = np.maximum(out['bulk'], out['folded'])
+            if 'bulk' in want:
+                out['ess_bulk'] = z['ess']
+            if 'tail' in want:
+                lo, hi = (ess_of(SPLIT_INDICATOR, pool['quantiles'][:, :, i])['ess'] for i in (0, 1))
+                with np.errstate(invalid='ignore'):
+                    out['ess_tail'] = np.minimum(lo, hi)
+            if 'mean' in want or 'mcse' in want:
+                x = ident.chain_ess(h, lag_tile)
+                out['ess_mean'] = x['ess']
+            if 'mcse' in want:
+                J = 2 * self.counts[:, None]
+                with np.errstate(invalid='ignore', divide='ignore'):
+                    # the pooled variance (ddof 1) from the chains' own: sum_j sum_i (x - m_j)^2 + h sum_j (m_j - mbar)^2
+                    var = ((J * (h - 1)) * x['mean_var'] + (h * (J - 1)) * x['between']) / (S[:, None] - 1)
+                    out['mcse_mean'] = np.sqrt(var) / np.sqrt(x['ess'])
+                out['ess_quantile'] = np.full((self.k, nc, len(q)), np.nan)
+                ranks = np.zeros((self.k, nc, len(q), 2), dtype=np.int64)
+                for i, p in enumerate(q):
+                    e = ess_of(SPLIT_INDICATOR, pool['quantiles'][:, :, 2 + i])['ess']
+                    out['ess_quantile'][:, :, i] = e
+                    for m, c in np.ndindex(self.k, nc):
+                        if np.isfinite(e[m, c]):
+                            ranks[m, c, i] = diagnostics.mcse_quantile_of(lambda r: 0.0, int(S[m]), e[m, c], p)[1]
+                out['mcse_quantile'] = np.full((self.k, nc, len(q)), np.nan)
+                if q:
+                    vals, _ = ident.order_stats(h, 0, 1, range(nc), ranks.reshape(self.k, -1))
+                    for m, c, i in np.ndindex(self.k, nc, len(q)):
+                        th1, th2 = vals[m, c].reshape(nc, len(q), 2)[c, i]
+                        if np.isfinite(out['ess_quantile'][m, c, i]):
+                            out['mcse_quantile'][m, c, i] = (th2 - th1) / 2.0
+        finally:
+            ident.close()
+            work.close()
+        for name, v in out.items():
+            if name != 'max_t':
+                v[bad] = np.nan
+        return out
 
     def order_stats(self, n, discard, thin, cols, ranks):
         """(values (k, ncols, nranks), counts (k,)): the elements of zero-based ranks ``ranks`` (k, nranks; one row is

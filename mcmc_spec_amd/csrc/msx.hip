@@ -82,6 +82,7 @@
 #include "reweight_kernels.h"
 #include "psis_kernels.h"
 #include "pointwise_kernels.h"
+#include "rank_kernels.h"
 #include "opt_run_kernels.h"
 
 // ================================================================================================
@@ -6225,6 +6226,204 @@ int msx_series_pointwise(msx_series *src, msx_ctx **ctxs, int64_t n, int64_t dis
             return fail(src, rc, who + ": member " + std::to_string(m) + ": " + err);
         if (worst_status) worst_status[m] = worst;
         o_out += (size_t)(kPwOut * pw_nobs(J.c)); o_ll += (size_t)pw_nobs(J.c) * (size_t)J.nsel;
+    }
+    return MSX_OK;
+}
+
+// ---- the split pool, transformed: ranks by a segmented radix sort (rank_kernels.h) --------------------
+static constexpr size_t kRankDefaultBytes = (size_t)256 << 20;
+static int64_t rank_tiles(int64_t S) { return (S + kRankTile - 1) / kRankTile; }
+
+// one segment's share of a round's arena: [keys 2 x 8 S | tile_first, tile_last 16 T | RankSeg | positions 2 x 4 S | tile_hist
+// 1024 T | hist8 8192 | digit_base 1024]; the 8-byte arrays come first, so a round's arena is the sum of its segments' shares
+int64_t msx_split_scratch_bytes(int64_t S) {
+    if (S < 1) return 0;
+    return 24 * S + (int64_t)(sizeof(uint32_t) * kRankDigits + 2 * sizeof(long long)) * rank_tiles(S) +
+           (int64_t)(sizeof(RankSeg) + sizeof(uint32_t) * (kRankPasses + 1) * kRankDigits);
+}
+
+int msx_series_split_transform(msx_series *src, int64_t n, int64_t discard, int64_t thin, const uint32_t *cols, int32_t ncols,
+                               int32_t transform, const double *param, int64_t scratch_bytes, msx_series *dst) {
+    if (!src) return MSX_ERR_INVALID;
+    const char *who = "msx_series_split_transform";
+    const std::string w(who);
+    const bool ranked = transform == kSplitRanknorm || transform == kSplitFoldRanknorm || transform == kSplitRank2;
+    const bool reads_param = transform == kSplitFoldRanknorm || transform == kSplitIndicator;
+    if (!dst || dst == src || !cols || ncols < 1 || discard < 0 || thin < 1 || scratch_bytes < 0 || transform < kSplitIdentity ||
+        transform > kSplitRank2 || (reads_param && !param))
+        return fail(src, MSX_ERR_INVALID, w + ": bad arguments (another series as dst, cols, discard >= 0, thin >= 1, a known transform and its param)");
+    if (dst->device != src->device) return fail(src, MSX_ERR_INVALID, w + ": dst lives on another device");
+    if (rw_attached(dst)) return fail(src, MSX_ERR_STATE, w + ": a run in flight appends to dst");
+    if (n < 1 || n > src->rows) return fail(src, MSX_ERR_RANGE, w + ": n must lie in 1 .. the rows the series holds");
+    const int64_t np = n > discard ? (n - discard + thin - 1) / thin : 0, h = np / 2;
+    if (np < 4) return fail(src, MSX_ERR_RANGE, w + ": the selection rows[0:n][discard::thin] needs at least 4 rows");
+    if (ncols > MSX_MAX_DIM) return fail(src, MSX_ERR_RANGE, w + ": more columns than a series is wide (MSX_MAX_DIM)");
+    if (int rc = summary_columns(src, who, cols, ncols)) return rc;
+    const int k = (int)src->off.size() - 1;
+    if ((int64_t)k * ncols > 65535) return fail(src, MSX_ERR_RANGE, w + ": more segments (members x columns) than one launch covers");
+    bool shaped = dst->nw == 2 * src->nw && dst->ndim == ncols && dst->off.size() == src->off.size();
+    for (int m = 0; shaped && m <= k; ++m) shaped = dst->off[(size_t)m] == 2 * src->off[(size_t)m];
+    if (!shaped) return fail(src, MSX_ERR_RANGE, w + ": dst needs 2 nw walkers, members of 2 W_m walkers and ndim = ncols");
+    const size_t budget = scratch_bytes ? (size_t)scratch_bytes : kRankDefaultBytes;
+    std::vector<RankSeg> segs((size_t)k * (size_t)ncols);
+    for (int m = 0; m < k; ++m)
+        for (int32_t j = 0; j < ncols; ++j) {
+            RankSeg &s = segs[(size_t)m * (size_t)ncols + (size_t)j];
+            memset(&s, 0, sizeof(s));
+            s.w0 = src->off[(size_t)m];
+            s.S = 2 * (src->off[(size_t)m + 1] - src->off[(size_t)m]) * h;
+            s.ntiles = rank_tiles(s.S);
+            s.col = cols[j];
+            s.jc = j;
+            s.param = reads_param ? param[(size_t)m * (size_t)ncols + (size_t)j] : 0.0;
+            if (s.S > (int64_t)INT32_MAX) return fail(src, MSX_ERR_RANGE, w + ": a member's column holds 2^31 values or more");
+            if (ranked && (size_t)msx_split_scratch_bytes(s.S) > budget)
+                return fail(src, MSX_ERR_RANGE, w + ": scratch_bytes is below one segment's need (msx_split_scratch_bytes)");
+        }
+    // rounds of consecutive segments within the budget (all of them at once when nothing is sorted)
+    std::vector<size_t> cut(1, 0);
+    size_t arena = 0, used = 0;
+    for (size_t i = 0; i < segs.size(); ++i) {
+        const size_t need = ranked ? (size_t)msx_split_scratch_bytes(segs[i].S) : sizeof(RankSeg);
+        if (ranked && used && used + need > budget) {
+            cut.push_back(i);
+            used = 0;
+        }
+        used += need;
+        arena = std::max(arena, used);
+    }
+    cut.push_back(segs.size());
+    HIP_TRY(src, hipSetDevice(src->device));
+    hipStream_t st = src->stream;
+    HIP_TRY(src, series_scratch(src, arena));     // (first: a failure here leaves dst's buffer as it was)
+    HIP_TRY(src, series_reserve(dst, h, 0, st));  // (every row 0 .. h - 1 is written below)
+    HIP_TRY(src, series_wait_growth(src));
+    if (dst->grown_set) HIP_TRY(src, hipStreamWaitEvent(st, dst->grown, 0));
+    const RankGeom g = {src->d_rows, src->cap, src->nw, np, h, discard, thin, dst->d_rows, dst->cap};
+    std::vector<uint32_t> h8;
+    for (size_t r = 0; r + 1 < cut.size(); ++r) {
+        RankSeg *S0 = segs.data() + cut[r];
+        const int64_t G = (int64_t)(cut[r + 1] - cut[r]);
+        int64_t N = 0, T = 0, tmax = 0;
+        for (int64_t i = 0; i < G; ++i) {
+            S0[i].base = N;
+            S0[i].tile0 = T;
+            N += S0[i].S;
+            T += S0[i].ntiles;
+            tmax = std::max(tmax, S0[i].ntiles);
+        }
+        const dim3 grid((unsigned)tmax, (unsigned)G);
+        if (!ranked) {
+            RankSeg *d_segs = (RankSeg *)src->d_scratch;
+            HIP_TRY(src, hipMemcpyAsync(d_segs, S0, sizeof(RankSeg) * (size_t)G, hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(rank_plain_kernel, grid, dim3(kRankThreads), 0, st, g, (const RankSeg *)d_segs, transform);
+            HIP_TRY(src, hipGetLastError());
+            HIP_TRY(src, hipStreamSynchronize(st));
+            continue;
+        }
+        unsigned long long *d_ka = (unsigned long long *)src->d_scratch, *d_kb = d_ka + N;
+        long long *d_first = (long long *)(d_kb + N), *d_last = d_first + T;
+        RankSeg *d_segs = (RankSeg *)(d_last + T);
+        uint32_t *d_pa = (uint32_t *)(d_segs + G), *d_pb = d_pa + N, *d_th = d_pb + N;
+        uint32_t *d_h8 = d_th + T * kRankDigits, *d_db = d_h8 + G * kRankPasses * kRankDigits;
+        HIP_TRY(src, hipMemcpyAsync(d_segs, S0, sizeof(RankSeg) * (size_t)G, hipMemcpyHostToDevice, st));
+        HIP_TRY(src, hipMemsetAsync(d_h8, 0, sizeof(uint32_t) * (size_t)(G * kRankPasses * kRankDigits), st));
+        hipLaunchKernelGGL(rank_key_kernel, grid, dim3(kRankThreads), 0, st, g, (const RankSeg *)d_segs, transform, d_ka, d_pa, d_h8);
+        HIP_TRY(src, hipGetLastError());
+        h8.resize((size_t)(G * kRankPasses * kRankDigits));
+        HIP_TRY(src, hipMemcpyAsync(h8.data(), d_h8, sizeof(uint32_t) * h8.size(), hipMemcpyDeviceToHost, st));
+        HIP_TRY(src, hipStreamSynchronize(st));
+        for (int p = 0; p < kRankPasses; ++p) {
+            // a digit that is the same all over every segment of the round moves nothing: no pass
+            bool uniform = true;
+            for (int64_t i = 0; uniform && i < G; ++i) {
+                const uint32_t *hp = h8.data() + (size_t)((i * kRankPasses + p) * kRankDigits);
+                uniform = std::find(hp, hp + kRankDigits, (uint32_t)S0[i].S) != hp + kRankDigits;
+            }
+            if (uniform) continue;
+            const int32_t shift = p * kRankDigitBits;
+            hipLaunchKernelGGL(rank_hist_kernel, grid, dim3(kRankThreads), 0, st, (const RankSeg *)d_segs, (const unsigned long long *)d_ka,
+                               shift, d_th);
+            HIP_TRY(src, hipGetLastError());
+            hipLaunchKernelGGL(rank_scan_kernel, dim3((unsigned)G), dim3(kRankDigits), 0, st, (const RankSeg *)d_segs, d_th, d_db);
+            HIP_TRY(src, hipGetLastError());
+            hipLaunchKernelGGL(rank_scatter_kernel, grid, dim3(kRankThreads), 0, st, (const RankSeg *)d_segs, (const unsigned long long *)d_ka,
+                               (const uint32_t *)d_pa, shift, (const uint32_t *)d_th, (const uint32_t *)d_db, d_kb, d_pb);
+            HIP_TRY(src, hipGetLastError());
+            std::swap(d_ka, d_kb);
+            std::swap(d_pa, d_pb);
+        }
+        hipLaunchKernelGGL(rank_flag_kernel, grid, dim3(kRankThreads), 0, st, (const RankSeg *)d_segs, (const unsigned long long *)d_ka, d_first,
+                           d_last);
+        HIP_TRY(src, hipGetLastError());
+        hipLaunchKernelGGL(rank_assign_kernel, grid, dim3(kRankThreads), 0, st, g, (const RankSeg *)d_segs, transform,
+                           (const unsigned long long *)d_ka, (const uint32_t *)d_pa, (const long long *)d_first, (const long long *)d_last);
+        HIP_TRY(src, hipGetLastError());
+        HIP_TRY(src, hipStreamSynchronize(st));
+    }
+    dst->rows = h;
+    return MSX_OK;
+}
+
+// ---- the chain-averaged autocovariance of a series whose walkers are the chains ----------------------
+int msx_series_chain_acov(msx_series *sr, int64_t n, int64_t lag0, int64_t nlag, const uint32_t *cols, int32_t ncols, double *acov_out,
+                          double *meanvar_out, double *between_out) {
+    if (!sr) return MSX_ERR_INVALID;
+    if (!acov_out || !meanvar_out || !between_out || !cols || ncols < 1 || lag0 < 0 || nlag < 1)
+        return fail(sr, MSX_ERR_INVALID, "msx_series_chain_acov: bad arguments (outputs, cols, lag0 >= 0, nlag >= 1)");
+    if (n < 2 || n > sr->rows) return fail(sr, MSX_ERR_RANGE, "msx_series_chain_acov: n must lie in 2 .. the rows the series holds");
+    if (lag0 + nlag > n) return fail(sr, MSX_ERR_RANGE, "msx_series_chain_acov: lags past the chains' length");
+    if (ncols > MSX_MAX_DIM) return fail(sr, MSX_ERR_RANGE, "msx_series_chain_acov: more columns than a series is wide (MSX_MAX_DIM)");
+    AcfDims dims = {};
+    for (int32_t q = 0; q < ncols; ++q) {
+        if (cols[q] >= (uint32_t)sr->ndim) return fail(sr, MSX_ERR_RANGE, "msx_series_chain_acov: a column outside the series");
+        dims.d[dims.nd++] = (int32_t)cols[q];
+    }
+    HIP_TRY(sr, hipSetDevice(sr->device));
+    const int k = (int)sr->off.size() - 1, nd = dims.nd;
+    const int64_t np = n, nser = (int64_t)nd * sr->nw, nsuper = (np + kAcfSuper - 1) / kAcfSuper;
+    const int64_t per_lag = nser * nsuper * (int64_t)sizeof(double);
+    int64_t sub = std::max<int64_t>(1, (int64_t)kAcfPartBudget / per_lag / kAcfLagTile) * kAcfLagTile;
+    sub = std::min(sub, nlag);
+    const int64_t kd = (int64_t)k * nd;
+    // scratch: [mean nser | part0 nser * nsuper | part nser * nsuper * sub | acov k * nd * sub | A(0) k * nd | between k * nd]
+    HIP_TRY(sr, series_scratch(sr, sizeof(double) * (size_t)(nser + nser * nsuper + nser * nsuper * sub + kd * sub + 2 * kd)));
+    double *d_mean = (double *)sr->d_scratch, *d_part0 = d_mean + nser, *d_part = d_part0 + nser * nsuper;
+    double *d_f = d_part + nser * nsuper * sub, *d_a0 = d_f + kd * sub, *d_btw = d_a0 + kd;
+    HIP_TRY(sr, series_wait_growth(sr));
+    hipStream_t st = sr->stream;
+    hipLaunchKernelGGL(acf_mean_kernel, dim3((unsigned)nser), dim3(kAcfMeanThreads), 0, st, (const double *)sr->d_rows, sr->cap, sr->nw, dims,
+                       np, (int64_t)0, (int64_t)1, d_mean);
+    HIP_TRY(sr, hipGetLastError());
+    hipLaunchKernelGGL(acf_lag_kernel, dim3((unsigned)nser, 1u, (unsigned)nsuper), dim3(kAcfThreads), 0, st, (const double *)sr->d_rows,
+                       sr->cap, sr->nw, dims, np, (int64_t)0, (int64_t)1, (const double *)d_mean, (int64_t)0, (int64_t)1, d_part0, nsuper,
+                       (int64_t)1);
+    HIP_TRY(sr, hipGetLastError());
+    hipLaunchKernelGGL(acov_reduce_kernel, dim3((unsigned)((kd + 255) / 256)), dim3(256), 0, st, (const double *)d_part0, nsuper, (int64_t)1,
+                       sr->nw, (int32_t)nd, (const int64_t *)sr->d_off, (int32_t)k, (int64_t)1, np, d_a0);
+    HIP_TRY(sr, hipGetLastError());
+    hipLaunchKernelGGL(acov_between_kernel, dim3((unsigned)((kd + 255) / 256)), dim3(256), 0, st, (const double *)d_mean, sr->nw, (int32_t)nd,
+                       (const int64_t *)sr->d_off, (int32_t)k, d_btw);
+    HIP_TRY(sr, hipGetLastError());
+    std::vector<double> h((size_t)(kd * sub)), h2((size_t)(2 * kd));
+    HIP_TRY(sr, hipMemcpyAsync(h2.data(), d_a0, sizeof(double) * (size_t)(2 * kd), hipMemcpyDeviceToHost, st));
+    for (int64_t lb = lag0; lb < lag0 + nlag; lb += sub) {
+        const int64_t cnt = std::min(sub, lag0 + nlag - lb), nout = kd * cnt;
+        hipLaunchKernelGGL(acf_lag_kernel, dim3((unsigned)nser, (unsigned)((cnt + kAcfLagTile - 1) / kAcfLagTile), (unsigned)nsuper),
+                           dim3(kAcfThreads), 0, st, (const double *)sr->d_rows, sr->cap, sr->nw, dims, np, (int64_t)0, (int64_t)1,
+                           (const double *)d_mean, lb, cnt, d_part, nsuper, cnt);
+        HIP_TRY(sr, hipGetLastError());
+        hipLaunchKernelGGL(acov_reduce_kernel, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, st, (const double *)d_part, nsuper, cnt, sr->nw,
+                           (int32_t)nd, (const int64_t *)sr->d_off, (int32_t)k, cnt, np, d_f);
+        HIP_TRY(sr, hipGetLastError());
+        HIP_TRY(sr, hipMemcpyAsync(h.data(), d_f, sizeof(double) * (size_t)nout, hipMemcpyDeviceToHost, st));
+        HIP_TRY(sr, hipStreamSynchronize(st));
+        for (int64_t mq = 0; mq < kd; ++mq)
+            memcpy(acov_out + mq * nlag + (lb - lag0), h.data() + mq * cnt, sizeof(double) * (size_t)cnt);
+    }
+    for (int64_t mq = 0; mq < kd; ++mq) {
+        meanvar_out[mq] = h2[(size_t)mq] * (double)n / (double)(n - 1);
+        between_out[mq] = h2[(size_t)(kd + mq)];
     }
     return MSX_OK;
 }

@@ -21,7 +21,8 @@ import numpy as np
 from . import _lib
 from .engine import _raise_for_status
 from .sampler import (_MOMENTS, EnsembleSampler, State, _accept, _check_tau, _device_integrated_time, _device_moments, _max_rhat,
-                      _propose, _pump, device_seed)
+                      _propose, _pump, device_seed, _device_rank_stats, _ess_kind, _ess_of, _host_rank_stats, _mcse_of,
+                      _rank_rhat_of, _selection)
 
 
 class TargetGroup:
@@ -232,6 +233,27 @@ class GroupSampler:
         outs = [s.get_moments(**kw) for s in self.samplers]
         return {name: np.array([o[name] for o in outs]) for name in _MOMENTS}
 
+    def _rank_stats(self, want, discard, thin, cols, q=(), k=None):
+        """``_lib.Series.rank_stats``' dict for target k alone, or (k None) every target's with a leading axis K:
+        ``diagnostics`` on the host chains that are asked for."""
+        if k is not None:
+            return self.samplers[k]._rank_stats(want, discard, thin, cols, q)
+        x = np.concatenate([_selection(s._chain, discard, thin, cols) for s in self.samplers], axis=1)
+        return _host_rank_stats(x, self.nwalkers, want, q)
+
+    def get_rank_rhat(self, k=None, discard=0, thin=1, cols=None):
+        """Target k's {'bulk', 'folded', 'rhat'} (EnsembleSampler.get_rank_rhat), or every target's for
+        k None: the arrays with a leading axis K."""
+        return _rank_rhat_of(self._rank_stats(('rhat',), discard, thin, cols, k=k), None if k is None else 0)
+
+    def get_ess(self, k=None, discard=0, thin=1, cols=None, kind='bulk'):
+        """Target k's effective sample size (ncols,) (EnsembleSampler.get_ess), or every target's (K, ncols) for k None."""
+        return _ess_of(self._rank_stats((_ess_kind(kind),), discard, thin, cols, k=k), kind, None if k is None else 0)
+
+    def get_mcse(self, k=None, discard=0, thin=1, cols=None, q=(0.16, 0.5, 0.84)):
+        """Target k's {'mean', 'quantiles'} (EnsembleSampler.get_mcse), or every target's for k None."""
+        return _mcse_of(self._rank_stats(('mcse',), discard, thin, cols, q, k=k), None if k is None else 0)
+
     def _host_members(self):
         """The targets' stored chains side by side: (n, sum of the walkers, ndim)."""
         return np.concatenate([np.array(s._chain) for s in self.samplers], axis=1)
@@ -424,6 +446,15 @@ class DeviceGroupSampler(GroupSampler):
         r = _device_moments(self._series, len(self.samplers[0]._chain), discard, thin, cols, False)['rhat']
         return r if k is None else r[k]
 
+    def _rank_stats(self, want, discard, thin, cols, q=(), k=None):
+        """GroupSampler._rank_stats; with autocorr='device' every target's from the chains on the device, the targets'
+        columns as the segments of one sort (rows queued past the stored chains are not part of it); target k's is cut from
+        that, with a leading axis of one."""
+        if self._series is None:
+            return super()._rank_stats(want, discard, thin, cols, q, k)
+        out = _device_rank_stats(self._series, len(self.samplers[0]._chain), discard, thin, cols, want, q)
+        return out if k is None else {name: v[k:k + 1] for name, v in out.items()}
+
     def get_moments(self, k=None, discard=0, thin=1, cols=None):
         """GroupSampler.get_moments; with autocorr='device' from the chains on the device (get_rhat's rules)."""
         if self._series is None:
@@ -519,7 +550,7 @@ class DeviceGroupSampler(GroupSampler):
                                    mode_old=self.mode, discard=discard, thin=thin)
 
 
-def run_group_protocol(sampler, pos, nburn, nsteps, nthin=10, dirname=None, fnames=None, rhat=None):
+def run_group_protocol(sampler, pos, nburn, nsteps, nthin=10, dirname=None, fnames=None, rhat=None, ess=None):
     """``sampler.run_reference_protocol`` (run_emcee's driver, mft6.py:1494-1529) applied to every target of a group
     sampler (GroupSampler or DeviceGroupSampler) stepped in lock-step: burn-in, reset, then production with one tau
     computation for all targets every ``nthin`` iterations.  Each target keeps its own ``old_acl``; a target that meets
@@ -534,7 +565,11 @@ def run_group_protocol(sampler, pos, nburn, nsteps, nthin=10, dirname=None, fnam
 
     ``rhat`` (a float; None: nothing changes): ``run_reference_protocol``'s -- a target finishes at a check only when the
     maximum of its split R-hat lies below ``rhat`` as well, and with ``dirname`` every check appends that maximum to the
-    target's ``{fname}_rhat.txt``."""
+    target's ``{fname}_rhat.txt``.
+
+    ``ess`` (a float; None: nothing changes): ``run_reference_protocol``'s -- a target finishes at a check only when the
+    smallest of its bulk and tail effective sample sizes has reached ``ess`` as well, and with ``dirname`` every check
+    appends that minimum to the target's ``{fname}_ess.txt``."""
     import os
     K, ndim = len(sampler.samplers), sampler.ndim
     fnames = ['run{}'.format(k) for k in range(K)] if fnames is None else [str(f) for f in fnames]
@@ -584,6 +619,12 @@ def run_group_protocol(sampler, pos, nburn, nsteps, nthin=10, dirname=None, fnam
                     mrhats = np.full(K, np.nan)
             else:
                 mrhats = {k: _max_rhat(lambda: sampler.get_rhat(k)) for k in active}
+        if ess is not None:   # (one computation for all targets; NaN while the chains are shorter than 4 rows)
+            try:
+                st = sampler._rank_stats(('bulk', 'tail'), 0, 1, None)
+                messes = np.min(np.minimum(st['ess_bulk'], st['ess_tail']), axis=1)
+            except ValueError:
+                messes = np.full(K, np.nan)
         for k in active:
             acl = acls[k]
             macl = np.mean(acl)
@@ -593,11 +634,16 @@ def run_group_protocol(sampler, pos, nburn, nsteps, nthin=10, dirname=None, fnam
                 if rhat is not None:
                     with open('{}/{}_rhat.txt'.format(dirs[k], fnames[k]), 'a') as f:
                         f.write(str(float(mrhats[k])) + '\n')
+                if ess is not None:
+                    with open('{}/{}_ess.txt'.format(dirs[k], fnames[k]), 'a') as f:
+                        f.write(str(float(messes[k])) + '\n')
             if not np.isnan(macl):
                 converged = np.all(acl * 50 < n)
                 converged &= np.all((np.abs(old_acl[k] - acl) / acl) < 0.1)
                 if rhat is not None:
                     converged &= mrhats[k] < rhat
+                if ess is not None:
+                    converged &= messes[k] >= ess
                 if converged:
                     stop[k] = n
                     continue

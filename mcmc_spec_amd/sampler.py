@@ -288,6 +288,26 @@ class EnsembleSampler:
         from . import diagnostics
         return diagnostics.moments(_selection(self._chain, discard, thin, cols))
 
+    def _rank_stats(self, want, discard, thin, cols, q=()):
+        """``_lib.Series.rank_stats``' dict (a leading axis of one member) from ``diagnostics`` on the host chain."""
+        return _host_rank_stats(_selection(self._chain, discard, thin, cols), None, want, q)
+
+    def get_rank_rhat(self, discard=0, thin=1, cols=None):
+        """{'bulk', 'folded', 'rhat'}, each (ncols,): the rank-normalised split R-hat of Vehtari et al. (2021) over the walkers
+        of the stored chain, rows ``[discard::thin]`` (at least 4), its folded companion, which sees a walker of another scale,
+        and their maximum (``diagnostics.rank_rhat``)."""
+        return _rank_rhat_of(self._rank_stats(('rhat',), discard, thin, cols), 0)
+
+    def get_ess(self, discard=0, thin=1, cols=None, kind='bulk'):
+        """The effective sample size (ncols,) of the stored chain's walkers taken together: ``kind`` 'bulk' (what the central
+        quantiles are worth), 'tail' (the 5 % and 95 % quantiles) or 'mean' (``diagnostics.ess``)."""
+        return _ess_of(self._rank_stats((_ess_kind(kind),), discard, thin, cols), kind, 0)
+
+    def get_mcse(self, discard=0, thin=1, cols=None, q=(0.16, 0.5, 0.84)):
+        """{'mean' (ncols,), 'quantiles' (ncols, len(q))}: the Monte-Carlo standard errors of the chain's mean and of its
+        quantiles ``q`` -- how many digits of a published percentile are real (``diagnostics.mcse``)."""
+        return _mcse_of(self._rank_stats(('mcse',), discard, thin, cols, q), 0)
+
     def get_modes(self, ncomp=2, discard=0, thin=1, cols=None, **fit_kw):
         """The posterior's modes: a joint Gaussian mixture of ``ncomp`` components over the columns ``cols`` (None: all)
         of ``get_chain(discard=, thin=, flat=True)``, as a ``modes.ModeFit`` (one member) whose ``labels()``, ``split()``
@@ -313,6 +333,59 @@ def _device_moments(series, n_total, discard, thin, cols, cov):
 
 
 _MOMENTS = ('mean', 'cov', 'count')
+
+
+# ---- rank-normalised R-hat, bulk / tail ESS and MCSE: one dict of (k, ncols) arrays, whoever computes it
+def _host_rank_stats(x, counts, want, q):
+    """``_lib.Series.rank_stats``' dict from ``diagnostics`` on the selection x (n', W, ncols); counts None: one member."""
+    from . import diagnostics
+    counts = [x.shape[1]] if counts is None else list(counts)
+    out = {}
+    if 'rhat' in want:
+        out.update(diagnostics.rank_rhat(x, counts))
+    for kind in ('bulk', 'tail', 'mean'):
+        if kind in want:
+            out['ess_' + kind] = diagnostics.ess(x, kind, counts)
+    if 'mcse' in want:
+        m = diagnostics.mcse(x, q, counts)
+        out['mcse_mean'], out['mcse_quantile'] = m['mean'], m['quantiles']
+    return out
+
+
+def _device_rank_stats(series, n_total, discard, thin, cols, want, q):
+    """``Series.rank_stats`` of the first n_total rows (the rows consumed; those queued past them are not part of it)."""
+    if len(range(discard, n_total, thin)) < 4:
+        raise ValueError('chain too short')
+    return series.rank_stats(n_total, discard, thin, cols, q, want)
+
+
+def _ess_kind(kind):
+    if kind not in ('bulk', 'tail', 'mean'):
+        raise ValueError("kind must be 'bulk', 'tail' or 'mean'")
+    return kind
+
+
+def _rank_rhat_of(stats, m):
+    """m: a member, or None for all of them (a leading axis)."""
+    return {name: stats[name] if m is None else stats[name][m] for name in ('bulk', 'folded', 'rhat')}
+
+
+def _ess_of(stats, kind, m):
+    return stats['ess_' + kind] if m is None else stats['ess_' + kind][m]
+
+
+def _mcse_of(stats, m):
+    return {name: stats[key] if m is None else stats[key][m] for name, key in (('mean', 'mcse_mean'), ('quantiles', 'mcse_quantile'))}
+
+
+def _min_ess(sampler):
+    """min over the columns of a check's bulk and tail ESS, from one computation of both; NaN while the chain is shorter
+    than 4 rows."""
+    try:
+        st = sampler._rank_stats(('bulk', 'tail'), 0, 1, None)
+        return float(min(np.min(st['ess_bulk']), np.min(st['ess_tail'])))   # (np.min keeps a NaN)
+    except ValueError:
+        return float('nan')
 
 
 def _window(f, c):
@@ -615,6 +688,13 @@ class DeviceEnsembleSampler(EnsembleSampler):
             return super().get_rhat(discard=discard, thin=thin, cols=cols)
         return _device_moments(self._series, len(self._chain), discard, thin, cols, False)['rhat'][0]
 
+    def _rank_stats(self, want, discard, thin, cols, q=()):
+        """EnsembleSampler._rank_stats; with autocorr='device' from the chain on the device (msx_series_split_transform,
+        msx_series_chain_acov), without a download (get_rhat's rule for rows queued but not consumed)."""
+        if self._series is None:
+            return super()._rank_stats(want, discard, thin, cols, q)
+        return _device_rank_stats(self._series, len(self._chain), discard, thin, cols, want, q)
+
     def get_moments(self, discard=0, thin=1, cols=None):
         """EnsembleSampler.get_moments; with autocorr='device' from the chain on the device (get_rhat's rules)."""
         if self._series is None:
@@ -730,14 +810,18 @@ def _max_rhat(get_rhat):
         return float('nan')
 
 
-def run_reference_protocol(sampler, pos, nburn, nsteps, nthin=10, dirname=None, fname='run', rhat=None):
+def run_reference_protocol(sampler, pos, nburn, nsteps, nthin=10, dirname=None, fname='run', rhat=None, ess=None):
     """The driver loop of ``run_emcee`` (mft6.py:1494-1529): burn-in, reset, production with the
     ``acl*50 < n`` / 10 % stability convergence test, thinned coordinate dumps and ``samples.txt``.
     Returns the flattened samples ``(nwalkers*nsteps_run, ndim)``.
 
     ``rhat`` (a float; None: the reference's rule alone, nothing else changes): a check stops only when
     ``max(sampler.get_rhat()) < rhat`` as well -- the second opinion that looks ACROSS the walkers, which tau cannot give
-     -- and with ``dirname`` every check appends that maximum to ``{fname}_rhat.txt``."""
+     -- and with ``dirname`` every check appends that maximum to ``{fname}_rhat.txt``.
+
+    ``ess`` (a float; None: nothing changes): a check stops only when the smallest bulk and tail effective sample size over
+    the columns (``sampler.get_ess``) has reached it as well, and with ``dirname`` every check appends
+    that minimum to ``{fname}_ess.txt``."""
     import os
     for n, s in enumerate(sampler.sample(pos, iterations=nburn)):
         if dirname and n % nthin == 0:
@@ -763,11 +847,18 @@ def run_reference_protocol(sampler, pos, nburn, nsteps, nthin=10, dirname=None, 
                 if dirname:
                     with open('{}/{}_rhat.txt'.format(dirname, fname), 'a') as f:
                         f.write(str(mrhat) + '\n')
+            if ess is not None:
+                mess = _min_ess(sampler)
+                if dirname:
+                    with open('{}/{}_ess.txt'.format(dirname, fname), 'a') as f:
+                        f.write(str(mess) + '\n')
             if not np.isnan(macl):
                 converged = np.all(acl * 50 < n)
                 converged &= np.all((np.abs(old_acl - acl) / acl) < 0.1)
                 if rhat is not None:
                     converged &= mrhat < rhat
+                if ess is not None:
+                    converged &= mess >= ess
                 if converged:
                     break
             old_acl = acl

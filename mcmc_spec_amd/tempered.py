@@ -404,6 +404,33 @@ class _Ladder:
         out = self._moments(t, discard, thin, cols, True)
         return {name: out[name] for name in ('mean', 'cov', 'count')}
 
+    def _rank_stats(self, t, want, discard, thin, cols, q=()):
+        """``_lib.Series.rank_stats``' dict for rung t (t None: every rung, a leading axis T): from the device series with
+        autocorr='device', otherwise ``diagnostics`` on the host chain."""
+        from .sampler import _device_rank_stats, _host_rank_stats, _selection
+        if self._series is not None:
+            return self._pick(self._owned(_device_rank_stats(self._series, len(self._chain), discard, thin, cols, want, q)), t)
+        rungs = range(self.ntemps) if t is None else [int(t)]
+        x = np.concatenate([_selection(self.get_chain(t=r), discard, thin, cols) for r in rungs], axis=1)
+        out = _host_rank_stats(x, [self.nwalkers] * len(rungs), want, q)
+        return out if t is None else {name: v[0] for name, v in out.items()}
+
+    def get_rank_rhat(self, t=0, discard=0, thin=1, cols=None):
+        """Rung t's {'bulk', 'folded', 'rhat'} -- rung 0 is the posterior -- or every rung's for ``t=None``
+        (``EnsembleSampler.get_rank_rhat``)."""
+        from .sampler import _rank_rhat_of
+        return _rank_rhat_of(self._rank_stats(t, ('rhat',), discard, thin, cols), None)
+
+    def get_ess(self, t=0, discard=0, thin=1, cols=None, kind='bulk'):
+        """Rung t's effective sample size (ncols,), or every rung's (T, ncols) for ``t=None`` (``EnsembleSampler.get_ess``)."""
+        from .sampler import _ess_kind, _ess_of
+        return _ess_of(self._rank_stats(t, (_ess_kind(kind),), discard, thin, cols), kind, None)
+
+    def get_mcse(self, t=0, discard=0, thin=1, cols=None, q=(0.16, 0.5, 0.84)):
+        """Rung t's {'mean', 'quantiles'}, or every rung's for ``t=None`` (``EnsembleSampler.get_mcse``)."""
+        from .sampler import _mcse_of
+        return _mcse_of(self._rank_stats(t, ('mcse',), discard, thin, cols, q), None)
+
     _device_modes = False    # get_modes: the device calls (the device samplers) or the definition (TemperedSampler)
 
     def get_modes(self, t=0, ncomp=2, discard=0, thin=1, cols=None, **fit_kw):

@@ -20,9 +20,8 @@ import numpy as np
 
 from . import _lib
 from .engine import _raise_for_status
-from .sampler import (_MOMENTS, EnsembleSampler, State, _accept, _check_tau, _device_integrated_time, _device_moments, _max_rhat,
-                      _propose, _pump, device_seed, _device_rank_stats, _ess_kind, _ess_of, _host_rank_stats, _mcse_of,
-                      _rank_rhat_of, _selection)
+from .sampler import EnsembleSampler, State, _accept, _max_rhat, _propose, _pump, device_seed
+from .stored import StoredChain
 
 
 class TargetGroup:
@@ -208,62 +207,52 @@ class GroupSampler:
         """One array per target."""
         return [s.acceptance_fraction for s in self.samplers]
 
+    # ---- the analyses: the stored-chain view's, the targets as its members (mcmc_spec_amd.stored; DESIGN.md section 27) ----
+    def _host_members(self, members=None):
+        """The targets' stored chains side by side, (n, sum of the walkers, ndim); ``members``: those targets' alone."""
+        chains = [np.array(self.samplers[k]._chain) for k in (range(len(self.samplers)) if members is None else members)]
+        return chains[0] if len(chains) == 1 and members is not None else np.concatenate(chains, axis=1)
+
+    def _stored(self):
+        return StoredChain(None, self._host_members, len(self.samplers[0]._chain), self.ndim, self.nwalkers)
+
     def get_autocorr_time(self, k=None, quiet=False, c=5.0, tol=50.0, discard=0, thin=1):
         """Target k's integrated autocorrelation time (ndim,), or every target's (K, ndim) for k None: each from the
-        target's own EnsembleSampler (EnsembleSampler.get_autocorr_time's keywords and rules)."""
-        kw = dict(quiet=quiet, c=c, tol=tol, discard=discard, thin=thin)
-        if k is not None:
-            return self.samplers[k].get_autocorr_time(**kw)
-        return np.array([s.get_autocorr_time(**kw) for s in self.samplers])
+        target's own walkers (EnsembleSampler.get_autocorr_time's keywords and rules)."""
+        return self._stored().autocorr_time(k, quiet, c, tol, discard, thin)
 
     def get_rhat(self, k=None, discard=0, thin=1, cols=None):
         """Target k's split R-hat (ncols,), or every target's (K, ncols) for k None: each over the target's own walkers
-        (EnsembleSampler.get_rhat's keywords and rules)."""
-        kw = dict(discard=discard, thin=thin, cols=cols)
-        if k is not None:
-            return self.samplers[k].get_rhat(**kw)
-        return np.array([s.get_rhat(**kw) for s in self.samplers])
+        (EnsembleSampler.get_rhat's keywords and rules; DESIGN.md section 21).  DeviceGroupSampler with autocorr='device':
+        every target's from the chains on the device, ONE msx_series_moments call over all targets (rows queued past the
+        stored chains are not part of it)."""
+        return self._stored().moments(k, discard, thin, cols, False)['rhat']
 
     def get_moments(self, k=None, discard=0, thin=1, cols=None):
         """Target k's {'mean', 'cov', 'count'} (EnsembleSampler.get_moments), or every target's for k None: the arrays
-        with a leading axis K."""
-        kw = dict(discard=discard, thin=thin, cols=cols)
-        if k is not None:
-            return self.samplers[k].get_moments(**kw)
-        outs = [s.get_moments(**kw) for s in self.samplers]
-        return {name: np.array([o[name] for o in outs]) for name in _MOMENTS}
-
-    def _rank_stats(self, want, discard, thin, cols, q=(), k=None):
-        """``_lib.Series.rank_stats``' dict for target k alone, or (k None) every target's with a leading axis K:
-        ``diagnostics`` on the host chains that are asked for."""
-        if k is not None:
-            return self.samplers[k]._rank_stats(want, discard, thin, cols, q)
-        x = np.concatenate([_selection(s._chain, discard, thin, cols) for s in self.samplers], axis=1)
-        return _host_rank_stats(x, self.nwalkers, want, q)
+        with a leading axis K.  DeviceGroupSampler with autocorr='device': from the chains on the device (get_rhat's rules)."""
+        out = self._stored().moments(k, discard, thin, cols, rhat=False)
+        return {name: out[name] for name in ('mean', 'cov', 'count')}
 
     def get_rank_rhat(self, k=None, discard=0, thin=1, cols=None):
         """Target k's {'bulk', 'folded', 'rhat'} (EnsembleSampler.get_rank_rhat), or every target's for
         k None: the arrays with a leading axis K."""
-        return _rank_rhat_of(self._rank_stats(('rhat',), discard, thin, cols, k=k), None if k is None else 0)
+        return self._stored().rank_rhat(k, discard, thin, cols)
 
     def get_ess(self, k=None, discard=0, thin=1, cols=None, kind='bulk'):
         """Target k's effective sample size (ncols,) (EnsembleSampler.get_ess), or every target's (K, ncols) for k None."""
-        return _ess_of(self._rank_stats((_ess_kind(kind),), discard, thin, cols, k=k), kind, None if k is None else 0)
+        return self._stored().ess(k, discard, thin, cols, kind)
 
     def get_mcse(self, k=None, discard=0, thin=1, cols=None, q=(0.16, 0.5, 0.84)):
         """Target k's {'mean', 'quantiles'} (EnsembleSampler.get_mcse), or every target's for k None."""
-        return _mcse_of(self._rank_stats(('mcse',), discard, thin, cols, q, k=k), None if k is None else 0)
-
-    def _host_members(self):
-        """The targets' stored chains side by side: (n, sum of the walkers, ndim)."""
-        return np.concatenate([np.array(s._chain) for s in self.samplers], axis=1)
+        return self._stored().mcse(k, discard, thin, cols, q)
 
     def get_modes(self, k=None, ncomp=2, discard=0, thin=1, cols=None, **fit_kw):
         """Every target's posterior modes (EnsembleSampler.get_modes: a ``modes.ModeFit`` with one member per target), or
-        target k's alone (the same object cut to that member)."""
-        from . import modes
-        out = modes.fit(self._host_members(), list(self.nwalkers), cols, ncomp, discard=discard, thin=thin, **fit_kw)
-        return out if k is None else out.select([k])
+        target k's alone (the same object cut to that member).  DeviceGroupSampler fits on the device, every target's EM jobs
+        in ONE msx_series_modes call: with autocorr='device' on the chains held there, otherwise the host chains are uploaded
+        first (DeviceEnsembleSampler.get_modes' rules)."""
+        return self._stored().modes(k, ncomp, discard, thin, cols, **fit_kw)
 
 
 class DeviceGroupSampler(GroupSampler):
@@ -423,52 +412,16 @@ class DeviceGroupSampler(GroupSampler):
                     s._last = State(c[off[k]:off[k + 1]], lp[off[k]:off[k + 1]])
         return [s._last for s in self.samplers]
 
+    def _stored(self):
+        """GroupSampler's view with the resident series (autocorr='device'), the targets' engines, and the mode fit on the
+        device (the targets step together: their chains have one length)."""
+        return StoredChain(self._series, self._host_members, len(self.samplers[0]._chain), self.ndim, self.nwalkers,
+                           self.group.engines, device_modes=True)
+
     def get_autocorr_time(self, k=None, quiet=False, c=5.0, tol=50.0, discard=0, thin=1):
         """GroupSampler.get_autocorr_time; with autocorr='device' every target's from the chains on the device, ONE
         msx_series_acf call per lag tile over all targets (the targets step together: their chains have one length)."""
-        if self._series is None:
-            return super().get_autocorr_time(k, quiet=quiet, c=c, tol=tol, discard=discard, thin=thin)
-        n_total = len(self.samplers[0]._chain)
-        n = len(range(discard, n_total, thin))
-        shape = (self.ndim,) if k is not None else (len(self.samplers), self.ndim)
-        if n < 4:
-            if quiet:
-                return np.full(shape, np.nan)
-            raise ValueError('chain too short')
-        tau = _device_integrated_time(self._series, n_total, c, discard, thin) * thin
-        return _check_tau(tau if k is None else tau[k], n, thin, tol, quiet)
-
-    def get_rhat(self, k=None, discard=0, thin=1, cols=None):
-        """GroupSampler.get_rhat; with autocorr='device' every target's from the chains on the device, ONE
-        msx_series_moments call over all targets (rows queued past the stored chains are not part of it)."""
-        if self._series is None:
-            return super().get_rhat(k, discard=discard, thin=thin, cols=cols)
-        r = _device_moments(self._series, len(self.samplers[0]._chain), discard, thin, cols, False)['rhat']
-        return r if k is None else r[k]
-
-    def _rank_stats(self, want, discard, thin, cols, q=(), k=None):
-        """GroupSampler._rank_stats; with autocorr='device' every target's from the chains on the device, the targets'
-        columns as the segments of one sort (rows queued past the stored chains are not part of it); target k's is cut from
-        that, with a leading axis of one."""
-        if self._series is None:
-            return super()._rank_stats(want, discard, thin, cols, q, k)
-        out = _device_rank_stats(self._series, len(self.samplers[0]._chain), discard, thin, cols, want, q)
-        return out if k is None else {name: v[k:k + 1] for name, v in out.items()}
-
-    def get_moments(self, k=None, discard=0, thin=1, cols=None):
-        """GroupSampler.get_moments; with autocorr='device' from the chains on the device (get_rhat's rules)."""
-        if self._series is None:
-            return super().get_moments(k, discard=discard, thin=thin, cols=cols)
-        out = _device_moments(self._series, len(self.samplers[0]._chain), discard, thin, cols, True)
-        return {name: out[name] if k is None else out[name][k] for name in _MOMENTS}
-
-    def get_modes(self, k=None, ncomp=2, discard=0, thin=1, cols=None, **fit_kw):
-        """GroupSampler.get_modes on the device, every target's EM jobs in ONE msx_series_modes call: with autocorr='device'
-        on the chains held there, otherwise the host chains are uploaded first (DeviceEnsembleSampler.get_modes' rules)."""
-        from . import modes
-        out = modes.of_sampler(self._series, self._host_members, len(self.samplers[0]._chain), self.group.engines[0].ctx,
-                               list(self.nwalkers), ncomp, discard, thin, cols, fit_kw)
-        return out if k is None else out.select([k])
+        return self._stored().autocorr_time(k, quiet, c, tol, discard, thin)
 
     def get_summary(self, k=None, q=(0.16, 0.5, 0.84), discard=0, thin=1, cols=None):
         """Every target's posterior summary from its stored chain, flattened over its walkers: {'count' (K,), 'min', 'max'
@@ -477,16 +430,7 @@ class DeviceGroupSampler(GroupSampler):
         section 14): with autocorr='device' on the chains held there -- the rows of the stored chains; rows queued past
         them are not part of it -- otherwise the host chains are uploaded first.  ``cols``: coordinates or
         ``summary.col_ratio(a, b)``; None for all coordinates."""
-        from . import summary
-        n_total = len(self.samplers[0]._chain)
-        if self._series is not None:
-            out = summary.summary_of(self._series, n_total, q, cols, discard, thin)
-        else:
-            if n_total < 1:
-                raise ValueError('the selection rows[0:n][discard::thin] is empty')
-            chain = np.concatenate([np.array(s._chain) for s in self.samplers], axis=1)
-            out = summary.summarize(chain, self.group.engines[0].ctx, self.nwalkers, q, cols, discard, thin)
-        return out if k is None else {name: v[k] for name, v in out.items()}
+        return self._stored().summary(k, q, discard, thin, cols)
 
     def get_products(self, cols, q=(0.16, 0.5, 0.84), discard=0, thin=1, indices=None, k=None):
         """``get_summary``'s dict over DERIVED columns (``mcmc_spec_amd.products``) of every target's stored chain, each
@@ -496,58 +440,29 @@ class DeviceGroupSampler(GroupSampler):
         target or a sequence of K (mft6.py:2486: the caller draws them); those samples are taken from the host copies of the
         chains and go through msx_products_batch target by target, whatever ``autocorr`` is.  ``k``: one target (the arrays lose their first
         axis).  Every engine needs staged products (``products.stage``)."""
-        from . import products, summary
-        engines = self.group.engines
-        n_total = len(self.samplers[0]._chain)
-        if indices is not None:
-            per = [indices] * len(engines) if np.ndim(indices[0]) == 0 else list(indices)
-            if len(per) != len(engines):
-                raise ValueError('indices: one array for all targets or one per target')
-            outs = []
-            for m, e in enumerate(engines):
-                flat = self.samplers[m].get_chain(flat=True, thin=thin, discard=discard)
-                outs.append(products._summary_of_values(e.ctx, products.evaluate(e, flat[np.asarray(per[m], dtype=np.int64)], cols), q))
-            out = {name: np.stack([o[name] for o in outs]) for name in outs[0]}
-        elif self._series is not None:
-            out = products.summarize_chain(self._series, n_total, engines, cols, q, discard, thin)
-        else:
-            if n_total < 1:
-                raise ValueError('the selection rows[0:n][discard::thin] is empty')
-            chain = np.concatenate([np.array(s._chain) for s in self.samplers], axis=1)
-            with summary.uploaded(chain, engines[0].ctx, self.nwalkers) as (series, n):
-                out = products.summarize_chain(series, n, engines, cols, q, discard, thin)
-        return out if k is None else {name: v[k] for name, v in out.items()}
+        return self._stored().products(cols, k, q, discard, thin, indices)
 
     def get_predictive(self, q=(0.16, 0.5, 0.84), discard=0, thin=1, k=None):
         """Every target's posterior predictive check (``mcmc_spec_amd.predictive``) of its stored
         chain, each target's samples evaluated with its own engine: a list of K dicts (the targets' pixel counts may
         differ), or target ``k``'s dict.  With autocorr='device' on the chains held there, otherwise the host chains are
         uploaded first; rows queued past the stored chains are not part of it."""
-        from . import predictive
-        out = predictive.of_chain(self._series, lambda: np.concatenate([np.array(s._chain) for s in self.samplers], axis=1),
-                                  len(self.samplers[0]._chain), self.group.engines, self.nwalkers, q, discard, thin)
-        return out if k is None else out[k]
+        return self._stored().predictive(k, q, discard, thin)
 
     def get_loo(self, discard=0, thin=1, reff=1.0, k=None):
         """Every target's PSIS-LOO, WAIC and khat per observation (``mcmc_spec_amd.psis``) of its
         stored chain, each target's samples evaluated with its own engine: a list of K ``psis.loo`` dicts, or target
         ``k``'s.  With autocorr='device' on the chains held there, otherwise the host chains are uploaded first."""
-        from . import psis
-        out = psis.of_chain(self._series, lambda: np.concatenate([np.array(s._chain) for s in self.samplers], axis=1),
-                            len(self.samplers[0]._chain), self.group.engines, self.nwalkers, discard, thin, reff)
-        return out if k is None else out[k]
+        return self._stored().loo(k, discard, thin, reff)
 
     def get_reweighted(self, engines_new, mode='logposterior', discard=0, thin=1):
         """``DeviceEnsembleSampler.get_reweighted`` for every target at once: ``engines_new`` holds one staged Engine per
         target (a target's own engine leaves its weights at 1), and the ``reweight.Reweighted`` it returns has one member
         per target.  With autocorr='device' on the chains held there, otherwise the host chains are uploaded first."""
-        from . import reweight
         engines_new = list(engines_new)
         if len(engines_new) != len(self.group.engines):
             raise ValueError('get_reweighted: one engine per target ({})'.format(len(self.group.engines)))
-        return reweight.of_sampler(self._series, lambda: np.concatenate([np.array(s._chain) for s in self.samplers], axis=1),
-                                   len(self.samplers[0]._chain), self.group.engines, engines_new, self.nwalkers, mode=mode,
-                                   mode_old=self.mode, discard=discard, thin=thin)
+        return self._stored().reweighted(engines_new, mode=mode, mode_old=self.mode, discard=discard, thin=thin)
 
 
 def run_group_protocol(sampler, pos, nburn, nsteps, nthin=10, dirname=None, fnames=None, rhat=None, ess=None):
@@ -621,7 +536,7 @@ def run_group_protocol(sampler, pos, nburn, nsteps, nthin=10, dirname=None, fnam
                 mrhats = {k: _max_rhat(lambda: sampler.get_rhat(k)) for k in active}
         if ess is not None:   # (one computation for all targets; NaN while the chains are shorter than 4 rows)
             try:
-                st = sampler._rank_stats(('bulk', 'tail'), 0, 1, None)
+                st = sampler._stored().rank_stats(None, ('bulk', 'tail'))
                 messes = np.min(np.minimum(st['ess_bulk'], st['ess_tail']), axis=1)
             except ValueError:
                 messes = np.full(K, np.nan)

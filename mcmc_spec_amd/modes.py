@@ -482,9 +482,3 @@ def uploaded(chain, ctx, counts=None, **fit_kw):
     out._owned = up.series
     return out
 
-
-def of_sampler(series, host_chain, n_total, ctx, counts, ncomp, discard, thin, cols, fit_kw):
-    """The samplers' ``get_modes``: the resident ``series`` when there is one, the uploaded host chain otherwise."""
-    if series is not None:
-        return fit_device(series, n_total, cols=cols, ncomp=ncomp, discard=discard, thin=thin, ctx=ctx, **fit_kw)
-    return uploaded(host_chain(), ctx, counts, cols=cols, ncomp=ncomp, discard=discard, thin=thin, **fit_kw)

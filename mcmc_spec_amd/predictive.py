@@ -107,14 +107,3 @@ def print_report(res, wl=None, label=''):
     where = 'pixel {}'.format(r['pixel']) if r['wavelength'] is None else '{:.5g} um'.format(r['wavelength'])
     print('{}  largest |<z>| = {:.3g} sigma at {}'.format(label, r['max_abs_z'], where))
 
-
-def of_chain(series, chain, n_total, engines, counts, q, discard, thin, scratch_mb=None):
-    """The samplers' plumbing: ``check_series`` on the resident chain ``series`` (rows 0 .. n_total - 1), or -- series None
-    -- on the host chain (n, nw, ndim) uploaded first."""
-    from . import summary
-    if series is not None:
-        return check_series(series, n_total, engines, q, discard, thin, scratch_mb=scratch_mb)
-    if n_total < 1:
-        raise ValueError('the selection rows[0:n][discard::thin] is empty')
-    with summary.uploaded(chain(), engines[0].ctx, counts) as (up, n):
-        return check_series(up, n, engines, q, discard, thin, scratch_mb=scratch_mb)

@@ -293,18 +293,6 @@ def loo_series(series, n, engines, discard=0, thin=1, reff=1.0, pointwise=False,
     return res
 
 
-def of_chain(series, chain, n_total, engines, counts, discard, thin, reff=1.0, scratch_mb=None):
-    """The samplers' ``get_loo``: ``loo_series`` on the resident chain ``series`` (rows 0 .. n_total - 1), or -- series None --
-    on the host chain (n, nw, ndim) uploaded first."""
-    from . import summary
-    if series is not None:
-        return loo_series(series, n_total, engines, discard, thin, reff, scratch_mb=scratch_mb)
-    if n_total < 1:
-        raise ValueError('the selection rows[0:n][discard::thin] is empty')
-    with summary.uploaded(chain(), engines[0].ctx, counts) as (up, n):
-        return loo_series(up, n, engines, discard, thin, reff, scratch_mb=scratch_mb)
-
-
 def print_report(res, label=''):
     """The examples' lines for a ``loo`` dict: the totals with their standard errors, the count of khat > 0.7 and the worst
     observations."""

@@ -8,8 +8,8 @@ This module holds
 
   * the NumPy DEFINITION of the four calls that reduce (``lincomb``, ``weights``, ``wmoments``, ``prefix_sums`` /
     ``draw``), in the device's order of operations, which tests/test_gpu_reweight.py holds the device to;
-  * the user layer on device series: ``rescore``, ``log_weights``, ``Reweighted``, and ``of_series`` / ``uploaded`` /
-    ``of_sampler`` for a resident or a host chain.
+  * the user layer on device series: ``rescore``, ``log_weights``, ``Reweighted``, and ``of_series`` / ``uploaded`` for
+    a resident or a host chain (the samplers' ``get_reweighted`` chooses between them: ``stored.StoredChain.reweighted``).
 
 Member m's FLAT sample is ``x[discard:n:thin][:, walkers of m].reshape(-1, ...)``: (row, walker) order, ``get_chain(flat=True)``'s.
 """
@@ -341,25 +341,9 @@ def of_series(series, n, engines_old, engines_new, ctx=None, mode='logposterior'
 
 
 def uploaded(chain, engines_old, engines_new, counts=None, **kw):
-    """``of_series`` for a host chain (n, nw, ndim) -- a host sampler's, one loaded from samples.txt --, through a series that
-    the result owns and frees with its ``close()``."""
-    chain = _lib.as_f64(chain)
-    if chain.ndim != 3 or chain.shape[0] < 1:
-        raise ValueError('chain must have shape (n, nwalkers, ndim), n >= 1')
+    """``of_series`` for a host chain (n, nw, ndim) -- a host sampler's, one loaded from samples.txt --, through a temporary series
+    (``summary.uploaded``'s) that the result owns and frees with its ``close()``."""
+    from . import summary
     ctx = list(engines_old)[0].ctx
-    series = _lib.Series(ctx, chain.shape[1], chain.shape[2], counts, cap_hint=chain.shape[0])
-    try:
-        series.append(chain)
-    except Exception:
-        series.close()
-        raise
-    return of_series(series, chain.shape[0], engines_old, engines_new, ctx=ctx, owned=[series], **kw)
-
-
-def of_sampler(series, host_chain, n_total, engines_old, engines_new, counts, **kw):
-    """The samplers' ``get_reweighted``: the resident ``series`` when there is one, the uploaded host chain otherwise."""
-    if n_total < 1:
-        raise ValueError('the selection rows[0:n][discard::thin] is empty')
-    if series is not None:
-        return of_series(series, n_total, engines_old, engines_new, **kw)
-    return uploaded(host_chain(), engines_old, engines_new, counts, **kw)
+    up = summary.uploaded(chain, ctx, counts)
+    return of_series(up.series, up.n, engines_old, engines_new, ctx=ctx, owned=[up.series], **kw)

@@ -259,130 +259,62 @@ class EnsembleSampler:
             pass
         return st
 
-    # ---- diagnostics --------------------------------------------------------------------------------------
+    # ---- diagnostics: every analysis is the stored-chain view's (mcmc_spec_amd.stored) ---------------
+    def _stored(self):
+        """The view of the stored chain that the analyses below ask."""
+        from .stored import StoredChain
+        return StoredChain(None, lambda members=None: np.array(self._chain), len(self._chain), self.ndim)
+
     def get_autocorr_time(self, quiet=False, c=5.0, tol=50.0, discard=0, thin=1):
         """Integrated autocorrelation time per dimension (Sokal window, like emcee's ``integrated_time``)."""
-        x = self.get_chain(discard=discard, thin=thin)  # (nsteps, nwalkers, ndim)
-        if x.shape[0] < 4:
-            if quiet:
-                return np.full(self.ndim, np.nan)
-            raise ValueError('chain too short')
-        n = x.shape[0]
-        f = np.empty((self.ndim, n))
-        for d in range(self.ndim):
-            f[d] = 0.0
-            for k in range(self.nwalkers):
-                f[d] += _autocorr_1d(x[:, k, d])
-            f[d] /= self.nwalkers
-        return _check_tau(_integrated_time(f, c) * thin, n, thin, tol, quiet)
+        return self._stored().autocorr_time(0, quiet, c, tol, discard, thin)
 
     def get_rhat(self, discard=0, thin=1, cols=None):
         """Split R-hat per column over the walkers of the stored chain, rows ``[discard::thin]`` (at least 4):
-        ``diagnostics.split_rhat``.  ``cols``: coordinates; None for all."""
-        from . import diagnostics
-        return diagnostics.split_rhat(_selection(self._chain, discard, thin, cols))
+        ``diagnostics.split_rhat``.  ``cols``: coordinates; None for all.  DeviceEnsembleSampler with
+        autocorr='device': from the chain on the device (msx_series_moments), without a download; rows the device holds past
+        len(self._chain) -- queued chunks not consumed yet -- are not part of it."""
+        return self._stored().moments(0, discard, thin, cols, False)['rhat']
 
     def get_moments(self, discard=0, thin=1, cols=None):
         """{'mean' (ncols,), 'cov' (ncols, ncols), 'count'}: the mean and covariance of
-        ``get_chain(discard=, thin=, flat=True)`` (``diagnostics.moments``)."""
-        from . import diagnostics
-        return diagnostics.moments(_selection(self._chain, discard, thin, cols))
-
-    def _rank_stats(self, want, discard, thin, cols, q=()):
-        """``_lib.Series.rank_stats``' dict (a leading axis of one member) from ``diagnostics`` on the host chain."""
-        return _host_rank_stats(_selection(self._chain, discard, thin, cols), None, want, q)
+        ``get_chain(discard=, thin=, flat=True)`` (``diagnostics.moments``); DeviceEnsembleSampler with autocorr='device': from
+        the chain on the device (get_rhat's rules)."""
+        out = self._stored().moments(0, discard, thin, cols, rhat=False)
+        return {name: out[name] for name in ('mean', 'cov', 'count')}
 
     def get_rank_rhat(self, discard=0, thin=1, cols=None):
         """{'bulk', 'folded', 'rhat'}, each (ncols,): the rank-normalised split R-hat of Vehtari et al. (2021) over the walkers
         of the stored chain, rows ``[discard::thin]`` (at least 4), its folded companion, which sees a walker of another scale,
         and their maximum (``diagnostics.rank_rhat``)."""
-        return _rank_rhat_of(self._rank_stats(('rhat',), discard, thin, cols), 0)
+        return self._stored().rank_rhat(0, discard, thin, cols)
 
     def get_ess(self, discard=0, thin=1, cols=None, kind='bulk'):
         """The effective sample size (ncols,) of the stored chain's walkers taken together: ``kind`` 'bulk' (what the central
         quantiles are worth), 'tail' (the 5 % and 95 % quantiles) or 'mean' (``diagnostics.ess``)."""
-        return _ess_of(self._rank_stats((_ess_kind(kind),), discard, thin, cols), kind, 0)
+        return self._stored().ess(0, discard, thin, cols, kind)
 
     def get_mcse(self, discard=0, thin=1, cols=None, q=(0.16, 0.5, 0.84)):
         """{'mean' (ncols,), 'quantiles' (ncols, len(q))}: the Monte-Carlo standard errors of the chain's mean and of its
         quantiles ``q`` -- how many digits of a published percentile are real (``diagnostics.mcse``)."""
-        return _mcse_of(self._rank_stats(('mcse',), discard, thin, cols, q), 0)
+        return self._stored().mcse(0, discard, thin, cols, q)
 
     def get_modes(self, ncomp=2, discard=0, thin=1, cols=None, **fit_kw):
         """The posterior's modes: a joint Gaussian mixture of ``ncomp`` components over the columns ``cols`` (None: all)
         of ``get_chain(discard=, thin=, flat=True)``, as a ``modes.ModeFit`` (one member) whose ``labels()``, ``split()``
         and ``summary()`` give every sample's mode and the per-mode quantiles (``mcmc_spec_amd.modes``; DESIGN.md section
-        23).  ``fit_kw``: ``modes.fit``'s max_iter, tol, ridge, center, scale, split_col, split_at."""
-        from . import modes
-        return modes.fit(np.array(self._chain), None, cols, ncomp, discard=discard, thin=thin, **fit_kw)
-
-
-def _selection(rows, discard, thin, cols):
-    """Stored rows (a list of (nw, ndim) arrays, or an array) as the selection (n', nw, ncols) of get_rhat / get_moments."""
-    x = np.asarray(rows)[discard::thin]
-    if x.ndim != 3 or x.shape[0] < 4:
-        raise ValueError('chain too short')
-    return x if cols is None else x[:, :, np.asarray(cols, dtype=np.int64).ravel()]
-
-
-def _device_moments(series, n_total, discard, thin, cols, cov):
-    """``Series.moments`` of the first n_total rows (the rows consumed; those queued past them are not part of it)."""
-    if len(range(discard, n_total, thin)) < 4:
-        raise ValueError('chain too short')
-    return series.moments(n_total, discard, thin, cols, cov)
-
-
-_MOMENTS = ('mean', 'cov', 'count')
-
-
-# ---- rank-normalised R-hat, bulk / tail ESS and MCSE (DESIGN.md section 26): one dict of (k, ncols) arrays, whoever computes it
-def _host_rank_stats(x, counts, want, q):
-    """``_lib.Series.rank_stats``' dict from ``diagnostics`` on the selection x (n', W, ncols); counts None: one member."""
-    from . import diagnostics
-    counts = [x.shape[1]] if counts is None else list(counts)
-    out = {}
-    if 'rhat' in want:
-        out.update(diagnostics.rank_rhat(x, counts))
-    for kind in ('bulk', 'tail', 'mean'):
-        if kind in want:
-            out['ess_' + kind] = diagnostics.ess(x, kind, counts)
-    if 'mcse' in want:
-        m = diagnostics.mcse(x, q, counts)
-        out['mcse_mean'], out['mcse_quantile'] = m['mean'], m['quantiles']
-    return out
-
-
-def _device_rank_stats(series, n_total, discard, thin, cols, want, q):
-    """``Series.rank_stats`` of the first n_total rows (the rows consumed; those queued past them are not part of it)."""
-    if len(range(discard, n_total, thin)) < 4:
-        raise ValueError('chain too short')
-    return series.rank_stats(n_total, discard, thin, cols, q, want)
-
-
-def _ess_kind(kind):
-    if kind not in ('bulk', 'tail', 'mean'):
-        raise ValueError("kind must be 'bulk', 'tail' or 'mean'")
-    return kind
-
-
-def _rank_rhat_of(stats, m):
-    """m: a member, or None for all of them (a leading axis)."""
-    return {name: stats[name] if m is None else stats[name][m] for name in ('bulk', 'folded', 'rhat')}
-
-
-def _ess_of(stats, kind, m):
-    return stats['ess_' + kind] if m is None else stats['ess_' + kind][m]
-
-
-def _mcse_of(stats, m):
-    return {name: stats[key] if m is None else stats[key][m] for name, key in (('mean', 'mcse_mean'), ('quantiles', 'mcse_quantile'))}
+        23).  ``fit_kw``: ``modes.fit``'s max_iter, tol, ridge, center, scale, split_col, split_at.  DeviceEnsembleSampler fits
+        on the device (msx_series_modes, msx_series_mode_labels): with autocorr='device' on the chain held there, without a
+        download (rows past len(self._chain) are not part of it); otherwise the host chain is uploaded first and the result
+        keeps that copy until its ``close()``."""
+        return self._stored().modes(None, ncomp, discard, thin, cols, **fit_kw)
 
 
 def _min_ess(sampler):
     """min over the columns of a check's bulk and tail ESS, from one computation of both; NaN while the chain is shorter
     than 4 rows."""
     try:
-        st = sampler._rank_stats(('bulk', 'tail'), 0, 1, None)
+        st = sampler._stored().rank_stats(0, ('bulk', 'tail'))
         return float(min(np.min(st['ess_bulk']), np.min(st['ess_tail'])))   # (np.min keeps a NaN)
     except ValueError:
         return float('nan')
@@ -597,6 +529,7 @@ class DeviceEnsembleSampler(EnsembleSampler):
         self.device_seed = device_seed(seed) if rng == 'device' else None   # (the generator's key; None: the host draws)
         self.overlapped = None   # set by the first chunk of a run: did its half-steps overlap (include/msx.h)?
         self.engine = engine
+        self.mode = mode
         self._mode = {'logposterior': _lib.MODE_LOGPOST, 'loglikelihood': _lib.MODE_LOGLIKE}[mode]
         fn = engine.logposterior if mode == 'logposterior' else engine.loglikelihood
         super().__init__(nwalkers, ndim, fn, a=a, vectorize=True, seed=seed, moves=moves, _general=_general)
@@ -667,48 +600,16 @@ class DeviceEnsembleSampler(EnsembleSampler):
     def acceptance_fraction(self):
         return self._accepted / max(self.iteration, 1)
 
+    def _stored(self):
+        """EnsembleSampler's view with the resident series (autocorr='device'), the engine, and the mode fit on the device."""
+        from .stored import StoredChain
+        return StoredChain(self._series, lambda members=None: np.array(self._chain), len(self._chain), self.ndim, engines=[self.engine],
+                           device_modes=True)
+
     def get_autocorr_time(self, quiet=False, c=5.0, tol=50.0, discard=0, thin=1):
         """EnsembleSampler.get_autocorr_time; with autocorr='device' from the chain on the device (msx_series_acf).
         Rows the device holds past len(self._chain) -- queued chunks not consumed yet -- are not part of it."""
-        if self._series is None:
-            return super().get_autocorr_time(quiet=quiet, c=c, tol=tol, discard=discard, thin=thin)
-        n_total = len(self._chain)
-        n = len(range(discard, n_total, thin))
-        if n < 4:
-            if quiet:
-                return np.full(self.ndim, np.nan)
-            raise ValueError('chain too short')
-        tau = _device_integrated_time(self._series, n_total, c, discard, thin)[0]
-        return _check_tau(tau * thin, n, thin, tol, quiet)
-
-    def get_rhat(self, discard=0, thin=1, cols=None):
-        """EnsembleSampler.get_rhat; with autocorr='device' from the chain on the device (msx_series_moments), without a
-        download.  Rows the device holds past len(self._chain) -- queued chunks not consumed yet -- are not part of it."""
-        if self._series is None:
-            return super().get_rhat(discard=discard, thin=thin, cols=cols)
-        return _device_moments(self._series, len(self._chain), discard, thin, cols, False)['rhat'][0]
-
-    def _rank_stats(self, want, discard, thin, cols, q=()):
-        """EnsembleSampler._rank_stats; with autocorr='device' from the chain on the device (msx_series_split_transform,
-        msx_series_chain_acov), without a download (get_rhat's rule for rows queued but not consumed)."""
-        if self._series is None:
-            return super()._rank_stats(want, discard, thin, cols, q)
-        return _device_rank_stats(self._series, len(self._chain), discard, thin, cols, want, q)
-
-    def get_moments(self, discard=0, thin=1, cols=None):
-        """EnsembleSampler.get_moments; with autocorr='device' from the chain on the device (get_rhat's rules)."""
-        if self._series is None:
-            return super().get_moments(discard=discard, thin=thin, cols=cols)
-        out = _device_moments(self._series, len(self._chain), discard, thin, cols, True)
-        return {name: out[name][0] for name in _MOMENTS}
-
-    def get_modes(self, ncomp=2, discard=0, thin=1, cols=None, **fit_kw):
-        """EnsembleSampler.get_modes on the device (msx_series_modes, msx_series_mode_labels): with autocorr='device' on
-        the chain held there, without a download (rows past len(self._chain) are not part of it); otherwise the host chain
-        is uploaded first and the result keeps that copy until its ``close()``."""
-        from . import modes
-        return modes.of_sampler(self._series, lambda: np.array(self._chain), len(self._chain), self.engine.ctx, None, ncomp, discard,
-                                thin, cols, fit_kw)
+        return self._stored().autocorr_time(0, quiet, c, tol, discard, thin)
 
     def get_summary(self, q=(0.16, 0.5, 0.84), discard=0, thin=1, cols=None):
         """The posterior summary of the stored chain, flattened over the walkers: {'count': N, 'min', 'max' (ncols,),
@@ -716,15 +617,7 @@ class DeviceEnsembleSampler(EnsembleSampler):
         elements the device selects (mcmc_spec_amd.summary).  With autocorr='device' from the chain
         held there (rows past len(self._chain) -- queued chunks not consumed yet -- are not part of it); otherwise the
         host chain is uploaded first.  ``cols``: coordinates or ``summary.col_ratio(a, b)``; None for all coordinates."""
-        from . import summary
-        n_total = len(self._chain)
-        if self._series is not None:
-            out = summary.summary_of(self._series, n_total, q, cols, discard, thin)
-        else:
-            if n_total < 1:
-                raise ValueError('the selection rows[0:n][discard::thin] is empty')
-            out = summary.summarize(np.array(self._chain), self.engine.ctx, None, q, cols, discard, thin)
-        return {name: v[0] for name, v in out.items()}
+        return self._stored().summary(0, q, discard, thin, cols)
 
     def get_products(self, cols, q=(0.16, 0.5, 0.84), discard=0, thin=1, indices=None):
         """``get_summary``'s dict over DERIVED columns of the stored chain (``mcmc_spec_amd.products``: names such as
@@ -734,20 +627,7 @@ class DeviceEnsembleSampler(EnsembleSampler):
         sample to use instead of all of it (the reference draws 2,000 with ``np.random.choice(len(sample), 2000,
         replace=False)``, mft6.py:2486; the caller draws them): those samples are taken from the host copy of the chain
         and go through msx_products_batch, whatever ``autocorr`` is.  The engine needs staged products (``products.stage``)."""
-        from . import products, summary
-        n_total = len(self._chain)
-        if indices is not None:
-            flat = self.get_chain(flat=True, thin=thin, discard=discard)
-            vals = products.evaluate(self.engine, flat[np.asarray(indices, dtype=np.int64)], cols)
-            return products._summary_of_values(self.engine.ctx, vals, q)
-        if self._series is not None:
-            out = products.summarize_chain(self._series, n_total, [self.engine], cols, q, discard, thin)
-        else:
-            if n_total < 1:
-                raise ValueError('the selection rows[0:n][discard::thin] is empty')
-            with summary.uploaded(np.array(self._chain), self.engine.ctx) as (series, n):
-                out = products.summarize_chain(series, n, [self.engine], cols, q, discard, thin)
-        return {name: v[0] for name, v in out.items()}
+        return self._stored().products(cols, 0, q, discard, thin, None if indices is None else [indices])
 
     def get_predictive(self, q=(0.16, 0.5, 0.84), discard=0, thin=1):
         """The posterior predictive check of the stored chain (``mcmc_spec_amd.predictive``): every
@@ -756,9 +636,7 @@ class DeviceEnsembleSampler(EnsembleSampler):
         autocorr='device' the chain held on the device is read, without a copy (rows past len(self._chain) -- queued chunks
         not consumed yet -- are not part of it); otherwise the host chain is uploaded first.  The engine needs staged
         products (``products.stage``)."""
-        from . import predictive
-        return predictive.of_chain(self._series, lambda: np.array(self._chain), len(self._chain), [self.engine], None, q, discard,
-                                   thin)[0]
+        return self._stored().predictive(0, q, discard, thin)
 
     def get_loo(self, discard=0, thin=1, reff=1.0):
         """PSIS-LOO, WAIC and khat per observation of the stored chain (``mcmc_spec_amd.psis``):
@@ -766,8 +644,7 @@ class DeviceEnsembleSampler(EnsembleSampler):
         the chain held on the device with autocorr='device', otherwise from the host chain uploaded first.  A relative score
         between models on identical data (``psis.compare``), and the observations one sample cannot stand in for (khat >
         0.7).  The engine needs staged products (``products.stage``)."""
-        from . import psis
-        return psis.of_chain(self._series, lambda: np.array(self._chain), len(self._chain), [self.engine], None, discard, thin, reff)[0]
+        return self._stored().loo(0, discard, thin, reff)
 
     def get_reweighted(self, engines_new, mode='logposterior', discard=0, thin=1):
         """The stored chain asked another question without a second run (``mcmc_spec_amd.reweight``):
@@ -777,11 +654,8 @@ class DeviceEnsembleSampler(EnsembleSampler):
         the second question is from the first; ``moments()`` and ``resample()`` answer it.  With autocorr='device' on the
         chain held there (rows past len(self._chain) are not part of it); otherwise the host chain is uploaded first.  The
         caller ``close()``s the result."""
-        from . import reweight
         e_new = engines_new[0] if isinstance(engines_new, (list, tuple)) else engines_new
-        own = 'logposterior' if self._mode == 1 else 'loglikelihood'
-        return reweight.of_sampler(self._series, lambda: np.array(self._chain), len(self._chain), [self.engine], [e_new], None,
-                                   mode=mode, mode_old=own, discard=discard, thin=thin)
+        return self._stored().reweighted([e_new], mode=mode, mode_old=self.mode, discard=discard, thin=thin)
 
 
 def _autocorr_1d(x):

@@ -62,6 +62,7 @@ from contextlib import closing
 import numpy as np
 
 from .sampler import EnsembleSampler, State, _propose, _pump, device_seed
+from .stored import StoredChain
 
 MAX_TEMPS = 64        # include/msx.h MSX_MAX_GROUP: rungs of a ladder
 SWAP_STREAM = 14      # the counter generator's stream of the swap draws (0..13: moves.counter_draws_moves)
@@ -315,196 +316,91 @@ def _ss_db(betas, idx):
     return db
 
 
-def _host_tau(x, c):
-    """EnsembleSampler.get_autocorr_time's tau (before ``* thin`` and the tol rule) of a chain x (n, nw, ndim)."""
-    from .sampler import _autocorr_1d, _integrated_time
-    n, nw, ndim = x.shape
-    f = np.empty((ndim, n))
-    for d in range(ndim):
-        f[d] = 0.0
-        for k in range(nw):
-            f[d] += _autocorr_1d(x[:, k, d])
-        f[d] /= nw
-    return _integrated_time(f, c)
-
-
 class _Ladder:
     """What both samplers keep and return."""
 
     _series = _dens = None   # DeviceTemperedSampler(autocorr='device'): the chain's and the densities' device series
     engine = None            # the staged Engine, where the sampler was built on one (get_summary, get_products)
-    _own = slice(None)       # this ladder's rungs among the device series' members (a target of a group run: its T of K T)
+    _device_modes = False    # get_modes: the device calls (the device samplers) or the definition (TemperedSampler)
 
-    def _owned(self, out):
-        """The rows of this ladder's rungs in a per-member result of the device series (an array, or a dict of arrays)."""
-        return {name: v[self._own] for name, v in out.items()} if isinstance(out, dict) else out[self._own]
-
-    def _series_engines(self):
-        """One engine per member of the device series."""
-        return [self.engine] * self.ntemps
-
-    def _series_db(self, db):
-        """db (T,) of this ladder's rungs as the device series' per-member db."""
-        return db
-
-    def _pick(self, out, t):
-        return out if t is None else {name: v[int(t)] for name, v in out.items()}
-
-    def _ctx(self):
-        if self.engine is None:
-            raise ValueError('this needs the GPU: build the sampler on a staged Engine')
-        return self.engine.ctx
-
-    def _flat_members(self):
-        """The stored chain as (n, T nw, ndim): the rungs as members, side by side."""
+    def _flat_members(self, members=None):
+        """The stored chain as (n, T nw, ndim): the rungs as members, side by side; ``members``: those rungs alone."""
         if not self._chain:
             raise ValueError('the selection rows[0:n][discard::thin] is empty')
-        return np.array(self._chain).reshape(len(self._chain), self.ntemps * self.nwalkers, self.ndim)
+        x = np.array(self._chain) if members is None else np.array(self._chain)[:, list(members)]
+        return x.reshape(len(self._chain), -1, self.ndim)
+
+    def _stored(self):
+        """The view of the stored chain that the analyses below ask (mcmc_spec_amd.stored): the rungs
+        are its members."""
+        T = self.ntemps
+        return StoredChain(self._series, self._flat_members, len(self._chain), self.ndim, [self.nwalkers] * T,
+                           None if self.engine is None else [self.engine] * T, device_modes=self._device_modes, joined=True)
 
     def get_autocorr_time(self, t=0, quiet=False, c=5.0, tol=50.0, discard=0, thin=1):
         """Rung t's integrated autocorrelation time (ndim,) -- rung 0 is the posterior -- or every rung's (T, ndim) for
         ``t=None``: ``EnsembleSampler.get_autocorr_time``'s rules and keywords.  With autocorr='device' from the chain on
         the device, one msx_series_acf call per lag tile over all rungs."""
-        from .sampler import _check_tau, _device_integrated_time
-        n_total = len(self._chain)
-        n = len(range(discard, n_total, thin))
-        rungs = range(self.ntemps) if t is None else [int(t)]
-        if n < 4:
-            if quiet:
-                return np.full((self.ntemps, self.ndim) if t is None else (self.ndim,), np.nan)
-            raise ValueError('chain too short')
-        if self._series is not None:
-            tau = self._owned(_device_integrated_time(self._series, n_total, c, discard, thin))[list(rungs)]
-        else:
-            tau = np.array([_host_tau(self.get_chain(t=r, discard=discard, thin=thin), c) for r in rungs])
-        return _check_tau((tau if t is None else tau[0]) * thin, n, thin, tol, quiet)
-
-    def _moments(self, t, discard, thin, cols, cov):
-        """Series.moments' dict for rung t (t None: every rung, a leading axis T): from the device series with
-        autocorr='device' (one msx_series_moments call over all members), otherwise ``diagnostics`` on the host chain."""
-        from . import diagnostics
-        from .sampler import _device_moments, _selection
-        if self._series is not None:
-            out = _device_moments(self._series, len(self._chain), discard, thin, cols, cov)
-            return self._pick(self._owned({name: v for name, v in out.items() if v is not None}), t)
-        rungs = range(self.ntemps) if t is None else [int(t)]
-        x = np.concatenate([_selection(self.get_chain(t=r), discard, thin, cols) for r in rungs], axis=1)
-        out = diagnostics.split_parts(x, [self.nwalkers] * len(rungs))
-        if cov:
-            out.update(diagnostics.moments(x, [self.nwalkers] * len(rungs)))
-        return out if t is None else {name: v[0] for name, v in out.items()}
+        return self._stored().autocorr_time(t, quiet, c, tol, discard, thin)
 
     def get_rhat(self, t=0, discard=0, thin=1, cols=None):
         """Rung t's split R-hat (ncols,) over its walkers -- rung 0 is the posterior -- or every rung's (T, ncols) for
-        ``t=None`` (``EnsembleSampler.get_rhat``'s keywords and rules)."""
-        return self._moments(t, discard, thin, cols, False)['rhat']
+        ``t=None`` (``EnsembleSampler.get_rhat``'s keywords and rules).  From the device series with
+        autocorr='device' (one msx_series_moments call over all members), otherwise ``diagnostics`` on the host chain."""
+        return self._stored().moments(t, discard, thin, cols, False)['rhat']
 
     def get_moments(self, t=0, discard=0, thin=1, cols=None):
         """Rung t's {'mean', 'cov', 'count'} (``EnsembleSampler.get_moments``); ``t=None``: every rung's."""
-        out = self._moments(t, discard, thin, cols, True)
+        out = self._stored().moments(t, discard, thin, cols, rhat=False)
         return {name: out[name] for name in ('mean', 'cov', 'count')}
-
-    def _rank_stats(self, t, want, discard, thin, cols, q=()):
-        """``_lib.Series.rank_stats``' dict for rung t (t None: every rung, a leading axis T): from the device series with
-        autocorr='device', otherwise ``diagnostics`` on the host chain."""
-        from .sampler import _device_rank_stats, _host_rank_stats, _selection
-        if self._series is not None:
-            return self._pick(self._owned(_device_rank_stats(self._series, len(self._chain), discard, thin, cols, want, q)), t)
-        rungs = range(self.ntemps) if t is None else [int(t)]
-        x = np.concatenate([_selection(self.get_chain(t=r), discard, thin, cols) for r in rungs], axis=1)
-        out = _host_rank_stats(x, [self.nwalkers] * len(rungs), want, q)
-        return out if t is None else {name: v[0] for name, v in out.items()}
 
     def get_rank_rhat(self, t=0, discard=0, thin=1, cols=None):
         """Rung t's {'bulk', 'folded', 'rhat'} -- rung 0 is the posterior -- or every rung's for ``t=None``
-        (``EnsembleSampler.get_rank_rhat``)."""
-        from .sampler import _rank_rhat_of
-        return _rank_rhat_of(self._rank_stats(t, ('rhat',), discard, thin, cols), None)
+        (``EnsembleSampler.get_rank_rhat``): from the device series with autocorr='device', otherwise
+        ``diagnostics`` on the host chain."""
+        return self._stored().rank_rhat(t, discard, thin, cols)
 
     def get_ess(self, t=0, discard=0, thin=1, cols=None, kind='bulk'):
         """Rung t's effective sample size (ncols,), or every rung's (T, ncols) for ``t=None`` (``EnsembleSampler.get_ess``)."""
-        from .sampler import _ess_kind, _ess_of
-        return _ess_of(self._rank_stats(t, (_ess_kind(kind),), discard, thin, cols), kind, None)
+        return self._stored().ess(t, discard, thin, cols, kind)
 
     def get_mcse(self, t=0, discard=0, thin=1, cols=None, q=(0.16, 0.5, 0.84)):
         """Rung t's {'mean', 'quantiles'}, or every rung's for ``t=None`` (``EnsembleSampler.get_mcse``)."""
-        from .sampler import _mcse_of
-        return _mcse_of(self._rank_stats(t, ('mcse',), discard, thin, cols, q), None)
-
-    _device_modes = False    # get_modes: the device calls (the device samplers) or the definition (TemperedSampler)
+        return self._stored().mcse(t, discard, thin, cols, q)
 
     def get_modes(self, t=0, ncomp=2, discard=0, thin=1, cols=None, **fit_kw):
         """Rung t's posterior modes -- rung 0 is the posterior -- as ``EnsembleSampler.get_modes`` gives them (a
         ``modes.ModeFit`` cut to that rung); ``t=None``: every rung's, one member per rung.  TemperedSampler uses the
         definition on the host chain; the device samplers the chain held on the device with autocorr='device' (every rung's
         jobs in one msx_series_modes call) and upload the host chain otherwise."""
-        from . import modes
-        rungs = list(range(self.ntemps)) if t is None else [int(t)]
-        if not self._device_modes:
-            out = modes.fit(self._flat_members(), [self.nwalkers] * self.ntemps, cols, ncomp, discard=discard, thin=thin, **fit_kw)
-            return out.select(rungs)
-        out = modes.of_sampler(self._series, self._flat_members, len(self._chain), self._ctx(), [self.nwalkers] * self.ntemps, ncomp,
-                               discard, thin, cols, fit_kw)
-        own = list(range(out.k))[self._own] if self._series is not None else list(range(self.ntemps))
-        return out.select([own[r] for r in rungs])
+        return self._stored().modes(t, ncomp, discard, thin, cols, **fit_kw)
 
     def get_summary(self, t=0, q=(0.16, 0.5, 0.84), discard=0, thin=1, cols=None):
         """Rung t's posterior summary over its stored chain, flattened over its walkers (``DeviceEnsembleSampler.get_summary``'s
         dict and numbers: DESIGN.md section 14); ``t=None``: every rung's, the arrays with a leading axis T.  With
         autocorr='device' from the chain held there; otherwise the host chain is uploaded first (the sampler must have
         been built on an Engine)."""
-        from . import summary
-        if self._series is not None:
-            return self._pick(self._owned(summary.summary_of(self._series, len(self._chain), q, cols, discard, thin)), t)
-        return self._pick(summary.summarize(self._flat_members(), self._ctx(), [self.nwalkers] * self.ntemps, q, cols, discard, thin), t)
+        return self._stored().summary(t, q, discard, thin, cols)
 
     def get_products(self, cols, t=0, q=(0.16, 0.5, 0.84), discard=0, thin=1, indices=None):
         """``get_summary``'s dict over DERIVED columns (``mcmc_spec_amd.products``) of rung t's stored chain (``t=None``: every
         rung's), as ``DeviceEnsembleSampler.get_products``; the one engine serves every rung.
         ``indices``: positions in the rung's flat sample ``get_chain(t, discard=, thin=, flat=True)`` to use instead of all
         of it; those go through msx_products_batch from the host copy."""
-        from . import products, summary
-        engines = [self.engine] * self.ntemps
-        self._ctx()
-        if indices is not None:
-            idx = np.asarray(indices, dtype=np.int64)
-            outs = []
-            for r in (range(self.ntemps) if t is None else [int(t)]):
-                flat = self.get_chain(t=r, flat=True, thin=thin, discard=discard)
-                outs.append(products._summary_of_values(self.engine.ctx, products.evaluate(self.engine, flat[idx], cols), q))
-            return {name: np.stack([o[name] for o in outs]) if t is None else outs[0][name] for name in outs[0]}
-        if self._series is not None:
-            return self._pick(self._owned(products.summarize_chain(self._series, len(self._chain), self._series_engines(), cols, q, discard,
-                                                                   thin)), t)
-        with summary.uploaded(self._flat_members(), self.engine.ctx, [self.nwalkers] * self.ntemps) as (series, n):
-            return self._pick(products.summarize_chain(series, n, engines, cols, q, discard, thin), t)
+        return self._stored().products(cols, t, q, discard, thin, indices)
 
     def get_predictive(self, t=0, q=(0.16, 0.5, 0.84), discard=0, thin=1):
         """Rung t's posterior predictive check (``mcmc_spec_amd.predictive``) of its stored chain --
         rung 0 is the posterior --, ``predictive.check``'s dict (``worst_status`` in place of ``terms`` and ``status``);
         ``t=None``: a list of every rung's.  With autocorr='device' from the chain held there, otherwise the host chain is
         uploaded first (the sampler must have been built on an Engine with staged products)."""
-        from . import predictive
-        self._ctx()
-        if self._series is not None:
-            out = predictive.of_chain(self._series, None, len(self._chain), self._series_engines(), None, q, discard, thin)[self._own]
-        else:
-            out = predictive.of_chain(None, self._flat_members, len(self._chain), [self.engine] * self.ntemps,
-                                      [self.nwalkers] * self.ntemps, q, discard, thin)
-        return out if t is None else out[int(t)]
+        return self._stored().predictive(t, q, discard, thin)
 
     def get_loo(self, t=0, discard=0, thin=1, reff=1.0):
         """Rung t's PSIS-LOO, WAIC and khat per observation (``mcmc_spec_amd.psis``) of its stored
         chain -- rung 0 is the posterior --, ``psis.loo``'s dict; ``t=None``: a list of every rung's.  With autocorr='device'
         from the chain held there, otherwise the host chain is uploaded first."""
-        from . import psis
-        self._ctx()
-        if self._series is not None:
-            out = psis.of_chain(self._series, None, len(self._chain), self._series_engines(), None, discard, thin, reff)[self._own]
-        else:
-            out = psis.of_chain(None, self._flat_members, len(self._chain), [self.engine] * self.ntemps, [self.nwalkers] * self.ntemps,
-                                discard, thin, reff)
-        return out if t is None else out[int(t)]
+        return self._stored().loo(t, discard, thin, reff)
 
     def get_reweighted(self, engines_new=None, t=0, mode='logposterior', discard=0, thin=1):
         """What rung t's stored chain says about another density (``mcmc_spec_amd.reweight``): a
@@ -513,34 +409,27 @@ class _Ladder:
         rung against the posterior, ``(1 - beta) * ll``), ``lpr`` and ``ll`` the chain scored once more under the sampler's
         own engine.  With autocorr='device' on the chain held there; otherwise the host chain is uploaded first.  The
         selected rows must all have been run with the ladder ``self.betas``."""
-        from . import reweight
-        self._ctx()
+        view = self._stored()
+        view._need_gpu()
         if np.any(self.get_betas(discard=discard, thin=thin) != self.betas):
             raise ValueError('get_reweighted: the selected rows were not all run with the ladder self.betas (an adaptive run moved it): '
                              'freeze the ladder (adapt=False) and discard= the adaptive rows')
-        if self._series is not None:
-            engines = self._series_engines()
-            own, host, counts = list(range(len(engines)))[self._own], None, None
-        else:
-            engines = [self.engine] * self.ntemps
-            own, host, counts = list(range(self.ntemps)), self._flat_members, [self.nwalkers] * self.ntemps
-        new = list(engines)
-        for m in own:
-            new[m] = self.engine if engines_new is None else engines_new
-        betas = np.ones(len(engines))
-        betas[own] = self.betas
-        return reweight.of_sampler(self._series, host, len(self._chain), engines, new, counts, mode=mode, discard=discard, thin=thin,
-                                   members=[own[int(t)]], betas=betas)
+        return view.reweighted([self.engine if engines_new is None else engines_new] * self.ntemps, int(t), self.betas, mode=mode,
+                               discard=discard, thin=thin)
 
     def _evidence(self, discard, thin, db, blocks):
-        """(mean, lme) (T, blocks + 1) of the stored ln L: ``host_evidence``, or msx_series_evidence on the device series."""
-        n_total = len(self._ll)
-        if len(range(int(discard), n_total, int(thin))) < 1:
-            raise ValueError('the selection rows[0:n][discard::thin] is empty')
-        if self._dens is not None:
-            mean, lme = self._dens.evidence(n_total, discard, thin, 0, None if db is None else self._series_db(db), blocks)
-            return self._owned(mean), None if lme is None else self._owned(lme)
-        return host_evidence(np.array(self._ll)[int(discard)::int(thin)], db, blocks)
+        """(mean, lme) (T, blocks + 1) of the stored ln L: ``host_evidence``, or msx_series_evidence on the device series (this
+        ladder's db scattered to its rungs among the series' members)."""
+        view = self._stored()
+        view._need(discard, thin, 1)
+        if self._dens is None:
+            return host_evidence(np.array(self._ll)[int(discard)::int(thin)], db, blocks)
+        if db is not None:
+            full = np.zeros(self._dens.k)
+            full[view.own] = db
+            db = full
+        mean, lme = self._dens.evidence(view.n, discard, thin, 0, db, blocks)
+        return mean[view.own], None if lme is None else lme[view.own]
 
     def mean_log_like(self, discard=0, thin=1):
         """(T,): the mean of ``ln L`` over each rung's stored samples, ``<ln L>_beta`` at the ladder's betas."""
@@ -1063,26 +952,26 @@ def _group_eval(group, qs, mode):
 
 class _TargetLadder(_Ladder):
     """``DeviceGroupTemperedSampler.target(k)``: target k's ladder -- its stored rows, counts, generators and the whole
-    ``_Ladder`` interface.  With the run's series on the device (K T members) its T rungs are the members ``_own``."""
+    ``_Ladder`` interface.  With the run's series on the device (K T members) its T rungs are the view's own members (``_stored``)."""
 
     def __init__(self, parent, k, nwalkers, betas, seed, seeds, moves, adaptive, lag, time):
         self.parent, self.k = parent, int(k)
         self.engine = parent.group.engines[k]
         self._init_ladder(nwalkers, parent.ndim, None, betas, None, seed, seeds, moves, adaptive, lag, time)
-        self._own = slice(self.k * self.ntemps, (self.k + 1) * self.ntemps)
 
     _series = property(lambda self: self.parent._series)
     _dens = property(lambda self: self.parent._dens)
     _device_modes = True
     _evaluate = DeviceTemperedSampler._evaluate
 
-    def _series_engines(self):
-        return [e for e in self.parent.group.engines for _ in range(self.ntemps)]
-
-    def _series_db(self, db):
-        full = np.zeros(len(self.parent.targets) * self.ntemps)
-        full[self._own] = db
-        return full
+    def _stored(self):
+        """_Ladder's view; with the run's series on the device its T rungs are the view's own among the K T members (each
+        target's rungs with the target's engine).  With autocorr='host' its own T rungs alone are uploaded."""
+        if self._series is None:
+            return super()._stored()
+        T, par = self.ntemps, self.parent
+        return StoredChain(self._series, self._flat_members, len(self._chain), self.ndim, [n for n in par.nwalkers for _ in range(T)],
+                           [e for e in par.group.engines for _ in range(T)], range(self.k * T, (self.k + 1) * T), device_modes=True, joined=True)
 
 
 class DeviceGroupTemperedSampler:
